@@ -13,6 +13,18 @@ to rank 0 (ilqgames_amd/sharding.py: RCCL over xGMI) inside the timed region.
 
 Prints ONE JSON line on rank 0.
 
+A plain run does only what the headline figure needs: set-up, `--warmup` W untimed iterations and one untimed solve,
+exactly `--steps` K timed iterations, the outputs of the last timed solve when `--dump-outputs DIR` is given, and the
+line.  Every solve runs `--solve-iters` L fixed iterations from a zero warm start (L = the configuration's own count, 20
+for the headline, at most K): K steps are K / L consecutive solves (a shorter one first where L does not divide K), so a
+step costs the same whatever K is and no solve runs past the library's iteration bound (max_solver_iters + 2 rounds on
+the asynchronous launch sequence).  `--repeats R` times that region R times and reports the median.  Everything else the line can carry (the copy-bandwidth denominator of
+the roofline, single-instance latency, the example's own parameters, the back-tracking workload, the other BASELINE.json
+configurations, the CPU baseline and the parity figure against the CPU oracle) is measured under `--full` only.
+
+`--dump-outputs DIR` writes the arrays the timed solve hands its caller (see dump_outputs) as DIR/<name>.npy: the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
 `--backend stub` replaces the device solve by a CPU stand-in over gloo: it exists so that the N > 1 code of
 this file (sharding, gather, max-over-ranks timing, the JSON line) is exercised by a 2-rank CPU test
 (tests/test_host_boundary.py); it measures nothing.
@@ -199,6 +211,29 @@ def launch_ranks_if_needed(gpus):
     sys.exit(rc)
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: bytes of arrays written at most (the headline batch is ~90 MB in fp64)
+DUMP_ARRAYS = ("xs", "us", "P", "alpha", "costs", "iters", "status", "converged")
+
+
+def dump_outputs(directory, bufs, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: the output arrays of the last timed solve (what ilqg_solve_batch_ex returns to its caller: xs, us,
+    P, alpha, costs, iters, status, converged), one DIR/<name>.npy each, floating arrays in the solve's precision and the
+    integer ones as float64.  A batch whose arrays exceed `budget` bytes is cut to the same fixed sample of instances in
+    every array (numpy default_rng(seed), in index order); instances.npy holds their indices."""
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    B = bufs["iters"].shape[0]
+    per_instance = sum(bufs[k][0].numel() * (bufs[k].element_size() if bufs[k].is_floating_point() else 8)
+                       for k in DUMP_ARRAYS)
+    keep = max(1, min(B, budget // per_instance))
+    ids = np.arange(B) if keep == B else np.sort(np.random.default_rng(seed).choice(B, keep, replace=False))
+    idx = torch.as_tensor(ids, dtype=torch.int64, device=bufs["iters"].device)
+    for k in DUMP_ARRAYS:
+        a = bufs[k].index_select(0, idx).cpu().numpy()
+        np.save(os.path.join(directory, k + ".npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+    np.save(os.path.join(directory, "instances.npy"), ids.astype(np.float64))
+
+
 HEADLINE_CONFIG = "modified_three_player_intersection"
 # shorthands for BASELINE.json's configurations: (config, dtype, instances per GPU, default steps)
 BASELINE_CONFIGS = {
@@ -237,7 +272,11 @@ def _bench_spec(examples, config, linesearch="auto"):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="outer iterations in one timed solve (default 20)")
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed outer iterations (default 20), run as solves of --solve-iters iterations each")
+    ap.add_argument("--solve-iters", type=int, default=None,
+                    help="fixed iterations of one solve (default: the configuration's own, 20 for the headline, and at "
+                         "most --steps); --steps beyond it are timed as consecutive solves from a zero warm start")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="instances per GPU (default 1024)")
     ap.add_argument("--dtype", choices=["f64", "f32"], default=None)
@@ -247,7 +286,14 @@ def main():
                          "configuration's per-GPU form, e.g. 3 = fp32, 8192 instances per GPU")
     ap.add_argument("--linesearch", choices=["auto", "own", "headline"], default="auto",
                     help="solver parameters: the configuration's own, or the headline's (see _bench_spec)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed repetitions of the K-step solve; the median is reported")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed repetitions of the K-step solve; the median is reported (R x K timed steps in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: copy bandwidth, latency, own parameters, the second "
+                         "workload, the other configurations, CPU baseline, parity (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed solve as DIR/<name>.npy (a seeded sample of the instances "
+                         "where the whole batch exceeds DUMP_BUDGET_BYTES)")
     ap.add_argument("--backend", choices=["hip", "stub"], default="hip")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true",
@@ -282,6 +328,7 @@ def main():
     args.dtype = args.dtype or base[1]
     args.batch = args.batch or base[2]
     args.steps = args.steps or (base[3] if args.baseline_config else 20)
+    args.solve_iters = args.solve_iters or min(args.steps, base[3] if args.baseline_config else 20)
 
     launch_ranks_if_needed(args.gpus)
 
@@ -326,6 +373,20 @@ def main():
         for k in ("xs", "us", "P", "alpha"):
             bufs[k].zero_()
 
+    L = args.solve_iters
+    iters_acc = torch.zeros_like(bufs["iters"], dtype=torch.int64)
+
+    def run_steps(n):
+        """n outer iterations of every instance as solves of at most L fixed iterations (the remainder first, so that
+        the last solve is always one of L), each from a zero warm start: what one step costs does not depend on n, and
+        no solve runs past the library's own iteration bound.  Adds the iterations done to iters_acc; no host sync."""
+        q, r = divmod(n, L)
+        for i, k in enumerate(([r] if r else []) + [L] * q):
+            if i:
+                reset()
+            backend.solve(x0_d, bufs, k)
+            iters_acc.add_(bufs["iters"])
+
     def gather():
         # the one exchange step: converged strategies of every instance to rank 0 (sharding.gather_to_root)
         if not distributed:
@@ -335,7 +396,7 @@ def main():
 
     # warmup (untimed): W iterations
     reset()
-    backend.solve(x0_d, bufs, max(1, args.warmup))
+    run_steps(max(1, args.warmup))
     gather()
     backend.sync()
     # A workload whose line searches back-track is run with ilqg_solve_options::counted: the host reads four counters
@@ -344,13 +405,21 @@ def main():
     warm_bt = backend.mean_backtracks(bufs, int(bufs["iters"].sum().item())) if args.backend == "hip" else 0.0
     if args.backend == "hip" and warm_bt > 0.25:
         backend.counted = True
+    # ... then one more untimed solve of L iterations in the launch mode just chosen: the first solve after the warm-up
+    # runs ~4 % slower per step than every one after it (headline, 20 steps: 0.532 against 0.512 ms on one box), and a
+    # counted solve launches kernels the warm-up did not.
+    reset()
+    backend.solve(x0_d, bufs, L)
+    gather()
+    backend.sync()
 
-    # timed: exactly K iterations of every instance = K (LQ kernel, trial kernel) rounds after the
-    # initial trial pass; all launches are enqueued back to back on the current stream.  The region is repeated
+    # timed: exactly K iterations of every instance, as solves of L (each L (LQ kernel, trial kernel) rounds after its
+    # initial trial pass); all launches are enqueued back to back on the current stream.  The region is repeated
     # `--repeats` times (each bracketed by barrier + synchronize, max over ranks); the MEDIAN repetition is reported.
     reps = []
     for _ in range(max(1, args.repeats)):
         reset()
+        iters_acc.zero_()
         if distributed:
             dist.barrier()
         backend.sync()
@@ -358,7 +427,7 @@ def main():
         t0 = time.perf_counter()
         if ev:
             ev[0].record()
-        backend.solve(x0_d, bufs, args.steps)
+        run_steps(args.steps)
         if ev:
             ev[1].record()
         gathered = gather()
@@ -378,6 +447,8 @@ def main():
         reps.append((el, ks, gs))
     reps_sorted = sorted(reps)
     elapsed, kernel_s, gather_s = reps_sorted[len(reps_sorted) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bufs)
 
     iters = bufs["iters"].cpu().numpy()
     status = bufs["status"].cpu().numpy()
@@ -386,7 +457,7 @@ def main():
     timed_result = {"ids": sample_ids}
     for k in ("P", "alpha", "costs", "xs", "iters"):
         timed_result[k] = bufs[k][sample_ids].cpu().numpy()
-    local_iters = int(iters.sum())
+    local_iters = int(iters_acc.sum().item())  # every solve of the (last) timed region
     total_iters = local_iters
     if distributed:
         ti = torch.tensor([total_iters], dtype=torch.int64, device=backend.device())
@@ -407,7 +478,7 @@ def main():
         n, m, N, T = spec.n, spec.m, len(spec.subsystems), spec.T
         pairs = backend.prob.pairs if args.backend == "hip" else [(i, i) for i in range(N)]
         pairs_m = [spec.udims[j] for _, j in pairs]
-        mean_bt = backend.mean_backtracks(bufs, local_iters)
+        mean_bt = backend.mean_backtracks(bufs, int(iters.sum()))  # the last solve's back-tracks per iteration
         bytes_iter = algorithmic_bytes_per_iteration(n, m, N, T, pairs_m, elem, backtracks=mean_bt)
         bytes_iter_b0 = algorithmic_bytes_per_iteration(n, m, N, T, pairs_m, elem, backtracks=0.0)
         value = total_iters / elapsed
@@ -441,7 +512,7 @@ def main():
         flops_exec_round = sweep_flops_executed_per_step(n, m, N, open_loop) * T * B
         peak_tf = FP64_PEAK_TFLOPS if elem == 8 else FP32_PEAK_TFLOPS
         peak_measured = None
-        if args.backend == "hip" and not args.no_copy_bandwidth:
+        if args.backend == "hip" and args.full and not args.no_copy_bandwidth:
             try:
                 peak_measured = backend.hip.copy_bandwidth_gbs()
             except Exception as e:  # the nominal figure stands on its own
@@ -451,8 +522,8 @@ def main():
             "n_gpus": dist.get_world_size() if distributed else 1, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": "%s n=%d N=%d T=%d batch=%d/GPU %s, fixed %d outer iterations, %s"
-                                   % (args.config, n, N, T, B, args.dtype, args.steps, params_desc),
+            "config": {"workload": "%s n=%d N=%d T=%d batch=%d/GPU %s, %d outer iterations as solves of fixed %d, %s"
+                                   % (args.config, n, N, T, B, args.dtype, args.steps, L, params_desc),
                        "parallelism": "instances sharded across %d GPU(s); RCCL gather of strategies" % world,
                        "launch_mode": ("host-counted rounds, speculative line search (warm-up back-tracked %.2f times per "
                                        "iteration)" % warm_bt) if getattr(backend, "counted", None) else
@@ -488,14 +559,14 @@ def main():
                                           "cores (16x16x4 tiles, padding included; open loop: inversion lemma instead of the n x n QR); "
                                           "peak = fp32 vector peak of MI355X_MICROARCH.md, halved for fp64 (derived, see bench.py)"}},
         }
-        if args.backend == "hip" and world == 1 and not args.no_latency:
+        if args.backend == "hip" and args.full and world == 1 and not args.no_latency:
             out["latency"] = latency_figures(backend, examples, abi, args, x0_d)
             out["own_params"] = own_params_figure(backend, examples, abi, args, x0_d)
             if args.config == HEADLINE_CONFIG and not args.no_second_workload:
                 out["second_workload"] = backtracking_workload(examples, abi, args, local_rank)
             if args.config == HEADLINE_CONFIG and args.baseline_config is None and not args.no_configs:
                 out["configs"] = baseline_configs_block(examples, abi, local_rank)
-        if args.backend == "hip" and not args.no_cpu_baseline and world == 1:
+        if args.backend == "hip" and args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, spec, x0, dtype, abi, out.get("latency"))
             out["parity"] = parity_figure(args, spec, x0, dtype, abi, timed_result)
         print(json.dumps(out))
@@ -753,16 +824,16 @@ def own_params_figure(backend, examples, abi, args, x0_d):
 
 def parity_figure(args, spec, x0, dtype, abi, timed):
     """BASELINE.json's metric names "P_t rel-err vs CPU": the strategies, trajectory and total costs the TIMED batch ended
-    with (eight instances spread over it, after the `steps` fixed iterations just timed, line searches included) against
+    with (eight instances spread over it, after the last timed solve's fixed iterations, line searches included) against
     the CPU oracle run on the same initial states in the same precision.  The oracle is the checker here, nothing else."""
     from oracle import pyoracle
     ids = timed["ids"]
-    ref = pyoracle.OracleProblem(spec).solve(dtype, x0[ids], fixed_iters=args.steps, threads=1)
+    ref = pyoracle.OracleProblem(spec).solve(dtype, x0[ids], fixed_iters=args.solve_iters, threads=1)
 
     def rel(a, b):
         return float(np.max(np.abs(np.asarray(a, np.float64) - b)) / max(1e-300, np.max(np.abs(b))))
     same = [int(i) for i in range(len(ids)) if int(timed["iters"][i]) == int(ref["iters"][i])]
-    fig = {"instances": [int(i) for i in ids], "iterations": args.steps, "dtype": args.dtype,
+    fig = {"instances": [int(i) for i in ids], "iterations": args.solve_iters, "dtype": args.dtype,
            "instances_with_equal_iteration_counts": len(same),
            "against": "oracle/ilqg_oracle.hpp (CPU restatement of the reference, same precision, same x0, same fixed iteration count)"}
     if same:
@@ -813,12 +884,12 @@ def cpu_baseline(args, spec, x0, dtype, abi, latency):
         runs = []
         for _ in range(5):
             c0 = time.perf_counter()
-            ref = op.solve(dt_, x0[:S], fixed_iters=args.steps, threads=1)
+            ref = op.solve(dt_, x0[:S], fixed_iters=args.solve_iters, threads=1)
             runs.append(int(ref["iters"].sum()) / (time.perf_counter() - c0))
         res[name] = sorted(runs)[2]
     ncpu = usable_cpus()
     # every usable core: instances per thread = what one thread does in ~1.2 s at the rate just measured
-    per = max(4, int(1.2 * res[args.dtype] / max(1, args.steps)) + 1)
+    per = max(4, int(1.2 * res[args.dtype] / max(1, args.solve_iters)) + 1)
     n_all = min(ncpu * per, 65536)
     all_cores, all_wall = None, None
     try:
@@ -827,7 +898,7 @@ def cpu_baseline(args, spec, x0, dtype, abi, latency):
         runs = []
         for _ in range(3):
             c0 = time.perf_counter()
-            ref = op.solve(dtype, xa, fixed_iters=args.steps, threads=ncpu)
+            ref = op.solve(dtype, xa, fixed_iters=args.solve_iters, threads=ncpu)
             w_ = time.perf_counter() - c0
             runs.append((int(ref["iters"].sum()) / w_, w_))
             if sum(r[1] for r in runs) > 8.0:  # bounded: a box that scales badly does not get three slow runs
@@ -839,12 +910,12 @@ def cpu_baseline(args, spec, x0, dtype, abi, latency):
            "value_f32": res["f32"], "value_f64": res["f64"],
            "sample": "median of 5 runs of %d of the same instances x %d iterations, oracle/ilqg_oracle.hpp, 1 thread — the "
                      "reference's execution model; the reference binary itself cannot be built here (Eigen3/glog/gflags absent)"
-                     % (S, args.steps),
+                     % (S, args.solve_iters),
            "value_all_cores": all_cores, "cores_all": ncpu,
            "cores_visible": os.cpu_count(),
            "sample_all_cores": "median run: OpenMP over %d instances (%d per thread) x %d iterations on %d threads (the CPUs this "
                                "process may use: affinity mask and cgroup quota; os.cpu_count() = %s), %s, %.2f s per run"
-                               % (n_all, per, args.steps, ncpu, os.cpu_count(), args.dtype, all_wall or 0.0)}
+                               % (n_all, per, args.solve_iters, ncpu, os.cpu_count(), args.dtype, all_wall or 0.0)}
     if latency is not None:
         s2, _ = _bench_spec(examples, args.config, args.linesearch)
         s2.params.initial_alpha_scaling = 0.5

@@ -191,6 +191,52 @@ def test_bench_gpus_flag_launches_its_own_ranks():
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
 
 
+def test_bench_dump_outputs_are_seeded_and_bounded(tmp_path):
+    """`bench.py --dump-outputs DIR` (one rank, the CPU stand-in): exactly --steps timed steps in the line, every output
+    array of the timed solve as a float .npy, a batch over the size budget cut to a seeded sample of instances, and two
+    runs with the same arguments writing the same arrays."""
+    import json
+    import bench
+    B, steps = 1024, 3
+    runs = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "stub", "--steps", str(steps), "--warmup", "1",
+               "--batch", str(B), "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == steps and out["repeats"]["count"] == 1
+        assert abs(out["value"] * out["ms_per_step"] * 1e-3 * steps - B * steps) < 1e-6
+        runs.append({f.name[:-4]: np.load(f) for f in d.glob("*.npy")})
+    a, b = runs
+    assert set(a) == set(bench.DUMP_ARRAYS) | {"instances"}
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET_BYTES + 8 * B <= 64 << 20
+    ids = a["instances"].astype(np.int64)
+    assert 0 < len(ids) < B and np.all(np.diff(ids) > 0)
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64), k
+        assert v.shape[0] == len(ids) and np.array_equal(v, b[k]), k
+    # the stand-in's strategy of instance i is i: the sample is the instances it names
+    assert np.array_equal(a["P"][:, 0, 0], ids)
+
+
+def test_bench_steps_beyond_one_solve_are_consecutive_solves():
+    """`--steps` K larger than one solve's fixed iterations L (20 for the headline) is timed as K / L solves, a shorter
+    one first: the line counts K steps and every instance-iteration of them, and names the solve length."""
+    import json
+    B, steps = 4, 45
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "stub", "--steps", str(steps), "--warmup", "130",
+           "--batch", str(B)]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == steps and "as solves of fixed 20" in out["config"]["workload"]
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 * steps - B * steps) < 1e-6
+
+
 def test_fast_trig_of_the_rollout_is_within_its_documented_error(tmp_path):
     """csrc/ilqg_trig.hpp is __host__ __device__: tests/host/trig_check.cpp compiles it for the host (plain g++ against
     the HIP headers) and compares sine / cosine / tangent with the C library in long double over the whole fast-path

@@ -1,8 +1,8 @@
 """Host-side C++ mirror of the reference API (include/ilqgames/, ilqgames_amd/host/).
 
-CPU part: the mirror compiles, and — where the reference checkout is present (this container, not
-the GPU box) — the reference's own example problem definitions compile UNCHANGED against it and
-flatten to the same descriptor as the hand-written builders in ilqgames_amd/examples.py.
+CPU part: the mirror compiles, and the reference's own example problem definitions, compiled UNCHANGED against it,
+flatten to the same descriptor as the hand-written builders in ilqgames_amd/examples.py (what they print is recorded
+under tests/golden/ by tests/golden/make_example_dumps.py).
 GPU part: tests/host/host_solve_demo.cpp drives Problem / ILQSolver / AugmentedLagrangianSolver /
 LQFeedbackSolver through the C ABI and is checked against the oracle.
 """
@@ -16,7 +16,7 @@ from ilqgames_amd import abi, examples
 import __graft_entry__ as entry
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 BIN = os.path.join(ROOT, "tests", "host", "_bin")
 
 EXAMPLES = [
@@ -132,15 +132,17 @@ def test_cpp_solution_splicer_keeps_five_rows_and_moves_the_start_time():
     assert cases == 5
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 @pytest.mark.parametrize("cls,stem,builder", EXAMPLES, ids=[e[1] for e in EXAMPLES])
-def test_reference_example_source_compiles_unchanged_and_flattens_like_examples_py(cls, stem, builder, tmp_path):
-    entry.build_host()
-    exe = str(tmp_path / ("dump_" + stem))
-    _compile(exe, [os.path.join(ROOT, "tests", "host", "dump_example.cpp"), os.path.join(REF, "src", stem + ".cpp")],
-             ['-DEXAMPLE_HEADER=<ilqgames/examples/%s.h>' % stem, "-DEXAMPLE_CLASS=" + cls])
-    text = subprocess.check_output([exe], text=True)
-    got = abi.ProblemSpec.from_dump(text)
+def test_reference_example_source_compiles_unchanged_and_flattens_like_examples_py(cls, stem, builder):
+    """The reference's src/<stem>.cpp compiled unchanged against the mirror with tests/host/dump_example.cpp prints
+    the flattened description recorded in tests/golden/example_dumps/<stem>.txt (tests/golden/make_example_dumps.py):
+    the builder of examples.py must flatten to the same.  The dump program and the mirrored example header it includes
+    must still compile against the mirror as it is now."""
+    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only"] + entry.host_compile_flags() +
+                          ['-DEXAMPLE_HEADER=<ilqgames/examples/%s.h>' % stem, "-DEXAMPLE_CLASS=" + cls,
+                           os.path.join(ROOT, "tests", "host", "dump_example.cpp")])
+    with open(os.path.join(GOLDEN, "example_dumps", stem + ".txt")) as f:
+        got = abi.ProblemSpec.from_dump(f.read())
     want = builder()
     g, w = got.canonical(), want.canonical()
     assert g["subsystems"] == w["subsystems"]
@@ -172,14 +174,10 @@ def test_every_reference_header_path_resolves_in_the_mirror(tmp_path):
             rel = os.path.relpath(os.path.join(dirpath, f), inc)
             if f.endswith(".h") and not rel.startswith("host"):
                 mine.add(rel)
-    if os.path.isdir(REF):  # the list above is the whole difference (checked where the reference is present)
-        theirs = set()
-        ref_inc = os.path.join(REF, "include", "ilqgames")
-        for dirpath, _, files in os.walk(ref_inc):
-            for f in files:
-                if f.endswith(".h"):
-                    theirs.add(os.path.relpath(os.path.join(dirpath, f), ref_inc))
-        assert theirs - mine == not_mirrored
+    # the list above is the whole difference (the reference's header paths: tests/golden/make_example_dumps.py)
+    with open(os.path.join(GOLDEN, "reference_headers.txt")) as f:
+        theirs = set(f.read().split())
+    assert theirs - mine == not_mirrored
     src = tmp_path / "all_headers.cpp"
     src.write_text("".join("#include <ilqgames/%s>\n" % h for h in sorted(mine)) + "int main() { return 0; }\n")
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only"] + entry.host_compile_flags() + [str(src)])
