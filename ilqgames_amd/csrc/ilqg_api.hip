@@ -118,6 +118,12 @@ struct LQBatchArgs {
   T *P, *alpha, *dx, *scratch;
   int T_steps, adaptive, batch, force_valu;
   T* costates = nullptr;
+  // the arrays of an ilqg_lq_*_batch call; no scratch, no costates, the caller's regularisation
+  LQBatchArgs(const ilqg_dims* d, const void* A_, const void* Bm_, const void* Q_, const void* l_, const void* R_,
+              const void* r_, const void* x0_, void* P_, void* alpha_, void* dx_)
+      : A((const T*)A_), Bm((const T*)Bm_), Q((const T*)Q_), l((const T*)l_), R((const T*)R_), r((const T*)r_),
+        x0((const T*)x0_), P((T*)P_), alpha((T*)alpha_), dx((T*)dx_), scratch(nullptr), T_steps(d->T),
+        adaptive(d->adaptive_regularization), batch(d->batch), force_valu(0) {}
 };
 
 template <typename T, int NX, int NP, int MU, bool FORCE_VALU>
@@ -353,9 +359,6 @@ __global__ void __launch_bounds__(64 * W, (sizeof(T) == 4 && W == 2) ? ILQG_TRIA
 
 // The same pass cut into three launches (ilqg_solve.hpp, TRIAL_ROLL / rows_part_instance / TRIAL_DECIDE), for
 // problems whose fused trial kernel fits fewer than three instances on a CU.
-#ifndef ILQG_SPLIT_ROW_EXTRA_CHUNKS
-#define ILQG_SPLIT_ROW_EXTRA_CHUNKS 0
-#endif
 #ifndef ILQG_ROLL_WAVES
 #define ILQG_ROLL_WAVES 4
 #endif
@@ -843,6 +846,18 @@ bool build_pairs(const ilqg_pair* pairs, int npairs, const int* udim, int N, Pai
   return true;
 }
 
+GenDims gen_dims_of(int n, int N, const int32_t* udim, int T) {
+  GenDims g{};
+  g.n = n; g.N = N; g.T = T;
+  g.uoff[0] = 0;
+  for (int i = 0; i < N; i++) {
+    g.udim[i] = udim[i];
+    g.uoff[i + 1] = g.uoff[i] + udim[i];
+  }
+  g.m = g.uoff[N];
+  return g;
+}
+
 // Supported (n, N, m_i) instantiations.  n=14/16/15/24: BASELINE configs 2-5;
 // (4,2,2): config 1 (TwoPlayerUnicycle4D); (2,2,1): test_lq_solver's point mass;
 // (6,3,2): synthetic parity cases.
@@ -901,21 +916,13 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::lq(const ilqg_dims* d, const PairTable& p
                                           const void* Q, const void* l, const void* R, const void* r, const void* x0,
                                           void* P, void* alpha, void* dx, hipStream_t stream) {
   using C = LQCfg<T, NX, NP, MU>;
-  LQBatchArgs<T> g;
-  g.A = (const T*)A; g.Bm = (const T*)Bm; g.Q = (const T*)Q; g.l = (const T*)l;
-  g.R = (const T*)R; g.r = (const T*)r; g.x0 = (const T*)x0;
-  g.P = (T*)P; g.alpha = (T*)alpha; g.dx = (T*)dx;
-  g.scratch = nullptr;
+  LQBatchArgs<T> g(d, A, Bm, Q, l, R, r, x0, P, alpha, dx);
   if (dx) {
     const size_t need = size_t(d->batch) * d->T * (NP * (NX + 1) + NX) * sizeof(T);
     ilqg_status s = Scratch().reserve(need);
     if (s != ILQG_OK) return s;
     g.scratch = (T*)ilqg_shared::scratch_state().ptr;
   }
-  g.T_steps = d->T;
-  g.adaptive = d->adaptive_regularization;
-  g.batch = d->batch;
-  g.force_valu = 0;
   // ilqg_dims::sweep_formulation = ILQG_CHOICE_OFF selects the VALU/LDS formulation where the MFMA one is the default
   const bool valu = C::USE_MFMA && d->sweep_formulation == ILQG_CHOICE_OFF;
   const bool use_pw = C::USE_MFMA && !valu;
@@ -934,19 +941,13 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::lq_openloop(const ilqg_dims* d, const Pai
                                                    const void* r, const void* x0, void* P, void* alpha, void* dx,
                                                    void* costates, hipStream_t stream) {
   using O = OLCfg<T, NX, NP, MU>;
-  LQBatchArgs<T> g;
-  g.A = (const T*)A; g.Bm = (const T*)Bm; g.Q = (const T*)Q; g.l = (const T*)l;
-  g.R = (const T*)R; g.r = (const T*)r; g.x0 = (const T*)x0;
-  g.P = (T*)P; g.alpha = (T*)alpha; g.dx = (T*)dx;
+  LQBatchArgs<T> g(d, A, Bm, Q, l, R, r, x0, P, alpha, dx);
   g.costates = (T*)costates;
   const size_t need = size_t(d->batch) * d->T * (costates ? O::ROW_FAT : O::ROW) * sizeof(T);
   ilqg_status s = Scratch().reserve(need);
   if (s != ILQG_OK) return s;
   g.scratch = (T*)ilqg_shared::scratch_state().ptr;
-  g.T_steps = d->T;
   g.adaptive = 0;
-  g.batch = d->batch;
-  g.force_valu = 0;
   const size_t lds = size_t(O::LDS_ELEMS) * sizeof(T);
   auto kern = lq_openloop_kernel<T, NX, NP, MU>;
   raise_lds_limit((const void*)kern, lds);
@@ -995,23 +996,8 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::lq_padded_batch(const ilqg_dims* d, const
       const PadLayout<T, NX, NP, MU, OL> PL(d->T, ptp.Rsz, ptp.rsz);
       const ilqg_status s = Scratch().reserve(size_t(d->batch) * PL.total * sizeof(T));
       if (s != ILQG_OK) return s;
-      GenDims gd{};
-      gd.n = d->n; gd.N = d->num_players; gd.T = d->T;
-      gd.uoff[0] = 0;
-      for (int i = 0; i < gd.N; i++) {
-        gd.udim[i] = d->udim[i];
-        gd.uoff[i + 1] = gd.uoff[i] + d->udim[i];
-      }
-      gd.m = gd.uoff[gd.N];
-      LQBatchArgs<T> g;
-      g.A = (const T*)A; g.Bm = (const T*)Bm; g.Q = (const T*)Q; g.l = (const T*)l;
-      g.R = (const T*)R; g.r = (const T*)r; g.x0 = (const T*)x0;
-      g.P = (T*)P; g.alpha = (T*)alpha; g.dx = (T*)dx;
-      g.scratch = nullptr;
-      g.T_steps = d->T;
-      g.adaptive = d->adaptive_regularization;
-      g.batch = d->batch;
-      g.force_valu = 0;
+      const GenDims gd = gen_dims_of(d->n, d->num_players, d->udim, d->T);
+      const LQBatchArgs<T> g(d, A, Bm, Q, l, R, r, x0, P, alpha, dx);
       PadArgs<T> pa{(T*)ilqg_shared::scratch_state().ptr, PL.total, ptp};
       using PS = PadSweep<T, NX, NP, MU, OL>;
       auto kern = padded_lq_batch_kernel<T, NX, NP, MU, OL>;
@@ -1108,8 +1094,8 @@ struct ilqg_problem {
 // Lagrangian's restarts), and while it does the device idles: what a read-back costs is the gap between two rounds.
 // A copy command plus a stream synchronisation is ~20 us of that; instead a one-wave kernel behind the round's last
 // launch stores the four counters and then a sequence number into host memory (pinned, coherent, mapped), and the
-// host spins on the sequence number.  ILQG_READBACK=copy keeps the copy + synchronise form (A/B measurements);
-// a device fault shows up in the periodic hipStreamQuery.
+// host spins on the sequence number; a device fault shows up in the periodic hipStreamQuery.  Where the pinned mirror
+// has no device address (hipHostGetDevicePointer failed) the counters come back by the copy + synchronise form.
 namespace {
 __global__ void ilq_publish_kernel(int* counts, int* host, int seq) {
   const int t = threadIdx.x;
@@ -1130,12 +1116,8 @@ __global__ void ilq_count_active_kernel(const int* active, int batch, int* count
 }
 
 inline ilqg_status read_round_counters(ilqg_problem* p, hipStream_t stream) {
-  static const bool copy_form = [] {
-    const char* e = getenv("ILQG_READBACK");
-    return e && std::string(e) == "copy";
-  }();
   p->counters_clean = false;
-  if (copy_form || !p->h_unfinished_dev) {
+  if (!p->h_unfinished_dev) {
     HIP_TRY(hipMemcpyAsync(p->h_unfinished, p->d_unfinished, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return ILQG_OK;
@@ -1210,6 +1192,244 @@ struct AlOuterClock {
   }
 };
 
+// ---------------------------------------------------------------------------------------------------------------
+// The round protocol both solve drivers share (DimsLaunch::solve on the specialised kernels, generic_solve on the
+// run-time-dimensioned ones).  Each driver keeps its own loop and its own pass launches; what differs between the two
+// is a parameter here, never a question of who is calling.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+
+// The anytime exit of one inner solve (ilqg_solve_options::max_runtime): the loop condition of src/ilq_solver.cpp:
+// 123-124, read where the batch is about to start an iteration, so timed solves do not batch rounds into bursts.  The
+// augmented-Lagrangian solver gives each inner solve of a constrained problem max_runtime / max_solver_iters
+// (src/augmented_lagrangian_solver.cpp:85-88), which is also where its AlOuterClock starts.
+struct InnerClock {
+  ilqg_problem* p;
+  bool on;
+  double budget, elapsed = 0.0, tic = 0.0;
+  bool iteration_open = false;
+  InnerClock(ilqg_problem* p_, bool on_, double max_runtime, bool al_constrained)
+      : p(p_), on(on_),
+        budget(!on_ ? 0.0 : al_constrained ? max_runtime / double(p_->desc.params.max_solver_iters) : max_runtime) {}
+  bool deadline_passed() {  // in front of an iteration: the one in flight ends here; true: the next may not start
+    const double now = AlOuterClock::wall();
+    if (iteration_open) {
+      p->loop_add(now - tic);
+      elapsed += now - tic;
+      iteration_open = false;
+    }
+    return !(elapsed < budget - p->loop_upper_bound());
+  }
+  void open_iteration() {
+    if (!on) return;
+    tic = AlOuterClock::wall();
+    iteration_open = true;
+  }
+  void restart() { elapsed = 0.0; }  // an augmented-Lagrangian restart: the next inner solve's own budget
+};
+
+ilqg_status iteration_bound(long long round, long long cap) {
+  return round > cap ? fail(ILQG_ERR_HIP, "solve did not terminate within its iteration bound") : ILQG_OK;
+}
+
+// Step sizes probed per listed instance in a round of a line-search tail: as many as the pool holds for a list this long,
+// ramping up from `probe_first` in a tail's first round (ilqg_solve_options::probe_first) and doubling per round (most
+// line searches that back-track at all end within a step or two; the ones that do not are mostly on their way through
+// all max_backtracking_steps of a failing search, and a round for the few instances left costs the latency of its
+// launches whatever it probes: 2, 4, 8, 16, 32, ...).
+// The library's `probe_first`: as many candidates per instance as keep the round's rollouts within one filling of the
+// chip (kProbeRoundBudget of them), between 2 and kProbeCandidates.  A short list is a few deep searches — the instances
+// that back-track at all mostly go on for tens of steps (the n = 16 intersection: ~10 % of the batch, mean depth ~30) —
+// and 32 at once ends them in a round or two (measured, B = 1024: 280 k -> 335 k it/s); a long list (config 4: ~40 % of
+// 4096 instances, most done within a step or two) pays for every candidate it does not need (226 k it/s at 2, 193 k at
+// 32).  Round 4, with two rollouts per wavefront and the gradient-only row pass: a budget of 8192 rollouts (config 5 /
+// n = 16 constrained / config 4: 249 k / 483 k / 248 k it/s; 4096: 240 / 469 / 252; 16384: 261 / 483 / 236; 4096
+// growing fourfold per round: 245 / 457 / 251).
+int probe_candidates(int pool_entries, int round_instances, int probe_first, int tail_rounds) {
+  int probe_k = pool_entries / round_instances;
+  if (probe_k > kProbeCandidates) probe_k = kProbeCandidates;
+  int first = probe_first;
+  if (first <= 0) {
+    first = kProbeRoundBudget / round_instances;
+    first = first < 2 ? 2 : (first > kProbeCandidates ? kProbeCandidates : first);
+  }
+  long long ramp = (long long)first << (tail_rounds < 8 ? tail_rounds : 8);
+  if (ramp < 2) ramp = 2;
+  return probe_k > ramp ? int(ramp) : probe_k;
+}
+
+// The specialised driver's choices on top of probe_candidates, measured on the MI355X and kept as
+// constants rather than scaled by the device's CU count:
+// - deep tails probe whole lane wavefronts up to this many per round, where they fill the chip;
+constexpr int kDeepTailWaves = 2400;
+// - the cost of a probing round per time step, max(one wave's chain, waves / SIMDs x a wave's issue time), in cycles as
+//   measured on the n = 15 scene: the paired form (two candidates per wave) and the lane form (64 / N candidates per
+//   wave, thirteen trigonometric evaluations in sequence, ~1180 instructions).
+constexpr double kPairChainCycles = 1500.0, kPairIssueCycles = 550.0;
+constexpr double kLaneChainCycles = 3500.0, kLaneIssueCycles = 1530.0;
+
+// What follows the per-instance blocks of a solve's workspace (ws_tail), as pointers.
+template <typename T>
+struct SolveTail {
+  int* pass_ids;    // [2][batch]: this round's back-tracking instances, the next round's
+  T* probe_pool;    // the speculative line search's candidates
+  int pool_entries;
+};
+
+// The SolveArgs fields every solve fills alike; the schedule's own ones (prof, rows_cw, compact, ...) are the driver's.
+template <typename T>
+SolveArgs<T> solve_args_of(const ilqg_problem* p, int32_t batch, const void* x0, void* xs, void* us, void* P,
+                           void* alpha, void* total_costs, int32_t* iters, int32_t* status, int32_t* converged,
+                           void* workspace, const ilqg_solve_options& opt, SolveTail<T>* tail) {
+  const DevProblem& d = p->dev;
+  SolveArgs<T> sa{};
+  sa.ol_row = p->desc.params.open_loop ? ol_row_elems(d.n, d.m, d.N) : 0;
+  sa.al_mode = opt.augmented_lagrangian ? 1 : 0;
+  sa.x0 = (const T*)x0; sa.xs = (T*)xs; sa.us = (T*)us; sa.P = (T*)P; sa.alpha = (T*)alpha;
+  sa.total_costs = (T*)total_costs; sa.iters = iters; sa.status = status; sa.converged = converged;
+  sa.ws = (T*)workspace;
+  sa.ws_stride = WsLayout(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, sa.ol_row, d.num_constraints, sa.al_mode).total;
+  sa.fixed_iters = opt.fixed_iters;
+  sa.batch = batch;
+  sa.prm = p->desc.params;
+  sa.active = opt.active;
+  sa.forced_steps = (const T*)opt.forced_steps;
+  sa.unfinished = p->d_unfinished;
+  sa.first = opt.resume ? 2 : 1;
+  const WsTail t = ws_tail(d, batch, sizeof(T), sa.ol_row);
+  tail->pass_ids = reinterpret_cast<int*>(static_cast<char*>(workspace) + t.ids_off);
+  tail->probe_pool = reinterpret_cast<T*>(static_cast<char*>(workspace) + t.pool_off);
+  tail->pool_entries = t.pool_entries;
+  return sa;
+}
+
+// The iterate log (ilqg_solve_options::iterate_log): checked and its counts cleared where the solve begins ...
+template <typename T>
+ilqg_status iterate_log_open(const ilqg_solve_options& opt, int32_t batch, hipStream_t stream, IterLog<T>* lg) {
+  *lg = IterLog<T>{};
+  if (!opt.iterate_log) return ILQG_OK;
+  const ilqg_iterate_log& il = *opt.iterate_log;
+  if (!il.xs || !il.us || !il.costs || !il.count || il.capacity < 1)
+    return fail(ILQG_ERR_INVALID, "iterate log: xs, us, costs, count and a capacity of at least one are required");
+  *lg = IterLog<T>{(T*)il.xs, (T*)il.us, (T*)il.costs, (T*)il.P, (T*)il.alpha, il.count, il.capacity};
+  HIP_TRY(hipMemsetAsync(il.count, 0, sizeof(int) * size_t(batch), stream));
+  return ILQG_OK;
+}
+
+// ... and copied in front of every exit / sweep launch
+template <typename T>
+ilqg_status iterate_log_launch(const ilqg_problem* p, const SolveArgs<T>& sa, const IterLog<T>& lg, hipStream_t stream) {
+  if (!lg.count) return ILQG_OK;
+  hipLaunchKernelGGL(ilq_log_kernel<T>, dim3(sa.batch), dim3(256), 0, stream, p->dev, sa, lg);
+  HIP_TRY(hipGetLastError());
+  return ILQG_OK;
+}
+
+// Split passes: the decision kernel lists the instances that want another pass (the initial quadraticisation,
+// back-tracking), and the next round covers those only — a tail of rounds that lasts until the last of them has made up
+// its mind.  The sweeps and exits the batch asks for wait until then: the sweep is launched once per iteration, which
+// keeps the batch in step (a sweep launch with a handful of instances costs a full sweep's latency).
+template <typename T>
+struct RoundLists {
+  SolveArgs<T>& sa;             // sa.ids: the instances of this round (null: the whole batch)
+  int* const pass_ids;          // the two lists (SolveTail)
+  const long long cap;          // the driver's iteration bound in rounds
+  int round_instances;          // how many instances this round covers
+  int list = 0;                 // which list is free for the round to write
+  int tail_rounds = 0;          // rounds since the whole batch was last in one
+  int tail_first_instances = 0;  // instances in the current tail's first round
+  bool probed_in_tail = false;  // the current tail has launched a probing pass
+  int waiting_lq = 0, waiting_exit = 0;  // instances already through this iteration's line search
+  RoundLists(SolveArgs<T>& sa_, int* pass_ids_, long long cap_)
+      : sa(sa_), pass_ids(pass_ids_), cap(cap_), round_instances(sa_.batch) {}
+  int* free_list() const { return pass_ids + size_t(list) * sa.batch; }
+  // a round over listed instances that probes probe_k step sizes of each (fewer than two: no probing launch)
+  ilqg_status tail_round(bool probe, int probe_k) {
+    tail_rounds++;
+    if (!probe) return ILQG_OK;
+    // an instance every candidate of which was rejected waits in ST_PROBE and is skipped by the regular pass: it is
+    // only picked up again by the next probing launch, so a tail that has probed must keep probing (the list only
+    // shrinks and the ramp only grows, so this cannot trigger; if it ever does, fail instead of dropping instances)
+    if (probed_in_tail && probe_k < 2) return fail(ILQG_ERR_HIP, "a probing line-search tail lost its probe launch");
+    if (probe_k >= 2) probed_in_tail = true;
+    return ILQG_OK;
+  }
+  // The round's counters are back.  *again: the instances it listed go round again, by themselves; otherwise the batch
+  // is whole again and *want_lq / *want_exit are what its iteration asks for.
+  ilqg_status after_round(const int* counters, long long round, bool* again, int* want_lq, int* want_exit) {
+    waiting_lq += counters[0];
+    waiting_exit += counters[1];
+    *again = counters[3] != 0;
+    if (*again) {
+      const ilqg_status s = iteration_bound(round, cap);
+      if (s != ILQG_OK) return s;
+      if (!sa.ids) tail_first_instances = counters[3];
+      sa.ids = sa.ids_next;
+      round_instances = counters[3];
+      list ^= 1;
+      return ILQG_OK;
+    }
+    sa.ids = nullptr;
+    round_instances = sa.batch;
+    tail_rounds = 0;
+    probed_in_tail = false;
+    *want_lq = waiting_lq;
+    *want_exit = waiting_exit;
+    waiting_lq = waiting_exit = 0;
+    return ILQG_OK;
+  }
+};
+
+// A driver's exit launch (ilq_exit_kernel).
+template <typename T>
+struct ExitLaunch {
+  void (*kernel)(DevProblem, SolveArgs<T>);
+  int threads;
+  size_t lds;
+  bool fill_first;     // clear the round counters in front of it where they are not clean
+  bool read_restarts;  // read the augmented Lagrangian's restarts back behind it
+};
+
+// The end of an iteration of the batch, once its rounds have left want_lq instances waiting for a sweep and want_exit
+// for the exit path: the anytime exit's deadline (which turns the sweep into an exit), the iterate log, the exit launch
+// and the restarts it made, the sweep (`sweep`: the driver's launch).  *done: the solve has ended.
+template <typename T, typename Sweep>
+ilqg_status end_iteration(ilqg_problem* p, SolveArgs<T>& sa, hipStream_t stream, const IterLog<T>& lg,
+                          InnerClock& clock, AlOuterClock& outer, const ExitLaunch<T>& ex, long long round,
+                          long long cap, int want_lq, int want_exit, const Sweep& sweep, bool* done) {
+  const DevProblem& d = p->dev;
+  if (clock.on && want_lq && clock.deadline_passed()) {
+    hipLaunchKernelGGL(ilq_deadline_kernel<T>, dim3(sa.batch), dim3(64), 0, stream, d, sa);
+    HIP_TRY(hipGetLastError());
+    want_exit = 1;
+    want_lq = 0;
+  }
+  if ((want_exit || want_lq) && iterate_log_launch(p, sa, lg, stream) != ILQG_OK) return ILQG_ERR_HIP;
+  int restarted = 0;
+  if (want_exit) {
+    if (ex.fill_first && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
+    if (outer.before_exit()) sa.outer_closed = 1;  // out of time: inner solves that end now are the last ones
+    hipLaunchKernelGGL(ex.kernel, dim3(sa.batch), dim3(ex.threads), ex.lds, stream, d, sa);
+    HIP_TRY(hipGetLastError());
+    p->counters_clean = false;
+    if (ex.read_restarts) {
+      if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
+      restarted = p->h_unfinished[2];
+      if (restarted) clock.restart();
+      outer.after_exit(restarted);
+    }
+  }
+  if (want_lq) {
+    clock.open_iteration();
+    const ilqg_status s = sweep();
+    if (s != ILQG_OK) return s;
+  }
+  *done = !want_lq && !restarted;
+  return *done ? ILQG_OK : iteration_bound(round, cap);
+}
+
+}  // namespace
+
 #define DT_DISPATCH(p, CALL) ((p)->desc.dtype == ILQG_F32 ? CALL(float) : CALL(double))
 
 static ilqg_status launch_linquad(const ilqg_problem* p, int32_t batch, const void* xs, const void* us,
@@ -1225,38 +1445,19 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   using C = LQCfg<T, NX, NP, MU>;
   const DevProblem& d = p->dev;
   const int32_t fixed_iters = opt.fixed_iters;
-  const int al_mode = opt.augmented_lagrangian ? 1 : 0, resume = opt.resume ? 1 : 0;
   const int32_t* const active = opt.active;
   auto choice = [](int32_t c, bool automatic) { return c == ILQG_CHOICE_ON ? true : (c == ILQG_CHOICE_OFF ? false : automatic); };
   static_assert(OLCfg<T, NX, NP, MU>::ROW == ol_row_elems(NX, NP * MU, NP) && OLCfg<T, NX, NP, MU>::ROW_FAT == ol_row_elems(NX, NP * MU, NP, true), "ol_row_elems");
-  const int ol_row = p->desc.params.open_loop ? ol_row_elems(d.n, d.m, d.N) : 0;
-  const WsLayout L(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, ol_row, d.num_constraints, al_mode);
-  SolveArgs<T> sa{};
-  sa.ol_row = ol_row;
-  sa.al_mode = al_mode;
-  sa.x0 = (const T*)x0; sa.xs = (T*)xs; sa.us = (T*)us; sa.P = (T*)P; sa.alpha = (T*)alpha;
-  sa.total_costs = (T*)total_costs; sa.iters = iters; sa.status = status; sa.converged = converged;
-  sa.ws = (T*)workspace; sa.ws_stride = L.total; sa.fixed_iters = fixed_iters; sa.batch = batch;
-  sa.prm = p->desc.params;
-  sa.active = active;
+  SolveTail<T> tail;
+  SolveArgs<T> sa = solve_args_of<T>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, opt, &tail);
+  const int al_mode = sa.al_mode;
+  const WsLayout L(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, sa.ol_row, d.num_constraints, al_mode);
 #if ILQG_DIAGNOSTIC_BUILD
   sa.prof = g_prof;
-#else
-  sa.prof = nullptr;
 #endif
-  sa.forced_steps = (const T*)opt.forced_steps;
-  sa.unfinished = p->d_unfinished;
-  // the tail of the workspace: the two lists of back-tracking instances and the line-search probe pool
-  const WsTail tail = ws_tail(d, batch, sizeof(T), ol_row);
   // ws_tail places the lists behind the augmented-Lagrangian layout (the larger one): whatever al_mode this solve runs in
-  if (WsLayout(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, ol_row, d.num_constraints, 1).total < L.total)
+  if (WsLayout(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, sa.ol_row, d.num_constraints, 1).total < L.total)
     return fail(ILQG_ERR_INVALID, "workspace layout: the tail offset does not cover this solve's per-instance blocks");
-  int* const pass_ids = reinterpret_cast<int*>(static_cast<char*>(workspace) + tail.ids_off);
-  T* const probe_pool = reinterpret_cast<T*>(static_cast<char*>(workspace) + tail.pool_off);
-  sa.ids = nullptr;
-  sa.ids_next = nullptr;
-  sa.probe_pool = nullptr;
-  sa.probe_k = 0;
   constexpr int W = TrialWaves<T>::W;
   // LDS of the sweep kernel that will run: the open-loop sweep's own working set plus the slot the expected
   // decrease is handed over in (n = 24: 54 KB, three instances per CU; the feedback layout would take 85 KB)
@@ -1343,7 +1544,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   const size_t lds_exit = quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T);
   // Split passes where the fused trial kernel's LDS leaves a CU with fewer than three instances (n = 24); the
   // host then counts every round, because an instance may ask for another pass (back-tracking) before its sweep.
-  // ILQG_SPLIT_TRIAL=0/1 overrides the choice (A/B measurements).
+  // ilqg_solve_options::split_trial overrides the choice.
   // Split passes: where the fused kernel cannot keep four instances on a CU, and for batches that are several times
   // what it keeps resident when the split integration kernel (a quarter of the registers, 4 KB of LDS) gains from
   // the co-residency — measured: n = 24, B = 4096: 65 k vs 39 k it/s.  For n <= 16 the fused kernel stays
@@ -1359,10 +1560,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   const int nt_exit = sched_batch <= 2 * num_cus ? 256 : 64;
   const bool big_batch = size_t(sched_batch) >= size_t(8) * num_cus;
   // the whole batch resident at once (four instances per CU): fair issue arbitration among the co-resident instances
-#ifndef ILQG_PRIO_ROTATION
-#define ILQG_PRIO_ROTATION 1
-#endif
-  sa.prio_div = (ILQG_PRIO_ROTATION && sched_batch > num_cus && sched_batch <= 4 * num_cus) ? num_cus : 0;
+  sa.prio_div = (sched_batch > num_cus && sched_batch <= 4 * num_cus) ? num_cus : 0;
   // ... and wherever the single-wave sweep (below) will run: it takes its expected decrease from its own adjoint pass, so
   // nothing is left for the fused kernel's row wave to overlap with the rollout, and the three split kernels each keep
   // more instances on a CU than the fused one (measured, n = 14, B = 8192, LQ single-wave + adjoint: fp64 1.58 M it/s
@@ -1382,28 +1580,14 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   if (split) {
     // The split row kernel is one wave per chunk with the chunk's scratch to itself, and its instances per CU are what
     // the scratch leaves room for: chunks of equal width (T = 100: 2 x 50 rows, 28 KB, five per CU — not 64 + 36 at 36 KB
-    // and four), or one chunk more where that buys a second wave per SIMD.
-    const int base = (d.T + sa.rows_cw - 1) / sa.rows_cw;
-    int best_cw = sa.rows_cw;
-    double best = 0.0;
-    for (int chunks = base; chunks <= base + ILQG_SPLIT_ROW_EXTRA_CHUNKS && chunks <= d.T; chunks++) {
-      const int cw = (d.T + chunks - 1) / chunks;
-      // (a static row kernel's scratch has the fixed strides of a 64-row chunk whatever its width: ilqg_rows.hpp)
-      const size_t lds = (static_id && static_in_regs) ? size_t(16) : split_maps_bytes + split_rows_elems(d, NX, static_id ? 64 : cw) * sizeof(T);
-      size_t per_cu = size_t(160) * 1024 / (lds + 256);
-      if (per_cu > 8) per_cu = 8;
-      const double score = double(per_cu) / double(chunks);
-      if (score > best * 1.05) {
-        best = score;
-        best_cw = cw;
-      }
-    }
-    sa.rows_cw = best_cw;
+    // and four).
+    const int chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;
+    sa.rows_cw = (d.T + chunks - 1) / chunks;
   }
   const bool counted = !opt.forced_steps && (split || !(fixed_iters > 0 && !al_mode) || choice(opt.counted, false));
   // Hand-off: whenever the host counts rounds anyway, the fused kernel keeps an instance only until its line
   // search rejects a step; the back-tracking instances then go through split passes with the speculative line
-  // search (ILQG_HANDOFF=0 keeps every pass in the fused kernel).
+  // search (ilqg_solve_options::handoff = OFF keeps every pass in the fused kernel).
   const bool handoff = counted && !split && !kProfile && sa.prm.linesearch && choice(opt.handoff, true);
   const bool lists = split || handoff;
   // The sweep's forward pass runs in the fused trial kernel that follows it, beside the rollout, whenever that is the
@@ -1460,13 +1644,8 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   auto k_proll_lanes = ilq_probe_roll_lanes_kernel<T, NX, NP, MU>;
   const size_t lds_proll_lanes = pairs ? size_t(rollout_lanes_lds_elems(d.n, d.m, d.N)) * sizeof(T) + 16 : 0;
   const int probe_lanes_min = opt.probe_lanes == ILQG_CHOICE_OFF ? (1 << 30) : (opt.probe_lanes == ILQG_CHOICE_ON ? 2 : 8);
-  const int decide_elems = int(trial_phase_quad_elems<T>(d, TRIAL_DECIDE, sa.rows_cw));
   const int row_chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;  // workgroups per instance of the row kernels
-  int round_instances = batch, list = 0;  // split passes: how many instances this round covers, which list is free
-  int tail_rounds = 0;                    // rounds since the whole batch was last in one
-  bool probed_in_tail = false;            // the current tail has launched a probing pass
-  bool deep_tails = false;                // a tail of this solve kept half of its list through three rounds (see the ramp below)
-  int tail_first_instances = 0;
+  bool deep_tails = false;  // a tail of this solve kept half of its list through three rounds (see the ramp below)
   if (lists) {
     raise_lds_limit((const void*)k_roll, lds_proll);
     raise_lds_limit((const void*)k_rows, lds_rows);
@@ -1478,153 +1657,82 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
     raise_lds_limit((const void*)k_prows, lds_prows);
   }
   sa.clear_counters = 1;
-  sa.first = resume ? 2 : 1;
   p->counters_clean = false;  // whatever an earlier solve left in the round counters
-  int waiting_lq = 0, waiting_exit = 0;  // split passes: instances already through this iteration's line search
-  bool exit_pending = false;             // a burst round went without its exit launch (see the burst loop)
+  RoundLists<T> rl(sa, tail.pass_ids, cap);
+  bool exit_pending = false;  // a burst round went without its exit launch (see the burst loop)
   // Free-running solves: the kernels select their instances by the stage each one is in, so a round launched for
   // nobody is harmless — the host therefore enqueues BURSTS of whole rounds (trial, exit, sweep) and reads the
   // counters back once per burst instead of once per round (a read-back is a stream synchronisation: ~20-30 us against
   // a ~0.45 ms round of a single instance).  The burst doubles up to eight rounds while no instance is back-tracking
   // and falls back to one as soon as one is (those go through the probing passes, which need the lists every round).
-  // the anytime exit (ilqg_solve_options::max_runtime): the host's clock is read where the batch is about to start an
-  // iteration, so rounds are not batched into bursts; the augmented-Lagrangian solver gives each inner solve of a
-  // constrained problem max_runtime / max_solver_iters (src/augmented_lagrangian_solver.cpp:85-88)
+  // Timed solves (InnerClock) read the clock in front of every iteration: no bursts.
   const bool timed = opt.max_runtime > 0.0 && counted;
-  const double budget = !timed ? 0.0 : ((al_mode && d.num_constraints > 0) ? opt.max_runtime / double(sa.prm.max_solver_iters) : opt.max_runtime);
-  auto wall = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double inner_elapsed = 0.0, tic = 0.0;
-  bool iteration_open = false;
-  AlOuterClock outer(p, timed && al_mode && d.num_constraints > 0, opt.max_runtime, budget);
+  const bool al_constrained = al_mode && d.num_constraints > 0;
+  InnerClock clock(p, timed, opt.max_runtime, al_constrained);
+  AlOuterClock outer(p, timed && al_constrained, opt.max_runtime, clock.budget);
   const bool bursts = counted && !kProfile && !timed && choice(opt.round_bursts, true);
   int burst = 1;
-  // the iterate log (ilqg_solve_options::iterate_log): copied in front of every exit / sweep launch
-  IterLog<T> lg{};
-  const bool logging = opt.iterate_log != nullptr;
-  if (logging) {
-    const ilqg_iterate_log& il = *opt.iterate_log;
-    if (!il.xs || !il.us || !il.costs || !il.count || il.capacity < 1)
-      return fail(ILQG_ERR_INVALID, "iterate log: xs, us, costs, count and a capacity of at least one are required");
-    lg = IterLog<T>{(T*)il.xs, (T*)il.us, (T*)il.costs, (T*)il.P, (T*)il.alpha, il.count, il.capacity};
-    HIP_TRY(hipMemsetAsync(il.count, 0, sizeof(int) * size_t(batch), stream));
+  IterLog<T> lg;
+  {
+    const ilqg_status s = iterate_log_open(opt, batch, stream, &lg);
+    if (s != ILQG_OK) return s;
   }
-  auto log_iterates = [&]() -> ilqg_status {
-    if (!logging) return ILQG_OK;
-    hipLaunchKernelGGL(ilq_log_kernel<T>, dim3(batch), dim3(256), 0, stream, d, sa, lg);
+  const ExitLaunch<T> ex{k_exit, nt_exit, lds_exit, false, counted && al_mode};
+  auto sweep = [&]() -> ilqg_status {
+    hipLaunchKernelGGL(k_lq, dim3(batch), dim3(nt_lq), lds_lq, stream, d, sa);
     HIP_TRY(hipGetLastError());
+    p->counters_clean = true;  // (SolveArgs::clear_counters)
     return ILQG_OK;
   };
-  for (long long round = 0;; round++) {
-    if (bursts && !sa.ids) {
-      // a fixed-iteration solve knows its last round: no burst runs past it
-      const long long left = (fixed_iters > 0 && !al_mode) ? (long long)fixed_iters - round : (long long)burst;
-      for (int q = 1; q < burst && q <= left; q++) {  // rounds without a read-back
-        if (!p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
-        p->counters_clean = false;
-        if (split) {  // the three-kernel form of the pass over the whole batch (no probing: nobody is listed)
-          sa.ids_next = pass_ids + size_t(list) * batch;
-          sa.round_count = batch;
-          hipLaunchKernelGGL(k_roll, dim3(pairs ? (batch + 1) / 2 : batch), dim3(64), lds_proll, stream, d, sa);
-          HIP_TRY(hipGetLastError());
-          sa.first = 0;
-          hipLaunchKernelGGL(k_rows, dim3(row_chunks, batch), dim3(64), lds_rows, stream, d, sa);
-          HIP_TRY(hipGetLastError());
-          hipLaunchKernelGGL(k_decide, dim3(batch), dim3(64), lds_decide, stream, d, sa);
-        } else {
-          sa.ids_next = handoff ? pass_ids + size_t(list) * batch : nullptr;
-          hipLaunchKernelGGL(k_trial, dim3(batch), dim3(64 * W), lds_trial, stream, d, sa);
-        }
-        HIP_TRY(hipGetLastError());
-        sa.first = 0;
-        if (log_iterates() != ILQG_OK) return ILQG_ERR_HIP;
-        // The exit path inside a burst only where it starts something (the augmented Lagrangian's next inner solve);
-        // an ILQSolver::Solve that ends here waits for the burst's last round, whose exit launch is then unconditional
-        // (a launch for nobody is ~5 us of every round of a lone instance).
-        if (al_mode) {
-          hipLaunchKernelGGL(k_exit, dim3(batch), dim3(nt_exit), lds_exit, stream, d, sa);
-          HIP_TRY(hipGetLastError());
-        } else {
-          exit_pending = true;
-        }
-        hipLaunchKernelGGL(k_lq, dim3(batch), dim3(nt_lq), lds_lq, stream, d, sa);
-        HIP_TRY(hipGetLastError());
-        p->counters_clean = true;  // (SolveArgs::clear_counters)
-        round++;
-      }
-    }
+  // One pass of a round: the split kernels — over the whole batch (split mode; nobody is listed in a burst round, so
+  // nothing is probed) or over the listed back-tracking instances with their probing launches — or the fused kernel.
+  auto pass = [&]() -> ilqg_status {
     if (counted && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
     p->counters_clean = false;  // (the round's kernels count into them)
     if (split || sa.ids) {  // a split pass: the whole batch (split mode) or the listed back-tracking instances
-      sa.ids_next = pass_ids + size_t(list) * batch;
-      // Step sizes probed per listed instance: as many as the pool holds for a list this long, doubling from two
-      // over the first rounds of a tail (most line searches that back-track at all end within a step or two; the
-      // ones that do not are mostly on their way through all max_backtracking_steps of a failing search, and a round
-      // for the few instances left costs the latency of its launches whatever it probes: 2, 4, 8, 16, 32, ...).
-      int probe_k = sa.ids ? tail.pool_entries / round_instances : 0;
-      if (probe_k > kProbeCandidates) probe_k = kProbeCandidates;
-      {
-        // the ramp: `first` candidates in a tail's first round, doubling per round (ilqg_solve_options::probe_first)
-        // The library's choice: as many candidates per instance as keep the round's rollouts within one filling of
-        // the chip (kProbeRoundBudget of them), between 2 and kProbeCandidates.  A short list is a few deep searches — the instances
-        // that back-track at all mostly go on for tens of steps (the n = 16 intersection: ~10 % of the batch, mean
-        // depth ~30) — and 32 at once ends them in a round or two (measured, B = 1024: 280 k -> 335 k it/s); a long list
-        // (config 4: ~40 % of 4096 instances, most done within a step or two) pays for every candidate it does not
-        // need (226 k it/s at 2, 193 k at 32).  Round 4, with two rollouts per wavefront and the gradient-only row pass: a
-        // budget of 8192 rollouts (config 5 / n = 16 constrained / config 4: 249 k / 483 k / 248 k it/s; 4096: 240 / 469 /
-        // 252; 16384: 261 / 483 / 236; 4096 growing fourfold per round: 245 / 457 / 251).
-        int first = opt.probe_first;
-        if (first <= 0) {
-          first = kProbeRoundBudget / (round_instances > 0 ? round_instances : 1);
-          first = first < 2 ? 2 : (first > kProbeCandidates ? kProbeCandidates : first);
-        }
-        long long ramp = (long long)first << (tail_rounds < 8 ? tail_rounds : 8);
-        if (ramp < 2) ramp = 2;
+      sa.ids_next = rl.free_list();
+      int probe_k = 0;
+      if (sa.ids) {
+        probe_k = probe_candidates(tail.pool_entries, rl.round_instances, opt.probe_first, rl.tail_rounds);
         // Deep searches: once a tail of this solve has kept half of its list through three rounds (2 + 4 + 8 or more
         // rejected candidates each: they are mostly on their way through all max_backtracking_steps), later tails skip the
         // ramp.  A probing round costs one wave's chain per time step until its waves fill the chip, so every candidate up
         // to that point is free: with the lane form (rollout_lanes: 64 / N candidates per wavefront) that is
-        // C floor(2400 / instances) candidates per instance — whole wavefronts —, as far as the pool holds them.
+        // C floor(kDeepTailWaves / instances) candidates per instance — whole wavefronts —, as far as the pool holds them.
         // (config 5's scene: rounds of 4, 10, 20, 21, 42 ... candidates -> 16 - 63 from a tail's first round on;
         // config 4's ~1600 back-tracking instances are mostly done after a step or two: they keep the ramp.)
-        constexpr int C_lane = rollout_lanes_per_wave(NP > 0 ? NP : 1);
-        if (sa.ids && tail_rounds == 0) tail_first_instances = round_instances;
-        if (sa.ids && tail_rounds == 3 && 2 * round_instances >= tail_first_instances) deep_tails = true;
-        if (sa.ids && deep_tails && opt.probe_first <= 0) {
-          int k_deep = probe_k;  // what the pool holds
+        if (rl.tail_rounds == 3 && 2 * rl.round_instances >= rl.tail_first_instances) deep_tails = true;
+        if (deep_tails && opt.probe_first <= 0) {
+          constexpr int C_lane = rollout_lanes_per_wave(NP > 0 ? NP : 1);
+          int k_deep = std::min(tail.pool_entries / rl.round_instances, kProbeCandidates);  // what the pool holds
           if (pairs && opt.probe_lanes != ILQG_CHOICE_OFF) {
-            const int free_waves = 2400 / round_instances;
+            const int free_waves = kDeepTailWaves / rl.round_instances;
             const int k_lane = C_lane * (free_waves > 1 ? free_waves : 1);
             if (k_deep > k_lane) k_deep = k_lane;
             if (k_deep >= C_lane) k_deep = k_deep / C_lane * C_lane;
           }
-          if (ramp < k_deep) ramp = k_deep;
+          if (probe_k < k_deep) probe_k = k_deep;
         }
-        if (probe_k > ramp) probe_k = int(ramp);
+        const ilqg_status s = rl.tail_round(probe, probe_k);
+        if (s != ILQG_OK) return s;
       }
-#ifdef ILQG_DEBUG_PROBE
-      if (sa.ids) fprintf(stderr, "tail %d instances %d probe_k %d deep %d\n", tail_rounds, round_instances, probe_k, int(deep_tails));
-#endif
-      if (sa.ids) tail_rounds++;
-      // see generic_solve: instances in ST_PROBE are only picked up again by a probing launch
-      if (probe && sa.ids && probed_in_tail && probe_k < 2) return fail(ILQG_ERR_HIP, "a probing line-search tail lost its probe launch");
+      const int round_instances = rl.round_instances;
       if (probe && probe_k >= 2) {
-        probed_in_tail = true;
         // the listed instances' next step sizes side by side; their states move to the first acceptable one
-        sa.probe_pool = probe_pool;
+        sa.probe_pool = tail.probe_pool;
         sa.probe_k = probe_k;
         const int proll_y = pairs ? (probe_k + 1) / 2 : probe_k;
         // the register-rich build while every rollout of the round is resident at once at two waves per SIMD
         const bool fat = (long long)round_instances * proll_y <= 8ll * num_cus;
         // A lane per (candidate, subsystem) where that is the shorter round.  A round of W waves takes about
-        // max(one wave's chain, W / SIMDs x a wave's issue time) per time step; measured on the n = 15 scene (cycles per
-        // step): the paired form ~1500 / ~550, the lane form — thirteen trigonometric evaluations in sequence,
-        // ~1180 instructions — ~3500 / ~1530, for 64 / N candidates instead of two.  So the lane form wins once its
-        // own waves fill the chip (config 5's scene from 16 candidates per instance on), and loses a round of a few
-        // deep searches (n = 16: ~100 instances x 128 candidates are 700 lane waves, one chain long).
+        // max(one wave's chain, W / SIMDs x a wave's issue time) per time step (the kProbe*Cycles model).  So the lane
+        // form wins once its own waves fill the chip (config 5's scene from 16 candidates per instance on), and loses a
+        // round of a few deep searches (n = 16: ~100 instances x 128 candidates are 700 lane waves, one chain long).
         constexpr int C = rollout_lanes_per_wave(NP > 0 ? NP : 1);
         const double simds = 4.0 * num_cus;
         const double w_pair = double(round_instances) * proll_y, w_lane = double(round_instances) * ((probe_k + C - 1) / C);
-        const double t_pair = std::max(1500.0, w_pair / simds * 550.0), t_lane = std::max(3500.0, w_lane / simds * 1530.0);
+        const double t_pair = std::max(kPairChainCycles, w_pair / simds * kPairIssueCycles),
+                     t_lane = std::max(kLaneChainCycles, w_lane / simds * kLaneIssueCycles);
         // (n > 16: the lane form's step carries a 2 n-term control product per lane and, for the six-state cars, spills
         // inside the time loop — n = 24 on the feedback sweep: 2.2 ms per launch against 0.4-0.6 for the paired form,
         // 99 k -> 83 k it/s; the model's constants are the n = 15 scene's, so AUTO leaves those shapes on pairs.)
@@ -1656,39 +1764,52 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
       HIP_TRY(hipGetLastError());
       hipLaunchKernelGGL(k_decide, dim3(round_instances), dim3(64), lds_decide, stream, d, sa);
     } else {
-      sa.ids_next = handoff ? pass_ids + size_t(list) * batch : nullptr;
+      sa.ids_next = handoff ? rl.free_list() : nullptr;
       hipLaunchKernelGGL(k_trial, dim3(batch), dim3(64 * W), lds_trial, stream, d, sa);
     }
     HIP_TRY(hipGetLastError());
     sa.first = 0;
-    int want_lq = 1, want_exit = 0, restarted = 0, again = 0;
+    return ILQG_OK;
+  };
+  for (long long round = 0;; round++) {
+    if (bursts && !sa.ids) {
+      // a fixed-iteration solve knows its last round: no burst runs past it
+      const long long left = (fixed_iters > 0 && !al_mode) ? (long long)fixed_iters - round : (long long)burst;
+      for (int q = 1; q < burst && q <= left; q++) {  // rounds without a read-back
+        ilqg_status s = pass();
+        if (s != ILQG_OK) return s;
+        if (iterate_log_launch(p, sa, lg, stream) != ILQG_OK) return ILQG_ERR_HIP;
+        // The exit path inside a burst only where it starts something (the augmented Lagrangian's next inner solve);
+        // an ILQSolver::Solve that ends here waits for the burst's last round, whose exit launch is then unconditional
+        // (a launch for nobody is ~5 us of every round of a lone instance).
+        if (al_mode) {
+          hipLaunchKernelGGL(k_exit, dim3(batch), dim3(nt_exit), lds_exit, stream, d, sa);
+          HIP_TRY(hipGetLastError());
+        } else {
+          exit_pending = true;
+        }
+        s = sweep();
+        if (s != ILQG_OK) return s;
+        round++;
+      }
+    }
+    ilqg_status s = pass();
+    if (s != ILQG_OK) return s;
+    int want_lq = 1, want_exit = 0;
     if (counted) {
       if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
       want_lq = p->h_unfinished[0];
       want_exit = p->h_unfinished[1];
-      again = p->h_unfinished[3];
       if (lists) {
-        // keep the batch in step: the sweep is launched once per iteration, when the last back-tracking instance
-        // has made up its mind (a sweep launch with a handful of instances costs a full sweep's latency)
-        waiting_lq += want_lq;
-        waiting_exit += want_exit;
-        if (again) {  // the next round covers the listed instances only
+        bool again = false;
+        s = rl.after_round(p->h_unfinished, round, &again, &want_lq, &want_exit);
+        if (s != ILQG_OK) return s;
+        if (again) {
           burst = 1;
-          if (round > cap) return fail(ILQG_ERR_HIP, "solve did not terminate within its iteration bound");
-          sa.ids = sa.ids_next;
-          round_instances = again;
-          list ^= 1;
           continue;
         }
-        sa.ids = nullptr;
-        round_instances = batch;
-        tail_rounds = 0;
-        probed_in_tail = false;
-        want_lq = waiting_lq;
-        want_exit = waiting_exit;
-        waiting_lq = waiting_exit = 0;
       }
-      if (bursts) burst = again ? 1 : (burst < 8 ? burst * 2 : 8);
+      if (bursts) burst = p->h_unfinished[3] ? 1 : (burst < 8 ? burst * 2 : 8);
     } else if (round == fixed_iters) {
       want_lq = 0;
       want_exit = 1;
@@ -1697,45 +1818,10 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
       want_exit = 1;
       exit_pending = false;
     }
-    if (timed && want_lq) {
-      // the loop condition of src/ilq_solver.cpp:123-124 for the iteration the batch is about to start
-      const double now = wall();
-      if (iteration_open) {
-        p->loop_add(now - tic);
-        inner_elapsed += now - tic;
-        iteration_open = false;
-      }
-      if (!(inner_elapsed < budget - p->loop_upper_bound())) {
-        hipLaunchKernelGGL(ilq_deadline_kernel<T>, dim3(batch), dim3(64), 0, stream, d, sa);
-        HIP_TRY(hipGetLastError());
-        want_exit = 1;
-        want_lq = 0;
-      }
-    }
-    if ((want_exit || want_lq) && log_iterates() != ILQG_OK) return ILQG_ERR_HIP;
-    if (want_exit) {
-      if (outer.before_exit()) sa.outer_closed = 1;  // out of time: inner solves that end now are the last ones
-      hipLaunchKernelGGL(k_exit, dim3(batch), dim3(nt_exit), lds_exit, stream, d, sa);
-      HIP_TRY(hipGetLastError());
-      p->counters_clean = false;
-      if (counted && al_mode) {
-        if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
-        restarted = p->h_unfinished[2];
-        if (restarted) inner_elapsed = 0.0;  // the next inner solve's own budget
-        outer.after_exit(restarted);
-      }
-    }
-    if (want_lq) {
-      if (timed) {
-        tic = wall();
-        iteration_open = true;
-      }
-      hipLaunchKernelGGL(k_lq, dim3(batch), dim3(nt_lq), lds_lq, stream, d, sa);
-      HIP_TRY(hipGetLastError());
-      p->counters_clean = true;  // (SolveArgs::clear_counters)
-    }
-    if (!want_lq && !restarted) break;
-    if (round > cap) return fail(ILQG_ERR_HIP, "solve did not terminate within its iteration bound");
+    bool done = false;
+    s = end_iteration(p, sa, stream, lg, clock, outer, ex, round, cap, want_lq, want_exit, sweep, &done);
+    if (s != ILQG_OK) return s;
+    if (done) break;
   }
   return ILQG_OK;
 }
@@ -1800,12 +1886,8 @@ static bool padded_pairs(const PairTable& pt, int N, int mu, PairTable* ptp, std
 }
 
 // Threads of a workgroup of the run-time-dimensioned sweeps (ilqg_lq_generic.hpp: every phase strides its entries over
-// the workgroup and ends with a barrier).  -DILQG_GEN_THREADS_SMALL=n: the size for games whose phases have at most 160
-// entries (A/B measurements).
-#ifndef ILQG_GEN_THREADS_SMALL
-#define ILQG_GEN_THREADS_SMALL 256
-#endif
-static inline int generic_sweep_threads(int n, int m) { return n * (n + m) <= 160 ? ILQG_GEN_THREADS_SMALL : 256; }
+// the workgroup and ends with a barrier; lq_generic_kernel's launch bound).
+static constexpr int kGenSweepThreads = 256;
 
 // LDS a CU can give one workgroup (gfx950: 160 KB)
 static constexpr size_t kLdsPerWorkgroup = size_t(160) * 1024;
@@ -1820,20 +1902,8 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
                                  void* total_costs, int32_t* iters, int32_t* status, int32_t* converged, void* workspace,
                                  const ilqg_solve_options& opt, hipStream_t stream) {
   const DevProblem& d = p->dev;
-  const int al_mode = opt.augmented_lagrangian ? 1 : 0, resume = opt.resume ? 1 : 0;
-  const int ol_row = p->desc.params.open_loop ? ol_row_elems(d.n, d.m, d.N) : 0;
-  const WsLayout L(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, ol_row, d.num_constraints, al_mode);
-  SolveArgs<T> sa{};
-  sa.ol_row = ol_row;
-  sa.al_mode = al_mode;
-  sa.x0 = (const T*)x0; sa.xs = (T*)xs; sa.us = (T*)us; sa.P = (T*)P; sa.alpha = (T*)alpha;
-  sa.total_costs = (T*)total_costs; sa.iters = iters; sa.status = status; sa.converged = converged;
-  sa.ws = (T*)workspace; sa.ws_stride = L.total; sa.fixed_iters = opt.fixed_iters; sa.batch = batch;
-  sa.prm = p->desc.params;
-  sa.active = opt.active;
-  sa.prof = nullptr;
-  sa.forced_steps = (const T*)opt.forced_steps;
-  sa.unfinished = p->d_unfinished;
+  SolveTail<T> tail;
+  SolveArgs<T> sa = solve_args_of<T>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, opt, &tail);
   p->last_schedule = ILQG_SCHEDULE_GENERIC | ILQG_SCHEDULE_SPLIT_TRIAL | ILQG_SCHEDULE_COUNTED |
                      (p->desc.params.open_loop ? ILQG_SCHEDULE_OPEN_LOOP : 0);
   sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), size_t(48) * 1024);
@@ -1855,9 +1925,6 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
   auto k_proll = ilq_probe_roll_kernel<T, 0, 0, 0>;
   auto k_prows = ilq_probe_rows_kernel<T, 0, 0, 0>;
   const size_t lds_prows = rows_maps_bytes(d) + probe_rows_elems(d, 0, sa.rows_cw) * sizeof(T);
-  const WsTail tail = ws_tail(d, batch, sizeof(T), ol_row);
-  int* const pass_ids = reinterpret_cast<int*>(static_cast<char*>(workspace) + tail.ids_off);
-  T* const probe_pool = reinterpret_cast<T*>(static_cast<char*>(workspace) + tail.pool_off);
   const bool probe = !opt.forced_steps && sa.prm.linesearch && opt.probe != ILQG_CHOICE_OFF;
   raise_lds_limit((const void*)k_proll, lds_roll);
   raise_lds_limit((const void*)k_prows, lds_prows);
@@ -1898,56 +1965,38 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
     }
   }
   const int row_chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;
-  long long cap = al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
-                          : (long long)(opt.fixed_iters > 0 ? opt.fixed_iters : sa.prm.max_solver_iters) + 2;
+  long long cap = sa.al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
+                             : (long long)(opt.fixed_iters > 0 ? opt.fixed_iters : sa.prm.max_solver_iters) + 2;
   cap = (cap + 2) * ((long long)sa.prm.max_backtracking_steps + 3);
   const bool timed = opt.max_runtime > 0.0;
-  const double budget = !timed ? 0.0 : ((al_mode && d.num_constraints > 0) ? opt.max_runtime / double(sa.prm.max_solver_iters) : opt.max_runtime);
-  auto wall = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double inner_elapsed = 0.0, tic = 0.0;
-  bool iteration_open = false;
-  AlOuterClock outer(p, timed && al_mode && d.num_constraints > 0, opt.max_runtime, budget);
-  IterLog<T> lg{};
-  const bool logging = opt.iterate_log != nullptr;
-  if (logging) {
-    const ilqg_iterate_log& il = *opt.iterate_log;
-    if (!il.xs || !il.us || !il.costs || !il.count || il.capacity < 1)
-      return fail(ILQG_ERR_INVALID, "iterate log: xs, us, costs, count and a capacity of at least one are required");
-    lg = IterLog<T>{(T*)il.xs, (T*)il.us, (T*)il.costs, (T*)il.P, (T*)il.alpha, il.count, il.capacity};
-    HIP_TRY(hipMemsetAsync(il.count, 0, sizeof(int) * size_t(batch), stream));
+  const bool al_constrained = sa.al_mode && d.num_constraints > 0;
+  InnerClock clock(p, timed, opt.max_runtime, al_constrained);
+  AlOuterClock outer(p, timed && al_constrained, opt.max_runtime, clock.budget);
+  IterLog<T> lg;
+  {
+    const ilqg_status s = iterate_log_open(opt, batch, stream, &lg);
+    if (s != ILQG_OK) return s;
   }
-  sa.first = resume ? 2 : 1;
   p->counters_clean = false;  // whatever an earlier solve left in the round counters
-  sa.ids = nullptr;
-  sa.ids_next = nullptr;
-  int waiting_lq = 0, waiting_exit = 0;
-  int round_instances = batch, list = 0, tail_rounds = 0;
-  bool probed_in_tail = false;
+  RoundLists<T> rl(sa, tail.pass_ids, cap);
+  const ExitLaunch<T> ex{k_exit, 64, lds_exit, true, sa.al_mode != 0};
+  auto sweep = [&]() -> ilqg_status {
+    if (pad_nx) return padded_launch(nullptr);
+    hipLaunchKernelGGL(k_lq, dim3(batch), dim3(kGenSweepThreads), lds_lq, stream, d, sa);
+    HIP_TRY(hipGetLastError());
+    return ILQG_OK;
+  };
   for (long long round = 0;; round++) {
     if (!p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
     p->counters_clean = false;
-    sa.ids_next = pass_ids + size_t(list) * batch;
-    if (sa.ids && probe) {
-      // step sizes probed per listed instance this round: what the pool holds for a list this long, ramping up over the
-      // rounds of a tail from a budget of kProbeRoundBudget rollouts (the rule of DimsLaunch::solve)
-      int probe_k = tail.pool_entries / round_instances;
-      if (probe_k > kProbeCandidates) probe_k = kProbeCandidates;
-      int first = opt.probe_first;
-      if (first <= 0) {
-        first = kProbeRoundBudget / round_instances;
-        first = first < 2 ? 2 : (first > kProbeCandidates ? kProbeCandidates : first);
-      }
-      long long ramp = (long long)first << (tail_rounds < 8 ? tail_rounds : 8);
-      if (ramp < 2) ramp = 2;
-      if (probe_k > ramp) probe_k = int(ramp);
-      tail_rounds++;
-      // an instance every candidate of which was rejected waits in ST_PROBE and is skipped by the regular pass: it is
-      // only picked up again by the next probing launch, so a tail that has probed must keep probing (the list only
-      // shrinks and the ramp only grows, so this cannot trigger; if it ever does, fail instead of dropping instances)
-      if (probed_in_tail && probe_k < 2) return fail(ILQG_ERR_HIP, "a probing line-search tail lost its probe launch");
-      if (probe_k >= 2) {
-        probed_in_tail = true;
-        sa.probe_pool = probe_pool;
+    sa.ids_next = rl.free_list();
+    const int round_instances = rl.round_instances;
+    if (sa.ids) {
+      const int probe_k = probe_candidates(tail.pool_entries, round_instances, opt.probe_first, rl.tail_rounds);
+      const ilqg_status s = rl.tail_round(probe, probe_k);
+      if (s != ILQG_OK) return s;
+      if (probe && probe_k >= 2) {
+        sa.probe_pool = tail.probe_pool;
         sa.probe_k = probe_k;
         hipLaunchKernelGGL(k_proll, dim3(round_instances, probe_k), dim3(64), lds_roll, stream, d, sa);
         HIP_TRY(hipGetLastError());
@@ -1966,80 +2015,16 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
     hipLaunchKernelGGL(k_decide, dim3(round_instances), dim3(64), lds_decide, stream, d, sa);
     HIP_TRY(hipGetLastError());
     if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
-    waiting_lq += p->h_unfinished[0];
-    waiting_exit += p->h_unfinished[1];
-    if (round > cap) return fail(ILQG_ERR_HIP, "solve did not terminate within its iteration bound");
-    if (p->h_unfinished[3]) {  // some instances want another pass (initial quadraticisation, back-tracking): they are listed
-      sa.ids = sa.ids_next;
-      round_instances = p->h_unfinished[3];
-      list ^= 1;
-      continue;
-    }
-    sa.ids = nullptr;
-    round_instances = batch;
-    tail_rounds = 0;
-    probed_in_tail = false;
-    int want_lq = waiting_lq, want_exit = waiting_exit, restarted = 0;
-    waiting_lq = waiting_exit = 0;
-    if (timed && want_lq) {  // the loop condition of src/ilq_solver.cpp:123-124 (see DimsLaunch::solve)
-      const double now = wall();
-      if (iteration_open) {
-        p->loop_add(now - tic);
-        inner_elapsed += now - tic;
-        iteration_open = false;
-      }
-      if (!(inner_elapsed < budget - p->loop_upper_bound())) {
-        hipLaunchKernelGGL(ilq_deadline_kernel<T>, dim3(batch), dim3(64), 0, stream, d, sa);
-        HIP_TRY(hipGetLastError());
-        want_exit = 1;
-        want_lq = 0;
-      }
-    }
-    if (logging && (want_exit || want_lq)) {
-      hipLaunchKernelGGL(ilq_log_kernel<T>, dim3(batch), dim3(256), 0, stream, d, sa, lg);
-      HIP_TRY(hipGetLastError());
-    }
-    if (want_exit) {
-      if (!p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
-      if (outer.before_exit()) sa.outer_closed = 1;
-      hipLaunchKernelGGL(k_exit, dim3(batch), dim3(64), lds_exit, stream, d, sa);
-      HIP_TRY(hipGetLastError());
-      p->counters_clean = false;
-      if (al_mode) {
-        if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
-        restarted = p->h_unfinished[2];
-        if (restarted) inner_elapsed = 0.0;
-        outer.after_exit(restarted);
-      }
-    }
-    if (want_lq) {
-      if (timed) {
-        tic = wall();
-        iteration_open = true;
-      }
-      if (pad_nx) {
-        const ilqg_status s = padded_launch(nullptr);
-        if (s != ILQG_OK) return s;
-      } else {
-        hipLaunchKernelGGL(k_lq, dim3(batch), dim3(generic_sweep_threads(d.n, d.m)), lds_lq, stream, d, sa);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    if (!want_lq && !restarted) break;
+    bool again = false, done = false;
+    int want_lq = 0, want_exit = 0;
+    ilqg_status s = rl.after_round(p->h_unfinished, round, &again, &want_lq, &want_exit);
+    if (s != ILQG_OK) return s;
+    if (again) continue;
+    s = end_iteration(p, sa, stream, lg, clock, outer, ex, round, cap, want_lq, want_exit, sweep, &done);
+    if (s != ILQG_OK) return s;
+    if (done) break;
   }
   return ILQG_OK;
-}
-
-static GenDims gen_dims_of(int n, int N, const int32_t* udim, int T) {
-  GenDims g{};
-  g.n = n; g.N = N; g.T = T;
-  g.uoff[0] = 0;
-  for (int i = 0; i < N; i++) {
-    g.udim[i] = udim[i];
-    g.uoff[i + 1] = g.uoff[i] + udim[i];
-  }
-  g.m = g.uoff[N];
-  return g;
 }
 
 // ilqg_lq_feedback_batch / ilqg_lq_openloop_batch of a shape without an instantiation on the padded sweep of (nx, N, mu)
@@ -2068,27 +2053,42 @@ static ilqg_status launch_lq_generic(const ilqg_dims* d, const PairTable& pt, bo
   if (gd.m > ILQG_MAX_UDIM_TOTAL) return fail(ILQG_ERR_UNSUPPORTED, "more than ILQG_MAX_UDIM_TOTAL controls in total");
   const size_t lds = (open_loop ? gen_openloop_lds_elems(gd.n, gd.N, gd.m) : gen_feedback_lds_elems(gd.n, gd.N, gd.m)) * sizeof(T);
   if (lds > kLdsPerWorkgroup) return fail(ILQG_ERR_UNSUPPORTED, "the game's value functions do not fit a CU's LDS");
-  LQBatchArgs<T> g;
-  g.A = (const T*)A; g.Bm = (const T*)Bm; g.Q = (const T*)Q; g.l = (const T*)l;
-  g.R = (const T*)R; g.r = (const T*)r; g.x0 = (const T*)x0;
-  g.P = (T*)P; g.alpha = (T*)alpha; g.dx = (T*)dx;
-  g.costates = open_loop ? (T*)costates : nullptr;
-  g.scratch = nullptr;
+  LQBatchArgs<T> g(d, A, Bm, Q, l, R, r, x0, P, alpha, dx);
   const int row = open_loop ? gen_ol_row_elems(gd.n, gd.m, gd.N, costates != nullptr) : 0;
   if (open_loop) {
     const ilqg_status s = Scratch().reserve(size_t(d->batch) * d->T * size_t(row) * sizeof(T));
     if (s != ILQG_OK) return s;
     g.scratch = (T*)ilqg_shared::scratch_state().ptr;
+    g.costates = (T*)costates;
+    g.adaptive = 0;
   }
-  g.T_steps = d->T;
-  g.adaptive = open_loop ? 0 : d->adaptive_regularization;
-  g.batch = d->batch;
-  g.force_valu = 0;
   auto kern = lq_generic_kernel<T>;
   raise_lds_limit((const void*)kern, lds);
-  hipLaunchKernelGGL(kern, dim3(d->batch), dim3(generic_sweep_threads(gd.n, gd.m)), lds, stream, g, gd, pt, open_loop ? 1 : 0, row);
+  hipLaunchKernelGGL(kern, dim3(d->batch), dim3(kGenSweepThreads), lds, stream, g, gd, pt, open_loop ? 1 : 0, row);
   HIP_TRY(hipGetLastError());
   return ILQG_OK;
+}
+
+// The argument checks of ilqg_lq_feedback_batch / ilqg_lq_openloop_batch and their control blocks; `uniform`: one m_i
+// (`mu`) for all players, what the specialised sweeps take.  They differ in the shortest horizon and in the reference
+// line that ties costates to delta_xs.
+static ilqg_status lq_batch_setup(const ilqg_dims* d, const void* A, const void* Bm, const void* Q, const void* l,
+                                  const void* R, const void* r, const ilqg_pair* pairs_host, int32_t npairs,
+                                  const void* P, const void* alpha, const void* dx, const void* costates, int min_T,
+                                  const char* costates_ref, PairTable* pt, bool* uniform, int* mu) {
+  if (!d || !A || !Bm || !Q || !l || !R || !r || !pairs_host || !P || !alpha)
+    return fail(ILQG_ERR_INVALID, "null argument");
+  if (d->num_players < 1 || d->n < 1 || d->T < min_T || d->T > kMaxT || d->batch < 0)
+    return fail(ILQG_ERR_INVALID, "bad dimensions");
+  if (d->num_players > ILQG_MAX_PLAYERS || d->n > ILQG_MAX_XDIM)
+    return fail(ILQG_ERR_UNSUPPORTED, "more than ILQG_MAX_XDIM states or ILQG_MAX_PLAYERS players");
+  if (costates && !dx) return fail(ILQG_ERR_INVALID, std::string("costates come with delta_xs (") + costates_ref + ")");
+  for (const void* ptr : {A, Bm, Q, l, R, r})
+    if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0) return fail(ILQG_ERR_INVALID, "array bases must be 16-byte aligned");
+  std::string err;
+  if (!build_pairs(pairs_host, npairs, d->udim, d->num_players, pt, &err)) return fail(ILQG_ERR_INVALID, err);
+  *uniform = uniform_udim(d->udim, d->num_players, mu);
+  return check_device();
 }
 
 // RouteProgressCost subtracts RelativeTimeTracker::initial_time_ from the time it is handed (src/route_progress_cost.cpp:
@@ -2197,21 +2197,11 @@ void ilqg_default_solver_params(ilqg_solver_params* p) {  // solver_params.h:50-
 ilqg_status ilqg_lq_feedback_batch(const ilqg_dims* d, const void* A, const void* Bm, const void* Q, const void* l,
                                    const void* R, const void* r, const ilqg_pair* pairs_host, int32_t npairs,
                                    const void* x0, void* P, void* alpha, void* dx, void* costates, void* stream) {
-  if (!d || !A || !Bm || !Q || !l || !R || !r || !pairs_host || !P || !alpha)
-    return fail(ILQG_ERR_INVALID, "null argument");
-  if (d->num_players < 1 || d->n < 1 || d->T < 1 || d->T > kMaxT || d->batch < 0)
-    return fail(ILQG_ERR_INVALID, "bad dimensions");
-  if (d->num_players > ILQG_MAX_PLAYERS || d->n > ILQG_MAX_XDIM)
-    return fail(ILQG_ERR_UNSUPPORTED, "more than ILQG_MAX_XDIM states or ILQG_MAX_PLAYERS players");
-  if (costates && !dx) return fail(ILQG_ERR_INVALID, "costates come with delta_xs (lq_feedback_solver.cpp:77-78)");
-  for (const void* ptr : {A, Bm, Q, l, R, r})
-    if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0) return fail(ILQG_ERR_INVALID, "array bases must be 16-byte aligned");
   PairTable pt;
-  std::string err;
-  if (!build_pairs(pairs_host, npairs, d->udim, d->num_players, &pt, &err)) return fail(ILQG_ERR_INVALID, err);
+  bool uniform = false;
   int mu = 0;
-  const bool uniform = uniform_udim(d->udim, d->num_players, &mu);  // the specialised sweeps: one m_i for all players
-  ilqg_status s = check_device();
+  ilqg_status s = lq_batch_setup(d, A, Bm, Q, l, R, r, pairs_host, npairs, P, alpha, dx, costates, 1,
+                                 "lq_feedback_solver.cpp:77-78", &pt, &uniform, &mu);
   if (s != ILQG_OK) return s;
   if (d->batch == 0) return ILQG_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -2273,21 +2263,11 @@ ilqg_status ilqg_lq_feedback_batch(const ilqg_dims* d, const void* A, const void
 ilqg_status ilqg_lq_openloop_batch(const ilqg_dims* d, const void* A, const void* Bm, const void* Q, const void* l,
                                    const void* R, const void* r, const ilqg_pair* pairs_host, int32_t npairs,
                                    const void* x0, void* P, void* alpha, void* dx, void* costates, void* stream) {
-  if (!d || !A || !Bm || !Q || !l || !R || !r || !pairs_host || !P || !alpha)
-    return fail(ILQG_ERR_INVALID, "null argument");
-  if (d->num_players < 1 || d->n < 1 || d->T < 2 || d->T > kMaxT || d->batch < 0)
-    return fail(ILQG_ERR_INVALID, "bad dimensions");
-  if (d->num_players > ILQG_MAX_PLAYERS || d->n > ILQG_MAX_XDIM)
-    return fail(ILQG_ERR_UNSUPPORTED, "more than ILQG_MAX_XDIM states or ILQG_MAX_PLAYERS players");
-  if (costates && !dx) return fail(ILQG_ERR_INVALID, "costates come with delta_xs (lq_open_loop_solver.cpp:83-84)");
-  for (const void* ptr : {A, Bm, Q, l, R, r})
-    if (reinterpret_cast<uintptr_t>(ptr) % 16 != 0) return fail(ILQG_ERR_INVALID, "array bases must be 16-byte aligned");
   PairTable pt;
-  std::string err;
-  if (!build_pairs(pairs_host, npairs, d->udim, d->num_players, &pt, &err)) return fail(ILQG_ERR_INVALID, err);
+  bool uniform = false;
   int mu = 0;
-  const bool uniform = uniform_udim(d->udim, d->num_players, &mu);
-  ilqg_status s = check_device();
+  const ilqg_status s = lq_batch_setup(d, A, Bm, Q, l, R, r, pairs_host, npairs, P, alpha, dx, costates, 2,
+                                       "lq_open_loop_solver.cpp:83-84", &pt, &uniform, &mu);
   if (s != ILQG_OK) return s;
   if (d->batch == 0) return ILQG_OK;
   hipStream_t st = (hipStream_t)stream;
