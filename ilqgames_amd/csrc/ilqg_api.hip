@@ -1194,8 +1194,8 @@ struct AlOuterClock {
 
 // ---------------------------------------------------------------------------------------------------------------
 // The round protocol both solve drivers share (DimsLaunch::solve on the specialised kernels, generic_solve on the
-// run-time-dimensioned ones).  Each driver keeps its own loop and its own pass launches; what differs between the two
-// is a parameter here, never a question of who is calling.
+// run-time-dimensioned ones).  Each driver fills a RoundPlan and run_rounds launches it; what differs between the two
+// is a value of the plan, never a question of who is calling.
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -1380,52 +1380,234 @@ struct RoundLists {
   }
 };
 
-// A driver's exit launch (ilq_exit_kernel).
+// One kernel of a round as a driver chose it; the grid is the round's.
 template <typename T>
-struct ExitLaunch {
-  void (*kernel)(DevProblem, SolveArgs<T>);
-  int threads;
-  size_t lds;
-  bool fill_first;     // clear the round counters in front of it where they are not clean
-  bool read_restarts;  // read the augmented Lagrangian's restarts back behind it
+struct KernelLaunch {
+  void (*kernel)(DevProblem, SolveArgs<T>) = nullptr;  // null: the solve has no such launch
+  int threads = 64;
+  size_t lds = 0;
 };
 
-// The end of an iteration of the batch, once its rounds have left want_lq instances waiting for a sweep and want_exit
-// for the exit path: the anytime exit's deadline (which turns the sweep into an exit), the iterate log, the exit launch
-// and the restarts it made, the sweep (`sweep`: the driver's launch).  *done: the solve has ended.
-template <typename T, typename Sweep>
-ilqg_status end_iteration(ilqg_problem* p, SolveArgs<T>& sa, hipStream_t stream, const IterLog<T>& lg,
-                          InnerClock& clock, AlOuterClock& outer, const ExitLaunch<T>& ex, long long round,
-                          long long cap, int want_lq, int want_exit, const Sweep& sweep, bool* done) {
+// The sweep of a run-time-dimensioned solve on the padded kernels of an instantiated shape (DimsLaunch::lq_padded).
+using PaddedSweep = ilqg_status (*)(const DevProblem&, const void*, const PairTable&, void*, size_t*, bool, hipStream_t);
+
+// What a solve launches and how its rounds go, as its driver chose them: run_rounds reads nothing else about the
+// schedule.  The split-pass launches (roll to prows) exist where `lists` holds.
+template <typename T>
+struct RoundPlan {
+  KernelLaunch<T> trial;                // the fused pass
+  KernelLaunch<T> roll, rows, decide;   // the split pass
+  KernelLaunch<T> proll, proll_fat, proll_single, proll_lanes, prows;  // probing rollouts (null: no such form), their rows
+  KernelLaunch<T> sweep, exit;          // (the sweep: unless `padded` runs it)
+  PaddedSweep padded = nullptr;
+  const PairTable* pad_pairs = nullptr; void* pad = nullptr;  // the padded sweep's control blocks and scratch
+  long long cap = 0;                    // the iteration bound in rounds
+  int row_chunks = 1;                   // workgroups per instance of the row kernels
+  int lane_width = 1;                   // candidates per wavefront of the lane form
+  int num_cus = 256;
+  bool split = false, counted = false, handoff = false, lists = false, bursts = false, probe = false, timed = false;
+  bool pairs = false;       // two rollouts per wavefront (roll, proll, proll_fat)
+  bool lanes_auto = false, deep_tails = false;  // AUTO may take the lane form; the deep-tail rule holds
+  bool exit_fill_first = false;  // clear the round counters in front of the exit launch where they are not clean
+  bool read_restarts = false;    // read the augmented Lagrangian's restarts back behind it
+};
+
+// LDS limits of every launch of a plan (raise_lds_limit; the padded sweep raises its own)
+template <typename T>
+void raise_lds_limits(const RoundPlan<T>& pl) {
+  for (const KernelLaunch<T>* k : {&pl.trial, &pl.roll, &pl.rows, &pl.decide, &pl.proll, &pl.proll_fat, &pl.proll_single,
+                                   &pl.proll_lanes, &pl.prows, &pl.sweep, &pl.exit})
+    if (k->kernel) raise_lds_limit((const void*)k->kernel, k->lds);
+}
+
+// The rounds of a solve, on either driver's plan.  One round = a pass (the fused trial kernel, or the split kernels over
+// the whole batch or over the listed back-tracking instances with their probing launches), then, for the instances
+// that asked, the exit kernel and the sweep.  The kernels count what their instances wait for; with fixed_iters = K
+// (no AL) and no counting the sequence is known — trial, K x (sweep, trial), exit — otherwise the host reads the counts
+// back each round, which makes a free-running solve synchronous with respect to `stream`.
+template <typename T>
+ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& tail, const RoundPlan<T>& plan,
+                       const ilqg_solve_options& opt, hipStream_t stream) {
   const DevProblem& d = p->dev;
-  if (clock.on && want_lq && clock.deadline_passed()) {
-    hipLaunchKernelGGL(ilq_deadline_kernel<T>, dim3(sa.batch), dim3(64), 0, stream, d, sa);
+  const int batch = sa.batch;
+  raise_lds_limits(plan);
+  IterLog<T> lg;
+  ilqg_status s = iterate_log_open(opt, batch, stream, &lg);
+  if (s != ILQG_OK) return s;
+  const bool al_constrained = sa.al_mode && d.num_constraints > 0;
+  InnerClock clock(p, plan.timed, opt.max_runtime, al_constrained);
+  AlOuterClock outer(p, plan.timed && al_constrained, opt.max_runtime, clock.budget);
+  p->counters_clean = false;  // whatever an earlier solve left in the round counters
+  RoundLists<T> rl(sa, tail.pass_ids, plan.cap);
+  auto launch = [&](const KernelLaunch<T>& k, dim3 grid) -> ilqg_status {
+    hipLaunchKernelGGL(k.kernel, grid, dim3(k.threads), k.lds, stream, d, sa);
     HIP_TRY(hipGetLastError());
-    want_exit = 1;
-    want_lq = 0;
-  }
-  if ((want_exit || want_lq) && iterate_log_launch(p, sa, lg, stream) != ILQG_OK) return ILQG_ERR_HIP;
-  int restarted = 0;
-  if (want_exit) {
-    if (ex.fill_first && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
-    if (outer.before_exit()) sa.outer_closed = 1;  // out of time: inner solves that end now are the last ones
-    hipLaunchKernelGGL(ex.kernel, dim3(sa.batch), dim3(ex.threads), ex.lds, stream, d, sa);
-    HIP_TRY(hipGetLastError());
-    p->counters_clean = false;
-    if (ex.read_restarts) {
-      if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
-      restarted = p->h_unfinished[2];
-      if (restarted) clock.restart();
-      outer.after_exit(restarted);
+    return ILQG_OK;
+  };
+  auto sweep = [&]() -> ilqg_status {
+    const ilqg_status s = plan.padded ? plan.padded(d, &sa, *plan.pad_pairs, plan.pad, nullptr, p->desc.params.open_loop != 0, stream)
+                                      : launch(plan.sweep, dim3(batch));
+    if (s == ILQG_OK && sa.clear_counters) p->counters_clean = true;  // (SolveArgs::clear_counters)
+    return s;
+  };
+  const int probe_lanes_min = opt.probe_lanes == ILQG_CHOICE_OFF ? (1 << 30) : (opt.probe_lanes == ILQG_CHOICE_ON ? 2 : 8);
+  const int C = plan.lane_width;
+  bool deep_tails = false;  // a tail of this solve kept half of its list through three rounds (see the ramp below)
+  // the listed instances' next step sizes side by side; their states move to the first acceptable one
+  auto probe_round = [&](int instances, int probe_k) -> ilqg_status {
+    sa.probe_pool = tail.probe_pool;
+    sa.probe_k = probe_k;
+    const int proll_y = plan.pairs ? (probe_k + 1) / 2 : probe_k;
+    // the register-rich build while every rollout of the round is resident at once at two waves per SIMD
+    const bool fat = (long long)instances * proll_y <= 8ll * plan.num_cus;
+    // A lane per (candidate, subsystem) where that is the shorter round.  A round of W waves takes about
+    // max(one wave's chain, W / SIMDs x a wave's issue time) per time step (the kProbe*Cycles model).  So the lane
+    // form wins once its own waves fill the chip (config 5's scene from 16 candidates per instance on), and loses a
+    // round of a few deep searches (n = 16: ~100 instances x 128 candidates are 700 lane waves, one chain long).
+    // (n > 16: the lane form's step carries a 2 n-term control product per lane and, for the six-state cars, spills
+    // inside the time loop — n = 24 on the feedback sweep: 2.2 ms per launch against 0.4-0.6 for the paired form,
+    // 99 k -> 83 k it/s; the model's constants are the n = 15 scene's, so AUTO leaves those shapes on pairs.)
+    const double simds = 4.0 * plan.num_cus;
+    const double w_pair = double(instances) * proll_y, w_lane = double(instances) * ((probe_k + C - 1) / C);
+    const double t_pair = std::max(kPairChainCycles, w_pair / simds * kPairIssueCycles),
+                 t_lane = std::max(kLaneChainCycles, w_lane / simds * kLaneIssueCycles);
+    const bool lanes = plan.proll_lanes.kernel && probe_k >= probe_lanes_min &&
+                       (opt.probe_lanes == ILQG_CHOICE_ON || (plan.lanes_auto && t_lane < 0.9 * t_pair));
+    // a candidate per wavefront while every one of them finds a SIMD of its own
+    const bool single = plan.proll_single.kernel && !lanes && (long long)instances * probe_k <= 4ll * plan.num_cus &&
+                        opt.probe_lanes != ILQG_CHOICE_ON;
+    const ilqg_status s = lanes    ? launch(plan.proll_lanes, dim3(instances, (probe_k + C - 1) / C))
+                          : single ? launch(plan.proll_single, dim3(instances, probe_k))
+                                   : launch(fat ? plan.proll_fat : plan.proll, dim3(instances, proll_y));
+    if (s != ILQG_OK || launch(plan.prows, dim3(plan.row_chunks, instances * probe_k)) != ILQG_OK) return ILQG_ERR_HIP;
+    return launch(KernelLaunch<T>{ilq_probe_pick_kernel<T>, kProbeCandidates, 0}, dim3(instances));
+  };
+  auto pass = [&]() -> ilqg_status {
+    if (plan.counted && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
+    p->counters_clean = false;  // (the round's kernels count into them)
+    if (!plan.split && !sa.ids) {
+      sa.ids_next = plan.handoff ? rl.free_list() : nullptr;
+      const ilqg_status s = launch(plan.trial, dim3(batch));
+      sa.first = 0;
+      return s;
     }
-  }
-  if (want_lq) {
-    clock.open_iteration();
-    const ilqg_status s = sweep();
+    sa.ids_next = rl.free_list();
+    const int instances = rl.round_instances;
+    if (sa.ids) {
+      int probe_k = probe_candidates(tail.pool_entries, instances, opt.probe_first, rl.tail_rounds);
+      // Deep searches: once a tail of this solve has kept half of its list through three rounds (2 + 4 + 8 or more
+      // rejected candidates each: they are mostly on their way through all max_backtracking_steps), later tails skip the
+      // ramp.  A probing round costs one wave's chain per time step until its waves fill the chip, so every candidate up
+      // to that point is free: with the lane form (rollout_lanes: 64 / N candidates per wavefront) that is
+      // C floor(kDeepTailWaves / instances) candidates per instance — whole wavefronts —, as far as the pool holds them.
+      // (config 5's scene: rounds of 4, 10, 20, 21, 42 ... candidates -> 16 - 63 from a tail's first round on;
+      // config 4's ~1600 back-tracking instances are mostly done after a step or two: they keep the ramp.)
+      if (plan.deep_tails && rl.tail_rounds == 3 && 2 * instances >= rl.tail_first_instances) deep_tails = true;
+      if (deep_tails && opt.probe_first <= 0) {
+        int k_deep = std::min(tail.pool_entries / instances, kProbeCandidates);  // what the pool holds
+        if (plan.pairs && opt.probe_lanes != ILQG_CHOICE_OFF) {
+          const int free_waves = kDeepTailWaves / instances;
+          const int k_lane = C * (free_waves > 1 ? free_waves : 1);
+          if (k_deep > k_lane) k_deep = k_lane;
+          if (k_deep >= C) k_deep = k_deep / C * C;
+        }
+        if (probe_k < k_deep) probe_k = k_deep;
+      }
+      ilqg_status s = rl.tail_round(plan.probe, probe_k);
+      if (s == ILQG_OK && plan.probe && probe_k >= 2) s = probe_round(instances, probe_k);
+      if (s != ILQG_OK) return s;
+    }
+    sa.round_count = instances;
+    if (launch(plan.roll, dim3(plan.pairs ? (instances + 1) / 2 : instances)) != ILQG_OK) return ILQG_ERR_HIP;
+    sa.first = 0;
+    if (launch(plan.rows, dim3(plan.row_chunks, instances)) != ILQG_OK) return ILQG_ERR_HIP;
+    return launch(plan.decide, dim3(instances));
+  };
+  // Free-running solves: the kernels select their instances by the stage each one is in, so a round launched for
+  // nobody is harmless — the host therefore enqueues BURSTS of whole rounds (trial, exit, sweep) and reads the
+  // counters back once per burst instead of once per round (a read-back is a stream synchronisation: ~20-30 us against
+  // a ~0.45 ms round of a single instance).  The burst doubles up to eight rounds while no instance is back-tracking
+  // and falls back to one as soon as one is (those go through the probing passes, which need the lists every round).
+  const bool fixed = opt.fixed_iters > 0 && !sa.al_mode;
+  int burst = 1;
+  bool exit_pending = false;  // a burst round went without its exit launch (see the burst loop)
+  for (long long round = 0;; round++) {
+    if (plan.bursts && !sa.ids) {
+      // a fixed-iteration solve knows its last round: no burst runs past it
+      const long long left = fixed ? (long long)opt.fixed_iters - round : (long long)burst;
+      for (int q = 1; q < burst && q <= left; q++) {  // rounds without a read-back
+        s = pass();
+        if (s != ILQG_OK) return s;
+        if (iterate_log_launch(p, sa, lg, stream) != ILQG_OK) return ILQG_ERR_HIP;
+        // The exit path inside a burst only where it starts something (the augmented Lagrangian's next inner solve);
+        // an ILQSolver::Solve that ends here waits for the burst's last round, whose exit launch is then unconditional
+        // (a launch for nobody is ~5 us of every round of a lone instance).
+        if (sa.al_mode) {
+          if (launch(plan.exit, dim3(batch)) != ILQG_OK) return ILQG_ERR_HIP;
+        } else {
+          exit_pending = true;
+        }
+        s = sweep();
+        if (s != ILQG_OK) return s;
+        round++;
+      }
+    }
+    s = pass();
     if (s != ILQG_OK) return s;
+    int want_lq = 1, want_exit = 0;
+    if (plan.counted) {
+      if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
+      want_lq = p->h_unfinished[0];
+      want_exit = p->h_unfinished[1];
+      if (plan.lists) {
+        bool again = false;
+        s = rl.after_round(p->h_unfinished, round, &again, &want_lq, &want_exit);
+        if (s != ILQG_OK) return s;
+        if (again) {
+          burst = 1;
+          continue;
+        }
+      }
+      if (plan.bursts) burst = p->h_unfinished[3] ? 1 : (burst < 8 ? burst * 2 : 8);
+    } else if (round == opt.fixed_iters) {
+      want_lq = 0;
+      want_exit = 1;
+    }
+    if (exit_pending) {  // instances that ended in a burst round without an exit launch
+      want_exit = 1;
+      exit_pending = false;
+    }
+    // The end of an iteration of the batch: want_lq instances wait for a sweep and want_exit for the exit path.  The
+    // anytime exit's deadline (which turns the sweep into an exit), the iterate log, the exit launch and the restarts it
+    // made, the sweep.
+    if (clock.on && want_lq && clock.deadline_passed()) {
+      hipLaunchKernelGGL(ilq_deadline_kernel<T>, dim3(batch), dim3(64), 0, stream, d, sa);
+      HIP_TRY(hipGetLastError());
+      want_exit = 1;
+      want_lq = 0;
+    }
+    if ((want_exit || want_lq) && iterate_log_launch(p, sa, lg, stream) != ILQG_OK) return ILQG_ERR_HIP;
+    int restarted = 0;
+    if (want_exit) {
+      if (plan.exit_fill_first && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
+      if (outer.before_exit()) sa.outer_closed = 1;  // out of time: inner solves that end now are the last ones
+      if (launch(plan.exit, dim3(batch)) != ILQG_OK) return ILQG_ERR_HIP;
+      p->counters_clean = false;
+      if (plan.read_restarts) {
+        if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
+        restarted = p->h_unfinished[2];
+        if (restarted) clock.restart();
+        outer.after_exit(restarted);
+      }
+    }
+    if (want_lq) {
+      clock.open_iteration();
+      s = sweep();
+      if (s != ILQG_OK) return s;
+    }
+    if (!want_lq && !restarted) return ILQG_OK;  // the solve has ended
+    if (iteration_bound(round, plan.cap) != ILQG_OK) return ILQG_ERR_HIP;
   }
-  *done = !want_lq && !restarted;
-  return *done ? ILQG_OK : iteration_bound(round, cap);
 }
 
 }  // namespace
@@ -1443,11 +1625,12 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
                                              int32_t* converged, void* workspace, const ilqg_solve_options& opt,
                                              hipStream_t stream) {
   using C = LQCfg<T, NX, NP, MU>;
+  using O = OLCfg<T, NX, NP, MU>;
   const DevProblem& d = p->dev;
   const int32_t fixed_iters = opt.fixed_iters;
-  const int32_t* const active = opt.active;
+  const bool open_loop = p->desc.params.open_loop;
   auto choice = [](int32_t c, bool automatic) { return c == ILQG_CHOICE_ON ? true : (c == ILQG_CHOICE_OFF ? false : automatic); };
-  static_assert(OLCfg<T, NX, NP, MU>::ROW == ol_row_elems(NX, NP * MU, NP) && OLCfg<T, NX, NP, MU>::ROW_FAT == ol_row_elems(NX, NP * MU, NP, true), "ol_row_elems");
+  static_assert(O::ROW == ol_row_elems(NX, NP * MU, NP) && O::ROW_FAT == ol_row_elems(NX, NP * MU, NP, true), "ol_row_elems");
   SolveTail<T> tail;
   SolveArgs<T> sa = solve_args_of<T>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, opt, &tail);
   const int al_mode = sa.al_mode;
@@ -1458,12 +1641,10 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   // ws_tail places the lists behind the augmented-Lagrangian layout (the larger one): whatever al_mode this solve runs in
   if (WsLayout(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, sa.ol_row, d.num_constraints, 1).total < L.total)
     return fail(ILQG_ERR_INVALID, "workspace layout: the tail offset does not cover this solve's per-instance blocks");
+
+  // The schedule: every AUTO decision, into `plan` and `sa`.  Nothing is launched here but the mask count.
+  RoundPlan<T> plan;
   constexpr int W = TrialWaves<T>::W;
-  // LDS of the sweep kernel that will run: the open-loop sweep's own working set plus the slot the expected
-  // decrease is handed over in (n = 24: 54 KB, three instances per CU; the feedback layout would take 85 KB)
-  size_t lq_elems = (C::USE_MFMA && !p->desc.params.open_loop) ? MfmaSweepLds<T, NX, NP, MU>::ELEMS + (C::MFMA_ONE_TILE ? 0 : 4) : C::LDS_ELEMS;
-  if (p->desc.params.open_loop) lq_elems = OLCfg<T, NX, NP, MU>::LDS_ELEMS + 4;
-  const size_t lds_lq_multi = lq_elems * sizeof(T);
   // Rows per chunk of the row stage: the widest whose scratch lets a CU hold four instances of the fused trial kernel
   // (the headline batch is four instances per CU); the split row kernels get the same width.
   {
@@ -1473,14 +1654,15 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
     sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), budget);
   }
   auto k_trial = ilq_trial_kernel<T, NX, NP, MU, W>;
-  const bool pw = C::USE_MFMA && !p->desc.params.open_loop;  // one wave per player (MFMA feedback sweep)
+  const bool pw = C::USE_MFMA && !open_loop;  // one wave per player (MFMA feedback sweep)
   // Compact rows (ilqg_common.hpp) between the row stage and the sweep: the one-tile player-parallel sweep and the
-  // open-loop sweep read them; the other sweeps take the dense arrays.
+  // open-loop sweep read them; the other sweeps take the dense arrays.  What the row stage writes and the sweep reads
+  // per time step shrinks from N (n^2 + n) + ... words to the ones a cost term can touch.
   // ... and only when the [T][rp_compact_w] rows fit the space they are kept in: the dense Q, l, R, r arrays up to the
   // sweep's scratch rows (a small or densely coupled problem's row carries the A and B words too)
   const bool compact_on = d.rp_compact_w > 0 && size_t(d.T) * size_t(d.rp_compact_w) <= L.lqscr - L.Q &&
                           choice(opt.compact_rows, true);
-  const bool ol_compact = p->desc.params.open_loop && compact_on;
+  const bool ol_compact = open_loop && compact_on;
   // A registered row-program structure (ilqg_rowprog_static.hpp): the row stage as straight-line code for it — in the
   // fused kernel (state rows in registers, i.e. without the chunk's (x, u) image in LDS, so it takes the 64-row chunk
   // where the interpreter's scratch would not fit four instances on a CU: n = 16 in fp64), in the split row kernel and
@@ -1519,42 +1701,16 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   // round anyway, so it counts its mask first (one more read-back per call); a fixed-iteration solve stays
   // asynchronous and keeps the buffer length.
   int sched_batch = batch;
-  if (active && !opt.forced_steps && !opt.deterministic && !(fixed_iters > 0 && !al_mode)) {
+  if (opt.active && !opt.forced_steps && !opt.deterministic && !(fixed_iters > 0 && !al_mode)) {
     HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));  // (whatever an earlier solve left there)
-    hipLaunchKernelGGL(ilq_count_active_kernel, dim3(1), dim3(256), 0, stream, active, int(batch), p->d_unfinished);
+    hipLaunchKernelGGL(ilq_count_active_kernel, dim3(1), dim3(256), 0, stream, opt.active, int(batch), p->d_unfinished);
     HIP_TRY(hipGetLastError());
     if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
     sched_batch = p->h_unfinished[3] > 0 ? p->h_unfinished[3] : 1;
   }
-  // fp32, one-tile sweep of three player waves, many instances per CU: the 128-register build (see ilq_lq_kernel)
-  constexpr bool has_packed = sizeof(T) == 4 && C::USE_MFMA && C::MFMA_ONE_TILE && NP == 3;
-  const bool packed = has_packed && pw && size_t(sched_batch) >= size_t(5) * 256;
-  auto k_lq_multi = packed ? ilq_lq_kernel<T, NX, NP, MU, (has_packed ? LQ_PLAYER_WAVES_PACKED : LQ_VALU_FEEDBACK)>
-            : pw ? ilq_lq_kernel<T, NX, NP, MU, (C::USE_MFMA ? LQ_PLAYER_WAVES : LQ_VALU_FEEDBACK)>
-                 : (p->desc.params.open_loop ? (ol_compact ? ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP_COMPACT> : ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP>)
-                                             : ilq_lq_kernel<T, NX, NP, MU, LQ_VALU_FEEDBACK>);
-  const int nt_lq_multi = p->desc.params.open_loop ? OLCfg<T, NX, NP, MU>::NT : (pw ? 64 * NP : C::NT);
-  raise_lds_limit((const void*)k_trial, lds_trial);
-
-  // One round = trial kernel, then (for the instances that asked) the exit kernel and the LQ kernel.
-  // The trial kernel counts what its instances wait for; with fixed_iters = K (no AL) the sequence is
-  // known — trial, K x (LQ, trial), exit — otherwise the host reads the counts back each round, which
-  // makes a free-running solve synchronous with respect to `stream`.
-  auto k_exit = ilq_exit_kernel<T, NX, NP, MU>;
-  const size_t lds_exit = quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T);
-  // Split passes where the fused trial kernel's LDS leaves a CU with fewer than three instances (n = 24); the
-  // host then counts every round, because an instance may ask for another pass (back-tracking) before its sweep.
-  // ilqg_solve_options::split_trial overrides the choice.
-  // Split passes: where the fused kernel cannot keep four instances on a CU, and for batches that are several times
-  // what it keeps resident when the split integration kernel (a quarter of the registers, 4 KB of LDS) gains from
-  // the co-residency — measured (DESIGN.md): n = 24, B = 4096: 65 k vs 39 k it/s.  For n <= 16 the fused kernel stays
-  // (round 3, with compact rows: n = 14 fp32, B = 8192: 1.97 M fused vs 1.79 M split; fp64: 1.34 M vs 1.27 M).
-  int num_cus = 256;
-  {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) num_cus = prop.multiProcessorCount;
-  }
+  int num_cus = 256, dev = 0;
+  hipDeviceProp_t prop;
+  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) num_cus = prop.multiProcessorCount;
   // (the exit kernel copies an instance's final iterate, T m n words of strategies among them: four waves where the
   // instances are few and the kernel is a link of the round's chain, one where they share the chip's bandwidth anyway)
   const int nt_exit = sched_batch <= 2 * num_cus ? 256 : 64;
@@ -1564,18 +1720,25 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   // ... and wherever the single-wave sweep (below) will run: it takes its expected decrease from its own adjoint pass, so
   // nothing is left for the fused kernel's row wave to overlap with the rollout, and the three split kernels each keep
   // more instances on a CU than the fused one (measured, n = 14, B = 8192, LQ single-wave + adjoint: fp64 1.58 M it/s
-  // fused vs 1.65 M split, fp32 2.61 M vs 2.77 M; B = 2048 fp64 1.40 M vs 1.50 M).
+  // fused vs 1.65 M split, fp32 2.61 M vs 2.77 M; B = 2048 fp64 1.40 M vs 1.50 M).  (want_1w foresees that sweep with
+  // its adjoint pass; single_wave below is the one that runs, which may take a fused kernel's forward pass instead.)
   constexpr bool has_1w = W1Cfg<T, NX, NP, MU>::SUPPORTED && C::USE_MFMA && C::MFMA_ONE_TILE;
   const bool want_1w = has_1w && pw && compact_on && !kProfile && d.rp_compact_w <= W1Cfg<T, NX, NP, MU>::kWords &&
                        choice(opt.single_wave_sweep, !opt.deterministic && size_t(sched_batch) >= size_t(5) * num_cus) &&
                        opt.adjoint_expected_decrease != ILQG_CHOICE_OFF;
+  // Split passes: where the fused kernel cannot keep four instances on a CU (n = 24), and for batches that are several
+  // times what it keeps resident when the split integration kernel (a quarter of the registers, 4 KB of LDS) gains from
+  // the co-residency — measured (DESIGN.md): n = 24, B = 4096: 65 k vs 39 k it/s.  For n <= 16 the fused kernel stays
+  // (round 3, with compact rows: n = 14 fp32, B = 8192: 1.97 M fused vs 1.79 M split; fp64: 1.34 M vs 1.27 M).  The
+  // host then counts every round: an instance may ask for another pass (back-tracking) before its sweep.
+  // ilqg_solve_options::split_trial overrides the choice.
   bool split = choice(opt.split_trial, 4 * lds_trial > size_t(160) * 1024 || (big_batch && NX > 16) || want_1w);
   if (kProfile || opt.forced_steps) split = false;  // the phase profile reads the fused kernel's counters
   if (split) {  // the split row kernels interpret the program: their chunk width is the interpreter's
     static_prog = 0;
     sa.rows_cw = rows_cw_interpreted;
   }
-  sa.compact = ((pw && C::MFMA_ONE_TILE && compact_on) || ol_compact) ? 1 : 0;
+  sa.compact = will_compact ? 1 : 0;
   const size_t split_maps_bytes = sa.compact ? 0 : rows_maps_bytes(d);  // the split row kernels' copy of the word maps
   if (split) {
     // The split row kernel is one wave per chunk with the chunk's scratch to itself, and its instances per CU are what
@@ -1592,9 +1755,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   const bool lists = split || handoff;
   // The sweep's forward pass runs in the fused trial kernel that follows it, beside the rollout, whenever that is the
   // kernel that follows (split passes and the open-loop sweep keep it in the sweep's kernel).
-  // Compact rows between the row stage and the one-tile player-parallel sweep (ilqg_common.hpp): what the row stage
-  // writes and the sweep reads per time step shrinks from N (n^2 + n) + ... words to the ones a cost term can touch.
-  sa.defer_forward = (!split && !p->desc.params.open_loop) ? 1 : 0;
+  sa.defer_forward = (!split && !open_loop) ? 1 : 0;
   {
     constexpr size_t fwd_elems = 4 * 2 * ((NX * NX + C::SCR + 3) & ~3) + 2 * NX + 8;
     if (trial_rows_elems(d, sa.rows_cw, static_prog != 0) < fwd_elems + 8) sa.defer_forward = 0;
@@ -1610,220 +1771,67 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   const bool single_wave = has_1w && pw && sa.compact && !kProfile && (adjoint || sa.defer_forward) &&
                            d.rp_compact_w <= W1Cfg<T, NX, NP, MU>::kWords &&
                            choice(opt.single_wave_sweep, !opt.deterministic && size_t(sched_batch) >= size_t(5) * num_cus);
-  auto k_lq = single_wave ? ilq_lq_kernel<T, NX, NP, MU, (has_1w ? LQ_SINGLE_WAVE : LQ_VALU_FEEDBACK)> : k_lq_multi;
-  const int nt_lq = single_wave ? 64 : nt_lq_multi;
-  const size_t lds_lq = single_wave ? size_t(W1Cfg<T, NX, NP, MU>::ELEMS + 4) * sizeof(T) : lds_lq_multi;
   if (single_wave) {
     sa.prio_div = 0;
     if (adjoint) sa.defer_forward = 0;  // the sweep forms the expected decrease itself: no forward pass anywhere
   }
-  raise_lds_limit((const void*)k_lq, lds_lq);
-  p->last_schedule = (single_wave ? ILQG_SCHEDULE_SINGLE_WAVE_SWEEP : 0) | ((single_wave && adjoint) ? ILQG_SCHEDULE_ADJOINT_DECREASE : 0) |
-                     (split ? ILQG_SCHEDULE_SPLIT_TRIAL : 0) | (sa.compact ? ILQG_SCHEDULE_COMPACT_ROWS : 0) |
-                     (counted ? ILQG_SCHEDULE_COUNTED : 0) | (p->desc.params.open_loop ? ILQG_SCHEDULE_OPEN_LOOP : 0) |
-                     ((static_prog || (static_id && split)) ? ILQG_SCHEDULE_STATIC_ROWS : 0);
-  long long cap = al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
-                          : (long long)sa.prm.max_solver_iters + 2;
-  if (split || counted) cap = (cap + 2) * ((long long)sa.prm.max_backtracking_steps + 3);
-  auto k_roll = ilq_roll_kernel<T, NX, NP, MU>;
-  auto k_decide = ilq_decide_kernel<T, NX, NP, MU>;
-  const size_t lds_roll = trial_phase_lds_bytes<T>(d, TRIAL_ROLL, sa.rows_cw),
-               lds_decide = trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw);
-  // (a static row kernel whose slots are registers needs no scratch beyond the (x, u) image of shapes past 16 states)
-  const size_t static_regs_lds = (rows_state_in_registers(NX, NP * MU) ? 0 : size_t(d.n + d.m) * 64) * sizeof(T) + 16;
-  const size_t lds_rows = (static_id && static_in_regs) ? static_regs_lds
-                                                        : split_maps_bytes + split_rows_elems(d, NX, static_id ? 64 : sa.rows_cw) * sizeof(T);
-  const size_t lds_prows = (static_id && static_in_regs) ? static_regs_lds
-                                                         : split_maps_bytes + probe_rows_elems(d, NX, static_id ? 64 : sa.rows_cw) * sizeof(T);  // merit only
-  constexpr bool pairs = rollout_pairs(NX, NP, MU);  // two rollouts per wavefront (ilqg_stages.hpp)
-  const size_t lds_proll = pairs ? size_t(rollout_pair_lds_elems(d.n, d.m)) * sizeof(T) + 16 : lds_roll;
-  const bool probe = lists && sa.prm.linesearch && choice(opt.probe, true);
-  auto k_proll = ilq_probe_roll_kernel<T, NX, NP, MU>;
-  auto k_proll_fat = ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8>;  // (fp32: the same kernel)
-  auto k_proll_single = ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, true>;
-  auto k_proll_lanes = ilq_probe_roll_lanes_kernel<T, NX, NP, MU>;
-  const size_t lds_proll_lanes = pairs ? size_t(rollout_lanes_lds_elems(d.n, d.m, d.N)) * sizeof(T) + 16 : 0;
-  const int probe_lanes_min = opt.probe_lanes == ILQG_CHOICE_OFF ? (1 << 30) : (opt.probe_lanes == ILQG_CHOICE_ON ? 2 : 8);
-  const int row_chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;  // workgroups per instance of the row kernels
-  bool deep_tails = false;  // a tail of this solve kept half of its list through three rounds (see the ramp below)
-  if (lists) {
-    raise_lds_limit((const void*)k_roll, lds_proll);
-    raise_lds_limit((const void*)k_rows, lds_rows);
-    raise_lds_limit((const void*)k_decide, lds_decide);
-    raise_lds_limit((const void*)k_proll, lds_proll);
-    raise_lds_limit((const void*)k_proll_fat, lds_proll);
-    raise_lds_limit((const void*)k_proll_single, lds_roll);
-    raise_lds_limit((const void*)k_proll_lanes, lds_proll_lanes);
-    raise_lds_limit((const void*)k_prows, lds_prows);
+  // The sweep kernel.  The open-loop sweep's LDS is its own working set plus the slot the expected decrease is handed
+  // over in (n = 24: 54 KB, three instances per CU; the feedback layout would take 85 KB).  fp32, one-tile sweep of
+  // three player waves, many instances per CU: the 128-register build (see ilq_lq_kernel).
+  constexpr bool has_packed = sizeof(T) == 4 && C::USE_MFMA && C::MFMA_ONE_TILE && NP == 3;
+  if (open_loop) {
+    plan.sweep = {ol_compact ? ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP_COMPACT> : ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP>,
+                  O::NT, (O::LDS_ELEMS + 4) * sizeof(T)};
+  } else if constexpr (!C::USE_MFMA) {
+    plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_VALU_FEEDBACK>, C::NT, C::LDS_ELEMS * sizeof(T)};
+  } else {
+    plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES>, 64 * NP,
+                  (MfmaSweepLds<T, NX, NP, MU>::ELEMS + (C::MFMA_ONE_TILE ? 0 : 4)) * sizeof(T)};
+    if constexpr (has_packed)
+      if (size_t(sched_batch) >= size_t(5) * 256) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED>;
+    if constexpr (has_1w)
+      if (single_wave) plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_SINGLE_WAVE>, 64, size_t(W1Cfg<T, NX, NP, MU>::ELEMS + 4) * sizeof(T)};
   }
   sa.clear_counters = 1;
-  p->counters_clean = false;  // whatever an earlier solve left in the round counters
-  RoundLists<T> rl(sa, tail.pass_ids, cap);
-  bool exit_pending = false;  // a burst round went without its exit launch (see the burst loop)
-  // Free-running solves: the kernels select their instances by the stage each one is in, so a round launched for
-  // nobody is harmless — the host therefore enqueues BURSTS of whole rounds (trial, exit, sweep) and reads the
-  // counters back once per burst instead of once per round (a read-back is a stream synchronisation: ~20-30 us against
-  // a ~0.45 ms round of a single instance).  The burst doubles up to eight rounds while no instance is back-tracking
-  // and falls back to one as soon as one is (those go through the probing passes, which need the lists every round).
-  // Timed solves (InnerClock) read the clock in front of every iteration: no bursts.
-  const bool timed = opt.max_runtime > 0.0 && counted;
-  const bool al_constrained = al_mode && d.num_constraints > 0;
-  InnerClock clock(p, timed, opt.max_runtime, al_constrained);
-  AlOuterClock outer(p, timed && al_constrained, opt.max_runtime, clock.budget);
-  const bool bursts = counted && !kProfile && !timed && choice(opt.round_bursts, true);
-  int burst = 1;
-  IterLog<T> lg;
-  {
-    const ilqg_status s = iterate_log_open(opt, batch, stream, &lg);
-    if (s != ILQG_OK) return s;
+  plan.trial = {k_trial, 64 * W, lds_trial};
+  plan.exit = {ilq_exit_kernel<T, NX, NP, MU>, nt_exit, quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T)};
+  plan.read_restarts = counted && al_mode;
+  constexpr bool pairs = rollout_pairs(NX, NP, MU);  // two rollouts per wavefront (ilqg_stages.hpp)
+  if (lists) {
+    const size_t lds_roll = trial_phase_lds_bytes<T>(d, TRIAL_ROLL, sa.rows_cw);
+    const size_t lds_proll = pairs ? size_t(rollout_pair_lds_elems(d.n, d.m)) * sizeof(T) + 16 : lds_roll;
+    // (a static row kernel whose slots are registers needs no scratch beyond the (x, u) image of shapes past 16 states)
+    const size_t static_regs_lds = (rows_state_in_registers(NX, NP * MU) ? 0 : size_t(d.n + d.m) * 64) * sizeof(T) + 16;
+    const int rows_cw = static_id ? 64 : sa.rows_cw;
+    const bool regs = static_id && static_in_regs;
+    plan.roll = {ilq_roll_kernel<T, NX, NP, MU>, 64, lds_proll};
+    plan.rows = {k_rows, 64, regs ? static_regs_lds : split_maps_bytes + split_rows_elems(d, NX, rows_cw) * sizeof(T)};
+    plan.decide = {ilq_decide_kernel<T, NX, NP, MU>, 64, trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw)};
+    plan.prows = {k_prows, 64, regs ? static_regs_lds : split_maps_bytes + probe_rows_elems(d, NX, rows_cw) * sizeof(T)};
+    plan.proll = {ilq_probe_roll_kernel<T, NX, NP, MU>, 64, lds_proll};
+    plan.proll_fat = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8>, 64, lds_proll};  // (fp32: the same kernel)
+    if (pairs) {  // (not `if constexpr`: every shape keeps these kernels)
+      plan.proll_single = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, true>, 64, lds_roll};
+      plan.proll_lanes = {ilq_probe_roll_lanes_kernel<T, NX, NP, MU>, 64, size_t(rollout_lanes_lds_elems(d.n, d.m, d.N)) * sizeof(T) + 16};
+    }
   }
-  const ExitLaunch<T> ex{k_exit, nt_exit, lds_exit, false, counted && al_mode};
-  auto sweep = [&]() -> ilqg_status {
-    hipLaunchKernelGGL(k_lq, dim3(batch), dim3(nt_lq), lds_lq, stream, d, sa);
-    HIP_TRY(hipGetLastError());
-    p->counters_clean = true;  // (SolveArgs::clear_counters)
-    return ILQG_OK;
-  };
-  // One pass of a round: the split kernels — over the whole batch (split mode; nobody is listed in a burst round, so
-  // nothing is probed) or over the listed back-tracking instances with their probing launches — or the fused kernel.
-  auto pass = [&]() -> ilqg_status {
-    if (counted && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
-    p->counters_clean = false;  // (the round's kernels count into them)
-    if (split || sa.ids) {  // a split pass: the whole batch (split mode) or the listed back-tracking instances
-      sa.ids_next = rl.free_list();
-      int probe_k = 0;
-      if (sa.ids) {
-        probe_k = probe_candidates(tail.pool_entries, rl.round_instances, opt.probe_first, rl.tail_rounds);
-        // Deep searches: once a tail of this solve has kept half of its list through three rounds (2 + 4 + 8 or more
-        // rejected candidates each: they are mostly on their way through all max_backtracking_steps), later tails skip the
-        // ramp.  A probing round costs one wave's chain per time step until its waves fill the chip, so every candidate up
-        // to that point is free: with the lane form (rollout_lanes: 64 / N candidates per wavefront) that is
-        // C floor(kDeepTailWaves / instances) candidates per instance — whole wavefronts —, as far as the pool holds them.
-        // (config 5's scene: rounds of 4, 10, 20, 21, 42 ... candidates -> 16 - 63 from a tail's first round on;
-        // config 4's ~1600 back-tracking instances are mostly done after a step or two: they keep the ramp.)
-        if (rl.tail_rounds == 3 && 2 * rl.round_instances >= rl.tail_first_instances) deep_tails = true;
-        if (deep_tails && opt.probe_first <= 0) {
-          constexpr int C_lane = rollout_lanes_per_wave(NP > 0 ? NP : 1);
-          int k_deep = std::min(tail.pool_entries / rl.round_instances, kProbeCandidates);  // what the pool holds
-          if (pairs && opt.probe_lanes != ILQG_CHOICE_OFF) {
-            const int free_waves = kDeepTailWaves / rl.round_instances;
-            const int k_lane = C_lane * (free_waves > 1 ? free_waves : 1);
-            if (k_deep > k_lane) k_deep = k_lane;
-            if (k_deep >= C_lane) k_deep = k_deep / C_lane * C_lane;
-          }
-          if (probe_k < k_deep) probe_k = k_deep;
-        }
-        const ilqg_status s = rl.tail_round(probe, probe_k);
-        if (s != ILQG_OK) return s;
-      }
-      const int round_instances = rl.round_instances;
-      if (probe && probe_k >= 2) {
-        // the listed instances' next step sizes side by side; their states move to the first acceptable one
-        sa.probe_pool = tail.probe_pool;
-        sa.probe_k = probe_k;
-        const int proll_y = pairs ? (probe_k + 1) / 2 : probe_k;
-        // the register-rich build while every rollout of the round is resident at once at two waves per SIMD
-        const bool fat = (long long)round_instances * proll_y <= 8ll * num_cus;
-        // A lane per (candidate, subsystem) where that is the shorter round.  A round of W waves takes about
-        // max(one wave's chain, W / SIMDs x a wave's issue time) per time step (the kProbe*Cycles model).  So the lane
-        // form wins once its own waves fill the chip (config 5's scene from 16 candidates per instance on), and loses a
-        // round of a few deep searches (n = 16: ~100 instances x 128 candidates are 700 lane waves, one chain long).
-        constexpr int C = rollout_lanes_per_wave(NP > 0 ? NP : 1);
-        const double simds = 4.0 * num_cus;
-        const double w_pair = double(round_instances) * proll_y, w_lane = double(round_instances) * ((probe_k + C - 1) / C);
-        const double t_pair = std::max(kPairChainCycles, w_pair / simds * kPairIssueCycles),
-                     t_lane = std::max(kLaneChainCycles, w_lane / simds * kLaneIssueCycles);
-        // (n > 16: the lane form's step carries a 2 n-term control product per lane and, for the six-state cars, spills
-        // inside the time loop — n = 24 on the feedback sweep: 2.2 ms per launch against 0.4-0.6 for the paired form,
-        // 99 k -> 83 k it/s; the model's constants are the n = 15 scene's, so AUTO leaves those shapes on pairs.)
-        const bool lanes = pairs && probe_k >= probe_lanes_min &&
-                           (opt.probe_lanes == ILQG_CHOICE_ON || (NX <= 16 && t_lane < 0.9 * t_pair));
-        // a candidate per wavefront while every one of them finds a SIMD of its own
-        const bool single = pairs && !lanes && (long long)round_instances * probe_k <= 4ll * num_cus &&
-                            opt.probe_lanes != ILQG_CHOICE_ON;
-        if (lanes) {
-          hipLaunchKernelGGL(k_proll_lanes, dim3(round_instances, (probe_k + C - 1) / C), dim3(64), lds_proll_lanes, stream, d, sa);
-        } else if (single) {
-          hipLaunchKernelGGL(k_proll_single, dim3(round_instances, probe_k), dim3(64), lds_roll, stream, d, sa);
-        } else {
-          hipLaunchKernelGGL(fat ? k_proll_fat : k_proll, dim3(round_instances, proll_y), dim3(64), lds_proll, stream, d, sa);
-        }
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_prows, dim3(row_chunks, round_instances * probe_k),
-                           dim3(64), lds_prows, stream, d, sa);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(ilq_probe_pick_kernel<T>, dim3(round_instances), dim3(kProbeCandidates), 0, stream, d, sa);
-        HIP_TRY(hipGetLastError());
-      }
-      sa.round_count = round_instances;
-      hipLaunchKernelGGL(k_roll, dim3(pairs ? (round_instances + 1) / 2 : round_instances), dim3(64), lds_proll, stream, d, sa);
-      HIP_TRY(hipGetLastError());
-      sa.first = 0;
-      hipLaunchKernelGGL(k_rows, dim3(row_chunks, round_instances), dim3(64),
-                         lds_rows, stream, d, sa);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_decide, dim3(round_instances), dim3(64), lds_decide, stream, d, sa);
-    } else {
-      sa.ids_next = handoff ? rl.free_list() : nullptr;
-      hipLaunchKernelGGL(k_trial, dim3(batch), dim3(64 * W), lds_trial, stream, d, sa);
-    }
-    HIP_TRY(hipGetLastError());
-    sa.first = 0;
-    return ILQG_OK;
-  };
-  for (long long round = 0;; round++) {
-    if (bursts && !sa.ids) {
-      // a fixed-iteration solve knows its last round: no burst runs past it
-      const long long left = (fixed_iters > 0 && !al_mode) ? (long long)fixed_iters - round : (long long)burst;
-      for (int q = 1; q < burst && q <= left; q++) {  // rounds without a read-back
-        ilqg_status s = pass();
-        if (s != ILQG_OK) return s;
-        if (iterate_log_launch(p, sa, lg, stream) != ILQG_OK) return ILQG_ERR_HIP;
-        // The exit path inside a burst only where it starts something (the augmented Lagrangian's next inner solve);
-        // an ILQSolver::Solve that ends here waits for the burst's last round, whose exit launch is then unconditional
-        // (a launch for nobody is ~5 us of every round of a lone instance).
-        if (al_mode) {
-          hipLaunchKernelGGL(k_exit, dim3(batch), dim3(nt_exit), lds_exit, stream, d, sa);
-          HIP_TRY(hipGetLastError());
-        } else {
-          exit_pending = true;
-        }
-        s = sweep();
-        if (s != ILQG_OK) return s;
-        round++;
-      }
-    }
-    ilqg_status s = pass();
-    if (s != ILQG_OK) return s;
-    int want_lq = 1, want_exit = 0;
-    if (counted) {
-      if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
-      want_lq = p->h_unfinished[0];
-      want_exit = p->h_unfinished[1];
-      if (lists) {
-        bool again = false;
-        s = rl.after_round(p->h_unfinished, round, &again, &want_lq, &want_exit);
-        if (s != ILQG_OK) return s;
-        if (again) {
-          burst = 1;
-          continue;
-        }
-      }
-      if (bursts) burst = p->h_unfinished[3] ? 1 : (burst < 8 ? burst * 2 : 8);
-    } else if (round == fixed_iters) {
-      want_lq = 0;
-      want_exit = 1;
-    }
-    if (exit_pending) {  // instances that ended in a burst round without an exit launch
-      want_exit = 1;
-      exit_pending = false;
-    }
-    bool done = false;
-    s = end_iteration(p, sa, stream, lg, clock, outer, ex, round, cap, want_lq, want_exit, sweep, &done);
-    if (s != ILQG_OK) return s;
-    if (done) break;
-  }
-  return ILQG_OK;
+  plan.cap = al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
+                     : (long long)sa.prm.max_solver_iters + 2;
+  if (split || counted) plan.cap = (plan.cap + 2) * ((long long)sa.prm.max_backtracking_steps + 3);
+  plan.row_chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;
+  plan.lane_width = rollout_lanes_per_wave(NP > 0 ? NP : 1);
+  plan.num_cus = num_cus;
+  plan.split = split; plan.counted = counted; plan.handoff = handoff; plan.lists = lists; plan.pairs = pairs;
+  plan.timed = opt.max_runtime > 0.0 && counted;  // (InnerClock reads the clock in front of every iteration: no bursts)
+  plan.bursts = counted && !kProfile && !plan.timed && choice(opt.round_bursts, true);
+  plan.probe = lists && sa.prm.linesearch && choice(opt.probe, true);
+  plan.lanes_auto = NX <= 16;
+  plan.deep_tails = true;
+  p->last_schedule = (single_wave ? ILQG_SCHEDULE_SINGLE_WAVE_SWEEP : 0) | ((single_wave && adjoint) ? ILQG_SCHEDULE_ADJOINT_DECREASE : 0) |
+                     (split ? ILQG_SCHEDULE_SPLIT_TRIAL : 0) | (sa.compact ? ILQG_SCHEDULE_COMPACT_ROWS : 0) |
+                     (counted ? ILQG_SCHEDULE_COUNTED : 0) | (open_loop ? ILQG_SCHEDULE_OPEN_LOOP : 0) |
+                     ((static_prog || (static_id && split)) ? ILQG_SCHEDULE_STATIC_ROWS : 0);
+  return run_rounds(p, sa, tail, plan, opt, stream);
 }
 
 #if defined(ILQG_PART_NX)
@@ -1907,124 +1915,59 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
   p->last_schedule = ILQG_SCHEDULE_GENERIC | ILQG_SCHEDULE_SPLIT_TRIAL | ILQG_SCHEDULE_COUNTED |
                      (p->desc.params.open_loop ? ILQG_SCHEDULE_OPEN_LOOP : 0);
   sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), size_t(48) * 1024);
-  const size_t lds_roll = trial_phase_lds_bytes<T>(d, TRIAL_ROLL, sa.rows_cw),
-               lds_decide = trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw);
+  const size_t lds_roll = trial_phase_lds_bytes<T>(d, TRIAL_ROLL, sa.rows_cw);
   const size_t lds_rows = rows_maps_bytes(d) + trial_rows_elems(d, sa.rows_cw) * sizeof(T);
-  const size_t lds_exit = quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T);
   const size_t lds_lq = ((p->desc.params.open_loop ? gen_openloop_lds_elems(d.n, d.N, d.m) : gen_feedback_lds_elems(d.n, d.N, d.m)) + 4) * sizeof(T);
   if (lds_lq > kLdsPerWorkgroup || lds_rows > kLdsPerWorkgroup)
     return fail(ILQG_ERR_UNSUPPORTED, "the game does not fit a CU's LDS");
-  auto k_roll = ilq_roll_kernel<T, 0, 0, 0>;
-  auto k_rows = ilq_rows_kernel<T, 0, 0, 0>;
-  auto k_decide = ilq_decide_kernel<T, 0, 0, 0>;
-  auto k_exit = ilq_exit_kernel<T, 0, 0, 0>;
-  auto k_lq = gen_lq_kernel<T>;
   // Back-tracking instances are listed and their next step sizes probed side by side, as in the specialised solve
   // (DimsLaunch::solve): without it a single failing line search of 100 steps costs the whole batch 100 serial passes
-  // (round 5: mixed_dubins_car_scene, B = 1024: 76 passes per iteration, 42 k it/s).
-  auto k_proll = ilq_probe_roll_kernel<T, 0, 0, 0>;
-  auto k_prows = ilq_probe_rows_kernel<T, 0, 0, 0>;
-  const size_t lds_prows = rows_maps_bytes(d) + probe_rows_elems(d, 0, sa.rows_cw) * sizeof(T);
-  const bool probe = !opt.forced_steps && sa.prm.linesearch && opt.probe != ILQG_CHOICE_OFF;
-  raise_lds_limit((const void*)k_proll, lds_roll);
-  raise_lds_limit((const void*)k_prows, lds_prows);
-  raise_lds_limit((const void*)k_roll, lds_roll);
-  raise_lds_limit((const void*)k_rows, lds_rows);
-  raise_lds_limit((const void*)k_decide, lds_decide);
-  raise_lds_limit((const void*)k_exit, lds_exit);
-  raise_lds_limit((const void*)k_lq, lds_lq);
+  // (round 5: mixed_dubins_car_scene, B = 1024: 76 passes per iteration, 42 k it/s).  One rollout per wavefront and
+  // candidate: the probing rollout has a single form, so "fat" is the same kernel.
+  RoundPlan<T> plan;
+  plan.roll = {ilq_roll_kernel<T, 0, 0, 0>, 64, lds_roll};
+  plan.rows = {ilq_rows_kernel<T, 0, 0, 0>, 64, lds_rows};
+  plan.decide = {ilq_decide_kernel<T, 0, 0, 0>, 64, trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw)};
+  plan.proll = plan.proll_fat = {ilq_probe_roll_kernel<T, 0, 0, 0>, 64, lds_roll};
+  plan.prows = {ilq_probe_rows_kernel<T, 0, 0, 0>, 64, rows_maps_bytes(d) + probe_rows_elems(d, 0, sa.rows_cw) * sizeof(T)};
+  plan.sweep = {gen_lq_kernel<T>, kGenSweepThreads, lds_lq};
+  plan.exit = {ilq_exit_kernel<T, 0, 0, 0>, 64, quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T)};
+  plan.exit_fill_first = true; plan.read_restarts = sa.al_mode != 0;
+  plan.cap = sa.al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
+                        : (long long)(opt.fixed_iters > 0 ? opt.fixed_iters : sa.prm.max_solver_iters) + 2;
+  plan.cap = (plan.cap + 2) * ((long long)sa.prm.max_backtracking_steps + 3);
+  plan.row_chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;
+  plan.split = plan.counted = plan.lists = true;
+  plan.probe = !opt.forced_steps && sa.prm.linesearch && opt.probe != ILQG_CHOICE_OFF;
+  plan.timed = opt.max_runtime > 0.0;
   // The sweep on a specialised kernel: the smallest instantiated shape the game embeds in (padded_lq_kernel).  AUTO: for
   // problems that have no instantiation of their own (ilqg_problem::generic); a problem sent here by
   // ilqg_solve_options::generic_kernels keeps the run-time-dimensioned sweeps unless padded_sweep = ON.
-  int pad_nx = 0, pad_mu = 0;
   PairTable ptp;
-  void* pad_buf = nullptr;
-  auto padded_launch = [&](size_t* elems_out) -> ilqg_status {
-#define X(NX_, NP_, MU_)                                                                                                      \
-    if (pad_nx == NX_ && d.N == NP_ && pad_mu == MU_)                                                                          \
-      return DimsLaunch<T, NX_, NP_, MU_>::lq_padded(d, &sa, ptp, pad_buf, elems_out, p->desc.params.open_loop != 0, stream);
-    ILQG_FOR_DIMS(X)
-#undef X
-    return fail(ILQG_ERR_UNSUPPORTED, "no shape to embed the game in");
-  };
   if (opt.padded_sweep == ILQG_CHOICE_ON || (opt.padded_sweep == ILQG_CHOICE_AUTO && p->generic)) {
+    int pad_nx = 0, pad_mu = 0;
     pick_padded_shape(d.n, d.N, d.udim, &pad_nx, &pad_mu);
     if (pad_nx == 0 && opt.padded_sweep == ILQG_CHOICE_ON)
       return fail(ILQG_ERR_UNSUPPORTED, "padded_sweep = ON: no instantiated shape holds this game (same player count, at "
                                         "least its states and its widest control)");
     if (pad_nx) {
+#define X(NX_, NP_, MU_) \
+      if (pad_nx == NX_ && d.N == NP_ && pad_mu == MU_) plan.padded = DimsLaunch<T, NX_, NP_, MU_>::lq_padded;
+      ILQG_FOR_DIMS(X)
+#undef X
       std::string err;
       if (!padded_pairs(d.pairs, d.N, pad_mu, &ptp, &err)) return fail(ILQG_ERR_INVALID, err);
       size_t elems = 0;
-      ilqg_status s = padded_launch(&elems);
+      ilqg_status s = plan.padded(d, &sa, ptp, nullptr, &elems, p->desc.params.open_loop != 0, stream);
       if (s != ILQG_OK) return s;
       s = Scratch().reserve(size_t(batch) * elems * sizeof(T));
       if (s != ILQG_OK) return s;
-      pad_buf = ilqg_shared::scratch_state().ptr;
+      plan.pad_pairs = &ptp;
+      plan.pad = ilqg_shared::scratch_state().ptr;
       p->last_schedule |= ILQG_SCHEDULE_PADDED_SWEEP;
     }
   }
-  const int row_chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;
-  long long cap = sa.al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
-                             : (long long)(opt.fixed_iters > 0 ? opt.fixed_iters : sa.prm.max_solver_iters) + 2;
-  cap = (cap + 2) * ((long long)sa.prm.max_backtracking_steps + 3);
-  const bool timed = opt.max_runtime > 0.0;
-  const bool al_constrained = sa.al_mode && d.num_constraints > 0;
-  InnerClock clock(p, timed, opt.max_runtime, al_constrained);
-  AlOuterClock outer(p, timed && al_constrained, opt.max_runtime, clock.budget);
-  IterLog<T> lg;
-  {
-    const ilqg_status s = iterate_log_open(opt, batch, stream, &lg);
-    if (s != ILQG_OK) return s;
-  }
-  p->counters_clean = false;  // whatever an earlier solve left in the round counters
-  RoundLists<T> rl(sa, tail.pass_ids, cap);
-  const ExitLaunch<T> ex{k_exit, 64, lds_exit, true, sa.al_mode != 0};
-  auto sweep = [&]() -> ilqg_status {
-    if (pad_nx) return padded_launch(nullptr);
-    hipLaunchKernelGGL(k_lq, dim3(batch), dim3(kGenSweepThreads), lds_lq, stream, d, sa);
-    HIP_TRY(hipGetLastError());
-    return ILQG_OK;
-  };
-  for (long long round = 0;; round++) {
-    if (!p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
-    p->counters_clean = false;
-    sa.ids_next = rl.free_list();
-    const int round_instances = rl.round_instances;
-    if (sa.ids) {
-      const int probe_k = probe_candidates(tail.pool_entries, round_instances, opt.probe_first, rl.tail_rounds);
-      const ilqg_status s = rl.tail_round(probe, probe_k);
-      if (s != ILQG_OK) return s;
-      if (probe && probe_k >= 2) {
-        sa.probe_pool = tail.probe_pool;
-        sa.probe_k = probe_k;
-        hipLaunchKernelGGL(k_proll, dim3(round_instances, probe_k), dim3(64), lds_roll, stream, d, sa);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_prows, dim3(row_chunks, round_instances * probe_k), dim3(64), lds_prows, stream, d, sa);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(ilq_probe_pick_kernel<T>, dim3(round_instances), dim3(kProbeCandidates), 0, stream, d, sa);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    sa.round_count = round_instances;
-    hipLaunchKernelGGL(k_roll, dim3(round_instances), dim3(64), lds_roll, stream, d, sa);
-    HIP_TRY(hipGetLastError());
-    sa.first = 0;
-    hipLaunchKernelGGL(k_rows, dim3(row_chunks, round_instances), dim3(64), lds_rows, stream, d, sa);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_decide, dim3(round_instances), dim3(64), lds_decide, stream, d, sa);
-    HIP_TRY(hipGetLastError());
-    if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
-    bool again = false, done = false;
-    int want_lq = 0, want_exit = 0;
-    ilqg_status s = rl.after_round(p->h_unfinished, round, &again, &want_lq, &want_exit);
-    if (s != ILQG_OK) return s;
-    if (again) continue;
-    s = end_iteration(p, sa, stream, lg, clock, outer, ex, round, cap, want_lq, want_exit, sweep, &done);
-    if (s != ILQG_OK) return s;
-    if (done) break;
-  }
-  return ILQG_OK;
+  return run_rounds(p, sa, tail, plan, opt, stream);
 }
 
 // ilqg_lq_feedback_batch / ilqg_lq_openloop_batch of a shape without an instantiation on the padded sweep of (nx, N, mu)
