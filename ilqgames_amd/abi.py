@@ -13,7 +13,7 @@ F32, F64 = 0, 1
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP, ERR_NO_DEVICE = 0, 1, 2, 3, 4
 
 # ilqg_dyn_kind
-ABI_VERSION = 8  # ILQG_ABI_VERSION of include/ilqg.h these mirrors were written against
+ABI_VERSION = 9  # ILQG_ABI_VERSION of include/ilqg.h these mirrors were written against
 DYN_UNICYCLE_4D, DYN_CAR_5D, DYN_CAR_6D = 1, 2, 3
 DYN_UNICYCLE_4D_DISTURBED, DYN_PLANAR_DISTURBANCE = 4, 5  # the two rows of TwoPlayerUnicycle4D
 DYN_DUBINS_CAR = 6  # (px, py, theta), u = (omega), param0 = speed
@@ -62,6 +62,15 @@ class Dims(C.Structure):
 
 CHOICE_AUTO, CHOICE_OFF, CHOICE_ON = 0, 1, 2
 SWEEP_GENERIC = 3  # ilqg_dims::sweep_formulation: the run-time-dimensioned sweeps
+
+
+class InstanceParam(C.Structure):
+    """ilqg_instance_param (include/ilqg.h): one per-instance cost parameter, (term index, ilqg_param_field)."""
+    _fields_ = [("term", C.c_int32), ("field", C.c_int32)]
+
+
+PARAM_WEIGHT, PARAM_VALUE = 0, 1
+PARAM_FIELDS = {"weight": PARAM_WEIGHT, "value": PARAM_VALUE}
 
 
 class IterateLog(C.Structure):
@@ -153,6 +162,7 @@ class ProblemSpec:
         self.x0 = None
         self._num_constraints = 0
         self.dense_params = []  # coefficients of the affine constraints (ilqg_problem_desc::dense_params)
+        self.term_names = {}   # name -> term index (name_term / term_index): no part of the descriptor
 
     # --- dynamics (ConcatenatedDynamicalSystem subsystem list) ---
     def add_player(self, kind, param0=0.0, state_reg=0.0, control_reg=0.0, structure=SUM):
@@ -185,8 +195,10 @@ class ProblemSpec:
 
     def _term(self, kind, role, player, arg=-1, idx=(0, 0, 0, 0), weight=1.0, value=0.0, flags=0,
               polyline=-1, child_begin=0, child_count=0, constraint=False, first_step=0, value2=0.0,
-              idx_extra=(0, 0)):
+              idx_extra=(0, 0), name=None):
         idx = tuple(idx) + (0,) * (4 - len(idx))
+        if name is not None:
+            self.name_term(name, len(self.terms))
         slot = -1
         if constraint:
             slot = self._num_constraints
@@ -196,6 +208,20 @@ class ProblemSpec:
                                child_count=child_count, constraint_slot=slot, first_step=first_step, value2=value2,
                                idx_extra=tuple(idx_extra)))
         return len(self.terms) - 1
+
+    def name_term(self, name, term):
+        """Gives the term with index `term` (as returned by the cost methods) a name for term_index — what the
+        per-instance parameters (hip.Problem.declare_instance_params) are declared by.  Returns the index."""
+        if name in self.term_names and self.term_names[name] != term:
+            raise ValueError("term name %r is taken by term %d" % (name, self.term_names[name]))
+        self.term_names[name] = term
+        return term
+
+    def term_index(self, name):
+        """Index into the descriptor's terms of the term named `name`."""
+        if name not in self.term_names:
+            raise KeyError("no term named %r (named: %s)" % (name, ", ".join(sorted(self.term_names)) or "none"))
+        return self.term_names[name]
 
     def final_time(self, threshold_time, term):
         """FinalTimeCost(cost, threshold_time) (cost/final_time_cost.h:55-88) around the term with index `term`

@@ -255,6 +255,7 @@ __device__ __forceinline__ QuadArgs<T> quad_args_of(const DevProblem& p, const Q
   a.r = g.r ? g.r + b * Tn * p.pairs.rsz : nullptr;
   a.merit_part = g.merit_part ? g.merit_part + b * Tn * N * 2 : nullptr;
   a.cost_part = g.cost_part ? g.cost_part + b * Tn * N : nullptr;
+  a.iv = instance_values(p, int(b));
   return a;
 }
 
@@ -485,7 +486,7 @@ __global__ void __launch_bounds__(256) ilq_exit_kernel(DevProblem p, SolveArgs<T
     const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
     if (stage != ST_INNER_DONE) return;
   }
-  const QuadTables<T> tb = quad_tables_load<T>(p, smem_raw);
+  const QuadTables<T> tb = quad_tables_load<T>(p, smem_raw, b);
   T* sm = reinterpret_cast<T*>(smem_raw + quad_tables_bytes(p, sizeof(T)));
   exit_part_instance<T, NX, NP, MU>(p, tb, sa, b, sm);
 }
@@ -1045,6 +1046,13 @@ struct ilqg_problem {
   int* d_cost_order = nullptr;
   int* d_row_prog = nullptr;
   std::vector<int> row_prog_host;  // the program as built (ilqg_problem_row_program)
+  // Per-instance cost parameters (ilqg.h): the term each op of the row program carries, the declared (term, field) list
+  // and its device side tables (the ops' columns behind the program in d_row_prog, DevProblem::inst_terms);
+  // dev.inst_values / inst_count are set while a table is bound, for `inst_batch` instances
+  std::vector<int> op_term;
+  std::vector<ilqg_instance_param> inst_params;
+  int* d_inst_terms = nullptr;
+  int inst_batch = 0;
   int static_prog = 0;             // id of the registered structure it matches (ilqg_rowprog_static.hpp), 0: none
   int* d_unfinished = nullptr;  // instances still running after an LQ-kernel launch
   int* h_unfinished = nullptr;  // pinned host mirror: [0..3] the counters, [8] the sequence number of read_round_counters
@@ -1680,10 +1688,13 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
       if (p->static_prog == ID_) {                                                                             \
         static_id = ID_;                                                                                       \
         static_in_regs = static_prog_in_registers<StaticRowProg<ID_>>();                                       \
-        k_rows = ilq_rows_kernel<T, NX, NP, MU, ID_>;                                                          \
-        k_prows = ilq_probe_rows_kernel<T, NX, NP, MU, ID_>;                                                   \
+        const bool bound = d.inst_values != nullptr; /* kernels of their own: the unbound ones are untouched */ \
+        k_rows = bound ? ilq_rows_kernel<T, NX, NP, MU, kBoundProg + ID_> : ilq_rows_kernel<T, NX, NP, MU, ID_>; \
+        k_prows = bound ? ilq_probe_rows_kernel<T, NX, NP, MU, kBoundProg + ID_>                               \
+                        : ilq_probe_rows_kernel<T, NX, NP, MU, ID_>;                                           \
         if (rows_state_in_registers(NX, NP * MU) && trial_lds_bytes<T>(d, W, 64, true) <= size_t(160) * 1024 / 4) { \
-          k_trial = ilq_trial_kernel<T, NX, NP, MU, W, ID_>;                                                   \
+          k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, kBoundProg + ID_>                               \
+                          : ilq_trial_kernel<T, NX, NP, MU, W, ID_>;                                           \
           static_prog = ID_;                                                                                   \
         }                                                                                                      \
       }
@@ -2522,6 +2533,7 @@ static ilqg_status problem_create_impl(const ilqg_problem_desc* desc, ilqg_probl
   }
   d.row_prog_words = int(rph.words.size());
   p->row_prog_host = rph.words;
+  p->op_term = rph.op_term;
   {
     // a registered structure (ilqg_rowprog_static.hpp)?  Word for word, parameters masked.
     std::vector<int> masked = rph.words;
@@ -2584,8 +2596,13 @@ static ilqg_status problem_create_impl(const ilqg_problem_desc* desc, ilqg_probl
     for (int i = 0; i < 16; i++) p->h_unfinished[i] = 0;
     if (hipHostGetDevicePointer((void**)&p->h_unfinished_dev, p->h_unfinished, 0) != hipSuccess) p->h_unfinished_dev = nullptr;
   }
-  if (e == hipSuccess) e = hipMalloc(&p->d_row_prog, sizeof(int) * rph.words.size());
-  if (e == hipSuccess) e = hipMemcpy(p->d_row_prog, rph.words.data(), sizeof(int) * rph.words.size(), hipMemcpyHostToDevice);
+  {
+    // the device image: the program, then the per-instance parameters' column of every op's weight / value (none: -1)
+    std::vector<int> image = rph.words;
+    image.resize(rph.words.size() + 2 * rph.op_term.size() + 2, -1);
+    if (e == hipSuccess) e = hipMalloc(&p->d_row_prog, sizeof(int) * image.size());
+    if (e == hipSuccess) e = hipMemcpy(p->d_row_prog, image.data(), sizeof(int) * image.size(), hipMemcpyHostToDevice);
+  }
   d.row_prog = p->d_row_prog;
   if (e != hipSuccess) {
     ilqg_problem_destroy(p);
@@ -2639,9 +2656,159 @@ void ilqg_problem_destroy(ilqg_problem* p) {
   if (p->d_tnom_d) (void)hipFree(p->d_tnom_d);
   if (p->d_cost_order) (void)hipFree(p->d_cost_order);
   if (p->d_row_prog) (void)hipFree(p->d_row_prog);
+  if (p->d_inst_terms) (void)hipFree(p->d_inst_terms);
   if (p->d_unfinished) (void)hipFree(p->d_unfinished);
   if (p->h_unfinished) (void)hipHostFree(p->h_unfinished);
   delete p;
+}
+
+// ---- per-instance cost parameters (ilqg.h) ----
+namespace {
+const char* cost_kind_name(int kind) {
+  switch (kind) {
+    case ILQG_COST_QUADRATIC: return "QUADRATIC";
+    case ILQG_COST_QUADRATIC_POLYLINE2: return "QUADRATIC_POLYLINE2";
+    case ILQG_COST_SEMIQUADRATIC: return "SEMIQUADRATIC";
+    case ILQG_COST_SEMIQUADRATIC_POLYLINE2: return "SEMIQUADRATIC_POLYLINE2";
+    case ILQG_COST_PROXIMITY: return "PROXIMITY";
+    case ILQG_COST_SIGNED_DISTANCE: return "SIGNED_DISTANCE";
+    case ILQG_COST_EXTREME_VALUE: return "EXTREME_VALUE";
+    case ILQG_CONSTRAINT_PROXIMITY: return "CONSTRAINT_PROXIMITY";
+    case ILQG_CONSTRAINT_SINGLE_DIMENSION: return "CONSTRAINT_SINGLE_DIMENSION";
+    case ILQG_COST_POLYLINE2_SIGNED_DISTANCE: return "POLYLINE2_SIGNED_DISTANCE";
+    case ILQG_COST_QUADRATIC_DIFFERENCE: return "QUADRATIC_DIFFERENCE";
+    case ILQG_COST_ORIENTATION: return "ORIENTATION";
+    case ILQG_COST_QUADRATIC_NORM: return "QUADRATIC_NORM";
+    case ILQG_COST_SEMIQUADRATIC_NORM: return "SEMIQUADRATIC_NORM";
+    case ILQG_COST_RELATIVE_DISTANCE: return "RELATIVE_DISTANCE";
+    case ILQG_COST_LOCALLY_CONVEX_PROXIMITY: return "LOCALLY_CONVEX_PROXIMITY";
+    case ILQG_COST_CURVATURE: return "CURVATURE";
+    case ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE: return "CONSTRAINT_POLYLINE2_SIGNED_DISTANCE";
+    case ILQG_COST_NOMINAL_PATH_LENGTH: return "NOMINAL_PATH_LENGTH";
+    case ILQG_COST_ROUTE_PROGRESS: return "ROUTE_PROGRESS";
+    case ILQG_COST_WEIGHTED_CONVEX_PROXIMITY: return "WEIGHTED_CONVEX_PROXIMITY";
+    case ILQG_CONSTRAINT_AFFINE_SCALAR: return "CONSTRAINT_AFFINE_SCALAR";
+    case ILQG_CONSTRAINT_AFFINE_VECTOR: return "CONSTRAINT_AFFINE_VECTOR";
+  }
+  return "unknown kind";
+}
+// Does a term of this kind read the field (the table of ilqg.h; ilqg_models.hpp: term_evaluate_leaf_of and the row ops)?
+// Null: yes; else why not.
+const char* instance_param_refusal(int kind, int field) {
+  const bool weight = field == ILQG_PARAM_WEIGHT;
+  switch (kind) {
+    case ILQG_COST_EXTREME_VALUE: return "an EXTREME_VALUE term has no parameters of its own: declare its children";
+    case ILQG_CONSTRAINT_AFFINE_SCALAR:
+    case ILQG_CONSTRAINT_AFFINE_VECTOR: return "the affine constraints keep their coefficients in dense blocks";
+    case ILQG_COST_NOMINAL_PATH_LENGTH:
+    case ILQG_COST_ROUTE_PROGRESS:
+      return weight ? nullptr : "its nominal speed is tabulated per time step when the problem is created";
+    case ILQG_COST_SIGNED_DISTANCE:
+    case ILQG_COST_POLYLINE2_SIGNED_DISTANCE: return weight ? "this kind does not read its weight" : nullptr;
+    case ILQG_CONSTRAINT_PROXIMITY:
+    case ILQG_CONSTRAINT_SINGLE_DIMENSION:
+    case ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE: return weight ? "a constraint has no weight" : nullptr;
+    case ILQG_COST_QUADRATIC_POLYLINE2:
+    case ILQG_COST_QUADRATIC_DIFFERENCE:
+    case ILQG_COST_RELATIVE_DISTANCE:
+    case ILQG_COST_CURVATURE: return weight ? nullptr : "this kind has no nominal or threshold";
+    case ILQG_COST_QUADRATIC:
+    case ILQG_COST_SEMIQUADRATIC:
+    case ILQG_COST_SEMIQUADRATIC_POLYLINE2:
+    case ILQG_COST_PROXIMITY:
+    case ILQG_COST_ORIENTATION:
+    case ILQG_COST_QUADRATIC_NORM:
+    case ILQG_COST_SEMIQUADRATIC_NORM:
+    case ILQG_COST_LOCALLY_CONVEX_PROXIMITY:
+    case ILQG_COST_WEIGHTED_CONVEX_PROXIMITY: return nullptr;
+  }
+  return "unknown cost kind";
+}
+ilqg_status instance_params_check_terms(int num_terms, const ilqg_cost_term* terms, int32_t count,
+                                        const ilqg_instance_param* params) {
+  if (count < 0 || count > ILQG_MAX_INSTANCE_PARAMS)
+    return fail(ILQG_ERR_INVALID, "instance parameters: count must be 0 .. ILQG_MAX_INSTANCE_PARAMS");
+  if (count > 0 && (!params || !terms)) return fail(ILQG_ERR_INVALID, "null argument");
+  for (int c = 0; c < count; c++) {
+    const int term = params[c].term, field = params[c].field;
+    const std::string where = "instance parameter " + std::to_string(c) + " (term " + std::to_string(term) + ", " +
+                              (field == ILQG_PARAM_WEIGHT ? "weight" : field == ILQG_PARAM_VALUE ? "value" : "field " + std::to_string(field)) + "): ";
+    if (term < 0 || term >= num_terms)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "term index out of range (the problem has " + std::to_string(num_terms) + " terms)");
+    if (field != ILQG_PARAM_WEIGHT && field != ILQG_PARAM_VALUE)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "not an ilqg_param_field");
+    for (int q = 0; q < c; q++)
+      if (params[q].term == term && params[q].field == field)
+        return fail(ILQG_ERR_UNSUPPORTED, where + "declared twice (also parameter " + std::to_string(q) + ")");
+    if (const char* why = instance_param_refusal(terms[term].kind, field))
+      return fail(ILQG_ERR_UNSUPPORTED, where + cost_kind_name(terms[term].kind) + ": " + why);
+  }
+  return ILQG_OK;
+}
+// A call that evaluates costs on `batch` instances while a table for another batch is bound would read past the table
+ilqg_status instance_batch_check(const ilqg_problem* p, int32_t batch) {
+  if (p->dev.inst_values && batch != p->inst_batch)
+    return fail(ILQG_ERR_INVALID, "per-instance parameter values are bound for a batch of " + std::to_string(p->inst_batch) +
+                                      ", this call has " + std::to_string(batch) + " instances");
+  return ILQG_OK;
+}
+}  // namespace
+
+ilqg_status ilqg_instance_params_check(const ilqg_problem_desc* desc, int32_t count, const ilqg_instance_param* params) {
+  if (!desc) return fail(ILQG_ERR_INVALID, "null argument");
+  return instance_params_check_terms(desc->num_terms, desc->terms, count, params);
+}
+
+ilqg_status ilqg_problem_declare_instance_params(ilqg_problem* p, int32_t count, const ilqg_instance_param* params) {
+  if (!p) return fail(ILQG_ERR_INVALID, "null argument");
+  if (p->dev.inst_values)
+    return fail(ILQG_ERR_INVALID, "instance parameters cannot be declared while values are bound: unbind first");
+  ilqg_status s = instance_params_check_terms(int(p->terms_host.size()), p->terms_host.data(), count, params);
+  if (s != ILQG_OK) return s;
+  // the row stage's side table: per op of the row program the column of its weight / value (the program is not touched)
+  std::vector<int> cols(p->op_term.size() * 2 + 2, -1), terms(size_t(count) * 2 + 2, 0);
+  for (int c = 0; c < count; c++) {
+    terms[2 * c] = params[c].term;
+    terms[2 * c + 1] = params[c].field;
+    for (size_t op = 0; op < p->op_term.size(); op++)
+      if (p->op_term[op] == params[c].term) cols[2 * op + (params[c].field == ILQG_PARAM_WEIGHT ? 0 : 1)] = c;
+  }
+  if (!p->d_row_prog) return fail(ILQG_ERR_INVALID, "a host-only problem handle has no device tables");
+  // kernels of earlier calls on any stream may still read the old tables (unbound: they look at neither)
+  hipError_t e = hipDeviceSynchronize();
+  int* d_terms = nullptr;
+  if (e == hipSuccess) e = hipMalloc(&d_terms, sizeof(int) * terms.size());
+  if (e == hipSuccess) e = hipMemcpy(d_terms, terms.data(), sizeof(int) * terms.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy(p->d_row_prog + p->row_prog_host.size(), cols.data(), sizeof(int) * cols.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (d_terms) (void)hipFree(d_terms);
+    return fail(ILQG_ERR_HIP, std::string("instance parameter tables: ") + hipGetErrorString(e));
+  }
+  if (p->d_inst_terms) (void)hipFree(p->d_inst_terms);
+  p->d_inst_terms = d_terms;
+  p->inst_params.assign(params, params + count);
+  return ILQG_OK;
+}
+
+ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, const float* values) {
+  if (!p) return fail(ILQG_ERR_INVALID, "null argument");
+  DevProblem& d = p->dev;
+  if (!values) {
+    d.inst_values = nullptr;
+    d.inst_terms = nullptr;
+    d.inst_count = 0;
+    p->inst_batch = 0;
+    return ILQG_OK;
+  }
+  if (p->inst_params.empty())
+    return fail(ILQG_ERR_INVALID, "no instance parameters are declared (ilqg_problem_declare_instance_params)");
+  if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance parameter values: batch must be positive");
+  d.inst_values = values;
+  d.inst_terms = p->d_inst_terms;
+  d.inst_count = int(p->inst_params.size());
+  p->inst_batch = batch;
+  return ILQG_OK;
 }
 
 ilqg_status ilqg_problem_pairs(const ilqg_problem* p, ilqg_pair* pairs_host, int32_t* npairs) {
@@ -2692,6 +2859,7 @@ ilqg_status ilqg_quadraticize_batch(const ilqg_problem* p, int32_t batch, const 
                                     void* R, void* r, const int32_t* active, void* stream) {
   if (!p || !xs || !us || !Q || !l || !R || !r) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch)) return sb;
   return launch_linquad(p, batch, xs, us, lambdas, mu, t_extreme, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
                         active, stream);
 }
@@ -2700,6 +2868,7 @@ ilqg_status ilqg_total_costs_batch(const ilqg_problem* p, int32_t batch, const v
                                    int32_t* t_extreme, const int32_t* active, void* stream) {
   if (!p || !xs || !us || !costs) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch)) return sb;
   const DevProblem& d = p->dev;
   const size_t esz = p->desc.dtype == ILQG_F32 ? 4 : 8;
   ilqg_status s = Scratch().reserve(size_t(batch) * d.T * d.N * esz);
@@ -2729,6 +2898,7 @@ ilqg_status ilqg_solve_batch_ex(ilqg_problem* p, int32_t batch, const void* x0, 
   if (!p || !x0 || !xs || !us || !P || !alpha || !total_costs || !iters || !status || !converged || !workspace || !options)
     return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch)) return sb;
   const ilqg_solve_options& o = *options;
   if (o.fixed_iters < 0) return fail(ILQG_ERR_INVALID, "fixed_iters must not be negative");
   if (o.forced_steps && (o.fixed_iters <= 0 || o.augmented_lagrangian))
@@ -2885,6 +3055,7 @@ ilqg_status ilqg_strategy_costs_batch(const ilqg_problem* p, int32_t batch, cons
                                       int32_t euler, void* costs, void* stream) {
   if (!p || !x0 || !xs || !us || !P || !alpha || !costs) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch)) return sb;
   return launch_strategy_costs(p, batch, x0, xs, us, P, alpha, 0.0, open_loop ? 1 : 0, euler ? 1 : 0, 1, costs, stream);
 }
 
@@ -2893,6 +3064,7 @@ ilqg_status ilqg_check_local_nash_batch(const ilqg_problem* p, int32_t batch, co
                                         int32_t open_loop, int32_t* is_nash, void* margin, void* stream) {
   if (!p || !x0 || !xs || !us || !P || !alpha || !is_nash) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch)) return sb;
   const DevProblem& d = p->dev;
   const int moves = 1 + 2 * d.m * (d.T - 1);
   if (moves > 65535) return fail(ILQG_ERR_UNSUPPORTED, "too many perturbations for one launch");
@@ -2918,8 +3090,10 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
                                              int32_t* is_psd, void* stream) {
   if (!p || !xs || !us || !is_psd) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch)) return sb;
   // PlayerCost::Quadraticize of every player at every step (:168-172), whatever the player's time structure: the
-  // quadraticisation kernel is launched on a copy of the problem whose players are all time-additive
+  // quadraticisation kernel is launched on a copy of the problem whose players are all time-additive (the copy carries
+  // the declared per-instance parameters and the bound table; each chunk below starts at its own row of it)
   ilqg_problem full = *p;
   for (int i = 0; i < full.dev.N; i++) full.dev.structure[i] = ILQG_SUM;
   const DevProblem& d = full.dev;
@@ -2941,6 +3115,7 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
     char* r = R + size_t(nb) * d.T * d.pairs.Rsz * esz;
     const char* xs_c = (const char*)xs + size_t(b0) * d.T * d.n * esz;
     const char* us_c = (const char*)us + size_t(b0) * d.T * d.m * esz;
+    if (p->dev.inst_values) full.dev.inst_values = p->dev.inst_values + size_t(b0) * p->dev.inst_count;
     s = launch_linquad(&full, nb, xs_c, us_c, nullptr, nullptr, nullptr, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
                        nullptr, stream);
     if (s != ILQG_OK) break;

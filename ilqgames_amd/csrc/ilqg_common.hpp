@@ -99,7 +99,22 @@ struct DevProblem {
   int rp_gslots;             // most gradient slots of a pass (numbered first: a merit-only evaluation keeps only these)
   int rp_maps_off, rp_maps_words;  // the program's word -> slot maps (copied into LDS by every workgroup)
   int rp_compact_off, rp_compact_w;  // compact rows (ilqg_rows.hpp): the block's offset in row_prog, words per row (0: none)
+  // Per-instance cost parameters (ilqg_problem_declare_instance_params / ilqg_problem_bind_instance_values): column c of
+  // row b of `inst_values` replaces the weight or the value of the declared term inst_terms[c] for instance b.  All null /
+  // 0 unless a table is bound: every reader then takes the baked parameters.  Read-only on the device.
+  const float* inst_values;  // [batch][inst_count], the caller's buffer
+  const int* inst_terms;     // [inst_count][2]: (term index, ilqg_param_field) (quad_tables_load)
+  // (the row stage's table — per op of row_prog the column of its weight / value, or -1 — follows the program's
+  // row_prog_words words in the device buffer `row_prog` points to)
+  int inst_count;
 };
+
+// Row b of the bound value table (null: nothing bound).  b is the instance a whole wavefront works on; the pointer is
+// formed from its first lane so that it lives in scalar registers wherever b came from.
+__device__ __forceinline__ const float* instance_values(const DevProblem& p, int b) {
+  if (!p.inst_values) return nullptr;
+  return p.inst_values + size_t(__builtin_amdgcn_readfirstlane(b)) * size_t(p.inst_count);
+}
 
 // arrays of a time step's image, as the row program's regions and the compact rows name them
 enum { RA_A = 0, RA_B = 1, RA_Q = 2, RA_L = 3, RA_R = 4, RA_r = 5 };

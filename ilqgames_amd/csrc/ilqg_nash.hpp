@@ -26,7 +26,7 @@ __host__ __device__ inline size_t strategy_cost_lds_elems(int n, int m, int num_
 template <typename T>
 __global__ void __launch_bounds__(64) strategy_costs_kernel(DevProblem p, StrategyCostArgs<T> a) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  const QuadTables<T> tb = quad_tables_load<T>(p, smem_raw);
+  const QuadTables<T> tb = quad_tables_load<T>(p, smem_raw, int(blockIdx.x));
   T* sx = reinterpret_cast<T*>(smem_raw + quad_tables_bytes(p, sizeof(T)));  // [x | u]
   const int n = p.n, m = p.m, N = p.N, Tn = p.T;
   T* snx = sx + n + m;       // [next x | u]

@@ -23,6 +23,8 @@ struct RowProgramHost {
   std::vector<int> words;  // the device image
   int num_pslots = 0, max_lslots = 0, max_gslots = 0, maps_off = 0, maps_words = 0;
   int compact_off = 0, compact_w = 0;  // the compact-row block (ilqg_rows.hpp: RP_OFF_COMPACT) and its row length
+  std::vector<int> op_term;  // per op, beside the image: the term whose weight / value the op carries (TERM, EXT_EVAL,
+                             // EXT_APPLY), -1 for the others — what a per-instance parameter of that term overrides
 };
 
 // `poly_off`: the problem's polyline offsets (points), host copy.
@@ -89,8 +91,10 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
   std::vector<int> passes, ops, sids, linit, regions, merit;
   std::vector<short> maps;
   int max_lslots = 0, max_gslots = 0;
+  std::vector<int> op_term;
   auto emit_op = [&](int mode, int sid_begin, int nsid, int aux, const DevTerm& c, const DevTerm& owner, int poly_first,
-                     int pattern_or_nseg) {
+                     int pattern_or_nseg, int term = -1) {
+    op_term.push_back(term);
     // `owner`: the top-level term whose role / player / constraint slot / first step apply (c itself, or the
     // ExtremeValueCost c is a child of)
     int o[ROP_WORDS] = {0};
@@ -300,13 +304,13 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
           for (int q = 0; q < c.child_count; q++) {
             const DevTerm& ch = dt[c.child_begin + q];
             want_closest(ch, c);
-            emit_op(ROP_EXT_EVAL, 0, 0, q, ch, c, 0, term_pattern_of(ch.kind, ch.idx[0]));
+            emit_op(ROP_EXT_EVAL, 0, 0, q, ch, c, 0, term_pattern_of(ch.kind, ch.idx[0]), c.child_begin + q);
           }
           for (int q = 0; q < c.child_count; q++) {
             const DevTerm& ch = dt[c.child_begin + q];
             want_closest(ch, c);
             const int b0 = leaf_sids(ch, c);
-            emit_op(ROP_EXT_APPLY, b0, int(sids.size()) - b0, q, ch, c, 0, term_pattern_of(ch.kind, ch.idx[0]));
+            emit_op(ROP_EXT_APPLY, b0, int(sids.size()) - b0, q, ch, c, 0, term_pattern_of(ch.kind, ch.idx[0]), c.child_begin + q);
           }
         } else if (c.kind == ILQG_COST_WEIGHTED_CONVEX_PROXIMITY) {
           // four ops (ilqg_models.hpp): the position block carries the value, then the speed block and the two
@@ -318,7 +322,7 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
           for (int q = 0; q < 4 && ok; q++) {
             const DevTerm sub = wcp_sub_term(c, ix, which[q]);
             const int b0 = leaf_sids(sub, c);
-            emit_op(ROP_TERM, b0, int(sids.size()) - b0, 0, sub, c, sub.polyline, term_pattern_of(sub.kind, sub.idx[0]));
+            emit_op(ROP_TERM, b0, int(sids.size()) - b0, 0, sub, c, sub.polyline, term_pattern_of(sub.kind, sub.idx[0]), ti);
           }
         } else if (term_is_affine(c.kind)) {
           // G and H slots as any leaf's, then 2 d scratch slots that no output word reads (the vector constraint's
@@ -334,7 +338,7 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
           want_closest(c, c);
           const int b0 = leaf_sids(c, c);
           emit_op(ROP_TERM, b0, int(sids.size()) - b0, 0, c, c, term_is_time_dependent(c.kind) ? c.polyline : 0,
-                  term_pattern_of(c.kind, c.idx[0]));
+                  term_pattern_of(c.kind, c.idx[0]), ti);
         }
       }
     if (!ok) { *err = "row program: a term's indices are out of range or not distinct"; return false; }
@@ -468,6 +472,7 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
   w[RP_WORDS] = int(w.size());
   out->num_pslots = NPS;
   out->max_lslots = max_lslots;
+  out->op_term = op_term;
   out->max_gslots = max_gslots;
   out->maps_off = w[RP_OFF_MAPS];
   out->maps_words = w[RP_MAPS_WORDS];

@@ -499,10 +499,19 @@ __device__ __forceinline__ Closest<T> polyline_closest_rows(typename ConstPtr<T>
 // immediate offset: kStaticRowStride elements between slots (the 64-row chunk's width + 1), 64 between image entries —
 // whatever the number of rows the chunk really holds (any width up to 64).
 constexpr int kStaticRowStride = 65;
+// Per-instance cost parameters (DevProblem::inst_values): a wavefront works on one instance, `iv` is that instance's row of
+// the bound table (QuadArgs::iv, null: nothing bound), and an op's weight / value come from its column of that row where
+// the op's term is declared — the column table [op] -> (weight column, value column), -1: the program's own word, follows
+// the row program's RP_WORDS words in its DEVICE image; the program itself is what the descriptor gives, whatever is
+// declared.  Everything is wave-uniform: scalar loads, scalar branches.  The interpreter patches the two lanes of the
+// descriptor it has fetched; the straight-line code exists in a second form, ProgStatic<ID, true>, whose ops read the
+// column table — kernels of their own, launched for a problem with a table bound, so that the unbound kernels are the
+// code they always were.
 struct ProgDynamic { static constexpr bool STATIC = false; };
 template <int ID> struct StaticRowProg;  // { static constexpr int kWords, w[kWords]; } per registered structure
-template <int ID> struct ProgStatic {
+template <int ID, bool BOUND = false> struct ProgStatic {
   static constexpr bool STATIC = true;
+  static constexpr bool kBound = BOUND;
   typedef StaticRowProg<ID> S;
 };
 
@@ -526,14 +535,23 @@ template <class S, int OP>
 struct SidsStatic {
   __device__ __forceinline__ constexpr int operator[](int e) const { return S::w[S::w[RP_OFF_OPS] + OP * ROP_WORDS + ROP_FIELDS + e]; }
 };
-template <class S, int OP>
+template <class S, int OP, bool BOUND = false>
 struct OpStatic {
   rp_cptr rt;  // this op's descriptor in the run-time program (parameters)
+  rp_cptr iv;  // BOUND: the instance's row of the per-instance parameters
+  rp_cptr cols;  // BOUND: this op's (weight, value) columns in it: an immediate offset from the program's base
   template <int F> __device__ __forceinline__ constexpr int field() const {
     constexpr int v = S::w[S::w[RP_OFF_OPS] + OP * ROP_WORDS + F];
     return v;
   }
-  template <int F> __device__ __forceinline__ int param() const { return rt[F]; }
+  template <int F> __device__ __forceinline__ int param() const {
+    constexpr int mode = S::w[S::w[RP_OFF_OPS] + OP * ROP_WORDS + RO_MODE];
+    if constexpr (BOUND && (F == RO_WEIGHT || F == RO_VALUE) && (mode == ROP_TERM || mode == ROP_EXT_EVAL || mode == ROP_EXT_APPLY)) {
+      const int c = cols[F == RO_WEIGHT ? 0 : 1];
+      if (c >= 0) return iv[c];
+    }
+    return rt[F];
+  }
   __device__ __forceinline__ SidsStatic<S, OP> sids() const { return SidsStatic<S, OP>{}; }
 };
 struct PassDynamic {
@@ -620,6 +638,7 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
   T* const acc = sm + (XREG ? 0 : NA) * ast;
   typedef typename std::conditional<XREG, MixArg<T>, RowArg<T>>::type Arg;
   const rp_cptr rp = (rp_cptr)p.row_prog;
+  const rp_cptr iv = (rp_cptr) reinterpret_cast<const int*>(a.iv);
   const typename ConstPtr<T>::type segs = (typename ConstPtr<T>::type)problem_segs<T>(p);
   // table offsets: compile-time under ProgStatic (the run-time program has the same layout: it matched word for word)
   auto hdr = [&](auto f) -> int {
@@ -892,7 +911,7 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
       if constexpr (ST) {
         static_for<PD::op_begin, PD::op_end>([&](auto opc) {
           constexpr int OP = decltype(opc)::value;
-          run_op(OpStatic<typename PROG::S, OP>{ops + OP * ROP_WORDS});
+          run_op(OpStatic<typename PROG::S, OP, PROG::kBound>{ops + OP * ROP_WORDS, iv, rp + (PROG::S::w[RP_WORDS] + OP * 2)});
         });
       } else {
         // An op's descriptor (ROP_WORDS words) is fetched as ONE vector load, word w by lane w, one op ahead, and its
@@ -904,8 +923,14 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
         int next_words = (lane < ROP_WORDS && op_begin < op_end) ? opsv[op_begin * ROP_WORDS + lane] : 0;
 #pragma unroll 1
         for (int op = op_begin; op < op_end; op++) {
-          const int words = next_words;
+          int words = next_words;
           if (op + 1 < op_end) next_words = lane < ROP_WORDS ? opsv[(op + 1) * ROP_WORDS + lane] : 0;
+          if (iv) {  // per-instance parameters: this instance's weight / value into their lanes of the descriptor
+            const rp_cptr icols = rp + rp[RP_WORDS];
+            const int wcol = icols[2 * op], vcol = icols[2 * op + 1];
+            if (wcol >= 0) words = lane == RO_WEIGHT ? iv[wcol] : words;
+            if (vcol >= 0) words = lane == RO_VALUE ? iv[vcol] : words;
+          }
           run_op(OpDynamic{words});
         }
       }

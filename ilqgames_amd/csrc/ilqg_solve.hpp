@@ -411,7 +411,7 @@ __host__ __device__ inline size_t trial_phase_lds_bytes(const DevProblem& p, int
 // What the rows of a pass are asked for, from the instance's state (the pass's rollout, if any, is done).
 template <typename T>
 __device__ __forceinline__ QuadArgs<T> trial_quad_args(const DevProblem& p, const InstanceBuffers<T>& ib,
-                                                       const SolveState<T>& s, bool compact) {
+                                                       const SolveState<T>& s, bool compact, int b) {
   const WsLayout& L = ib.L;
   T* const w = ib.w;
   const int qmode = s.qmode;
@@ -436,10 +436,14 @@ __device__ __forceinline__ QuadArgs<T> trial_quad_args(const DevProblem& p, cons
   qa.merit_part = qmode == Q_TRIAL ? w + L.mpart : nullptr;
   qa.cost_part = (qmode == Q_COSTS || qmode == Q_TRIAL || qmode == Q_LIN) ? w + L.cpart : nullptr;
   qa.phacc = nullptr;
+  qa.iv = instance_values(p, b);
   return qa;
 }
 
-template <int ID> struct RowProgSel { typedef ProgStatic<ID> type; };
+// PROGID of the row kernels: 0 = the interpreter, k = the straight-line code of registered structure k, kBoundProg + k =
+// the same for a problem with per-instance parameters bound (ilqg_rows.hpp: ProgStatic<k, true>)
+constexpr int kBoundProg = 1000;
+template <int ID> struct RowProgSel { typedef ProgStatic<(ID >= kBoundProg ? ID - kBoundProg : ID), (ID >= kBoundProg)> type; };
 template <> struct RowProgSel<0> { typedef ProgDynamic type; };
 
 // Row kernel of the split pass: one chunk of rows of instance b, one wave with its own scratch.
@@ -449,7 +453,7 @@ __device__ __forceinline__ void rows_part_instance(const DevProblem& p, const sh
                                                    int b, int chunk, T* sm) {
   const InstanceBuffers<T> ib(p, sa, b);
   const SolveState<T> s = state_load<T>(ib.w, ib.L);
-  const QuadArgs<T> qa = trial_quad_args<T>(p, ib, s, sa.compact != 0);
+  const QuadArgs<T> qa = trial_quad_args<T>(p, ib, s, sa.compact != 0, b);
   const int k0 = chunk * sa.rows_cw;
   const int nrows = p.T - k0 < sa.rows_cw ? p.T - k0 : sa.rows_cw;
   rows_chunk<T, NX, NP * MU, NP, rows_state_in_registers(NX, NP * MU), false, typename RowProgSel<PROGID>::type>(
@@ -596,6 +600,7 @@ __device__ __forceinline__ void probe_rows_instance(const DevProblem& p, const s
   qa.merit_part = e + E.mpart;
   qa.cost_part = nullptr;
   qa.phacc = nullptr;
+  qa.iv = instance_values(p, b);
   const int k0 = chunk * sa.rows_cw;
   const int nrows = p.T - k0 < sa.rows_cw ? p.T - k0 : sa.rows_cw;
   rows_chunk<T, NX, NP * MU, NP, rows_state_in_registers(NX, NP * MU), true, typename RowProgSel<PROGID>::type>(
@@ -889,7 +894,7 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
     // ---- linearise / quadraticise the trajectory: every wave claims rows as they become ready ----
     const int qmode = s.qmode;
     if constexpr (PHASE == TRIAL_FUSED) {
-    QuadArgs<T> qa = trial_quad_args<T>(p, ib, s, sa.compact != 0);
+    QuadArgs<T> qa = trial_quad_args<T>(p, ib, s, sa.compact != 0, b);
     qa.phacc = (kProfile && sa.prof) ? qph : nullptr;
     qa.tl = kTimeline ? sa.prof : nullptr;
     qa.tl_b = b;

@@ -467,8 +467,10 @@ __host__ __device__ inline size_t quad_tables_bytes(const DevProblem& p, size_t 
 }
 
 // Cooperative copy of the tables into LDS; every thread of the workgroup calls, then syncs.
+// `inst`: the instance the workgroup works on — with per-instance parameters bound (DevProblem::inst_values) the weight /
+// value of the declared terms of the LDS copy are that instance's.
 template <typename T>
-__device__ __forceinline__ QuadTables<T> quad_tables_load(const DevProblem& p, void* region) {
+__device__ __forceinline__ QuadTables<T> quad_tables_load(const DevProblem& p, void* region, int inst) {
   const int t = threadIdx.x, NT = blockDim.x;
   T* segs = reinterpret_cast<T*>(region);
   const T* gsegs = problem_segs<T>(p);
@@ -503,6 +505,15 @@ __device__ __forceinline__ QuadTables<T> quad_tables_load(const DevProblem& p, v
     lc[LC_FROMCOST + t] = p.pairs.from_cost[t];
   }
   __syncthreads();
+  if (const float* iv = instance_values(p, inst)) {
+    constexpr int TW = int(sizeof(DevTerm) / sizeof(int));
+    for (int c = t; c < p.inst_count; c += NT) {
+      const int term = p.inst_terms[2 * c], field = p.inst_terms[2 * c + 1];
+      const int word = int((field == ILQG_PARAM_WEIGHT ? offsetof(DevTerm, weight) : offsetof(DevTerm, value)) / sizeof(int));
+      terms_i[term * TW + word] = __float_as_int(iv[c]);
+    }
+    __syncthreads();
+  }
   QuadTables<T> tb;
   tb.terms = reinterpret_cast<const DevTerm*>(terms_i);
   tb.segs = segs;
@@ -529,6 +540,7 @@ struct QuadArgs {
   bool compact_lin = false, compact_quad = false;  // ... of the linearisation (A, Bm) / of the quadraticisation (Q, l, R, r)
   T* merit_part;       // [T][N][2] = (|r_ii|^2, |l_i|^2) or nullptr
   T* cost_part;        // [T][N] PlayerCost::Evaluate or nullptr
+  const float* iv = nullptr;  // this instance's row of the bound per-instance parameters (instance_values) or nullptr
   long long* phacc = nullptr;  // optional phase profile accumulators (registers of the caller)
   long long* tl = nullptr;     // optional timeline stamps (ilqg_common.hpp, -DILQG_TIMELINE=1): slots 40.. of instance tl_b
   int tl_b = 0;

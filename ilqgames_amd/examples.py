@@ -18,7 +18,9 @@ from .abi import (DYN_CAR_5D, DYN_CAR_6D, DYN_DUBINS_CAR, DYN_PLANAR_DISTURBANCE
 def _lane_costs(spec, player, lane, xy, lane_w, boundary_w, half_width):
     # QuadraticPolyline2Cost + right/left SemiquadraticPolyline2Cost, e.g.
     # src/modified_three_player_intersection_example.cpp:196-209
-    spec.quadratic_polyline2(player, lane_w, lane, xy)
+    # (terms that scenes name — "p<player+1>_lane" here — are reachable through ProblemSpec.term_index: what the
+    # per-instance parameters are declared by; names change no descriptor)
+    spec.name_term("p%d_lane" % (player + 1), spec.quadratic_polyline2(player, lane_w, lane, xy))
     spec.semiquadratic_polyline2(player, boundary_w, lane, xy, half_width, True)
     spec.semiquadratic_polyline2(player, boundary_w, lane, xy, -half_width, False)
 
@@ -51,17 +53,14 @@ def modified_three_player_intersection(T=100, dt=0.1):
     for pl, vidx, vmax, vnom in ((0, P1V, 12.0, 8.0), (1, P2V, 12.0, 6.0), (2, P3V, 2.0, 1.5)):
         s.semiquadratic(pl, 100.0, vidx, 1.0, False)   # MinV
         s.semiquadratic(pl, 100.0, vidx, vmax, True)   # MaxV
-        s.quadratic(pl, 10.0, vidx, vnom)              # NominalV
+        s.name_term("p%d_nominal_speed" % (pl + 1), s.quadratic(pl, 10.0, vidx, vnom))  # NominalV
     for pl in range(3):
         s.quadratic(pl, 0.1, 0, 0.0, control_of=pl)
         s.quadratic(pl, 0.1, 1, 0.0, control_of=pl)
     w = 0.0  # kProximityCostWeight = 0.0 (:89)
-    s.proximity(0, w, (P1X, P1Y), (P2X, P2Y), 6.0)
-    s.proximity(0, w, (P1X, P1Y), (P3X, P3Y), 6.0)
-    s.proximity(1, w, (P2X, P2Y), (P1X, P1Y), 6.0)
-    s.proximity(1, w, (P2X, P2Y), (P3X, P3Y), 6.0)
-    s.proximity(2, w, (P3X, P3Y), (P1X, P1Y), 6.0)
-    s.proximity(2, w, (P3X, P3Y), (P2X, P2Y), 6.0)
+    xy = ((P1X, P1Y), (P2X, P2Y), (P3X, P3Y))
+    for a, b in ((0, 1), (0, 2), (1, 0), (1, 2), (2, 0), (2, 1)):
+        s.name_term("p%d_proximity_p%d" % (a + 1, b + 1), s.proximity(a, w, xy[a], xy[b], 6.0))
     x0 = np.zeros(14)
     x0[[P1X, P1Y, P1H, P1V]] = [p1x0, p1y0, np.float32(math.pi / 2), 4.0]
     x0[[P2X, P2Y, P2H, P2V]] = [p2x0, p2y0, np.float32(-math.pi / 2), 3.0]
@@ -185,7 +184,7 @@ def roundabout_merging(T=100, dt=0.1, open_loop=True):
         V = 6 * i + 4
         s.semiquadratic(i, 1000.0, V, 1.0, False)
         s.semiquadratic(i, 1000.0, V, 12.0, True)
-        s.quadratic(i, 10.0, V, 10.0)
+        s.name_term("p%d_nominal_speed" % (i + 1), s.quadratic(i, 10.0, V, 10.0))
     for i in range(4):
         s.quadratic(i, 50.0, 5, 0.0)  # every player uses kP1AIdx (:356-365), reproduced
     for i in range(4):
@@ -195,8 +194,8 @@ def roundabout_merging(T=100, dt=0.1, open_loop=True):
     def xy(i):
         return (6 * i, 6 * i + 1)
     for i, (a, b) in enumerate(((1, 3), (0, 2), (1, 3), (0, 2))):  # :395-436 (which pairs are ADDED)
-        s.proximity(i, 100.0, xy(i), xy(a), 6.0)
-        s.proximity(i, 100.0, xy(i), xy(b), 6.0)
+        s.name_term("p%d_proximity_p%d" % (i + 1, a + 1), s.proximity(i, 100.0, xy(i), xy(a), 6.0))
+        s.name_term("p%d_proximity_p%d" % (i + 1, b + 1), s.proximity(i, 100.0, xy(i), xy(b), 6.0))
     s.x0 = x0
     return s
 
@@ -220,10 +219,10 @@ def three_player_collision_avoidance_reachability(T=100, dt=0.1, d0=5.0, v0=5.0,
     for i in range(3):
         s.quadratic(i, 0.1, -1, 0.0, control_of=i)
     for i in range(3):
-        s.single_dimension_constraint(i, 0, 1.0, True, control_of=i)
-        s.single_dimension_constraint(i, 0, -1.0, False, control_of=i)
-        s.single_dimension_constraint(i, 1, 0.1, True, control_of=i)
-        s.single_dimension_constraint(i, 1, -0.1, False, control_of=i)
+        s.name_term("p%d_u0_max" % (i + 1), s.single_dimension_constraint(i, 0, 1.0, True, control_of=i))
+        s.name_term("p%d_u0_min" % (i + 1), s.single_dimension_constraint(i, 0, -1.0, False, control_of=i))
+        s.name_term("p%d_u1_max" % (i + 1), s.single_dimension_constraint(i, 1, 0.1, True, control_of=i))
+        s.name_term("p%d_u1_min" % (i + 1), s.single_dimension_constraint(i, 1, -0.1, False, control_of=i))
 
     def sd(a, b):
         return lambda role: s.signed_distance(-1, (X[a], Y[a]), (X[b], Y[b]), buffer, True, role=role)
@@ -233,6 +232,8 @@ def three_player_collision_avoidance_reachability(T=100, dt=0.1, d0=5.0, v0=5.0,
         s.extreme_value(i, children[i], is_min=False)
         for t in s.terms[begin:]:
             t["player"] = i
+        for q in range(len(children[i])):
+            s.name_term("p%d_distance_child%d" % (i + 1, q), begin + q)
     x0 = np.zeros(15)
     pert = 0.1
     f = np.float32
@@ -273,17 +274,19 @@ def three_player_intersection_reachability(T=100, dt=0.1):
     for pl, vidx, vmax, vnom in ((1, P2V, 12.0, 6.0), (2, P3V, 2.0, 1.5)):
         s.semiquadratic(pl, 100.0, vidx, 1.0, False)   # MinV
         s.semiquadratic(pl, 100.0, vidx, vmax, True)   # MaxV
-        s.quadratic(pl, 10.0, vidx, vnom)              # NominalV
+        s.name_term("p%d_nominal_speed" % (pl + 1), s.quadratic(pl, 10.0, vidx, vnom))  # NominalV
     for pl in range(3):
         s.quadratic(pl, 0.1, 0, 0.0, control_of=pl)
         s.quadratic(pl, 0.1, 1, 0.0, control_of=pl)
-    s.proximity(1, 0.0, (P2X, P2Y), (P1X, P1Y), 6.0)
-    s.proximity(1, 0.0, (P2X, P2Y), (P3X, P3Y), 6.0)
-    s.proximity(2, 0.0, (P3X, P3Y), (P1X, P1Y), 6.0)
-    s.proximity(2, 0.0, (P3X, P3Y), (P2X, P2Y), 6.0)
+    s.name_term("p2_proximity_p1", s.proximity(1, 0.0, (P2X, P2Y), (P1X, P1Y), 6.0))
+    s.name_term("p2_proximity_p3", s.proximity(1, 0.0, (P2X, P2Y), (P3X, P3Y), 6.0))
+    s.name_term("p3_proximity_p1", s.proximity(2, 0.0, (P3X, P3Y), (P1X, P1Y), 6.0))
+    s.name_term("p3_proximity_p2", s.proximity(2, 0.0, (P3X, P3Y), (P2X, P2Y), 6.0))
     begin = len(s.terms)
     s.extreme_value(0, [lambda role: s.signed_distance(0, (P1X, P1Y), (P2X, P2Y), 6.0, True, role=role),
                         lambda role: s.signed_distance(0, (P1X, P1Y), (P3X, P3Y), 6.0, True, role=role)], is_min=False)
+    s.name_term("p1_distance_p2", begin)
+    s.name_term("p1_distance_p3", begin + 1)
     f = np.float32
     x0 = np.zeros(14)
     x0[[P1X, P1Y, P1H, P1V]] = [-2.0, -30.0, float(f(np.pi / 2)), 4.0]
@@ -799,21 +802,21 @@ def mixed_dubins_car_scene(T=100, dt=0.1, open_loop=False, constrained=False):
     DX, DY, DH = 0, 1, 2
     CX, CY, CH, CPHI, CV = 3, 4, 5, 6, 7
     lane = s.add_polyline([(-50.0, -2.0), (0.0, -2.0), (20.0, 2.0), (80.0, 2.0)])
-    s.quadratic(0, 2.0, DX, 12.0)
-    s.quadratic(0, 2.0, DY, 3.0)
-    s.proximity(0, 20.0, (DX, DY), (CX, CY), 4.0)
+    s.name_term("p1_goal_x", s.quadratic(0, 2.0, DX, 12.0))
+    s.name_term("p1_goal_y", s.quadratic(0, 2.0, DY, 3.0))
+    s.name_term("p1_proximity_p2", s.proximity(0, 20.0, (DX, DY), (CX, CY), 4.0))
     s.quadratic(0, 5.0, 0, 0.0, control_of=0)
-    s.quadratic_polyline2(1, 10.0, lane, (CX, CY))
-    s.quadratic(1, 4.0, CV, 6.0)
+    s.name_term("p2_lane", s.quadratic_polyline2(1, 10.0, lane, (CX, CY)))
+    s.name_term("p2_nominal_speed", s.quadratic(1, 4.0, CV, 6.0))
     s.semiquadratic(1, 50.0, CPHI, 0.4, True)
-    s.proximity(1, 20.0, (CX, CY), (DX, DY), 4.0)
+    s.name_term("p2_proximity_p1", s.proximity(1, 20.0, (CX, CY), (DX, DY), 4.0))
     s.quadratic(1, 5.0, 0, 0.0, control_of=1)
     s.quadratic(1, 2.0, 1, 0.0, control_of=1)
     s.quadratic(1, 0.5, 0, 0.0, control_of=0)  # the car's cost sees the Dubins car's turn rate: an (1, 0) block
     if constrained:
-        s.single_dimension_constraint(0, 0, 1.2, True, control_of=0)
-        s.single_dimension_constraint(1, CV, 8.0, True)
-        s.proximity_constraint(1, (CX, CY), (DX, DY), 2.0, False)
+        s.name_term("p1_turn_rate_max", s.single_dimension_constraint(0, 0, 1.2, True, control_of=0))
+        s.name_term("p2_speed_max", s.single_dimension_constraint(1, CV, 8.0, True))
+        s.name_term("p2_clearance_p1", s.proximity_constraint(1, (CX, CY), (DX, DY), 2.0, False))
     s.x0 = [0.0, 4.0, float(np.float32(-0.4)), -10.0, -2.0, 0.0, 0.0, 5.0]
     s.position_dims, s.heading_dims, s.speed_dims = [(DX, DY), (CX, CY)], [DH, CH], [None, CV]
     return s

@@ -24,6 +24,7 @@ EXPORTS = [
     "ilqg_check_local_nash_batch", "ilqg_check_sufficient_nash_batch",
     "ilqg_receding_horizon_shift_batch", "ilqg_default_solve_options", "ilqg_solve_batch_ex", "ilqg_solve_state_batch",
     "ilqg_set_scratch", "ilqg_problem_last_schedule", "ilqg_copy_bandwidth", "ilqg_problem_row_program", "ilqg_row_program_build",
+    "ilqg_problem_declare_instance_params", "ilqg_problem_bind_instance_values", "ilqg_instance_params_check",
 ]
 
 
@@ -161,6 +162,25 @@ def row_program_build(spec, dtype=abi.F64):
     return w, int(sid.value)
 
 
+def _instance_params(spec, params):
+    """[(term, "weight" | "value"), ...] -> (ilqg_instance_param array, count); a term is an index into the spec's
+    terms or a name given to it (ProblemSpec.term_index)."""
+    arr = (abi.InstanceParam * max(1, len(params)))()
+    for c, (term, field) in enumerate(params):
+        arr[c].term = spec.term_index(term) if isinstance(term, str) else int(term)
+        arr[c].field = abi.PARAM_FIELDS[field] if isinstance(field, str) else int(field)
+    return arr, len(params)
+
+
+def instance_params_check(spec, params, dtype=abi.F64):
+    """ilqg_instance_params_check: raises IlqgError where Problem.declare_instance_params would — host only, no device
+    needed."""
+    desc, keep = spec.build(dtype)
+    arr, count = _instance_params(spec, params)
+    _check(lib().ilqg_instance_params_check(C.byref(desc), count, arr))
+    del keep
+
+
 class Problem:
     """Owns an ilqg_problem* (device tables of one reference `Problem`)."""
 
@@ -192,6 +212,33 @@ class Problem:
     def _empty(self, *shape):
         import torch
         return torch.empty(shape, dtype=torch_dtype(self.dtype), device="cuda")
+
+    # ---- per-instance cost parameters (ilqg.h) ----
+    def declare_instance_params(self, params):
+        """ilqg_problem_declare_instance_params: params = [(term, "weight" | "value"), ...], a term being its index in
+        the spec or its name; column c of the table bind_instance_values binds overrides params[c].  [] clears."""
+        arr, count = _instance_params(self.spec, params)
+        _check(lib().ilqg_problem_declare_instance_params(self.h, count, arr))
+        self.instance_params = [(int(arr[c].term), int(arr[c].field)) for c in range(count)]
+
+    def bind_instance_values(self, values):
+        """ilqg_problem_bind_instance_values: a float32 [B][count] table (uploaded if it is not a CUDA tensor), read by
+        every later call on this problem until bind_instance_values(None); the tensor is kept alive while bound and
+        returned — a CUDA float32 tensor passed in is bound as it is, so the caller may rewrite it between calls."""
+        import torch
+        if values is None:
+            _check(lib().ilqg_problem_bind_instance_values(self.h, 0, None))
+            self._instance_values = None
+            return None
+        if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float32 and
+                values.is_contiguous()):
+            values = torch.as_tensor(np.ascontiguousarray(values, dtype=np.float32), device="cuda").contiguous()
+        count = len(getattr(self, "instance_params", []))
+        if values.dim() != 2 or values.shape[1] != count:
+            raise ValueError("instance values must be [batch][%d], got %s" % (count, tuple(values.shape)))
+        _check(lib().ilqg_problem_bind_instance_values(self.h, values.shape[0], C.c_void_p(values.data_ptr())))
+        self._instance_values = values
+        return values
 
     def rollout(self, x0, xs_ref, us_ref, P, alpha, alpha_scale=None):
         x0, xs_ref, us_ref, P, alpha, alpha_scale = [_dev(v, self.dtype) for v in

@@ -426,6 +426,7 @@ class Packer {
     td.term.arg = arg;
     td.term.constraint_slot = is_constraint ? out_->num_constraints++ : -1;
     out_->terms.push_back(td.term);
+    out_->term_objects.push_back(&cost);
     return true;
   }
 
@@ -452,6 +453,24 @@ class Packer {
 };
 
 }  // namespace
+
+bool ResolveInstanceParams(const ProblemDescription& description, const InstanceParams& params,
+                           std::vector<ilqg_instance_param>* out, std::string* why) {
+  std::string scratch;
+  if (why == nullptr) why = &scratch;
+  out->clear();
+  for (size_t c = 0; c < params.params.size(); c++) {
+    int term = -1;
+    for (size_t q = 0; q < description.term_objects.size() && term < 0; q++)
+      if (description.term_objects[q] == params.params[c].term) term = static_cast<int>(q);
+    if (term < 0) {
+      *why = "instance parameter " + std::to_string(c) + " names an object that is no cost or constraint of the problem";
+      return false;
+    }
+    out->push_back(ilqg_instance_param{term, static_cast<int32_t>(params.params[c].field)});
+  }
+  return true;
+}
 
 bool DescribeDynamics(const MultiPlayerIntegrableSystem& dynamics, ilqg_problem_desc* d, std::string* why) {
   std::string scratch;
@@ -863,6 +882,18 @@ void ShardContext::AllGather(const void* send, void* recv, size_t bytes_per_rank
 }
 
 class DeviceSolve {
+  // unbinds (and clears the declaration) when the solve that bound a table returns
+  struct InstanceBinding {
+    explicit InstanceBinding(ilqg_problem* h) : handle(h) {}
+    ~InstanceBinding() {
+      if (!bound) return;
+      (void)ilqg_problem_bind_instance_values(handle, 0, nullptr);
+      (void)ilqg_problem_declare_instance_params(handle, 0, nullptr);
+    }
+    ilqg_problem* handle;
+    bool bound = false;
+  };
+
  public:
   DeviceSolve(const Problem& problem, const SolverParams& params) : dtype_(Options().dtype) {
     CheckSupportedParams(params);
@@ -895,9 +926,28 @@ class DeviceSolve {
   BatchResult Run(const std::vector<VectorXf>& x0s, const OperatingPoint& warm_op,
                   const std::vector<Strategy>& warm_strategies, bool augmented_lagrangian,
                   bool repeat_single = false, const ShardContext* shard = nullptr, size_t total = 0,
-                  Time max_runtime = std::numeric_limits<Time>::infinity()) {
+                  Time max_runtime = std::numeric_limits<Time>::infinity(), const InstanceParams* instance_params = nullptr,
+                  size_t first_row = 0) {
     size_t B = x0s.size();
     CHECK_GT(B, 0);
+    // per-instance cost parameters: rows [first_row, first_row + B) of the caller's table, bound for this solve only
+    InstanceBinding binding(handle_);
+    if (instance_params != nullptr && !instance_params->params.empty()) {
+      std::vector<ilqg_instance_param> declared;
+      std::string why;
+      CHECK(ResolveInstanceParams(description_, *instance_params, &declared, &why)) << why;
+      const size_t count = declared.size();
+      CHECK_GE(instance_params->values.size(), (first_row + B) * count) << "instance parameter values: one row per instance";
+      CHECK_EQ(ilqg_problem_declare_instance_params(handle_, static_cast<int32_t>(count), declared.data()), ILQG_OK)
+          << ilqg_last_error();
+      const float* rows = instance_params->values.data() + first_row * count;
+      HipCheck(hipMemcpy(d_instance_values_.Reserve(B * count * sizeof(float)), rows, B * count * sizeof(float),
+                         hipMemcpyHostToDevice), "instance parameter values");
+      CHECK_EQ(ilqg_problem_bind_instance_values(handle_, static_cast<int32_t>(B),
+                                                 static_cast<const float*>(d_instance_values_.get())), ILQG_OK)
+          << ilqg_last_error();
+      binding.bound = true;
+    }
     const auto start = Clock::now();
     // pack the warm start once, replicate per instance
     std::vector<float> x0(B * n_), xs(B * T_ * n_), us(B * T_ * m_), P(B * T_ * m_ * n_), alpha(B * T_ * m_);
@@ -1094,7 +1144,7 @@ class DeviceSolve {
   int n_ = 0, m_ = 0, N_ = 0, T_ = 0;
   std::vector<int> udims_;
   bool solved_single_ = false, last_kind_ = false;
-  DeviceBuffer d_x0_, d_xs_, d_us_, d_P_, d_alpha_, d_costs_, d_iters_, d_status_, d_conv_, d_workspace_;
+  DeviceBuffer d_x0_, d_xs_, d_us_, d_P_, d_alpha_, d_costs_, d_iters_, d_status_, d_conv_, d_workspace_, d_instance_values_;
   DeviceBuffer d_log_xs_, d_log_us_, d_log_costs_, d_log_P_, d_log_alpha_, d_log_count_;
 };
 
@@ -1817,6 +1867,24 @@ void GameSolver::RefreshDevice() {
 host::BatchResult GameSolver::SolveBatch(const std::vector<VectorXf>& x0s) {
   RefreshDevice();
   return device_->Run(x0s, problem_->CurrentOperatingPoint(), problem_->CurrentStrategies(), augmented_lagrangian_);
+}
+
+host::BatchResult GameSolver::SolveBatch(const std::vector<VectorXf>& x0s, const host::InstanceParams& instance_params) {
+  RefreshDevice();
+  return device_->Run(x0s, problem_->CurrentOperatingPoint(), problem_->CurrentStrategies(), augmented_lagrangian_,
+                      /*repeat_single=*/false, nullptr, 0, std::numeric_limits<Time>::infinity(), &instance_params, 0);
+}
+
+host::BatchResult GameSolver::SolveBatchSharded(const std::vector<VectorXf>& x0s, const host::InstanceParams& instance_params,
+                                                const host::ShardContext& shard) {
+  RefreshDevice();
+  size_t lo, hi;
+  host::InstanceRange(x0s.size(), shard.Info().rank, shard.Info().world, &lo, &hi);
+  CHECK_GT(hi, lo) << "a sharded batch needs at least one instance per rank";
+  const std::vector<VectorXf> mine(x0s.begin() + lo, x0s.begin() + hi);
+  return device_->Run(mine, problem_->CurrentOperatingPoint(), problem_->CurrentStrategies(), augmented_lagrangian_,
+                      /*repeat_single=*/false, &shard, x0s.size(), std::numeric_limits<Time>::infinity(),
+                      &instance_params, lo);
 }
 
 host::BatchResult GameSolver::SolveBatchSharded(const std::vector<VectorXf>& x0s, const host::ShardContext& shard) {

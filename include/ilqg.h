@@ -309,6 +309,62 @@ typedef struct ilqg_problem ilqg_problem;
 ilqg_status ilqg_problem_create(const ilqg_problem_desc* desc, ilqg_problem** out);
 void ilqg_problem_destroy(ilqg_problem* p);
 
+/* ---- Per-instance cost parameters --------------------------------------------------------------------------------
+ * A batch is thousands of games in one launch; by default they differ in x0 (and warm start) alone.  With a value table
+ * bound to the handle, instance b of every later call evaluates the declared terms with row b of the table in place of
+ * ilqg_cost_term::weight / value — different goals, nominal speeds, weights and thresholds in one batch.  The reference
+ * has no counterpart: one Problem there is one game.
+ *
+ * The table is bound to the PROBLEM because ilqg_solve_again_batch, ilqg_quadraticize_batch, ilqg_total_costs_batch and
+ * the Nash checks take no options struct and must all see the same game.  Every entry point that evaluates a cost
+ * honours it: ilqg_solve_batch_ex and the three calls that are it (every mode), ilqg_quadraticize_batch,
+ * ilqg_total_costs_batch, ilqg_strategy_costs_batch, ilqg_check_local_nash_batch, ilqg_check_sufficient_nash_batch; each
+ * of them returns ILQG_ERR_INVALID, before anything is launched, when its `batch` is not the bound one.  Entry points
+ * that evaluate no cost (rollout, linearize, the LQ sweeps, receding-horizon shift / sync / splice, plan integrate) are
+ * unaffected.  No scheduling choice depends on a binding; the row program (ilqg_problem_row_program) and the static
+ * structure it matched are those of the descriptor.
+ *
+ * Values are float, like the descriptor's, and are converted to the problem's arithmetic where the baked value is: an
+ * overridden instance computes, bit for bit, what a problem created with that float in its descriptor computes.
+ *
+ * What may be declared — `term` indexes ilqg_problem_desc::terms (top-level terms and the children of an EXTREME_VALUE):
+ *   kind                                   weight   value
+ *   QUADRATIC, SEMIQUADRATIC               yes      yes (nominal / threshold)
+ *   SEMIQUADRATIC_POLYLINE2                yes      yes
+ *   QUADRATIC_POLYLINE2                    yes      no  (has none)
+ *   PROXIMITY, LOCALLY_CONVEX_PROXIMITY,
+ *   WEIGHTED_CONVEX_PROXIMITY              yes      yes (threshold)
+ *   ORIENTATION, QUADRATIC_NORM,
+ *   SEMIQUADRATIC_NORM                     yes      yes
+ *   QUADRATIC_DIFFERENCE, CURVATURE,
+ *   RELATIVE_DISTANCE                      yes      no  (has none)
+ *   NOMINAL_PATH_LENGTH, ROUTE_PROGRESS    yes      no  (tabulated per step by ilqg_problem_create)
+ *   SIGNED_DISTANCE,
+ *   POLYLINE2_SIGNED_DISTANCE              no       yes (the weight is not read)
+ *   CONSTRAINT_PROXIMITY, _SINGLE_DIMENSION,
+ *   _POLYLINE2_SIGNED_DISTANCE             no       yes (threshold; a constraint has no weight)
+ *   EXTREME_VALUE                          no       no  (declare its children)
+ *   CONSTRAINT_AFFINE_SCALAR / _VECTOR     no       no  (dense coefficient blocks)
+ * Anything else — a "no" above, a term index out of range, a field that is not an ilqg_param_field, the same (term,
+ * field) twice — is ILQG_ERR_UNSUPPORTED with the term named in ilqg_last_error(); nothing is ever silently ignored.
+ * Out of scope: value2, polyline geometry, subsystem parameters, regularisation, solver parameters. */
+typedef enum { ILQG_PARAM_WEIGHT = 0, ILQG_PARAM_VALUE = 1 } ilqg_param_field;
+typedef struct {
+  int32_t term;  /* index into ilqg_problem_desc::terms */
+  int32_t field; /* ilqg_param_field */
+} ilqg_instance_param;
+#define ILQG_MAX_INSTANCE_PARAMS 256
+
+/* Which (term, field) pairs vary per instance: column c of the value table overrides params[c].  count = 0 clears the
+ * declaration.  ILQG_ERR_INVALID while a table is bound (unbind first). */
+ilqg_status ilqg_problem_declare_instance_params(ilqg_problem* p, int32_t count, const ilqg_instance_param* params);
+/* values: device float [batch][count], or NULL to unbind.  The table is READ AT EVERY LATER CALL on this handle, not
+ * copied: the caller may rewrite it between calls (in stream order with them) and keeps it alive while it is bound.
+ * ILQG_ERR_INVALID without a declaration, or with batch <= 0. */
+ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, const float* values);
+/* Host only, no device needed: the checks of the declare call against a descriptor. */
+ilqg_status ilqg_instance_params_check(const ilqg_problem_desc* desc, int32_t count, const ilqg_instance_param* params);
+
 /* Bytes of device workspace a solve of `batch` instances needs: the per-instance iterates, linearisations and
  * loop states, the lists of back-tracking instances and the pool of the speculative line search.  A solve
  * allocates nothing. */
@@ -669,7 +725,9 @@ const char* ilqg_last_error(void);
 ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
 
 /* Library / device introspection (used by the loader to fail loudly). */
-#define ILQG_ABI_VERSION 8 /* 8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
+#define ILQG_ABI_VERSION 9 /* 9: per-instance cost parameters (ilqg_instance_param, ilqg_problem_declare_instance_params,
+                                 ilqg_problem_bind_instance_values, ilqg_instance_params_check);
+                              8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;
                               6: ilqg_problem_last_schedule;

@@ -1051,7 +1051,27 @@ struct ProblemDescription {
   std::vector<ilqg_pair> pairs;  // (i, j) control blocks in PlayerCost first-touch order
   int num_constraints = 0;
   std::vector<float> dense_params;  // coefficient blocks of the affine constraints
+  std::vector<const Cost*> term_objects;  // per term: the Cost / Constraint object it was flattened from
 };
+
+// Per-instance cost parameters of a batched solve (include/ilqg.h; an EXTENSION: one reference Problem is one game).
+// `params` names what varies — the weight or the value (nominal / threshold) of a Cost or Constraint object of the
+// Problem, by address; the flattener resolves each to its term index — and `values` holds one row per instance,
+// column c overriding params[c]: [x0s.size()][params.size()], row-major.
+struct InstanceParams {
+  struct Param {
+    const Cost* term;        // a cost or constraint added to one of the Problem's PlayerCosts (or an ExtremeValueCost's child)
+    ilqg_param_field field;  // ILQG_PARAM_WEIGHT / ILQG_PARAM_VALUE
+  };
+  std::vector<Param> params;
+  std::vector<float> values;
+  void Add(const Cost* term, ilqg_param_field field) { params.push_back(Param{term, field}); }
+  void Add(const std::shared_ptr<const Cost>& term, ilqg_param_field field) { Add(term.get(), field); }
+};
+// The (term index, field) list of `params` in `description` (what ilqg_problem_declare_instance_params takes).
+// Returns false and sets *why when an object is not a term of the description.
+bool ResolveInstanceParams(const ProblemDescription& description, const InstanceParams& params,
+                           std::vector<ilqg_instance_param>* out, std::string* why);
 
 // Walks Problem::Dynamics() and Problem::PlayerCosts() (after Initialize()) and fills the POD
 // descriptor of include/ilqg.h.  Returns false and sets *why when some object has no device kernel.
@@ -1175,10 +1195,16 @@ class GameSolver {
   // Batched form of Solve(): one instance per entry of x0s, all sharing the Problem definition and
   // its current operating point / strategies as warm start.  This is the call that fills the GPU.
   host::BatchResult SolveBatch(const std::vector<VectorXf>& x0s);
+  // The same with per-instance cost parameters (host::InstanceParams): instance b plays the game whose declared
+  // weights / nominals / thresholds are row b of instance_params.values.  The reference has no such call.
+  host::BatchResult SolveBatch(const std::vector<VectorXf>& x0s, const host::InstanceParams& instance_params);
   // The same over several GPUs: every rank passes the SAME global list; rank r solves its block
   // (host::InstanceRange) on its GPU, the per-instance results (operating points, strategies, costs, flags) are
   // all-gathered with RCCL, and every rank returns the BatchResult of the whole batch, in the order of x0s.
   host::BatchResult SolveBatchSharded(const std::vector<VectorXf>& x0s, const host::ShardContext& shard);
+  // ... with per-instance cost parameters: every rank passes the SAME global table, rank r binds the rows of its block.
+  host::BatchResult SolveBatchSharded(const std::vector<VectorXf>& x0s, const host::InstanceParams& instance_params,
+                                      const host::ShardContext& shard);
   const SolverParams& Params() const { return params_; }
   bool IsAugmentedLagrangian() const { return augmented_lagrangian_; }
 

@@ -1,0 +1,106 @@
+#!/usr/bin/env python
+"""What per-instance cost parameters cost and what they buy: the headline scene (n = 14 intersection, T = 100) at
+B = 1024, fp64, 20 fixed iterations from a zero warm start, bench.py's line-search parameters.
+
+  (a) unbound                 the problem as bench.py solves it
+  (b) bound, identity         a table bound whose every row holds the baked values: the price of the overlay's reads
+  (c) bound, spread           a seeded spread of nominal speeds, lane weights and proximity weights, one vector per instance
+  (d) one problem per vector  what a user had before: V problems created with V of those vectors, each solving its
+                              B / V instances, one after another (V small so that this stays short; with one vector
+                              per instance it would be B solves of one instance each)
+
+A fixed-iteration solve still back-tracks: the games of the spread are harder than the baked one (the scene bakes proximity
+weight 0), and an iteration that rejects step sizes costs more passes.  So the line also carries, as the yardstick for (c),
+`baked_spread_vector_its`: ONE problem created with the first vector of the spread solving all B instances unbound, and
+the mean number of rejected step sizes per instance in the last iteration of (a), (c) and that run.
+
+Prints one JSON line: iterations/s of each.   python scripts/param_sweep_bench.py [--batch 1024] [--repeats 5] [--vectors 16]"""
+import argparse
+import copy
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+DECLARED = [("p1_nominal_speed", "value", 6.0, 10.0), ("p2_nominal_speed", "value", 4.0, 8.0),
+            ("p3_nominal_speed", "value", 1.0, 2.0), ("p1_lane", "weight", 15.0, 35.0), ("p2_lane", "weight", 15.0, 35.0),
+            ("p3_lane", "weight", 15.0, 35.0), ("p1_proximity_p2", "weight", 0.0, 30.0), ("p2_proximity_p1", "weight", 0.0, 30.0),
+            ("p3_proximity_p1", "weight", 0.0, 30.0)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--vectors", type=int, default=16)
+    ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
+    args = ap.parse_args()
+    import torch
+    from ilqgames_amd import abi, examples, hip
+    dtype = abi.F64 if args.dtype == "f64" else abi.F32
+    B, K, V = args.batch, args.iters, args.vectors
+    assert B % V == 0
+    spec = examples.modified_three_player_intersection()
+    spec.params.initial_alpha_scaling = 0.1
+    spec.params.expected_decrease_fraction = 0.001
+    x0 = hip._dev(examples.jittered_x0(spec, B, seed=0), dtype)
+    params = [(d[0], d[1]) for d in DECLARED]
+    rng = np.random.default_rng(0)
+    lo, hi = np.array([d[2] for d in DECLARED]), np.array([d[3] for d in DECLARED])
+    spread = (lo + (hi - lo) * rng.random((B, len(DECLARED)))).astype(np.float32)
+    identity = np.tile(np.array([spec.terms[spec.term_index(n)][f] for n, f in params], dtype=np.float32), (B, 1))
+
+    def timed(solves):
+        """Median over the repeats of the device time of `solves` = [(problem, x0 slice, buffers)], run back to back."""
+        times = []
+        for rep in range(args.repeats + 1):  # the first pass is the warm-up
+            for _, _, bufs in solves:
+                for k in ("xs", "us", "P", "alpha"):
+                    bufs[k].zero_()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            for prob, x, bufs in solves:
+                prob.solve(x, bufs, fixed_iters=K)
+            e1.record()
+            torch.cuda.synchronize()
+            if rep > 0:
+                times.append(e0.elapsed_time(e1) * 1e-3)
+        return float(np.median(times))
+
+    prob = hip.Problem(spec, dtype)
+    bufs = prob.alloc_solve_buffers(B)
+    out = dict(batch=B, iters=K, dtype=args.dtype, declared=len(DECLARED), vectors=V)
+    out["unbound_its"] = B * K / timed([(prob, x0, bufs)])
+    out["unbound_backtracks"] = float(prob.solve_state(bufs)["backtracks"].float().mean().item())
+    prob.declare_instance_params(params)
+    prob.bind_instance_values(identity)
+    out["bound_identity_its"] = B * K / timed([(prob, x0, bufs)])
+    prob.bind_instance_values(spread)
+    out["bound_spread_its"] = B * K / timed([(prob, x0, bufs)])
+    out["bound_spread_backtracks"] = float(prob.solve_state(bufs)["backtracks"].float().mean().item())
+    prob.bind_instance_values(None)
+    # the alternative: V problems, B / V instances each, one after another
+    per = B // V
+    solves = []
+    for v in range(V):
+        s = copy.deepcopy(spec)
+        for (name, field), val in zip(params, spread[v]):
+            s.terms[s.term_index(name)][field] = float(val)
+        p = hip.Problem(s, dtype)
+        solves.append((p, x0[v * per:(v + 1) * per].contiguous(), p.alloc_solve_buffers(per)))
+    out["per_vector_problems_its"] = B * K / timed(solves)
+    one = solves[0][0]
+    one_bufs = one.alloc_solve_buffers(B)
+    out["baked_spread_vector_its"] = B * K / timed([(one, x0, one_bufs)])
+    out["baked_spread_vector_backtracks"] = float(one.solve_state(one_bufs)["backtracks"].float().mean().item())
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
