@@ -813,52 +813,6 @@ void raise_lds_limit(const void* kern, size_t lds) {
   if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
 }
 
-bool build_pairs(const ilqg_pair* pairs, int npairs, const int* udim, int N, PairTable* pt, std::string* err) {
-  if (npairs > kMaxPairs) {
-    *err = "too many control blocks";
-    return false;
-  }
-  std::memset(pt, 0, sizeof(*pt));
-  pt->npairs = npairs;
-  for (int i = 0; i < kMaxPlayers; i++) pt->pii[i] = -1;
-  int Rsz = 0, rsz = 0;
-  for (int q = 0; q < npairs; q++) {
-    const int i = pairs[q].i, j = pairs[q].j;
-    if (i < 0 || i >= N || j < 0 || j >= N) {
-      *err = "control block index out of range";
-      return false;
-    }
-    pt->pi[q] = i;
-    pt->pj[q] = j;
-    pt->roff[q] = Rsz;
-    pt->rgoff[q] = rsz;
-    pt->from_cost[q] = 1;
-    Rsz += udim[j] * udim[j];
-    rsz += udim[j];
-    if (i == j) pt->pii[i] = q;
-  }
-  pt->Rsz = Rsz;
-  pt->rsz = rsz;
-  for (int i = 0; i < N; i++)
-    if (pt->pii[i] < 0) {
-      *err = "player " + std::to_string(i) + " is missing a control Hessian";  // lq_feedback_solver.cpp:139-140
-      return false;
-    }
-  return true;
-}
-
-GenDims gen_dims_of(int n, int N, const int32_t* udim, int T) {
-  GenDims g{};
-  g.n = n; g.N = N; g.T = T;
-  g.uoff[0] = 0;
-  for (int i = 0; i < N; i++) {
-    g.udim[i] = udim[i];
-    g.uoff[i + 1] = g.uoff[i] + udim[i];
-  }
-  g.m = g.uoff[N];
-  return g;
-}
-
 // Supported (n, N, m_i) instantiations.  n=14/16/15/24: BASELINE configs 2-5;
 // (4,2,2): config 1 (TwoPlayerUnicycle4D); (2,2,1): test_lq_solver's point mass;
 // (6,3,2): synthetic parity cases.
@@ -869,6 +823,8 @@ GenDims gen_dims_of(int n, int N, const int32_t* udim, int T) {
 #endif
 
 }  // namespace
+
+#include "ilqg_problem.hpp"  // the problem object: its host tables, its device buffers, the handle
 
 // Launchers of the kernels that are instantiated per (n, N, m_i).  Members are defined out of class (not inline),
 // so `extern template struct DimsLaunch<...>` in the main unit of a split build leaves their code — and the
@@ -1014,13 +970,6 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::lq_padded_batch(const ilqg_dims* d, const
 
 namespace {
 
-bool uniform_udim(const int32_t* udim, int N, int* mu) {
-  for (int i = 1; i < N; i++)
-    if (udim[i] != udim[0]) return false;
-  *mu = udim[0];
-  return true;
-}
-
 ilqg_status check_device() {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
@@ -1029,74 +978,6 @@ ilqg_status check_device() {
 }
 
 }  // namespace
-
-struct ilqg_problem {
-  DevProblem dev;
-  ilqg_problem_desc desc;
-  std::vector<ilqg_cost_term> terms_host;
-  DevTerm* d_terms = nullptr;
-  int* d_poly_off = nullptr;
-  float* d_poly_pts = nullptr;
-  float* d_segs_f = nullptr;
-  double* d_segs_d = nullptr;
-  float* d_dense_f = nullptr;
-  double* d_dense_d = nullptr;
-  double* d_tnom_f = nullptr;
-  double* d_tnom_d = nullptr;
-  int* d_cost_order = nullptr;
-  int* d_row_prog = nullptr;
-  std::vector<int> row_prog_host;  // the program as built (ilqg_problem_row_program)
-  // Per-instance cost parameters (ilqg.h): the term each op of the row program carries, the declared (term, field) list
-  // and its device side tables (the ops' columns behind the program in d_row_prog, DevProblem::inst_terms);
-  // dev.inst_values / inst_count are set while a table is bound, for `inst_batch` instances
-  std::vector<int> op_term;
-  std::vector<ilqg_instance_param> inst_params;
-  int* d_inst_terms = nullptr;
-  int inst_batch = 0;
-  int static_prog = 0;             // id of the registered structure it matches (ilqg_rowprog_static.hpp), 0: none
-  int* d_unfinished = nullptr;  // instances still running after an LQ-kernel launch
-  int* h_unfinished = nullptr;  // pinned host mirror: [0..3] the counters, [8] the sequence number of read_round_counters
-  int* h_unfinished_dev = nullptr;  // ... as the device addresses it
-  int publish_seq = 0;
-  bool counters_clean = false;  // d_unfinished was cleared by the last thing that touched it (read_round_counters)
-  int mu_uniform = 0;
-  bool has_route_progress = false;  // a RouteProgressCost term: its tables are a first solve's (initial time 0)
-  int last_schedule = 0;  // ILQG_SCHEDULE_* of the last solve (ilqg_problem_last_schedule)
-  bool generic = false;  // no specialised instantiation holds this problem: every entry point runs the run-time-dimensioned kernels
-  // LoopTimer of the solver object (include/ilqgames/utils/loop_timer.h:60-98, src/loop_timer.cpp:55-92): the last ten
-  // iteration times, kept across solves as the reference's member is; only solves with a max_runtime feed and read it
-  double loop_times[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int loop_count = 0, loop_next = 0;
-  void loop_add(double seconds) {
-    loop_times[loop_next] = seconds;
-    loop_next = (loop_next + 1) % 10;
-    if (loop_count < 10) loop_count++;
-  }
-  double loop_upper_bound() const {  // mean + 3 sigma (unbiased), 0.02 s until two samples exist
-    if (loop_count < 2) return 0.02;
-    double mean = 0.0, var = 0.0;
-    for (int i = 0; i < loop_count; i++) mean += loop_times[i];
-    mean /= loop_count;
-    for (int i = 0; i < loop_count; i++) var += (loop_times[i] - mean) * (loop_times[i] - mean);
-    return mean + 3.0 * std::sqrt(var / (loop_count - 1));
-  }
-  // AugmentedLagrangianSolver's own LoopTimer (solver/augmented_lagrangian_solver.h: `timer_`), over its outer iterations
-  double al_loop_times[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int al_loop_count = 0, al_loop_next = 0;
-  void al_loop_add(double seconds) {
-    al_loop_times[al_loop_next] = seconds;
-    al_loop_next = (al_loop_next + 1) % 10;
-    if (al_loop_count < 10) al_loop_count++;
-  }
-  double al_loop_upper_bound() const {
-    if (al_loop_count < 2) return 0.02;
-    double mean = 0.0, var = 0.0;
-    for (int i = 0; i < al_loop_count; i++) mean += al_loop_times[i];
-    mean /= al_loop_count;
-    for (int i = 0; i < al_loop_count; i++) var += (al_loop_times[i] - mean) * (al_loop_times[i] - mean);
-    return mean + 3.0 * std::sqrt(var / (al_loop_count - 1));
-  }
-};
 
 // The round counters' way back to the host.  A counted solve reads them once per round (twice with the augmented
 // Lagrangian's restarts), and while it does the device idles: what a read-back costs is the gap between two rounds.
@@ -1126,15 +1007,15 @@ __global__ void ilq_count_active_kernel(const int* active, int batch, int* count
 inline ilqg_status read_round_counters(ilqg_problem* p, hipStream_t stream) {
   p->counters_clean = false;
   if (!p->h_unfinished_dev) {
-    HIP_TRY(hipMemcpyAsync(p->h_unfinished, p->d_unfinished, 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(p->h_unfinished.get(), p->d_unfinished.get(), 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return ILQG_OK;
   }
   const int seq = ++p->publish_seq;
-  hipLaunchKernelGGL(ilq_publish_kernel, dim3(1), dim3(64), 0, stream, p->d_unfinished, p->h_unfinished_dev, seq);
+  hipLaunchKernelGGL(ilq_publish_kernel, dim3(1), dim3(64), 0, stream, p->d_unfinished.get(), p->h_unfinished_dev, seq);
   HIP_TRY(hipGetLastError());
   p->counters_clean = true;
-  volatile int* const flag = p->h_unfinished + 8;
+  volatile int* const flag = p->h_unfinished.get() + 8;
   for (long long spins = 0;; spins++) {
     if (__atomic_load_n(const_cast<int*>(flag), __ATOMIC_ACQUIRE) == seq) return ILQG_OK;
     __builtin_ia32_pause();
@@ -1179,12 +1060,12 @@ struct AlOuterClock {
       elapsed += now - last;
       last = now;
       if (open_count > 0) {
-        p->al_loop_add(now - open_since[open_head]);
+        p->al_loop_timer.add(now - open_since[open_head]);
         open_head = (open_head + 1) % kOpen;
         open_count--;
       }
     }
-    return !(elapsed < max_runtime - p->al_loop_upper_bound());
+    return !(elapsed < max_runtime - p->al_loop_timer.upper_bound());
   }
   void after_exit(int restarted) {
     if (!on || !restarted) return;
@@ -1222,11 +1103,11 @@ struct InnerClock {
   bool deadline_passed() {  // in front of an iteration: the one in flight ends here; true: the next may not start
     const double now = AlOuterClock::wall();
     if (iteration_open) {
-      p->loop_add(now - tic);
+      p->loop_timer.add(now - tic);
       elapsed += now - tic;
       iteration_open = false;
     }
-    return !(elapsed < budget - p->loop_upper_bound());
+    return !(elapsed < budget - p->loop_timer.upper_bound());
   }
   void open_iteration() {
     if (!on) return;
@@ -1302,7 +1183,7 @@ SolveArgs<T> solve_args_of(const ilqg_problem* p, int32_t batch, const void* x0,
   sa.prm = p->desc.params;
   sa.active = opt.active;
   sa.forced_steps = (const T*)opt.forced_steps;
-  sa.unfinished = p->d_unfinished;
+  sa.unfinished = p->d_unfinished.get();
   sa.first = opt.resume ? 2 : 1;
   const WsTail t = ws_tail(d, batch, sizeof(T), sa.ol_row);
   tail->pass_ids = reinterpret_cast<int*>(static_cast<char*>(workspace) + t.ids_off);
@@ -1491,7 +1372,7 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
     return launch(KernelLaunch<T>{ilq_probe_pick_kernel<T>, kProbeCandidates, 0}, dim3(instances));
   };
   auto pass = [&]() -> ilqg_status {
-    if (plan.counted && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
+    if (plan.counted && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished.get(), 0, 4 * sizeof(int), stream));
     p->counters_clean = false;  // (the round's kernels count into them)
     if (!plan.split && !sa.ids) {
       sa.ids_next = plan.handoff ? rl.free_list() : nullptr;
@@ -1569,7 +1450,7 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
       want_exit = p->h_unfinished[1];
       if (plan.lists) {
         bool again = false;
-        s = rl.after_round(p->h_unfinished, round, &again, &want_lq, &want_exit);
+        s = rl.after_round(p->h_unfinished.get(), round, &again, &want_lq, &want_exit);
         if (s != ILQG_OK) return s;
         if (again) {
           burst = 1;
@@ -1597,7 +1478,7 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
     if ((want_exit || want_lq) && iterate_log_launch(p, sa, lg, stream) != ILQG_OK) return ILQG_ERR_HIP;
     int restarted = 0;
     if (want_exit) {
-      if (plan.exit_fill_first && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));
+      if (plan.exit_fill_first && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished.get(), 0, 4 * sizeof(int), stream));
       if (outer.before_exit()) sa.outer_closed = 1;  // out of time: inner solves that end now are the last ones
       if (launch(plan.exit, dim3(batch)) != ILQG_OK) return ILQG_ERR_HIP;
       p->counters_clean = false;
@@ -1621,11 +1502,6 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
 }  // namespace
 
 #define DT_DISPATCH(p, CALL) ((p)->desc.dtype == ILQG_F32 ? CALL(float) : CALL(double))
-
-static ilqg_status launch_linquad(const ilqg_problem* p, int32_t batch, const void* xs, const void* us,
-                                  const void* lambdas, const void* mu, const int32_t* t_extreme, void* A, void* Bm,
-                                  void* Q, void* l, void* R, void* r, void* merit_part, void* cost_part,
-                                  const int32_t* active, void* stream);
 
 template <typename T, int NX, int NP, int MU>
 ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, const void* x0, void* xs, void* us,
@@ -1713,8 +1589,8 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   // asynchronous and keeps the buffer length.
   int sched_batch = batch;
   if (opt.active && !opt.forced_steps && !opt.deterministic && !(fixed_iters > 0 && !al_mode)) {
-    HIP_TRY(hipMemsetAsync(p->d_unfinished, 0, 4 * sizeof(int), stream));  // (whatever an earlier solve left there)
-    hipLaunchKernelGGL(ilq_count_active_kernel, dim3(1), dim3(256), 0, stream, opt.active, int(batch), p->d_unfinished);
+    HIP_TRY(hipMemsetAsync(p->d_unfinished.get(), 0, 4 * sizeof(int), stream));  // (whatever an earlier solve left there)
+    hipLaunchKernelGGL(ilq_count_active_kernel, dim3(1), dim3(256), 0, stream, opt.active, int(batch), p->d_unfinished.get());
     HIP_TRY(hipGetLastError());
     if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
     sched_batch = p->h_unfinished[3] > 0 ? p->h_unfinished[3] : 1;
@@ -1858,11 +1734,11 @@ ILQG_FOR_DIMS(X)
 #undef X
 #endif
 
-static ilqg_status launch_linquad(const ilqg_problem* p, int32_t batch, const void* xs, const void* us,
+// `d`: the problem as the kernels get it, p->dev or a variant of it
+static ilqg_status launch_linquad(const ilqg_problem* p, const DevProblem& d, int32_t batch, const void* xs, const void* us,
                                   const void* lambdas, const void* mu, const int32_t* t_extreme, void* A, void* Bm,
                                   void* Q, void* l, void* R, void* r, void* merit_part, void* cost_part,
                                   const int32_t* active, void* stream) {
-  const DevProblem& d = p->dev;
   const void* const ptrs[14] = {xs, us, lambdas, mu, t_extreme, A, Bm, Q, l, R, r, merit_part, cost_part, active};
   if (p->generic)  // the row stage with run-time dimensions (rows_chunk<T, 0, 0, 0>)
     return p->desc.dtype == ILQG_F32 ? DimsLaunch<float, 0, 0, 0>::rows(d, batch, ptrs, (hipStream_t)stream)
@@ -2103,13 +1979,7 @@ ilqg_status ilqg_copy_bandwidth(void* dst, const void* src, size_t bytes, void* 
 ilqg_status ilqg_problem_row_program(const ilqg_problem* p, int32_t* words_out, int32_t capacity, int32_t* num_words,
                                      int32_t* static_id) {
   if (!p || !num_words) return fail(ILQG_ERR_INVALID, "null argument");
-  *num_words = int32_t(p->row_prog_host.size());
-  if (static_id) *static_id = p->static_prog;
-  if (words_out) {
-    if (capacity < *num_words) return fail(ILQG_ERR_INVALID, "ilqg_problem_row_program: buffer too small");
-    std::memcpy(words_out, p->row_prog_host.data(), sizeof(int32_t) * p->row_prog_host.size());
-  }
-  return ILQG_OK;
+  return copy_row_program(p->row_prog, p->static_prog, words_out, capacity, num_words, static_id);
 }
 
 ilqg_status ilqg_problem_last_schedule(const ilqg_problem* p, int32_t* schedule_out) {
@@ -2243,517 +2113,33 @@ ilqg_status ilqg_lq_openloop_batch(const ilqg_dims* d, const void* A, const void
                               : launch_lq_generic<double>(d, pt, true, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, st);
 }
 
-// `host_only`: everything ilqg_problem_create does on the host — validation, flattening, the row program and its match
-// against the registered structures — without touching a device; the handle then only serves ilqg_problem_row_program
-// and ilqg_problem_destroy (ilqg_row_program_build).
-static ilqg_status problem_create_impl(const ilqg_problem_desc* desc, ilqg_problem** out, bool host_only) {
+// ---- the problem object (ilqg_problem.hpp) ----
+ilqg_status ilqg_problem_create(const ilqg_problem_desc* desc, ilqg_problem** out) {
   if (!desc || !out) return fail(ILQG_ERR_INVALID, "null argument");
-  if (desc->num_players < 1 || desc->num_players > ILQG_MAX_PLAYERS) return fail(ILQG_ERR_INVALID, "bad player count");
-  if (desc->T < 2 || desc->T > kMaxT) return fail(ILQG_ERR_INVALID, "bad horizon");
-  if (!host_only) {
-    ilqg_status s = check_device();
-    if (s != ILQG_OK) return s;
-  }
-  auto* p = new ilqg_problem;
-  p->desc = *desc;
-  DevProblem& d = p->dev;
-  std::memset(&d, 0, sizeof(d));
-  d.N = desc->num_players;
-  d.T = desc->T;
-  d.dt = desc->dt;
-  d.xoff[0] = 0;
-  d.uoff[0] = 0;
-  for (int i = 0; i < d.N; i++) {
-    const ilqg_subsystem& sub = desc->subsystems[i];
-    const int want_x = (sub.kind == ILQG_DYN_UNICYCLE_4D || sub.kind == ILQG_DYN_UNICYCLE_4D_DISTURBED ||
-                        sub.kind == ILQG_DYN_POINT_MASS_2D || sub.kind == ILQG_DYN_DELAYED_DUBINS_CAR) ? 4
-                       : sub.kind == ILQG_DYN_UNICYCLE_5D ? 5 : sub.kind == ILQG_DYN_CAR_7D ? 7
-                       : sub.kind == ILQG_DYN_CAR_5D ? 5 : sub.kind == ILQG_DYN_CAR_6D ? 6
-                       : sub.kind == ILQG_DYN_PLANAR_DISTURBANCE ? 0 : sub.kind == ILQG_DYN_DUBINS_CAR ? 3
-                       : sub.kind == ILQG_DYN_AIR_3D_EVADER ? 3 : sub.kind == ILQG_DYN_AIR_3D_PURSUER ? 0 : -1;
-    const bool one_control = sub.kind == ILQG_DYN_DUBINS_CAR || sub.kind == ILQG_DYN_AIR_3D_EVADER ||
-                             sub.kind == ILQG_DYN_AIR_3D_PURSUER || sub.kind == ILQG_DYN_DELAYED_DUBINS_CAR;
-    const int want_u = one_control ? 1 : 2;
-    // TwoPlayerUnicycle4D is exactly the pair (disturbed unicycle, disturbance) and nothing else
-    const bool paired = sub.kind == ILQG_DYN_UNICYCLE_4D_DISTURBED || sub.kind == ILQG_DYN_PLANAR_DISTURBANCE ||
-                        sub.kind == ILQG_DYN_AIR_3D_EVADER || sub.kind == ILQG_DYN_AIR_3D_PURSUER;
-    const bool pair_ok = !paired ||
-                         (desc->num_players == 2 && desc->subsystems[0].kind == ILQG_DYN_UNICYCLE_4D_DISTURBED &&
-                          desc->subsystems[1].kind == ILQG_DYN_PLANAR_DISTURBANCE) ||
-                         (desc->num_players == 2 && desc->subsystems[0].kind == ILQG_DYN_AIR_3D_EVADER &&
-                          desc->subsystems[1].kind == ILQG_DYN_AIR_3D_PURSUER);
-    if (!pair_ok) {
-      delete p;
-      return fail(ILQG_ERR_UNSUPPORTED, "the shared-state kinds only occur as the pairs (4, 5) and (7, 8)");
-    }
-    if ((sub.kind == ILQG_DYN_POINT_MASS_2D) != (desc->subsystems[0].kind == ILQG_DYN_POINT_MASS_2D)) {
-      delete p;
-      return fail(ILQG_ERR_UNSUPPORTED, "point masses (kind 9) only occur in games made of point masses");
-    }
-    if (want_x < 0 || sub.xdim != want_x || sub.udim != want_u) {
-      delete p;
-      return fail(ILQG_ERR_UNSUPPORTED, "unknown subsystem kind / dimension");
-    }
-    d.sub_kind[i] = sub.kind;
-    d.sub_param[i] = sub.param0;
-    d.udim[i] = sub.udim;
-    d.xoff[i + 1] = d.xoff[i] + sub.xdim;
-    d.uoff[i + 1] = d.uoff[i] + sub.udim;
-    d.state_reg[i] = desc->player_costs[i].state_regularization;
-    d.control_reg[i] = desc->player_costs[i].control_regularization;
-    d.structure[i] = desc->player_costs[i].structure;
-  }
-  d.n = d.xoff[d.N];
-  d.m = d.uoff[d.N];
-  if (d.n > ILQG_MAX_XDIM || d.m > ILQG_MAX_UDIM_TOTAL) {  // before any table is sized by them
-    delete p;
-    return fail(ILQG_ERR_UNSUPPORTED, "more than ILQG_MAX_XDIM states or ILQG_MAX_UDIM_TOTAL controls");
-  }
-  {
-    bool plain = false;
-    for (int i = 0; i < d.N; i++) plain = plain || is_plain_rk4_kind(d.sub_kind[i]);
-    // Unicycle5D / Car7D / DelayedDubinsCar rows need an instantiation that carries the plain RK4 (dims_use_plain_rk4,
-    // csrc/ilqg_stages.hpp); in any other shape they run on the run-time-dimensioned path, which picks its integrator
-    // from the models
-    if (plain && !dims_use_plain_rk4(d.n, d.N, d.udim[0])) p->generic = true;
-  }
-  // DistanceBetween of the first subsystem: (px, py) where the model overrides it (two_player_unicycle_4d.h:141-147
-  // too), the whole block where it does not (the two Dubins cars: single_player_dynamical_system.h:69-71)
-  d.sync_dist_dims = d.sub_kind[0] == ILQG_DYN_DUBINS_CAR ? 3 : (d.sub_kind[0] == ILQG_DYN_DELAYED_DUBINS_CAR ? 4 : 2);
-  // pair table in PlayerCost first-touch order: control costs, then control constraints
-  std::vector<ilqg_pair> pairs;
-  std::vector<int> from_cost;
-  for (int i = 0; i < d.N; i++)
-    for (int pass = 0; pass < 2; pass++)
-      for (int ti = 0; ti < desc->num_terms; ti++) {
-        const ilqg_cost_term& t = desc->terms[ti];
-        if (t.player != i) continue;
-        if (pass == 0 && t.role != ILQG_ROLE_CONTROL_COST) continue;
-        if (pass == 1 && t.role != ILQG_ROLE_CONTROL_CONSTRAINT) continue;
-        bool found = false;
-        for (auto& pr : pairs) found = found || (pr.i == i && pr.j == t.arg);
-        if (!found) {
-          pairs.push_back({i, t.arg});
-          from_cost.push_back(pass == 0 ? 1 : 0);
-        }
-      }
-  std::string err;
-  if (!build_pairs(pairs.data(), (int)pairs.size(), d.udim, d.N, &d.pairs, &err)) {
-    delete p;
-    return fail(ILQG_ERR_INVALID, err);
-  }
-  for (size_t q = 0; q < pairs.size(); q++) d.pairs.from_cost[q] = from_cost[q];
-  d.num_terms = desc->num_terms;
-  d.num_polylines = desc->num_polylines;
-  std::vector<DevTerm> dt(desc->num_terms > 0 ? desc->num_terms : 1);
-  int nc = 0;
-  for (int ti = 0; ti < desc->num_terms; ti++) {
-    const ilqg_cost_term& t = desc->terms[ti];
-    DevTerm& o = dt[ti];
-    o.kind = t.kind; o.role = t.role; o.player = t.player; o.arg = t.arg;
-    for (int q = 0; q < 4; q++) o.idx[q] = t.idx[q];
-    o.weight = t.weight; o.value = t.value; o.flags = t.flags; o.polyline = t.polyline;
-    o.child_begin = t.child_begin; o.child_count = t.child_count; o.slot = t.constraint_slot;
-    o.k_start = t.first_step;
-    if (t.kind == ILQG_COST_WEIGHTED_CONVEX_PROXIMITY) {  // its two speed indices ride in `polyline` (wcp_indices)
-      if (t.role != ILQG_ROLE_STATE_COST || t.idx_extra[0] < 0 || t.idx_extra[0] >= d.n || t.idx_extra[1] < 0 ||
-          t.idx_extra[1] >= d.n) {
-        delete p;
-        return fail(ILQG_ERR_INVALID, "WeightedConvexProximityCost must be a top-level state cost with speed indices "
-                                      "inside the state");
-      }
-      o.polyline = t.idx_extra[0] | (t.idx_extra[1] << 16);
-    }
-    // Constraint::is_equality_ is only carried for the affine constraints (ilqg.h): on any other kind the multiplier
-    // update would drop its clip at zero while the mu gate stayed an inequality's
-    if ((t.flags & ILQG_FLAG_EQUALITY) && t.kind != ILQG_CONSTRAINT_AFFINE_SCALAR && t.kind != ILQG_CONSTRAINT_AFFINE_VECTOR) {
-      delete p;
-      return fail(ILQG_ERR_INVALID, "ILQG_FLAG_EQUALITY is only defined for the affine constraints");
-    }
-    if (t.constraint_slot >= 0 && t.constraint_slot + 1 > nc) nc = t.constraint_slot + 1;
-  }
-  d.num_constraints = nc;
-  // ---- where each term's argument vector sits inside a row's [x | u] ----
-  for (int ti = 0; ti < desc->num_terms; ti++) {
-    DevTerm& o = dt[ti];
-    const bool on_state = o.role == ILQG_ROLE_STATE_COST || o.role == ILQG_ROLE_STATE_CONSTRAINT ||
-                          o.role == ILQG_ROLE_CHILD;
-    o.arg_off = on_state ? 0 : d.n + d.uoff[o.arg];
-    o.arg_dim = on_state ? d.n : d.udim[o.arg];
-  }
-  // ---- coefficient blocks of the affine constraints, in both precisions (DevProblem::dense_f / dense_d) ----
-  std::vector<float> dense_f;
-  std::vector<double> dense_d;
-  for (int ti = 0; ti < desc->num_terms; ti++) {
-    DevTerm& o = dt[ti];
-    if (!term_is_affine(o.kind)) continue;
-    const int dim = o.arg_dim;
-    const bool vec = o.kind == ILQG_CONSTRAINT_AFFINE_VECTOR;
-    const long long count = vec ? (long long)dim * dim + dim : dim + 1;
-    const bool constraint_role = o.role == ILQG_ROLE_STATE_CONSTRAINT || o.role == ILQG_ROLE_CONTROL_CONSTRAINT;
-    if (!constraint_role || o.slot < 0 || desc->dense_params == nullptr || desc->terms[ti].polyline < 0 ||
-        (long long)desc->terms[ti].polyline + count > desc->num_dense_params) {
-      delete p;
-      return fail(ILQG_ERR_INVALID, "an affine constraint must be a state / control constraint with a multiplier slot "
-                                    "and a coefficient block inside ilqg_problem_desc::dense_params");
-    }
-    const float* src = desc->dense_params + desc->terms[ti].polyline;
-    o.polyline = int(dense_f.size());  // from here on: the offset of its block in the device tables
-    auto emit = [&](auto& out) {
-      using S = typename std::decay<decltype(out)>::type::value_type;
-      for (long long e = 0; e < count; e++) out.push_back(S(src[e]));
-      if (vec)  // ATA_ = A^T A, AAT_ = A A^T as the constructor forms them (affine_vector_constraint.h:60-61)
-        for (int which = 0; which < 2; which++)
-          for (int j = 0; j < dim; j++)
-            for (int i = 0; i < dim; i++) {
-              S acc = S(0);
-              for (int q = 0; q < dim; q++)
-                acc += which == 0 ? S(src[q + dim * i]) * S(src[q + dim * j]) : S(src[i + dim * q]) * S(src[j + dim * q]);
-              out.push_back(acc);
-            }
-    };
-    const size_t before = dense_f.size();
-    emit(dense_f);
-    emit(dense_d);
-    (void)before;
-  }
-  p->terms_host.assign(desc->terms, desc->terms + desc->num_terms);
-  const int npts = desc->num_polylines ? desc->polyline_offsets[desc->num_polylines] : 0;
-  // LineSegment2 objects of every polyline, in both precisions (line_segment2.h:55-62)
-  std::vector<float> segs_f;
-  std::vector<double> segs_d;
-  {
-    auto emit = [&](auto& out, auto ax, auto ay, auto bx, auto by) {
-      using S = decltype(ax);
-      const S dx = ax - bx, dy = ay - by;
-      const S len = std::sqrt(dx * dx + dy * dy);
-      out.push_back(ax); out.push_back(ay); out.push_back(bx); out.push_back(by);
-      out.push_back(len); out.push_back((bx - ax) / len); out.push_back((by - ay) / len);
-    };
-    for (int q = 0; q < desc->num_polylines; q++) {
-      const int b0 = desc->polyline_offsets[q], e0 = desc->polyline_offsets[q + 1];
-      const float* pts = desc->polyline_points + 2 * b0;
-      const int nseg = e0 - b0 - 1;
-      for (int c = 0; c < nseg; c++) {
-        auto P = [&](int idx, int xy) { return pts[2 * idx + xy]; };
-        const int pm = c > 0 ? c - 1 : c, pn = c + 2 <= nseg ? c + 2 : c + 1;
-        emit(segs_f, P(c, 0), P(c, 1), P(c + 1, 0), P(c + 1, 1));
-        emit(segs_f, P(pm, 0), P(pm, 1), P(c + 1, 0), P(c + 1, 1));
-        emit(segs_f, P(c, 0), P(c, 1), P(pn, 0), P(pn, 1));
-        emit(segs_d, double(P(c, 0)), double(P(c, 1)), double(P(c + 1, 0)), double(P(c + 1, 1)));
-        emit(segs_d, double(P(pm, 0)), double(P(pm, 1)), double(P(c + 1, 0)), double(P(c + 1, 1)));
-        emit(segs_d, double(P(c, 0)), double(P(c, 1)), double(P(pn, 0)), double(P(pn, 1)));
-      }
-    }
-  }
-  d.total_segs = int(segs_f.size() / kSegStride);
-  // Per-step nominals of the time-dependent costs, one table per such term and geometry precision (doubles: the
-  // path-length nominal is a double product in the reference, nominal_path_length_cost.cpp:53; the route point is a
-  // pair of the geometry's scalars, exact in double).  t = RelativeTime(k) = double(k) * dt (relative_time_tracker.h:
-  // 63-65); the route position is a float (a scalar of the geometry) made from a double expression
-  // (route_progress_cost.cpp:57-59) and Polyline2::PointAt walks the cumulative lengths (src/polyline2.cpp:68-103).
-  std::vector<double> tnom_f, tnom_d;
-  {
-    int ntab = 0;
-    for (int ti = 0; ti < desc->num_terms; ti++) {
-      DevTerm& o = dt[ti];
-      if (!term_is_time_dependent(o.kind)) continue;
-      const bool route = o.kind == ILQG_COST_ROUTE_PROGRESS;
-      if (o.role != ILQG_ROLE_STATE_COST || (route && (o.polyline < 0 || o.polyline >= desc->num_polylines))) {
-        ilqg_problem_destroy(p);
-        return fail(ILQG_ERR_INVALID, "a time-dependent cost must be a top-level state cost (with a polyline, for "
-                                      "RouteProgressCost)");
-      }
-      const int src_poly = o.polyline;
-      if (route) {
-        // Polyline2::PointAt CHECKs its argument (src/polyline2.cpp:68-103): a route position that is negative at any
-        // step, or a polyline without a segment, is a programmer error there and ILQG_ERR_INVALID here
-        const int nseg_r = desc->polyline_offsets[src_poly + 1] - desc->polyline_offsets[src_poly] - 1;
-        const double pos_first = double(desc->terms[ti].value2);
-        const double pos_last = pos_first + double(d.T - 1) * d.dt * double(o.value);
-        if (nseg_r < 1 || !(pos_first >= 0.0) || !(pos_last >= 0.0)) {
-          ilqg_problem_destroy(p);
-          return fail(ILQG_ERR_INVALID, "RouteProgressCost: the route needs a segment and a route position that stays "
-                                        "non-negative over the horizon (initial_route_pos, nominal_speed)");
-        }
-        p->has_route_progress = true;
-      }
-      auto point_at = [&](const auto& segs, auto route_pos, double* px, double* py) {
-        using S = decltype(route_pos);
-        const int first = desc->polyline_offsets[src_poly] - src_poly;
-        const int nseg = desc->polyline_offsets[src_poly + 1] - desc->polyline_offsets[src_poly] - 1;
-        std::vector<S> cumulative(1, S(0));
-        for (int c = 0; c < nseg; c++) cumulative.push_back(cumulative.back() + segs[size_t(first + c) * kSegStride + 4]);
-        auto upper = std::upper_bound(cumulative.begin(), cumulative.end(), route_pos);
-        if (upper == cumulative.end()) upper--;
-        upper--;
-        const size_t idx = size_t(upper - cumulative.begin());
-        const S remaining = route_pos - cumulative[idx];
-        const S* sg = &segs[size_t(first + idx) * kSegStride];
-        *px = double(S(sg[0] + remaining * sg[5]));
-        *py = double(S(sg[1] + remaining * sg[6]));
-      };
-      for (int k = 0; k < d.T; k++) {
-        const double t = double(k) * d.dt;
-        double f0 = t * double(o.value), f1 = 0.0, d0 = f0, d1 = 0.0;
-        if (route) {
-          const double pos = double(desc->terms[ti].value2) + (t - 0.0) * double(o.value);
-          point_at(segs_f, float(pos), &f0, &f1);
-          point_at(segs_d, double(pos), &d0, &d1);
-        }
-        tnom_f.push_back(f0); tnom_f.push_back(f1);
-        tnom_d.push_back(d0); tnom_d.push_back(d1);
-      }
-      o.polyline = ntab++;  // from here on: the term's table
-    }
-  }
-  // TotalCosts summation order per player: state costs then control costs, table order
-  int maxc = 0;
-  for (int i = 0; i < d.N; i++) {
-    int cnt = 0;
-    for (int ti = 0; ti < desc->num_terms; ti++)
-      if (dt[ti].player == i && (dt[ti].role == ILQG_ROLE_STATE_COST || dt[ti].role == ILQG_ROLE_CONTROL_COST)) cnt++;
-    if (cnt > maxc) maxc = cnt;
-  }
-  d.cost_order_stride = maxc + 1;
-  std::vector<int> order(size_t(d.N) * d.cost_order_stride, 0);
-  for (int i = 0; i < d.N; i++) {
-    int* o = order.data() + size_t(i) * d.cost_order_stride;
-    for (int role = 0; role < 2; role++)
-      for (int ti = 0; ti < desc->num_terms; ti++)
-        if (dt[ti].player == i && dt[ti].role == role) o[1 + o[0]++] = ti;
-  }
-  RowProgramHost rph;
-  {
-    std::string rerr;
-    if (!build_row_program(d, dt, desc->polyline_offsets, &rph, &rerr)) {
-      ilqg_problem_destroy(p);
-      return fail(ILQG_ERR_UNSUPPORTED, rerr);
-    }
-  }
-  d.row_prog_words = int(rph.words.size());
-  p->row_prog_host = rph.words;
-  p->op_term = rph.op_term;
-  {
-    // a registered structure (ilqg_rowprog_static.hpp)?  Word for word, parameters masked.
-    std::vector<int> masked = rph.words;
-    row_program_mask_parameters(&masked);
-#define X(ID_, NX_, NP_, MU_)                                                                                         \
-    if (p->static_prog == 0 && d.n == NX_ && d.N == NP_ && int(masked.size()) == StaticRowProg<ID_>::kWords &&         \
-        std::memcmp(masked.data(), StaticRowProg<ID_>::w, sizeof(int) * masked.size()) == 0)                          \
-      p->static_prog = ID_;
-    ILQG_STATIC_PROGS(X)
-#undef X
-  }
-  d.rp_pslots = rph.num_pslots;
-  d.rp_lslots = rph.max_lslots;
-  d.rp_gslots = rph.max_gslots;
-  d.rp_maps_off = rph.maps_off;
-  d.rp_maps_words = rph.maps_words;
-  d.rp_compact_off = rph.compact_off;
-  d.rp_compact_w = rph.compact_w;
-  if (host_only) {
-    *out = p;
-    return ILQG_OK;
-  }
-  // ---- device tables ----
-  hipError_t e = hipMalloc(&p->d_terms, sizeof(DevTerm) * dt.size());
-  if (e == hipSuccess) e = hipMalloc(&p->d_poly_off, sizeof(int) * (desc->num_polylines + 1));
-  if (e == hipSuccess && desc->num_polylines)
-    e = hipMemcpy(p->d_poly_off, desc->polyline_offsets, sizeof(int) * (desc->num_polylines + 1), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&p->d_poly_pts, sizeof(float) * 2 * (npts > 0 ? npts : 1));
-  if (e == hipSuccess && npts)
-    e = hipMemcpy(p->d_poly_pts, desc->polyline_points, sizeof(float) * 2 * npts, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&p->d_segs_f, sizeof(float) * (segs_f.size() + 1));
-  if (e == hipSuccess && !segs_f.empty())
-    e = hipMemcpy(p->d_segs_f, segs_f.data(), sizeof(float) * segs_f.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&p->d_segs_d, sizeof(double) * (segs_d.size() + 1));
-  if (e == hipSuccess && !segs_d.empty())
-    e = hipMemcpy(p->d_segs_d, segs_d.data(), sizeof(double) * segs_d.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&p->d_tnom_f, sizeof(double) * (tnom_f.size() + 2));
-  if (e == hipSuccess && !tnom_f.empty())
-    e = hipMemcpy(p->d_tnom_f, tnom_f.data(), sizeof(double) * tnom_f.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&p->d_tnom_d, sizeof(double) * (tnom_d.size() + 2));
-  if (e == hipSuccess && !tnom_d.empty())
-    e = hipMemcpy(p->d_tnom_d, tnom_d.data(), sizeof(double) * tnom_d.size(), hipMemcpyHostToDevice);
-  d.time_nominal_f = p->d_tnom_f;
-  d.time_nominal_d = p->d_tnom_d;
-  if (e == hipSuccess) e = hipMalloc(&p->d_dense_f, sizeof(float) * (dense_f.size() + 1));
-  if (e == hipSuccess && !dense_f.empty())
-    e = hipMemcpy(p->d_dense_f, dense_f.data(), sizeof(float) * dense_f.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&p->d_dense_d, sizeof(double) * (dense_d.size() + 1));
-  if (e == hipSuccess && !dense_d.empty())
-    e = hipMemcpy(p->d_dense_d, dense_d.data(), sizeof(double) * dense_d.size(), hipMemcpyHostToDevice);
-  d.dense_f = p->d_dense_f;
-  d.dense_d = p->d_dense_d;
-  if (e == hipSuccess) e = hipMalloc(&p->d_cost_order, sizeof(int) * order.size());
-  if (e == hipSuccess) e = hipMemcpy(p->d_cost_order, order.data(), sizeof(int) * order.size(), hipMemcpyHostToDevice);
-  // the term table is uploaded last: it carries the argument offsets computed above
-  if (e == hipSuccess) e = hipMemcpy(p->d_terms, dt.data(), sizeof(DevTerm) * dt.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&p->d_unfinished, 4 * sizeof(int));
-  if (e == hipSuccess) e = hipHostMalloc(&p->h_unfinished, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
-  if (e == hipSuccess) {
-    for (int i = 0; i < 16; i++) p->h_unfinished[i] = 0;
-    if (hipHostGetDevicePointer((void**)&p->h_unfinished_dev, p->h_unfinished, 0) != hipSuccess) p->h_unfinished_dev = nullptr;
-  }
-  {
-    // the device image: the program, then the per-instance parameters' column of every op's weight / value (none: -1)
-    std::vector<int> image = rph.words;
-    image.resize(rph.words.size() + 2 * rph.op_term.size() + 2, -1);
-    if (e == hipSuccess) e = hipMalloc(&p->d_row_prog, sizeof(int) * image.size());
-    if (e == hipSuccess) e = hipMemcpy(p->d_row_prog, image.data(), sizeof(int) * image.size(), hipMemcpyHostToDevice);
-  }
-  d.row_prog = p->d_row_prog;
-  if (e != hipSuccess) {
-    ilqg_problem_destroy(p);
-    return fail(ILQG_ERR_HIP, std::string("problem tables: ") + hipGetErrorString(e));
-  }
-  d.segs_f = p->d_segs_f;
-  d.segs_d = p->d_segs_d;
-  d.cost_order = p->d_cost_order;
-  d.terms = p->d_terms;
-  d.poly_off = p->d_poly_off;
-  d.poly_pts = p->d_poly_pts;
-  p->desc.terms = nullptr;
-  p->desc.polyline_offsets = nullptr;
-  p->desc.polyline_points = nullptr;
-  p->desc.dense_params = nullptr;
-  if (!uniform_udim(d.udim, d.N, &p->mu_uniform)) p->mu_uniform = 0;
-  {
-    bool instantiated = false;
-#define X(NX_, NP_, MU_) instantiated = instantiated || (d.n == NX_ && d.N == NP_ && p->mu_uniform == MU_);
-    ILQG_FOR_DIMS(X)
-#undef X
-    if (!instantiated) p->generic = true;
-  }
-  *out = p;
-  return ILQG_OK;
-}
-
-ilqg_status ilqg_problem_create(const ilqg_problem_desc* desc, ilqg_problem** out) { return problem_create_impl(desc, out, false); }
-
-ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words_out, int32_t capacity, int32_t* num_words,
-                                   int32_t* static_id) {
-  if (!num_words) return fail(ILQG_ERR_INVALID, "null argument");
-  ilqg_problem* p = nullptr;
-  ilqg_status s = problem_create_impl(desc, &p, true);
-  if (s != ILQG_OK) return s;
-  s = ilqg_problem_row_program(p, words_out, capacity, num_words, static_id);
-  ilqg_problem_destroy(p);
+  ProblemTables tables;
+  std::unique_ptr<ilqg_problem> p;
+  // (the sizes in front of the device: a bad player count or horizon is reported on a machine without one too)
+  ilqg_status s = check_problem_sizes(*desc, &tables);
+  if (s == ILQG_OK) s = check_device();
+  if (s == ILQG_OK) s = build_problem_tables(*desc, &tables);
+  if (s == ILQG_OK) s = upload_problem(*desc, tables, &p);
+  if (s == ILQG_OK) *out = p.release();
   return s;
 }
 
-void ilqg_problem_destroy(ilqg_problem* p) {
-  if (!p) return;
-  if (p->d_terms) (void)hipFree(p->d_terms);
-  if (p->d_poly_off) (void)hipFree(p->d_poly_off);
-  if (p->d_poly_pts) (void)hipFree(p->d_poly_pts);
-  if (p->d_segs_f) (void)hipFree(p->d_segs_f);
-  if (p->d_segs_d) (void)hipFree(p->d_segs_d);
-  if (p->d_dense_f) (void)hipFree(p->d_dense_f);
-  if (p->d_dense_d) (void)hipFree(p->d_dense_d);
-  if (p->d_tnom_f) (void)hipFree(p->d_tnom_f);
-  if (p->d_tnom_d) (void)hipFree(p->d_tnom_d);
-  if (p->d_cost_order) (void)hipFree(p->d_cost_order);
-  if (p->d_row_prog) (void)hipFree(p->d_row_prog);
-  if (p->d_inst_terms) (void)hipFree(p->d_inst_terms);
-  if (p->d_unfinished) (void)hipFree(p->d_unfinished);
-  if (p->h_unfinished) (void)hipHostFree(p->h_unfinished);
-  delete p;
+// The host half of creation alone (validation, flattening, the row program and its match against the registered
+// structures): no device is touched and no handle made.
+ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words_out, int32_t capacity, int32_t* num_words,
+                                   int32_t* static_id) {
+  if (!num_words || !desc) return fail(ILQG_ERR_INVALID, "null argument");
+  ProblemTables tables;
+  const ilqg_status s = build_problem_tables(*desc, &tables);
+  return s != ILQG_OK ? s : copy_row_program(tables.row_prog, tables.static_prog, words_out, capacity, num_words, static_id);
 }
+
+void ilqg_problem_destroy(ilqg_problem* p) { delete p; }
 
 // ---- per-instance cost parameters (ilqg.h) ----
-namespace {
-const char* cost_kind_name(int kind) {
-  switch (kind) {
-    case ILQG_COST_QUADRATIC: return "QUADRATIC";
-    case ILQG_COST_QUADRATIC_POLYLINE2: return "QUADRATIC_POLYLINE2";
-    case ILQG_COST_SEMIQUADRATIC: return "SEMIQUADRATIC";
-    case ILQG_COST_SEMIQUADRATIC_POLYLINE2: return "SEMIQUADRATIC_POLYLINE2";
-    case ILQG_COST_PROXIMITY: return "PROXIMITY";
-    case ILQG_COST_SIGNED_DISTANCE: return "SIGNED_DISTANCE";
-    case ILQG_COST_EXTREME_VALUE: return "EXTREME_VALUE";
-    case ILQG_CONSTRAINT_PROXIMITY: return "CONSTRAINT_PROXIMITY";
-    case ILQG_CONSTRAINT_SINGLE_DIMENSION: return "CONSTRAINT_SINGLE_DIMENSION";
-    case ILQG_COST_POLYLINE2_SIGNED_DISTANCE: return "POLYLINE2_SIGNED_DISTANCE";
-    case ILQG_COST_QUADRATIC_DIFFERENCE: return "QUADRATIC_DIFFERENCE";
-    case ILQG_COST_ORIENTATION: return "ORIENTATION";
-    case ILQG_COST_QUADRATIC_NORM: return "QUADRATIC_NORM";
-    case ILQG_COST_SEMIQUADRATIC_NORM: return "SEMIQUADRATIC_NORM";
-    case ILQG_COST_RELATIVE_DISTANCE: return "RELATIVE_DISTANCE";
-    case ILQG_COST_LOCALLY_CONVEX_PROXIMITY: return "LOCALLY_CONVEX_PROXIMITY";
-    case ILQG_COST_CURVATURE: return "CURVATURE";
-    case ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE: return "CONSTRAINT_POLYLINE2_SIGNED_DISTANCE";
-    case ILQG_COST_NOMINAL_PATH_LENGTH: return "NOMINAL_PATH_LENGTH";
-    case ILQG_COST_ROUTE_PROGRESS: return "ROUTE_PROGRESS";
-    case ILQG_COST_WEIGHTED_CONVEX_PROXIMITY: return "WEIGHTED_CONVEX_PROXIMITY";
-    case ILQG_CONSTRAINT_AFFINE_SCALAR: return "CONSTRAINT_AFFINE_SCALAR";
-    case ILQG_CONSTRAINT_AFFINE_VECTOR: return "CONSTRAINT_AFFINE_VECTOR";
-  }
-  return "unknown kind";
-}
-// Does a term of this kind read the field (the table of ilqg.h; ilqg_models.hpp: term_evaluate_leaf_of and the row ops)?
-// Null: yes; else why not.
-const char* instance_param_refusal(int kind, int field) {
-  const bool weight = field == ILQG_PARAM_WEIGHT;
-  switch (kind) {
-    case ILQG_COST_EXTREME_VALUE: return "an EXTREME_VALUE term has no parameters of its own: declare its children";
-    case ILQG_CONSTRAINT_AFFINE_SCALAR:
-    case ILQG_CONSTRAINT_AFFINE_VECTOR: return "the affine constraints keep their coefficients in dense blocks";
-    case ILQG_COST_NOMINAL_PATH_LENGTH:
-    case ILQG_COST_ROUTE_PROGRESS:
-      return weight ? nullptr : "its nominal speed is tabulated per time step when the problem is created";
-    case ILQG_COST_SIGNED_DISTANCE:
-    case ILQG_COST_POLYLINE2_SIGNED_DISTANCE: return weight ? "this kind does not read its weight" : nullptr;
-    case ILQG_CONSTRAINT_PROXIMITY:
-    case ILQG_CONSTRAINT_SINGLE_DIMENSION:
-    case ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE: return weight ? "a constraint has no weight" : nullptr;
-    case ILQG_COST_QUADRATIC_POLYLINE2:
-    case ILQG_COST_QUADRATIC_DIFFERENCE:
-    case ILQG_COST_RELATIVE_DISTANCE:
-    case ILQG_COST_CURVATURE: return weight ? nullptr : "this kind has no nominal or threshold";
-    case ILQG_COST_QUADRATIC:
-    case ILQG_COST_SEMIQUADRATIC:
-    case ILQG_COST_SEMIQUADRATIC_POLYLINE2:
-    case ILQG_COST_PROXIMITY:
-    case ILQG_COST_ORIENTATION:
-    case ILQG_COST_QUADRATIC_NORM:
-    case ILQG_COST_SEMIQUADRATIC_NORM:
-    case ILQG_COST_LOCALLY_CONVEX_PROXIMITY:
-    case ILQG_COST_WEIGHTED_CONVEX_PROXIMITY: return nullptr;
-  }
-  return "unknown cost kind";
-}
-ilqg_status instance_params_check_terms(int num_terms, const ilqg_cost_term* terms, int32_t count,
-                                        const ilqg_instance_param* params) {
-  if (count < 0 || count > ILQG_MAX_INSTANCE_PARAMS)
-    return fail(ILQG_ERR_INVALID, "instance parameters: count must be 0 .. ILQG_MAX_INSTANCE_PARAMS");
-  if (count > 0 && (!params || !terms)) return fail(ILQG_ERR_INVALID, "null argument");
-  for (int c = 0; c < count; c++) {
-    const int term = params[c].term, field = params[c].field;
-    const std::string where = "instance parameter " + std::to_string(c) + " (term " + std::to_string(term) + ", " +
-                              (field == ILQG_PARAM_WEIGHT ? "weight" : field == ILQG_PARAM_VALUE ? "value" : "field " + std::to_string(field)) + "): ";
-    if (term < 0 || term >= num_terms)
-      return fail(ILQG_ERR_UNSUPPORTED, where + "term index out of range (the problem has " + std::to_string(num_terms) + " terms)");
-    if (field != ILQG_PARAM_WEIGHT && field != ILQG_PARAM_VALUE)
-      return fail(ILQG_ERR_UNSUPPORTED, where + "not an ilqg_param_field");
-    for (int q = 0; q < c; q++)
-      if (params[q].term == term && params[q].field == field)
-        return fail(ILQG_ERR_UNSUPPORTED, where + "declared twice (also parameter " + std::to_string(q) + ")");
-    if (const char* why = instance_param_refusal(terms[term].kind, field))
-      return fail(ILQG_ERR_UNSUPPORTED, where + cost_kind_name(terms[term].kind) + ": " + why);
-  }
-  return ILQG_OK;
-}
-// A call that evaluates costs on `batch` instances while a table for another batch is bound would read past the table
-ilqg_status instance_batch_check(const ilqg_problem* p, int32_t batch) {
-  if (p->dev.inst_values && batch != p->inst_batch)
-    return fail(ILQG_ERR_INVALID, "per-instance parameter values are bound for a batch of " + std::to_string(p->inst_batch) +
-                                      ", this call has " + std::to_string(batch) + " instances");
-  return ILQG_OK;
-}
-}  // namespace
-
 ilqg_status ilqg_instance_params_check(const ilqg_problem_desc* desc, int32_t count, const ilqg_instance_param* params) {
   if (!desc) return fail(ILQG_ERR_INVALID, "null argument");
   return instance_params_check_terms(desc->num_terms, desc->terms, count, params);
@@ -2763,32 +2149,8 @@ ilqg_status ilqg_problem_declare_instance_params(ilqg_problem* p, int32_t count,
   if (!p) return fail(ILQG_ERR_INVALID, "null argument");
   if (p->dev.inst_values)
     return fail(ILQG_ERR_INVALID, "instance parameters cannot be declared while values are bound: unbind first");
-  ilqg_status s = instance_params_check_terms(int(p->terms_host.size()), p->terms_host.data(), count, params);
-  if (s != ILQG_OK) return s;
-  // the row stage's side table: per op of the row program the column of its weight / value (the program is not touched)
-  std::vector<int> cols(p->op_term.size() * 2 + 2, -1), terms(size_t(count) * 2 + 2, 0);
-  for (int c = 0; c < count; c++) {
-    terms[2 * c] = params[c].term;
-    terms[2 * c + 1] = params[c].field;
-    for (size_t op = 0; op < p->op_term.size(); op++)
-      if (p->op_term[op] == params[c].term) cols[2 * op + (params[c].field == ILQG_PARAM_WEIGHT ? 0 : 1)] = c;
-  }
-  if (!p->d_row_prog) return fail(ILQG_ERR_INVALID, "a host-only problem handle has no device tables");
-  // kernels of earlier calls on any stream may still read the old tables (unbound: they look at neither)
-  hipError_t e = hipDeviceSynchronize();
-  int* d_terms = nullptr;
-  if (e == hipSuccess) e = hipMalloc(&d_terms, sizeof(int) * terms.size());
-  if (e == hipSuccess) e = hipMemcpy(d_terms, terms.data(), sizeof(int) * terms.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = hipMemcpy(p->d_row_prog + p->row_prog_host.size(), cols.data(), sizeof(int) * cols.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (d_terms) (void)hipFree(d_terms);
-    return fail(ILQG_ERR_HIP, std::string("instance parameter tables: ") + hipGetErrorString(e));
-  }
-  if (p->d_inst_terms) (void)hipFree(p->d_inst_terms);
-  p->d_inst_terms = d_terms;
-  p->inst_params.assign(params, params + count);
-  return ILQG_OK;
+  const ilqg_status s = instance_params_check_terms(int(p->terms_host.size()), p->terms_host.data(), count, params);
+  return s != ILQG_OK ? s : declare_instance_params(p, count, params);
 }
 
 ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, const float* values) {
@@ -2805,7 +2167,7 @@ ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, co
     return fail(ILQG_ERR_INVALID, "no instance parameters are declared (ilqg_problem_declare_instance_params)");
   if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance parameter values: batch must be positive");
   d.inst_values = values;
-  d.inst_terms = p->d_inst_terms;
+  d.inst_terms = p->d_inst_terms.get();
   d.inst_count = int(p->inst_params.size());
   p->inst_batch = batch;
   return ILQG_OK;
@@ -2850,7 +2212,7 @@ ilqg_status ilqg_linearize_batch(const ilqg_problem* p, int32_t batch, const voi
                                  void* Bm, const int32_t* active, void* stream) {
   if (!p || !xs || !us || !A || !Bm) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
-  return launch_linquad(p, batch, xs, us, nullptr, nullptr, nullptr, A, Bm, nullptr, nullptr, nullptr, nullptr,
+  return launch_linquad(p, p->dev, batch, xs, us, nullptr, nullptr, nullptr, A, Bm, nullptr, nullptr, nullptr, nullptr,
                         nullptr, nullptr, active, stream);
 }
 
@@ -2860,7 +2222,7 @@ ilqg_status ilqg_quadraticize_batch(const ilqg_problem* p, int32_t batch, const 
   if (!p || !xs || !us || !Q || !l || !R || !r) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
   if (ilqg_status sb = instance_batch_check(p, batch)) return sb;
-  return launch_linquad(p, batch, xs, us, lambdas, mu, t_extreme, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
+  return launch_linquad(p, p->dev, batch, xs, us, lambdas, mu, t_extreme, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
                         active, stream);
 }
 
@@ -2873,7 +2235,7 @@ ilqg_status ilqg_total_costs_batch(const ilqg_problem* p, int32_t batch, const v
   const size_t esz = p->desc.dtype == ILQG_F32 ? 4 : 8;
   ilqg_status s = Scratch().reserve(size_t(batch) * d.T * d.N * esz);
   if (s != ILQG_OK) return s;
-  s = launch_linquad(p, batch, xs, us, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+  s = launch_linquad(p, p->dev, batch, xs, us, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                      nullptr, nullptr, ilqg_shared::scratch_state().ptr, active, stream);
   if (s != ILQG_OK) return s;
 #define CALL(TY_)                                                                                             \
@@ -3094,9 +2456,9 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
   // PlayerCost::Quadraticize of every player at every step (:168-172), whatever the player's time structure: the
   // quadraticisation kernel is launched on a copy of the problem whose players are all time-additive (the copy carries
   // the declared per-instance parameters and the bound table; each chunk below starts at its own row of it)
-  ilqg_problem full = *p;
-  for (int i = 0; i < full.dev.N; i++) full.dev.structure[i] = ILQG_SUM;
-  const DevProblem& d = full.dev;
+  DevProblem full = p->dev;
+  for (int i = 0; i < full.N; i++) full.structure[i] = ILQG_SUM;
+  const DevProblem& d = full;
   const size_t esz = p->desc.dtype == ILQG_F32 ? 4 : 8;
   const size_t per_inst = size_t(d.T) * (size_t(d.N) * d.n * d.n + size_t(d.N) * d.n + d.pairs.Rsz + d.pairs.rsz) * esz;
   int chunk = int((size_t(256) << 20) / per_inst);
@@ -3115,8 +2477,8 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
     char* r = R + size_t(nb) * d.T * d.pairs.Rsz * esz;
     const char* xs_c = (const char*)xs + size_t(b0) * d.T * d.n * esz;
     const char* us_c = (const char*)us + size_t(b0) * d.T * d.m * esz;
-    if (p->dev.inst_values) full.dev.inst_values = p->dev.inst_values + size_t(b0) * p->dev.inst_count;
-    s = launch_linquad(&full, nb, xs_c, us_c, nullptr, nullptr, nullptr, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
+    if (p->dev.inst_values) full.inst_values = p->dev.inst_values + size_t(b0) * p->dev.inst_count;
+    s = launch_linquad(p, full, nb, xs_c, us_c, nullptr, nullptr, nullptr, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
                        nullptr, stream);
     if (s != ILQG_OK) break;
 #define CALL(TY_)                                                                                                  \

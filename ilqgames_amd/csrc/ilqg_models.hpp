@@ -114,6 +114,26 @@ constexpr int kSubStatesMax = 8;
 __host__ __device__ inline bool is_plain_rk4_kind(int kind) {
   return kind == ILQG_DYN_UNICYCLE_5D || kind == ILQG_DYN_CAR_7D || kind == ILQG_DYN_DELAYED_DUBINS_CAR;
 }
+// What a description's subsystem of this kind must look like (host only: creation validates against it).  xdim < 0: no
+// such kind; `paired`: a row of a two-player model with one shared state, which only occurs beside its partner.
+struct SubsystemShape { int xdim, udim; bool paired; };
+inline SubsystemShape subsystem_shape(int kind) {
+  switch (kind) {
+    case ILQG_DYN_UNICYCLE_4D: return {4, 2, false};
+    case ILQG_DYN_CAR_5D: return {5, 2, false};
+    case ILQG_DYN_CAR_6D: return {6, 2, false};
+    case ILQG_DYN_UNICYCLE_4D_DISTURBED: return {4, 2, true};
+    case ILQG_DYN_PLANAR_DISTURBANCE: return {0, 2, true};
+    case ILQG_DYN_DUBINS_CAR: return {3, 1, false};
+    case ILQG_DYN_AIR_3D_EVADER: return {3, 1, true};
+    case ILQG_DYN_AIR_3D_PURSUER: return {0, 1, true};
+    case ILQG_DYN_POINT_MASS_2D: return {4, 2, false};
+    case ILQG_DYN_UNICYCLE_5D: return {5, 2, false};
+    case ILQG_DYN_CAR_7D: return {7, 2, false};
+    case ILQG_DYN_DELAYED_DUBINS_CAR: return {4, 1, false};
+  }
+  return {-1, 2, false};
+}
 template <typename T>
 __device__ __forceinline__ void sub_eval8(int kind, T L, const T* x, T u0, T u1, T* xd, T d0 = T(0), T d1 = T(0)) {
   if (kind == ILQG_DYN_UNICYCLE_5D) {

@@ -1,0 +1,655 @@
+// ilqg_problem.hpp — the problem object behind the C ABI's `ilqg_problem` handle (include/ilqg.h):
+//   ProblemTables          what creation computes on the host: the DevProblem with its scalar fields filled and every table
+//                          a kernel reads.  build_problem_tables() touches no device, so a refusal has nothing to release;
+//                          the host-only entry point (ilqg_row_program_build) is a ProblemTables and nothing else.
+//   DeviceBuffer / upload  a table on the device, freed by whoever holds it (the two deleters: no other hipFree here).
+//   ilqg_problem           the handle: the device tables, the DevProblem that points at them and what the solves keep
+//                          between calls.  ilqg_problem_destroy is `delete`.
+// Part of ilqg_api.hip, included once behind its fail() and ILQG_FOR_DIMS.  Every translation unit of the library sees the
+// handle and the buffers (the per-shape units reach into the handle); only the main unit the builder and the upload.
+#pragma once
+
+#include <algorithm>
+#include <memory>
+
+#include "ilqg_rowprog.hpp"         // RowProgramHost, build_row_program
+#include "ilqg_rowprog_static.hpp"  // the registered structures
+#include "ilqg_stages.hpp"          // DevProblem, the models, dims_use_plain_rk4
+
+namespace ilqg {
+
+// LoopTimer (include/ilqgames/utils/loop_timer.h:60-98, src/loop_timer.cpp:55-92): the last ten iteration times
+struct LoopTimer {
+  double times[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int count = 0, next = 0;
+  void add(double seconds) {
+    times[next] = seconds;
+    next = (next + 1) % 10;
+    if (count < 10) count++;
+  }
+  double upper_bound() const {  // mean + 3 sigma (unbiased), 0.02 s until two samples exist
+    if (count < 2) return 0.02;
+    double mean = 0.0, var = 0.0;
+    for (int i = 0; i < count; i++) mean += times[i];
+    mean /= count;
+    for (int i = 0; i < count; i++) var += (times[i] - mean) * (times[i] - mean);
+    return mean + 3.0 * std::sqrt(var / (count - 1));
+  }
+};
+
+struct HipFree { void operator()(void* p) const { (void)hipFree(p); } };
+struct HipHostFree { void operator()(void* p) const { (void)hipHostFree(p); } };
+template <class X> using DeviceBuffer = std::unique_ptr<X[], HipFree>;
+using PinnedInts = std::unique_ptr<int[], HipHostFree>;
+
+// A table that exists once per precision of the geometry: on the host, and on the device
+template <class F, class D> struct BothPrecisions { std::vector<F> f; std::vector<D> d; };
+template <class F, class D> struct DeviceBothPrecisions { DeviceBuffer<F> f; DeviceBuffer<D> d; };
+
+inline GenDims gen_dims_of(int n, int N, const int32_t* udim, int T) {
+  GenDims g{};
+  g.n = n; g.N = N; g.T = T;
+  g.uoff[0] = 0;
+  for (int i = 0; i < N; i++) {
+    g.udim[i] = udim[i];
+    g.uoff[i + 1] = g.uoff[i] + udim[i];
+  }
+  g.m = g.uoff[N];
+  return g;
+}
+
+}  // namespace ilqg
+
+struct ilqg_problem {
+  ilqg::DevProblem dev;    // what the kernels get: its pointers are the buffers below
+  ilqg_problem_desc desc;  // the description's scalars (its pointers are null: the caller's arrays are not kept)
+  std::vector<ilqg_cost_term> terms_host;
+  ilqg::DeviceBuffer<ilqg::DevTerm> d_terms;
+  ilqg::DeviceBuffer<int> d_poly_off;
+  ilqg::DeviceBuffer<float> d_poly_pts;
+  ilqg::DeviceBothPrecisions<float, double> d_segs, d_dense;
+  ilqg::DeviceBothPrecisions<double, double> d_time_nominal;
+  ilqg::DeviceBuffer<int> d_cost_order;
+  // the row program as built (ilqg_problem_row_program), with the term each op carries, and its device image
+  ilqg::RowProgramHost row_prog;
+  ilqg::DeviceBuffer<int> d_row_prog;
+  // Per-instance cost parameters (ilqg.h): the declared (term, field) list and its device table (DevProblem::inst_terms);
+  // dev.inst_values / inst_count are set while a table is bound, for `inst_batch` instances
+  std::vector<ilqg_instance_param> inst_params;
+  ilqg::DeviceBuffer<int> d_inst_terms;
+  int inst_batch = 0;
+  int static_prog = 0;                // id of the registered structure it matches (ilqg_rowprog_static.hpp), 0: none
+  ilqg::DeviceBuffer<int> d_unfinished;  // instances still running after an LQ-kernel launch
+  ilqg::PinnedInts h_unfinished;  // pinned host mirror: [0..3] the counters, [8] the sequence number of read_round_counters
+  int* h_unfinished_dev = nullptr;  // ... as the device addresses it
+  int publish_seq = 0;
+  bool counters_clean = false;  // d_unfinished was cleared by the last thing that touched it (read_round_counters)
+  int mu_uniform = 0;
+  bool has_route_progress = false;  // a RouteProgressCost term: its tables are a first solve's (initial time 0)
+  int last_schedule = 0;  // ILQG_SCHEDULE_* of the last solve (ilqg_problem_last_schedule)
+  bool generic = false;  // no specialised instantiation holds this problem: every entry point runs the run-time-dimensioned kernels
+  // The solver object's LoopTimer over its iterations, kept across solves as the reference's member is (only solves with a
+  // max_runtime feed and read it), and AugmentedLagrangianSolver's own (`timer_`) over its outer iterations
+  ilqg::LoopTimer loop_timer, al_loop_timer;
+};
+
+#if !defined(ILQG_PART_NX)
+namespace {
+
+bool build_pairs(const ilqg_pair* pairs, int npairs, const int* udim, int N, PairTable* pt, std::string* err) {
+  if (npairs > kMaxPairs) {
+    *err = "too many control blocks";
+    return false;
+  }
+  std::memset(pt, 0, sizeof(*pt));
+  pt->npairs = npairs;
+  for (int i = 0; i < kMaxPlayers; i++) pt->pii[i] = -1;
+  int Rsz = 0, rsz = 0;
+  for (int q = 0; q < npairs; q++) {
+    const int i = pairs[q].i, j = pairs[q].j;
+    if (i < 0 || i >= N || j < 0 || j >= N) {
+      *err = "control block index out of range";
+      return false;
+    }
+    pt->pi[q] = i;
+    pt->pj[q] = j;
+    pt->roff[q] = Rsz;
+    pt->rgoff[q] = rsz;
+    pt->from_cost[q] = 1;
+    Rsz += udim[j] * udim[j];
+    rsz += udim[j];
+    if (i == j) pt->pii[i] = q;
+  }
+  pt->Rsz = Rsz;
+  pt->rsz = rsz;
+  for (int i = 0; i < N; i++)
+    if (pt->pii[i] < 0) {
+      *err = "player " + std::to_string(i) + " is missing a control Hessian";  // lq_feedback_solver.cpp:139-140
+      return false;
+    }
+  return true;
+}
+
+bool uniform_udim(const int32_t* udim, int N, int* mu) {
+  for (int i = 1; i < N; i++)
+    if (udim[i] != udim[0]) return false;
+  *mu = udim[0];
+  return true;
+}
+
+// ---- the host half: a description's tables ----
+struct ProblemTables {
+  DevProblem dev;              // scalar fields filled, pointers null
+  std::vector<DevTerm> terms;  // at least one entry
+  std::vector<int> poly_off;   // [num_polylines + 1] (none: empty)
+  std::vector<float> poly_pts;
+  BothPrecisions<float, double> segs;           // DevProblem::segs_f / segs_d
+  BothPrecisions<float, double> dense;          // DevProblem::dense_f / dense_d
+  BothPrecisions<double, double> time_nominal;  // DevProblem::time_nominal_f / time_nominal_d
+  std::vector<int> cost_order;
+  RowProgramHost row_prog;
+  int static_prog = 0;  // id of the registered structure the program matches (ilqg_rowprog_static.hpp), 0: none
+  int mu_uniform = 0;   // the players' common control dimension, 0: they differ
+  bool has_route_progress = false;
+  bool generic = false;  // no specialised instantiation holds the problem
+};
+
+ilqg_status check_problem_sizes(const ilqg_problem_desc& desc, ProblemTables*) {
+  if (desc.num_players < 1 || desc.num_players > ILQG_MAX_PLAYERS) return fail(ILQG_ERR_INVALID, "bad player count");
+  if (desc.T < 2 || desc.T > kMaxT) return fail(ILQG_ERR_INVALID, "bad horizon");
+  return ILQG_OK;
+}
+
+// The concatenated system: each subsystem's place in the state and the controls, and which kernels hold its shape
+ilqg_status flatten_subsystems(const ilqg_problem_desc& desc, ProblemTables* t) {
+  DevProblem& d = t->dev;
+  std::memset(&d, 0, sizeof(d));
+  d.N = desc.num_players;
+  d.T = desc.T;
+  d.dt = desc.dt;
+  const int kind0 = desc.subsystems[0].kind, kind1 = desc.subsystems[1].kind;
+  // TwoPlayerUnicycle4D is exactly the pair (disturbed unicycle, disturbance) and nothing else; Air3D likewise
+  const bool is_pair = desc.num_players == 2 && ((kind0 == ILQG_DYN_UNICYCLE_4D_DISTURBED && kind1 == ILQG_DYN_PLANAR_DISTURBANCE) ||
+                                                 (kind0 == ILQG_DYN_AIR_3D_EVADER && kind1 == ILQG_DYN_AIR_3D_PURSUER));
+  for (int i = 0; i < d.N; i++) {
+    const ilqg_subsystem& sub = desc.subsystems[i];
+    const SubsystemShape want = subsystem_shape(sub.kind);
+    if (want.paired && !is_pair)
+      return fail(ILQG_ERR_UNSUPPORTED, "the shared-state kinds only occur as the pairs (4, 5) and (7, 8)");
+    if ((sub.kind == ILQG_DYN_POINT_MASS_2D) != (kind0 == ILQG_DYN_POINT_MASS_2D))
+      return fail(ILQG_ERR_UNSUPPORTED, "point masses (kind 9) only occur in games made of point masses");
+    if (want.xdim < 0 || sub.xdim != want.xdim || sub.udim != want.udim)
+      return fail(ILQG_ERR_UNSUPPORTED, "unknown subsystem kind / dimension");
+    d.sub_kind[i] = sub.kind;
+    d.sub_param[i] = sub.param0;
+    d.udim[i] = sub.udim;
+    d.xoff[i + 1] = d.xoff[i] + sub.xdim;
+    d.uoff[i + 1] = d.uoff[i] + sub.udim;
+    d.state_reg[i] = desc.player_costs[i].state_regularization;
+    d.control_reg[i] = desc.player_costs[i].control_regularization;
+    d.structure[i] = desc.player_costs[i].structure;
+  }
+  d.n = d.xoff[d.N];
+  d.m = d.uoff[d.N];
+  if (d.n > ILQG_MAX_XDIM || d.m > ILQG_MAX_UDIM_TOTAL)  // before any table is sized by them
+    return fail(ILQG_ERR_UNSUPPORTED, "more than ILQG_MAX_XDIM states or ILQG_MAX_UDIM_TOTAL controls");
+  // DistanceBetween of the first subsystem: (px, py) where the model overrides it (two_player_unicycle_4d.h:141-147
+  // too), the whole block where it does not (the two Dubins cars: single_player_dynamical_system.h:69-71)
+  d.sync_dist_dims = d.sub_kind[0] == ILQG_DYN_DUBINS_CAR ? 3 : (d.sub_kind[0] == ILQG_DYN_DELAYED_DUBINS_CAR ? 4 : 2);
+  if (!uniform_udim(d.udim, d.N, &t->mu_uniform)) t->mu_uniform = 0;
+  bool plain = false, instantiated = false;
+  for (int i = 0; i < d.N; i++) plain = plain || is_plain_rk4_kind(d.sub_kind[i]);
+#define X(NX_, NP_, MU_) instantiated = instantiated || (d.n == NX_ && d.N == NP_ && t->mu_uniform == MU_);
+  ILQG_FOR_DIMS(X)
+#undef X
+  // Unicycle5D / Car7D / DelayedDubinsCar rows need an instantiation that carries the plain RK4 (dims_use_plain_rk4,
+  // ilqg_stages.hpp); in any other shape they run on the run-time-dimensioned path, which picks its integrator by model
+  t->generic = !instantiated || (plain && !dims_use_plain_rk4(d.n, d.N, d.udim[0]));
+  return ILQG_OK;
+}
+
+// The control blocks (i, j) in PlayerCost's first-touch order: control costs, then control constraints
+ilqg_status build_pair_table(const ilqg_problem_desc& desc, ProblemTables* t) {
+  DevProblem& d = t->dev;
+  std::vector<ilqg_pair> pairs;
+  std::vector<int> from_cost;
+  for (int i = 0; i < d.N; i++)
+    for (int pass = 0; pass < 2; pass++)
+      for (int ti = 0; ti < desc.num_terms; ti++) {
+        const ilqg_cost_term& c = desc.terms[ti];
+        if (c.player != i) continue;
+        if (pass == 0 && c.role != ILQG_ROLE_CONTROL_COST) continue;
+        if (pass == 1 && c.role != ILQG_ROLE_CONTROL_CONSTRAINT) continue;
+        bool found = false;
+        for (auto& pr : pairs) found = found || (pr.i == i && pr.j == c.arg);
+        if (!found) {
+          pairs.push_back({i, c.arg});
+          from_cost.push_back(pass == 0 ? 1 : 0);
+        }
+      }
+  std::string err;
+  if (!build_pairs(pairs.data(), (int)pairs.size(), d.udim, d.N, &d.pairs, &err)) return fail(ILQG_ERR_INVALID, err);
+  for (size_t q = 0; q < pairs.size(); q++) d.pairs.from_cost[q] = from_cost[q];
+  return ILQG_OK;
+}
+
+// The description's terms as the kernels read them, and where each one's argument vector sits inside a row's [x | u]
+ilqg_status build_term_table(const ilqg_problem_desc& desc, ProblemTables* t) {
+  DevProblem& d = t->dev;
+  d.num_terms = desc.num_terms;
+  d.num_polylines = desc.num_polylines;
+  t->terms.assign(desc.num_terms > 0 ? desc.num_terms : 1, DevTerm());
+  int nc = 0;
+  for (int ti = 0; ti < desc.num_terms; ti++) {
+    const ilqg_cost_term& c = desc.terms[ti];
+    DevTerm& o = t->terms[ti];
+    o.kind = c.kind; o.role = c.role; o.player = c.player; o.arg = c.arg;
+    for (int q = 0; q < 4; q++) o.idx[q] = c.idx[q];
+    o.weight = c.weight; o.value = c.value; o.flags = c.flags; o.polyline = c.polyline;
+    o.child_begin = c.child_begin; o.child_count = c.child_count; o.slot = c.constraint_slot;
+    o.k_start = c.first_step;
+    if (c.kind == ILQG_COST_WEIGHTED_CONVEX_PROXIMITY) {  // its two speed indices ride in `polyline` (wcp_indices)
+      if (c.role != ILQG_ROLE_STATE_COST || c.idx_extra[0] < 0 || c.idx_extra[0] >= d.n || c.idx_extra[1] < 0 ||
+          c.idx_extra[1] >= d.n)
+        return fail(ILQG_ERR_INVALID, "WeightedConvexProximityCost must be a top-level state cost with speed indices "
+                                      "inside the state");
+      o.polyline = c.idx_extra[0] | (c.idx_extra[1] << 16);
+    }
+    // Constraint::is_equality_ is only carried for the affine constraints (ilqg.h): on any other kind the multiplier
+    // update would drop its clip at zero while the mu gate stayed an inequality's
+    if ((c.flags & ILQG_FLAG_EQUALITY) && c.kind != ILQG_CONSTRAINT_AFFINE_SCALAR && c.kind != ILQG_CONSTRAINT_AFFINE_VECTOR)
+      return fail(ILQG_ERR_INVALID, "ILQG_FLAG_EQUALITY is only defined for the affine constraints");
+    if (c.constraint_slot >= 0 && c.constraint_slot + 1 > nc) nc = c.constraint_slot + 1;
+    const bool on_state = o.role == ILQG_ROLE_STATE_COST || o.role == ILQG_ROLE_STATE_CONSTRAINT || o.role == ILQG_ROLE_CHILD;
+    o.arg_off = on_state ? 0 : d.n + d.uoff[o.arg];
+    o.arg_dim = on_state ? d.n : d.udim[o.arg];
+  }
+  d.num_constraints = nc;
+  return ILQG_OK;
+}
+
+// Coefficient blocks of the affine constraints (DevProblem::dense_f / dense_d), each precision from the description's
+// floats in its own arithmetic; DevTerm::polyline of such a term becomes its block's offset
+ilqg_status build_affine_blocks(const ilqg_problem_desc& desc, ProblemTables* t) {
+  for (int ti = 0; ti < desc.num_terms; ti++) {
+    DevTerm& o = t->terms[ti];
+    if (!term_is_affine(o.kind)) continue;
+    const int dim = o.arg_dim;
+    const bool vec = o.kind == ILQG_CONSTRAINT_AFFINE_VECTOR;
+    const long long count = vec ? (long long)dim * dim + dim : dim + 1;
+    const bool constraint_role = o.role == ILQG_ROLE_STATE_CONSTRAINT || o.role == ILQG_ROLE_CONTROL_CONSTRAINT;
+    if (!constraint_role || o.slot < 0 || desc.dense_params == nullptr || desc.terms[ti].polyline < 0 ||
+        (long long)desc.terms[ti].polyline + count > desc.num_dense_params)
+      return fail(ILQG_ERR_INVALID, "an affine constraint must be a state / control constraint with a multiplier slot "
+                                    "and a coefficient block inside ilqg_problem_desc::dense_params");
+    const float* src = desc.dense_params + desc.terms[ti].polyline;
+    o.polyline = int(t->dense.f.size());
+    auto emit = [&](auto& out) {
+      using S = typename std::decay<decltype(out)>::type::value_type;
+      for (long long e = 0; e < count; e++) out.push_back(S(src[e]));
+      if (vec)  // ATA_ = A^T A, AAT_ = A A^T as the constructor forms them (affine_vector_constraint.h:60-61)
+        for (int which = 0; which < 2; which++)
+          for (int j = 0; j < dim; j++)
+            for (int i = 0; i < dim; i++) {
+              S acc = S(0);
+              for (int q = 0; q < dim; q++)
+                acc += which == 0 ? S(src[q + dim * i]) * S(src[q + dim * j]) : S(src[i + dim * q]) * S(src[j + dim * q]);
+              out.push_back(acc);
+            }
+    };
+    emit(t->dense.f);
+    emit(t->dense.d);
+  }
+  return ILQG_OK;
+}
+
+// The polylines, and the LineSegment2 objects of each (line_segment2.h:55-62) with its two shortcuts
+// (DevProblem::segs_f / segs_d), each precision from the points' floats in its own arithmetic
+ilqg_status build_segments(const ilqg_problem_desc& desc, ProblemTables* t) {
+  if (desc.num_polylines) {
+    t->poly_off.assign(desc.polyline_offsets, desc.polyline_offsets + desc.num_polylines + 1);
+    t->poly_pts.assign(desc.polyline_points, desc.polyline_points + 2 * size_t(t->poly_off.back()));
+  }
+  auto emit = [&](auto& out, const float* a, const float* b) {
+    using S = typename std::decay<decltype(out)>::type::value_type;
+    const S ax = a[0], ay = a[1], bx = b[0], by = b[1];
+    const S dx = ax - bx, dy = ay - by;
+    const S len = std::sqrt(dx * dx + dy * dy);
+    out.push_back(ax); out.push_back(ay); out.push_back(bx); out.push_back(by);
+    out.push_back(len); out.push_back((bx - ax) / len); out.push_back((by - ay) / len);
+  };
+  for (int q = 0; q < desc.num_polylines; q++) {
+    const float* pts = desc.polyline_points + 2 * desc.polyline_offsets[q];
+    const int nseg = desc.polyline_offsets[q + 1] - desc.polyline_offsets[q] - 1;
+    for (int c = 0; c < nseg; c++) {
+      const int pm = c > 0 ? c - 1 : c, pn = c + 2 <= nseg ? c + 2 : c + 1;
+      auto segment_and_shortcuts = [&](auto& out) {
+        emit(out, pts + 2 * c, pts + 2 * (c + 1));
+        emit(out, pts + 2 * pm, pts + 2 * (c + 1));
+        emit(out, pts + 2 * c, pts + 2 * pn);
+      };
+      segment_and_shortcuts(t->segs.f);
+      segment_and_shortcuts(t->segs.d);
+    }
+  }
+  t->dev.total_segs = int(t->segs.f.size() / kSegStride);
+  return ILQG_OK;
+}
+
+// Polyline2::PointAt (src/polyline2.cpp:68-103) on the segment table of one precision: walks the cumulative lengths
+template <class S>
+void polyline_point_at(const ilqg_problem_desc& desc, int polyline, const std::vector<S>& segs, S route_pos, double* px,
+                       double* py) {
+  const int first = desc.polyline_offsets[polyline] - polyline;
+  const int nseg = desc.polyline_offsets[polyline + 1] - desc.polyline_offsets[polyline] - 1;
+  std::vector<S> cumulative(1, S(0));
+  for (int c = 0; c < nseg; c++) cumulative.push_back(cumulative.back() + segs[size_t(first + c) * kSegStride + 4]);
+  auto upper = std::upper_bound(cumulative.begin(), cumulative.end(), route_pos);
+  if (upper == cumulative.end()) upper--;
+  upper--;
+  const size_t idx = size_t(upper - cumulative.begin());
+  const S remaining = route_pos - cumulative[idx];
+  const S* sg = &segs[size_t(first + idx) * kSegStride];
+  *px = double(S(sg[0] + remaining * sg[5]));
+  *py = double(S(sg[1] + remaining * sg[6]));
+}
+
+// Per-step nominals of the time-dependent costs, one table per such term and geometry precision (doubles: the
+// path-length nominal is a double product in the reference, nominal_path_length_cost.cpp:53; the route point is a
+// pair of the geometry's scalars, exact in double).  t = RelativeTime(k) = double(k) * dt (relative_time_tracker.h:
+// 63-65); the route position is a scalar of the geometry made from a double expression (route_progress_cost.cpp:57-59).
+// DevTerm::polyline of such a term becomes its table.
+ilqg_status build_time_nominals(const ilqg_problem_desc& desc, ProblemTables* t) {
+  const DevProblem& d = t->dev;
+  int ntab = 0;
+  for (int ti = 0; ti < desc.num_terms; ti++) {
+    DevTerm& o = t->terms[ti];
+    if (!term_is_time_dependent(o.kind)) continue;
+    const bool route = o.kind == ILQG_COST_ROUTE_PROGRESS;
+    if (o.role != ILQG_ROLE_STATE_COST || (route && (o.polyline < 0 || o.polyline >= desc.num_polylines)))
+      return fail(ILQG_ERR_INVALID, "a time-dependent cost must be a top-level state cost (with a polyline, for "
+                                    "RouteProgressCost)");
+    const int src_poly = o.polyline;
+    if (route) {
+      // Polyline2::PointAt CHECKs its argument (src/polyline2.cpp:68-103): a route position that is negative at any
+      // step, or a polyline without a segment, is a programmer error there and ILQG_ERR_INVALID here
+      const int nseg_r = desc.polyline_offsets[src_poly + 1] - desc.polyline_offsets[src_poly] - 1;
+      const double pos_first = double(desc.terms[ti].value2);
+      const double pos_last = pos_first + double(d.T - 1) * d.dt * double(o.value);
+      if (nseg_r < 1 || !(pos_first >= 0.0) || !(pos_last >= 0.0))
+        return fail(ILQG_ERR_INVALID, "RouteProgressCost: the route needs a segment and a route position that stays "
+                                      "non-negative over the horizon (initial_route_pos, nominal_speed)");
+      t->has_route_progress = true;
+    }
+    for (int k = 0; k < d.T; k++) {
+      const double tk = double(k) * d.dt;
+      const double pos = double(desc.terms[ti].value2) + (tk - 0.0) * double(o.value);
+      auto nominal = [&](const auto& segs, std::vector<double>& out) {
+        using S = typename std::decay<decltype(segs)>::type::value_type;
+        double x = tk * double(o.value), y = 0.0;
+        if (route) polyline_point_at(desc, src_poly, segs, S(pos), &x, &y);
+        out.push_back(x);
+        out.push_back(y);
+      };
+      nominal(t->segs.f, t->time_nominal.f);
+      nominal(t->segs.d, t->time_nominal.d);
+    }
+    o.polyline = ntab++;
+  }
+  return ILQG_OK;
+}
+
+// TotalCosts summation order per player: [count, state costs then control costs in table order]
+ilqg_status build_cost_order(const ilqg_problem_desc& desc, ProblemTables* t) {
+  DevProblem& d = t->dev;
+  const std::vector<DevTerm>& dt = t->terms;
+  int maxc = 0;
+  for (int i = 0; i < d.N; i++) {
+    int cnt = 0;
+    for (int ti = 0; ti < desc.num_terms; ti++)
+      if (dt[ti].player == i && (dt[ti].role == ILQG_ROLE_STATE_COST || dt[ti].role == ILQG_ROLE_CONTROL_COST)) cnt++;
+    if (cnt > maxc) maxc = cnt;
+  }
+  d.cost_order_stride = maxc + 1;
+  t->cost_order.assign(size_t(d.N) * d.cost_order_stride, 0);
+  for (int i = 0; i < d.N; i++) {
+    int* o = t->cost_order.data() + size_t(i) * d.cost_order_stride;
+    for (int role = 0; role < 2; role++)
+      for (int ti = 0; ti < desc.num_terms; ti++)
+        if (dt[ti].player == i && dt[ti].role == role) o[1 + o[0]++] = ti;
+  }
+  return ILQG_OK;
+}
+
+// The row program (ilqg_rowprog.hpp), and the registered structure it is, if any (ilqg_rowprog_static.hpp): word for
+// word, parameters masked
+ilqg_status build_row_program_and_match(const ilqg_problem_desc& desc, ProblemTables* t) {
+  DevProblem& d = t->dev;
+  RowProgramHost& rph = t->row_prog;
+  std::string err;
+  if (!build_row_program(d, t->terms, desc.polyline_offsets, &rph, &err)) return fail(ILQG_ERR_UNSUPPORTED, err);
+  d.row_prog_words = int(rph.words.size());
+  d.rp_pslots = rph.num_pslots;
+  d.rp_lslots = rph.max_lslots;
+  d.rp_gslots = rph.max_gslots;
+  d.rp_maps_off = rph.maps_off;
+  d.rp_maps_words = rph.maps_words;
+  d.rp_compact_off = rph.compact_off;
+  d.rp_compact_w = rph.compact_w;
+  std::vector<int> masked = rph.words;
+  row_program_mask_parameters(&masked);
+#define X(ID_, NX_, NP_, MU_)                                                                                   \
+  if (t->static_prog == 0 && d.n == NX_ && d.N == NP_ && int(masked.size()) == StaticRowProg<ID_>::kWords &&    \
+      std::memcmp(masked.data(), StaticRowProg<ID_>::w, sizeof(int) * masked.size()) == 0)                      \
+    t->static_prog = ID_;
+  ILQG_STATIC_PROGS(X)
+#undef X
+  return ILQG_OK;
+}
+
+// Everything creation does before it touches a device: the first check a description fails is the one reported
+ilqg_status build_problem_tables(const ilqg_problem_desc& desc, ProblemTables* t) {
+  *t = ProblemTables();
+  using Step = ilqg_status (*)(const ilqg_problem_desc&, ProblemTables*);
+  for (Step step : {check_problem_sizes, flatten_subsystems, build_pair_table, build_term_table, build_affine_blocks,
+                    build_segments, build_time_nominals, build_cost_order, build_row_program_and_match})
+    if (ilqg_status s = step(desc, t)) return s;
+  return ILQG_OK;
+}
+
+// ---- the device half: upload into the handle that owns what was uploaded ----
+ilqg_status hip_failed(const char* what, hipError_t e) {
+  return fail(ILQG_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+template <class X>
+hipError_t copy_to_device(X* dst, const std::vector<X>& host) {
+  return host.empty() ? hipSuccess : hipMemcpy(dst, host.data(), sizeof(X) * host.size(), hipMemcpyHostToDevice);
+}
+
+// A device buffer of host.size() + pad_elems elements whose head is `host` (the pad is not written)
+template <class X>
+ilqg_status upload(const std::vector<X>& host, size_t pad_elems, const char* what, DeviceBuffer<X>* out) {
+  X* raw = nullptr;
+  hipError_t e = hipMalloc((void**)&raw, sizeof(X) * (host.size() + pad_elems));
+  out->reset(raw);
+  if (e == hipSuccess) e = copy_to_device(raw, host);
+  return e == hipSuccess ? ILQG_OK : hip_failed(what, e);
+}
+template <class F, class D>
+ilqg_status upload(const BothPrecisions<F, D>& host, size_t pad_elems, const char* what, DeviceBothPrecisions<F, D>* out) {
+  const ilqg_status s = upload(host.f, pad_elems, what, &out->f);
+  return s != ILQG_OK ? s : upload(host.d, pad_elems, what, &out->d);
+}
+
+// The round counters' pinned host mirror (read_round_counters), zeroed, and its device address (null: it has none)
+ilqg_status alloc_counter_mirror(const char* what, PinnedInts* out, int** device_address) {
+  int* raw = nullptr;
+  const hipError_t e = hipHostMalloc((void**)&raw, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent);
+  if (e != hipSuccess) return hip_failed(what, e);
+  out->reset(raw);
+  for (int i = 0; i < 16; i++) raw[i] = 0;
+  if (hipHostGetDevicePointer((void**)device_address, raw, 0) != hipSuccess) *device_address = nullptr;
+  return ILQG_OK;
+}
+
+ilqg_status upload_problem(const ilqg_problem_desc& desc, const ProblemTables& t, std::unique_ptr<ilqg_problem>* out) {
+  auto p = std::make_unique<ilqg_problem>();
+  p->desc = desc;
+  p->desc.terms = nullptr;
+  p->desc.polyline_offsets = nullptr;
+  p->desc.polyline_points = nullptr;
+  p->desc.dense_params = nullptr;
+  p->terms_host.assign(desc.terms, desc.terms + desc.num_terms);
+  p->row_prog = t.row_prog;
+  p->static_prog = t.static_prog;
+  p->mu_uniform = t.mu_uniform;
+  p->has_route_progress = t.has_route_progress;
+  p->generic = t.generic;
+  // the row program's device image: the program, then per op the per-instance column of its weight / value (none: -1)
+  std::vector<int> image = t.row_prog.words;
+  image.resize(image.size() + 2 * t.row_prog.op_term.size() + 2, -1);
+  const char* what = "problem tables";
+  ilqg_status s = ILQG_OK;
+  auto up = [&](const auto& host, size_t pad_elems, auto* buffer) {
+    if (s == ILQG_OK) s = upload(host, pad_elems, what, buffer);
+  };
+  up(t.terms, 0, &p->d_terms);
+  up(t.poly_off, t.poly_off.empty() ? 1 : 0, &p->d_poly_off);
+  up(t.poly_pts, t.poly_pts.empty() ? 2 : 0, &p->d_poly_pts);
+  up(t.segs, 1, &p->d_segs);
+  up(t.time_nominal, 2, &p->d_time_nominal);
+  up(t.dense, 1, &p->d_dense);
+  up(t.cost_order, 0, &p->d_cost_order);
+  up(std::vector<int>(), 4, &p->d_unfinished);  // the four round counters: cleared by whoever counts
+  if (s == ILQG_OK) s = alloc_counter_mirror(what, &p->h_unfinished, &p->h_unfinished_dev);
+  up(image, 0, &p->d_row_prog);
+  if (s != ILQG_OK) return s;
+  DevProblem& d = p->dev;
+  d = t.dev;
+  d.terms = p->d_terms.get();
+  d.poly_off = p->d_poly_off.get();
+  d.poly_pts = p->d_poly_pts.get();
+  d.segs_f = p->d_segs.f.get();
+  d.segs_d = p->d_segs.d.get();
+  d.time_nominal_f = p->d_time_nominal.f.get();
+  d.time_nominal_d = p->d_time_nominal.d.get();
+  d.dense_f = p->d_dense.f.get();
+  d.dense_d = p->d_dense.d.get();
+  d.cost_order = p->d_cost_order.get();
+  d.row_prog = p->d_row_prog.get();
+  *out = std::move(p);
+  return ILQG_OK;
+}
+
+// ilqg_problem_row_program / ilqg_row_program_build
+ilqg_status copy_row_program(const RowProgramHost& prog, int static_prog, int32_t* words_out, int32_t capacity,
+                             int32_t* num_words, int32_t* static_id) {
+  *num_words = int32_t(prog.words.size());
+  if (static_id) *static_id = static_prog;
+  if (words_out) {
+    if (capacity < *num_words) return fail(ILQG_ERR_INVALID, "ilqg_problem_row_program: buffer too small");
+    std::memcpy(words_out, prog.words.data(), sizeof(int32_t) * prog.words.size());
+  }
+  return ILQG_OK;
+}
+
+// ---- per-instance cost parameters (ilqg.h) ----
+const char* cost_kind_name(int kind) {  // ilqg_cost_kind without its prefix
+  static const char* const names[] = {
+      "QUADRATIC", "QUADRATIC_POLYLINE2", "SEMIQUADRATIC", "SEMIQUADRATIC_POLYLINE2", "PROXIMITY", "SIGNED_DISTANCE",
+      "EXTREME_VALUE", "CONSTRAINT_PROXIMITY", "CONSTRAINT_SINGLE_DIMENSION", "POLYLINE2_SIGNED_DISTANCE",
+      "QUADRATIC_DIFFERENCE", "ORIENTATION", "QUADRATIC_NORM", "SEMIQUADRATIC_NORM", "RELATIVE_DISTANCE",
+      "LOCALLY_CONVEX_PROXIMITY", "CURVATURE", "CONSTRAINT_POLYLINE2_SIGNED_DISTANCE", "NOMINAL_PATH_LENGTH",
+      "ROUTE_PROGRESS", "WEIGHTED_CONVEX_PROXIMITY", "CONSTRAINT_AFFINE_SCALAR", "CONSTRAINT_AFFINE_VECTOR"};
+  static_assert(ILQG_COST_QUADRATIC == 1 && ILQG_CONSTRAINT_AFFINE_VECTOR == sizeof(names) / sizeof(names[0]), "one name per kind");
+  return kind >= 1 && kind <= ILQG_CONSTRAINT_AFFINE_VECTOR ? names[kind - 1] : "unknown kind";
+}
+// Does a term of this kind read the field (the table of ilqg.h; ilqg_models.hpp: term_evaluate_leaf_of and the row ops)?
+// Null: yes; else why not.
+const char* instance_param_refusal(int kind, int field) {
+  const bool weight = field == ILQG_PARAM_WEIGHT;
+  switch (kind) {
+    case ILQG_COST_EXTREME_VALUE: return "an EXTREME_VALUE term has no parameters of its own: declare its children";
+    case ILQG_CONSTRAINT_AFFINE_SCALAR:
+    case ILQG_CONSTRAINT_AFFINE_VECTOR: return "the affine constraints keep their coefficients in dense blocks";
+    case ILQG_COST_NOMINAL_PATH_LENGTH:
+    case ILQG_COST_ROUTE_PROGRESS:
+      return weight ? nullptr : "its nominal speed is tabulated per time step when the problem is created";
+    case ILQG_COST_SIGNED_DISTANCE:
+    case ILQG_COST_POLYLINE2_SIGNED_DISTANCE: return weight ? "this kind does not read its weight" : nullptr;
+    case ILQG_CONSTRAINT_PROXIMITY:
+    case ILQG_CONSTRAINT_SINGLE_DIMENSION:
+    case ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE: return weight ? "a constraint has no weight" : nullptr;
+    case ILQG_COST_QUADRATIC_POLYLINE2:
+    case ILQG_COST_QUADRATIC_DIFFERENCE:
+    case ILQG_COST_RELATIVE_DISTANCE:
+    case ILQG_COST_CURVATURE: return weight ? nullptr : "this kind has no nominal or threshold";
+    case ILQG_COST_QUADRATIC:
+    case ILQG_COST_SEMIQUADRATIC:
+    case ILQG_COST_SEMIQUADRATIC_POLYLINE2:
+    case ILQG_COST_PROXIMITY:
+    case ILQG_COST_ORIENTATION:
+    case ILQG_COST_QUADRATIC_NORM:
+    case ILQG_COST_SEMIQUADRATIC_NORM:
+    case ILQG_COST_LOCALLY_CONVEX_PROXIMITY:
+    case ILQG_COST_WEIGHTED_CONVEX_PROXIMITY: return nullptr;
+  }
+  return "unknown cost kind";
+}
+ilqg_status instance_params_check_terms(int num_terms, const ilqg_cost_term* terms, int32_t count,
+                                        const ilqg_instance_param* params) {
+  if (count < 0 || count > ILQG_MAX_INSTANCE_PARAMS)
+    return fail(ILQG_ERR_INVALID, "instance parameters: count must be 0 .. ILQG_MAX_INSTANCE_PARAMS");
+  if (count > 0 && (!params || !terms)) return fail(ILQG_ERR_INVALID, "null argument");
+  for (int c = 0; c < count; c++) {
+    const int term = params[c].term, field = params[c].field;
+    const std::string where = "instance parameter " + std::to_string(c) + " (term " + std::to_string(term) + ", " +
+                              (field == ILQG_PARAM_WEIGHT ? "weight" : field == ILQG_PARAM_VALUE ? "value" : "field " + std::to_string(field)) + "): ";
+    if (term < 0 || term >= num_terms)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "term index out of range (the problem has " + std::to_string(num_terms) + " terms)");
+    if (field != ILQG_PARAM_WEIGHT && field != ILQG_PARAM_VALUE)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "not an ilqg_param_field");
+    for (int q = 0; q < c; q++)
+      if (params[q].term == term && params[q].field == field)
+        return fail(ILQG_ERR_UNSUPPORTED, where + "declared twice (also parameter " + std::to_string(q) + ")");
+    if (const char* why = instance_param_refusal(terms[term].kind, field))
+      return fail(ILQG_ERR_UNSUPPORTED, where + cost_kind_name(terms[term].kind) + ": " + why);
+  }
+  return ILQG_OK;
+}
+// A call that evaluates costs on `batch` instances while a table for another batch is bound would read past the table
+ilqg_status instance_batch_check(const ilqg_problem* p, int32_t batch) {
+  if (p->dev.inst_values && batch != p->inst_batch)
+    return fail(ILQG_ERR_INVALID, "per-instance parameter values are bound for a batch of " + std::to_string(p->inst_batch) +
+                                      ", this call has " + std::to_string(batch) + " instances");
+  return ILQG_OK;
+}
+
+// ilqg_problem_declare_instance_params: the checked list into the handle, its (term, field) table and the row stage's
+// side table (per op of the row program the column of its weight / value; the program is not touched) onto the device
+ilqg_status declare_instance_params(ilqg_problem* p, int32_t count, const ilqg_instance_param* params) {
+  const std::vector<int>& op_term = p->row_prog.op_term;
+  std::vector<int> cols(op_term.size() * 2 + 2, -1), terms(size_t(count) * 2 + 2, 0);
+  for (int c = 0; c < count; c++) {
+    terms[2 * c] = params[c].term;
+    terms[2 * c + 1] = params[c].field;
+    for (size_t op = 0; op < op_term.size(); op++)
+      if (op_term[op] == params[c].term) cols[2 * op + (params[c].field == ILQG_PARAM_WEIGHT ? 0 : 1)] = c;
+  }
+  const char* what = "instance parameter tables";
+  // kernels of earlier calls on any stream may still read the old tables (unbound: they look at neither)
+  hipError_t e = hipDeviceSynchronize();
+  if (e != hipSuccess) return hip_failed(what, e);
+  DeviceBuffer<int> d_terms;
+  const ilqg_status s = upload(terms, 0, what, &d_terms);
+  if (s != ILQG_OK) return s;
+  e = copy_to_device(p->d_row_prog.get() + p->row_prog.words.size(), cols);
+  if (e != hipSuccess) return hip_failed(what, e);
+  p->d_inst_terms = std::move(d_terms);  // the old table goes only now that the new one is up
+  p->inst_params.assign(params, params + count);
+  return ILQG_OK;
+}
+
+}  // namespace
+#endif  // !ILQG_PART_NX
