@@ -501,7 +501,9 @@ __global__ void __launch_bounds__(256) ilq_exit_kernel(DevProblem p, SolveArgs<T
 #endif
 // KIND LQ_SINGLE_WAVE: one wave per instance (ilqg_lq_feedback1w.hpp), compiled for as many waves per SIMD as its LDS
 // lets a CU hold instances (fp64: 20 KB -> eight per CU, two per SIMD; fp32: 10 KB -> sixteen, four per SIMD).
-template <typename T, int NX, int NP, int MU, int KIND>
+// FORMS = false: the same sweep with the m x m solve's broadcasts through read-lanes (ilqg_solve_options::sweep_forms =
+// OFF), a second instantiation of the kinds that have the row-broadcast form: each step loop carries one of the two.
+template <typename T, int NX, int NP, int MU, int KIND, bool FORMS = true>
 __global__ void __launch_bounds__((KIND == LQ_SINGLE_WAVE ? 64 : KIND == LQ_VALU_FEEDBACK ? LQCfg<T, NX, NP, MU>::NT : ((KIND == LQ_OPEN_LOOP || KIND == LQ_OPEN_LOOP_COMPACT) ? OLCfg<T, NX, NP, MU>::NT : 64 * NP)),
                                   (KIND == LQ_SINGLE_WAVE ? (sizeof(T) == 4 ? 4 : ILQG_1W_WAVES_F64) : KIND == LQ_PLAYER_WAVES_PACKED ? 4 : KIND == LQ_PLAYER_WAVES ? (NX <= 16 ? NP : 2) : ((KIND == LQ_OPEN_LOOP || KIND == LQ_OPEN_LOOP_COMPACT) ? 3 : 1)))
 ilq_lq_kernel(DevProblem p, SolveArgs<T> sa) {
@@ -513,7 +515,7 @@ ilq_lq_kernel(DevProblem p, SolveArgs<T> sa) {
     const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
     if (stage != ST_LQ) return;
   }
-  lq_part_instance<T, NX, NP, MU, (KIND == LQ_PLAYER_WAVES_PACKED ? LQ_PLAYER_WAVES : KIND)>(p, sa, b, reinterpret_cast<T*>(smem_raw));
+  lq_part_instance<T, NX, NP, MU, (KIND == LQ_PLAYER_WAVES_PACKED ? LQ_PLAYER_WAVES : KIND), FORMS>(p, sa, b, reinterpret_cast<T*>(smem_raw));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1674,10 +1676,25 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   } else {
     plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES>, 64 * NP,
                   (MfmaSweepLds<T, NX, NP, MU>::ELEMS + (C::MFMA_ONE_TILE ? 0 : 4)) * sizeof(T)};
-    if constexpr (has_packed)
-      if (size_t(sched_batch) >= size_t(5) * 256) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED>;
-    if constexpr (has_1w)
-      if (single_wave) plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_SINGLE_WAVE>, 64, size_t(W1Cfg<T, NX, NP, MU>::ELEMS + 4) * sizeof(T)};
+    // ilqg_solve_options::sweep_forms = OFF: the read-lane instantiation of the same kind (only where the two differ)
+    constexpr bool has_forms = C::MFMA_ONE_TILE && SolveRows<NP * MU, NX + 1>::FITS;
+    const bool forms = choice(opt.sweep_forms, true);
+    if constexpr (has_forms)
+      if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES, false>;
+    if constexpr (has_packed) {
+      if (size_t(sched_batch) >= size_t(5) * 256) {
+        plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED>;
+        if constexpr (has_forms)
+          if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED, false>;
+      }
+    }
+    if constexpr (has_1w) {
+      if (single_wave) {
+        plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_SINGLE_WAVE>, 64, size_t(W1Cfg<T, NX, NP, MU>::ELEMS + 4) * sizeof(T)};
+        if constexpr (has_forms)
+          if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_SINGLE_WAVE, false>;
+      }
+    }
   }
   sa.clear_counters = 1;
   plan.trial = {k_trial, 64 * W, lds_trial};
@@ -2276,7 +2293,8 @@ ilqg_status ilqg_solve_batch_ex(ilqg_problem* p, int32_t batch, const void* x0, 
   const DevProblem& d = p->dev;
   hipStream_t st = (hipStream_t)stream;
   if (o.generic_kernels < ILQG_CHOICE_AUTO || o.generic_kernels > ILQG_CHOICE_ON || o.padded_sweep < ILQG_CHOICE_AUTO ||
-      o.padded_sweep > ILQG_CHOICE_ON || o.probe_lanes < ILQG_CHOICE_AUTO || o.probe_lanes > ILQG_CHOICE_ON)
+      o.padded_sweep > ILQG_CHOICE_ON || o.probe_lanes < ILQG_CHOICE_AUTO || o.probe_lanes > ILQG_CHOICE_ON ||
+      o.sweep_forms < ILQG_CHOICE_AUTO || o.sweep_forms > ILQG_CHOICE_ON)
     return fail(ILQG_ERR_INVALID, "scheduling choices are ilqg_choice values");
   if (p->generic || o.generic_kernels == ILQG_CHOICE_ON)
     return p->desc.dtype == ILQG_F32

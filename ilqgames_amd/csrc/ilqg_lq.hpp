@@ -16,7 +16,8 @@
 //   * larger n: lq_feedback_instance — lane t = i*NX + c owns COLUMN c of Z_i in registers;
 //     F^T Z_i F is two passes of "uniform matrix x private column" with broadcast LDS operands.
 // In both, the (m x m) Nash system with its n+1 right-hand sides lives one COLUMN PER LANE in wave 0
-// (v_readlane broadcasts, no LDS and no barriers inside the factorisation): Householder QR as the
+// (v_readlane broadcasts — DPP row broadcasts over replicated pivot columns in the solve's own sweeps,
+// lu_solve_columns_rows —, no LDS and no barriers inside the factorisation): Householder QR as the
 // reference, or elimination without pivoting once the Gershgorin step has made S diagonally dominant.
 // The per-step [B|A|Q|l|R|r] block is staged global -> LDS by DMA one step ahead (double-buffered).
 #pragma once
@@ -266,6 +267,55 @@ __device__ __forceinline__ void lu_solve_columns(T (&col)[M], int lane, T (&x)[M
     for (int k2 = i + 1; k2 < M; k2++) s -= bcast(col[i], k2) * x[k2];
     x[i] = s * dinv[i];
   }
+}
+
+// The same elimination with ROW broadcasts.  A broadcast through v_readlane is a trip over the scalar unit: two reads
+// into a scalar pair for an fp64 value, then wait states before a vector instruction may use the pair.  DPP
+// row_newbcast:k copies lane k of each 16-lane row to every lane of that row and stays in the vector registers (one
+// v_mov_b64_dpp for a double).  So the columns of [S | Y | y_zeta] are laid over the rows with the M pivot columns
+// REPLICATED in lanes 0 .. M-1 of every row and 16 - M right-hand sides behind them: lane (row g, position j) holds
+// S[:, j] for j < M, else right-hand side g (16 - M) + (j - M).  The replicas execute the same instructions on the same
+// values, so every row finds the multipliers, the pivots' reciprocals and U's entries on its own lanes 0 .. M-1.  Every
+// floating-point operation and its order are those of lu_solve_columns: the results are the same bits.
+template <int M, int NRHS>
+struct SolveRows {
+  static constexpr int PER = 16 - M;  // right-hand sides per 16-lane row
+  static constexpr bool FITS = M >= 1 && M < 16 && 4 * PER >= NRHS;
+};
+// (mov_dpp, not update_dpp: every lane is written, so there is no previous value to keep — update_dpp's `old` operand
+// costs a move that initialises the destination in front of every broadcast.)
+template <int K>
+__device__ __forceinline__ float row_bcast(float v) {
+  return __builtin_amdgcn_mov_dpp(v, 0x150 + K, 0xf, 0xf, false);  // row_newbcast:K
+}
+template <int K>
+__device__ __forceinline__ double row_bcast(double v) {
+  return __builtin_amdgcn_mov_dpp(v, 0x150 + K, 0xf, 0xf, false);
+}
+// All 64 lanes must be active (a row's lanes 0 .. M-1 are the sources).
+template <typename T, int M>
+__device__ __forceinline__ void lu_solve_columns_rows(T (&col)[M], T (&x)[M]) {
+  T dinv[M];
+  static_for<M - 1>([&](auto K) {
+    constexpr int k = decltype(K)::value;
+    const T rinv = fast_recip(col[k]);
+    dinv[k] = row_bcast<k>(rinv);
+    T f[M];
+#pragma unroll
+    for (int i = k + 1; i < M; i++) f[i] = row_bcast<k>(col[i] * rinv);
+#pragma unroll
+    for (int i = k + 1; i < M; i++) col[i] -= f[i] * col[k];
+  });
+  dinv[M - 1] = row_bcast<M - 1>(fast_recip(col[M - 1]));
+  static_for<M>([&](auto I) {
+    constexpr int i = M - 1 - decltype(I)::value;
+    T s = col[i];
+    static_for<M - 1 - i>([&](auto Q) {
+      constexpr int k2 = i + 1 + decltype(Q)::value;
+      s -= row_bcast<k2>(col[i]) * x[k2];
+    });
+    x[i] = s * dinv[i];
+  });
 }
 
 // Gaussian elimination with PARTIAL PIVOTING in the same column-per-lane layout, for systems that carry no
@@ -913,7 +963,9 @@ __device__ __forceinline__ void dma_tile(const T* g_, T* tile, int nrows, int nc
 // SOLVER: the instantiation the solve's sweep kernel runs (compact rows in, symmetric costs, regularised system, forward
 // pass deferred to the trial kernel) with those choices made at compile time: the dense staging, the QR solve and the
 // forward pass are not in its loop or its register allocation.
-template <typename T, int NX, int NP, int MU, bool SOLVER = false>
+// ROWBC: the m x m solve with row broadcasts (lu_solve_columns_rows) where its layout fits, else with read-lanes — a
+// compile-time choice, so that a kernel's step loop carries one of the two (ilqg_solve_options::sweep_forms).
+template <typename T, int NX, int NP, int MU, bool SOLVER = false, bool ROWBC = true>
 __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a, const PairTable& pt, T* sm) {
   using C = LQCfg<T, NX, NP, MU>;
   using W = PWCfg<T, NX, NP, MU>;
@@ -1321,8 +1373,15 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
       // Written without divergent regions: every lane loads a column (lanes past the last right-hand side
       // re-read y_zeta and are never stored), the R_ii and Gershgorin terms are added as value-or-zero.
       T col[M], x[M];
-      const bool isS = lane < M;
-      const T* src = (lane < M + NX) ? sSY + M * lane : sYz;
+      // where this lane's column is: S[:, sc] on the S lanes, else right-hand side `rhs` (Y's columns, then y_zeta).
+      // kRows: the layout of lu_solve_columns_rows — S replicated in lanes 0 .. M-1 of every 16-lane row.
+      // (SOLVER only: elsewhere the choice between the elimination and the QR solve is a run-time one, and the QR
+      // solve's lane tests belong to the column-per-lane layout.)
+      constexpr bool kRows = ROWBC && SOLVER && SolveRows<M, NX + 1>::FITS;
+      const int sc = kRows ? j : lane;
+      const int rhs = kRows ? g * SolveRows<M, NX + 1>::PER + (j - M) : lane - M;
+      const bool isS = sc < M;
+      const T* src = isS ? sSY + M * sc : (rhs < NX ? sSY + M * (M + rhs) : sYz);
 #pragma unroll
       for (int r = 0; r < M; r++) {
         col[r] = src[r];
@@ -1334,17 +1393,19 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
         T l1 = T(0);
 #pragma unroll
         for (int r = 0; r < M; r++) l1 += lq_abs(col[r]);
-        const T diag = src[isS ? lane : 0];
+        const T diag = src[isS ? sc : 0];
         const T radius = l1 - lq_abs(diag);
         const T eval_lo = diag - radius;
         const T bump = (isS && adaptive && eval_lo < T(1e-3f)) ? radius + T(1e-3f) : T(0);
 #pragma unroll
-        for (int r = 0; r < M; r++) col[r] = col[r] + ((r == lane) ? bump : T(0));
+        for (int r = 0; r < M; r++) col[r] = col[r] + ((r == sc) ? bump : T(0));
       }
       ILQG_PH(10);
       // (Measured and dropped, round 5: the Gauss-Jordan form — every pivot clears its column in all other rows, no
       // back-substitution chain; same instruction count, headline -0.7 %, single-instance latency unchanged.)
-      if (adaptive)
+      if constexpr (kRows)
+        lu_solve_columns_rows<T, M>(col, x);
+      else if (adaptive)
         lu_solve_columns<T, M>(col, lane, x);
       else
         qr_solve_columns<T, M>(col, lane, x);
@@ -1353,15 +1414,15 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
         // [P | alpha] in one piece: column lane - M of the tile, alpha in column NX = JB (F = A - B [P | alpha] then
         // carries beta = -B alpha); alpha is read from there too (sAlr) — one divergent region and M stores less on the
         // solving wave's way to the barrier
-        if (lane >= M && lane <= M + NX) {
+        if (!isS && rhs <= NX) {
 #pragma unroll
-          for (int r = 0; r < M; r++) sPt[r + LD * (lane - M)] = x[r];
+          for (int r = 0; r < M; r++) sPt[r + LD * rhs] = x[r];
         }
       } else {
-        if (lane >= M && lane < M + NX) {
+        if (!isS && rhs < NX) {
 #pragma unroll
-          for (int r = 0; r < M; r++) sPt[r + LD * (lane - M)] = x[r];
-        } else if (lane == M + NX) {
+          for (int r = 0; r < M; r++) sPt[r + LD * rhs] = x[r];
+        } else if (!isS && rhs == NX) {
 #pragma unroll
           for (int r = 0; r < M; r++) sAl[r] = x[r];
         }

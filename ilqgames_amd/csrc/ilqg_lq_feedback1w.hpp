@@ -71,7 +71,9 @@ struct W1Cfg {
   static constexpr bool SUPPORTED = NX < 16 && M <= 16 && C::NSOLVE <= 32 && NP <= 4 && MU == 2;  // (MU == 2: rows_reduce4)
 };
 
-template <typename T, int NX, int NP, int MU>
+// ROWBC: the m x m solve with row broadcasts (lu_solve_columns_rows, ilqg_lq.hpp) instead of read-lanes; the sweep only
+// ever runs for the solve, whose system is regularised (LQArgs::adaptive = 1), so the row form has no QR branch.
+template <typename T, int NX, int NP, int MU, bool ROWBC = true>
 __device__ __forceinline__ void lq_feedback_instance_mfma_1w(const LQArgs<T>& a, const PairTable& pt, T* sm) {
   using C = LQCfg<T, NX, NP, MU>;
   using W = W1Cfg<T, NX, NP, MU>;
@@ -302,8 +304,12 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_1w(const LQArgs<T>& a,
     // trip for the Nash system — holds M more values across the row products: 186 -> 256 VGPRs and 320 B of scratch.)
     {
       T col[M], x[M];
-      const bool isS = lane < M;
-      const T* src = (lane < M + NX) ? sSY + M * lane : sYz;
+      // where this lane's column is (see the player-parallel sweep): S[:, sc], else right-hand side `rhs`
+      constexpr bool kRows = ROWBC && SolveRows<M, NX + 1>::FITS;
+      const int sc = kRows ? j : lane;
+      const int rhs = kRows ? g * SolveRows<M, NX + 1>::PER + (j - M) : lane - M;
+      const bool isS = sc < M;
+      const T* src = isS ? sSY + M * sc : (rhs < NX ? sSY + M * (M + rhs) : sYz);
 #pragma unroll
       for (int r = 0; r < M; r++) {
         col[r] = src[r];
@@ -313,22 +319,24 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_1w(const LQArgs<T>& a,
         T l1 = T(0);
 #pragma unroll
         for (int r = 0; r < M; r++) l1 += lq_abs(col[r]);
-        const T diag = src[isS ? lane : 0];
+        const T diag = src[isS ? sc : 0];
         const T radius = l1 - lq_abs(diag);
         const T eval_lo = diag - radius;
         const T bump = (isS && a.adaptive && eval_lo < T(1e-3f)) ? radius + T(1e-3f) : T(0);
 #pragma unroll
-        for (int r = 0; r < M; r++) col[r] = col[r] + ((r == lane) ? bump : T(0));
+        for (int r = 0; r < M; r++) col[r] = col[r] + ((r == sc) ? bump : T(0));
       }
-      if (a.adaptive)
+      if constexpr (kRows)
+        lu_solve_columns_rows<T, M>(col, x);
+      else if (a.adaptive)
         lu_solve_columns<T, M>(col, lane, x);
       else
         qr_solve_columns<T, M>(col, lane, x);
       // [P | alpha] in one piece: column lane - M of the tile, alpha in column NX = JB (F = A - B [P | alpha] then carries
       // beta = -B alpha); alpha is read from there too (sAl below)
-      if (lane >= M && lane <= M + NX) {
+      if (!isS && rhs <= NX) {
 #pragma unroll
-        for (int r = 0; r < M; r++) sPt[r + LD * (lane - M)] = x[r];
+        for (int r = 0; r < M; r++) sPt[r + LD * rhs] = x[r];
       }
     }
     lds_sync(true);

@@ -513,7 +513,14 @@ typedef struct {
                                      with a lane per stage: an eighth of the instructions per rollout, a longer chain per
                                      step (AUTO: rounds with more rollouts than the chip holds at once, eight or more
                                      candidates per instance).  Bit-identical trajectories.  (ABI 8)                      */
-  int32_t reserved2;
+  int32_t sweep_forms;          /* ilqg_choice: the one-tile feedback sweeps (player-parallel and single-wave) run the
+                                     m x m Nash solve of a step with DPP row broadcasts — the pivot columns replicated in
+                                     every 16-lane row, values stay in vector registers — instead of read-lane broadcasts
+                                     over the scalar unit (AUTO: on wherever the columns fit the rows: m < 16 and
+                                     n + 1 <= 4 (16 - m)).  The same operations in the same order: bit-identical.  OFF
+                                     keeps the read-lane instantiation selectable for A/B runs and the bit-for-bit test
+                                     (tests/test_gpu_sweep_forms.py).  (This field was reserved2 = 0 up to this release:
+                                     same layout, same ABI version.)                                                    */
   const struct ilqg_iterate_log* iterate_log; /* NULL, or where every logged iterate of the solve goes (below)          */
   double max_runtime;           /* > 0: the anytime exit of ILQSolver::Solve (src/ilq_solver.cpp:123-124) on the host's
                                      clock, seconds — once it has passed, instances leave the loop at their next
@@ -726,7 +733,8 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
 
 /* Library / device introspection (used by the loader to fail loudly). */
 #define ILQG_ABI_VERSION 9 /* 9: per-instance cost parameters (ilqg_instance_param, ilqg_problem_declare_instance_params,
-                                 ilqg_problem_bind_instance_values, ilqg_instance_params_check);
+                                 ilqg_problem_bind_instance_values, ilqg_instance_params_check); still 9:
+                                 ilqg_solve_options::sweep_forms (was reserved2 = 0 = AUTO: no layout or behaviour change);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;

@@ -80,6 +80,29 @@ if os.path.exists(os.path.join(src, sqdb)):
         sh = lambda c: "%.0f %%" % (100.0 * med.get(c, 0.0) / wc)  # noqa: E731
         out.append("| %s | %.0f | %.3g | %.3g | %s | %s | %s | %s | %s |" % (nm[:80], med.get("SQ_WAVES", 0), med.get("SQ_BUSY_CYCLES", 0), wc,
                    sh("SQ_WAIT_ANY"), sh("SQ_WAIT_INST_ANY"), sh("SQ_ACTIVE_INST_ANY"), sh("SQ_ACTIVE_INST_VALU"), sh("SQ_ACTIVE_INST_LDS")))
+# instruction mix (own pass): whatever counters the pass collected, per kernel, medians over the batch launches, and per wave
+mixdb = "pmc_mix/bench_results.db"
+if os.path.exists(os.path.join(src, mixdb)):
+    cols, rows = q(mixdb, "select kernel_name, counter_name, value, duration from counters_collection "
+                          "where kernel_name like '%ilq%' order by start")
+    ctrs = sorted(set(r[1] for r in rows))
+    waves = {}  # SQ_WAVES per kernel from the wave-level pass, where it ran
+    if os.path.exists(os.path.join(src, sqdb)):
+        _, wrows = q(sqdb, "select kernel_name, value from counters_collection where counter_name = 'SQ_WAVES' and kernel_name like '%ilq%'")
+        for nm in set(r[0] for r in wrows):
+            vals = [r[1] for r in wrows if r[0] == nm]
+            vals = [v for v in vals if v > 0.2 * max(vals)] or vals
+            waves[nm] = statistics.median(vals)
+    out.append("\n## rocprofv3 --pmc " + " ".join(ctrs) + " (own pass): medians per kernel over the batch launches (per wave "
+               "in brackets where the SQ_WAVES pass ran)\n\n| kernel | " + " | ".join(ctrs) + " |\n|---|" + "---|" * len(ctrs))
+    for nm in sorted(set(r[0] for r in rows)):
+        cells = []
+        for c in ctrs:
+            vals = [r[2] for r in rows if r[0] == nm and r[1] == c]
+            vals = [v for v in vals if v > 0.2 * max(vals)] or vals
+            med = statistics.median(vals) if vals else 0.0
+            cells.append("%.4g" % med + (" (%.1f)" % (med / waves[nm]) if waves.get(nm) else ""))
+        out.append("| %s | %s |" % (nm[:80], " | ".join(cells)))
 # HBM traffic per round for bench.py's roofline block: 2 x FETCH_SIZE (profiles/r03_counter_calibration.md: the counter
 # reports half of the bytes read) + WRITE_SIZE, summed over the kernels of one round (sweep + trial kernels)
 try:
