@@ -225,7 +225,7 @@ __global__ void rollout_kernel(DevProblem p, RolloutBatchArgs<T> g) {
   const size_t Tn = p.T, n = p.n, m = p.m;
   RolloutArgs<T> a{g.x0 + b * n,          g.xs_ref + b * Tn * n, g.us_ref + b * Tn * m, g.P + b * Tn * m * n,
                    g.alpha + b * Tn * m,  g.alpha_scale ? g.alpha_scale[b] : T(1),
-                   g.xs + b * Tn * n,     g.us + b * Tn * m};
+                   g.xs + b * Tn * n,     g.us + b * Tn * m,     instance_values(p, int(b))};
   rollout_instance_rt<T>(p, a, sm, threadIdx.x);
 }
 
@@ -339,7 +339,7 @@ struct TrialWaves {
 #ifndef ILQG_TRIAL_OCCUPANCY_F32
 #define ILQG_TRIAL_OCCUPANCY_F32 2
 #endif
-template <typename T, int NX, int NP, int MU, int W, int PROGID = 0>
+template <typename T, int NX, int NP, int MU, int W, int PROGID = 0, bool BOUND = (PROGID >= kBoundProg)>
 __global__ void __launch_bounds__(64 * W, (sizeof(T) == 4 && W == 2) ? ILQG_TRIAL_OCCUPANCY_F32 : W) ilq_trial_kernel(DevProblem p, SolveArgs<T> sa) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = blockIdx.x;
@@ -355,7 +355,7 @@ __global__ void __launch_bounds__(64 * W, (sizeof(T) == 4 && W == 2) ? ILQG_TRIA
   }
   const short* maps = rows_maps_load(p, smem_raw);
   T* sm = reinterpret_cast<T*>(smem_raw + rows_maps_bytes(p));
-  trial_part_instance<T, NX, NP, MU, W, TRIAL_FUSED, PROGID>(p, maps, sa, b, sm);
+  trial_part_instance<T, NX, NP, MU, W, TRIAL_FUSED, PROGID, BOUND>(p, maps, sa, b, sm);
 }
 
 // The same pass cut into three launches (ilqg_solve.hpp, TRIAL_ROLL / rows_part_instance / TRIAL_DECIDE), for
@@ -1539,7 +1539,8 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
     const size_t budget = per_instance > fixed ? (per_instance - fixed) / trial_row_waves(W) : 0;
     sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), budget);
   }
-  auto k_trial = ilq_trial_kernel<T, NX, NP, MU, W>;
+  // (a problem with per-instance parameters bound runs fused kernels of its own, here and below: ilqg_solve.hpp)
+  auto k_trial = d.inst_values ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
   const bool pw = C::USE_MFMA && !open_loop;  // one wave per player (MFMA feedback sweep)
   // Compact rows (ilqg_common.hpp) between the row stage and the sweep: the one-tile player-parallel sweep and the
   // open-loop sweep read them; the other sweeps take the dense arrays.  What the row stage writes and the sweep reads
@@ -2166,8 +2167,28 @@ ilqg_status ilqg_problem_declare_instance_params(ilqg_problem* p, int32_t count,
   if (!p) return fail(ILQG_ERR_INVALID, "null argument");
   if (p->dev.inst_values)
     return fail(ILQG_ERR_INVALID, "instance parameters cannot be declared while values are bound: unbind first");
-  const ilqg_status s = instance_params_check_terms(int(p->terms_host.size()), p->terms_host.data(), count, params);
-  return s != ILQG_OK ? s : declare_instance_params(p, count, params);
+  ilqg_status s = instance_params_check_terms(int(p->terms_host.size()), p->terms_host.data(), count, params);
+  if (s == ILQG_OK) s = instance_total_check(size_t(count), p->inst_subs.size());
+  return s != ILQG_OK ? s : declare_instance_columns(p, std::vector<ilqg_instance_param>(params, params + count), p->inst_subs);
+}
+
+// ---- per-instance subsystem parameters (ilqg.h) ----
+ilqg_status ilqg_instance_subsystem_params_check(const ilqg_problem_desc* desc, int32_t count, const int32_t* subsystems) {
+  if (!desc) return fail(ILQG_ERR_INVALID, "null argument");
+  if (desc->num_players < 0 || desc->num_players > kMaxPlayers)
+    return fail(ILQG_ERR_INVALID, "instance subsystem parameters: num_players out of range");
+  int kinds[kMaxPlayers];
+  for (int i = 0; i < desc->num_players; i++) kinds[i] = desc->subsystems[i].kind;
+  return instance_subsystems_check(desc->num_players, kinds, count, subsystems);
+}
+
+ilqg_status ilqg_problem_declare_instance_subsystem_params(ilqg_problem* p, int32_t count, const int32_t* subsystems) {
+  if (!p) return fail(ILQG_ERR_INVALID, "null argument");
+  if (p->dev.inst_values)
+    return fail(ILQG_ERR_INVALID, "instance parameters cannot be declared while values are bound: unbind first");
+  ilqg_status s = instance_subsystems_check(p->dev.N, p->dev.sub_kind, count, subsystems);
+  if (s == ILQG_OK) s = instance_total_check(p->inst_params.size(), size_t(count));
+  return s != ILQG_OK ? s : declare_instance_columns(p, p->inst_params, std::vector<int>(subsystems, subsystems + count));
 }
 
 ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, const float* values) {
@@ -2180,12 +2201,12 @@ ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, co
     p->inst_batch = 0;
     return ILQG_OK;
   }
-  if (p->inst_params.empty())
+  if (p->inst_params.empty() && p->inst_subs.empty())
     return fail(ILQG_ERR_INVALID, "no instance parameters are declared (ilqg_problem_declare_instance_params)");
   if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance parameter values: batch must be positive");
   d.inst_values = values;
   d.inst_terms = p->d_inst_terms.get();
-  d.inst_count = int(p->inst_params.size());
+  d.inst_count = int(p->inst_params.size() + p->inst_subs.size());
   p->inst_batch = batch;
   return ILQG_OK;
 }
@@ -2211,6 +2232,7 @@ ilqg_status ilqg_rollout_batch(const ilqg_problem* p, int32_t batch, const void*
                                void* xs, void* us, const int32_t* active, void* stream) {
   if (!p || !x0 || !xs_ref || !us_ref || !P || !alpha || !xs || !us) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
   const DevProblem& d = p->dev;
 #define CALL(TY_)                                                                                              \
   [&]() -> ilqg_status {                                                                                     \
@@ -2229,6 +2251,7 @@ ilqg_status ilqg_linearize_batch(const ilqg_problem* p, int32_t batch, const voi
                                  void* Bm, const int32_t* active, void* stream) {
   if (!p || !xs || !us || !A || !Bm) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
   return launch_linquad(p, p->dev, batch, xs, us, nullptr, nullptr, nullptr, A, Bm, nullptr, nullptr, nullptr, nullptr,
                         nullptr, nullptr, active, stream);
 }
@@ -2397,6 +2420,7 @@ ilqg_status ilqg_receding_horizon_shift_batch(const ilqg_problem* p, int32_t bat
   if (int_end > d.T) return fail(ILQG_ERR_INVALID, "receding horizon: integration runs past the plan");
   if (new_plan_t0_host) *new_plan_t0_host = new_t0;
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
 #define CALL(TY_)                                                                                                  \
   [&]() -> ilqg_status {                                                                                         \
     RecedingArgs<TY_> g{};                                                                                         \
@@ -2529,6 +2553,7 @@ ilqg_status ilqg_plan_integrate_batch(const ilqg_problem* p, int32_t batch, int3
   if (s != ILQG_OK) return s;
   if (!x || !active) return fail(ILQG_ERR_INVALID, "null argument");
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
   const DevProblem& d = p->dev;
 #define CALL(TY_)                                                                                                  \
   [&]() -> ilqg_status {                                                                                         \
@@ -2559,6 +2584,7 @@ ilqg_status ilqg_receding_horizon_sync_batch(const ilqg_problem* p, int32_t batc
     return fail(ILQG_ERR_INVALID, "the next solve's buffers must not alias the stored plan");
   if (p->has_route_progress) return fail(ILQG_ERR_UNSUPPORTED, kRouteProgressReceding);
   if (batch <= 0) return ILQG_OK;
+  if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
   const DevProblem& d = p->dev;
 #define CALL(TY_)                                                                                                  \
   [&]() -> ilqg_status {                                                                                         \

@@ -99,11 +99,13 @@ struct DevProblem {
   int rp_gslots;             // most gradient slots of a pass (numbered first: a merit-only evaluation keeps only these)
   int rp_maps_off, rp_maps_words;  // the program's word -> slot maps (copied into LDS by every workgroup)
   int rp_compact_off, rp_compact_w;  // compact rows (ilqg_rows.hpp): the block's offset in row_prog, words per row (0: none)
-  // Per-instance cost parameters (ilqg_problem_declare_instance_params / ilqg_problem_bind_instance_values): column c of
-  // row b of `inst_values` replaces the weight or the value of the declared term inst_terms[c] for instance b.  All null /
-  // 0 unless a table is bound: every reader then takes the baked parameters.  Read-only on the device.
+  // Per-instance parameters (ilqg_problem_declare_instance_params / _declare_instance_subsystem_params,
+  // ilqg_problem_bind_instance_values): column c of row b of `inst_values` replaces, for instance b, the weight or the
+  // value of the declared term inst_terms[c], or param0 of a declared subsystem (the cost columns first).  All null / 0
+  // unless a table is bound: every reader then takes the baked parameters.  Read-only on the device.
   const float* inst_values;  // [batch][inst_count], the caller's buffer
-  const int* inst_terms;     // [inst_count][2]: (term index, ilqg_param_field) (quad_tables_load)
+  const int* inst_terms;     // [inst_count][2]: (term index, ilqg_param_field) (quad_tables_load), (-1, subsystem) for a
+                             // subsystem column; then [kMaxPlayers]: subsystem -> its column or -1 (subsystem_param)
   // (the row stage's table — per op of row_prog the column of its weight / value, or -1 — follows the program's
   // row_prog_words words in the device buffer `row_prog` points to)
   int inst_count;
@@ -114,6 +116,16 @@ struct DevProblem {
 __device__ __forceinline__ const float* instance_values(const DevProblem& p, int b) {
   if (!p.inst_values) return nullptr;
   return p.inst_values + size_t(__builtin_amdgcn_readfirstlane(b)) * size_t(p.inst_count);
+}
+
+// ilqg_subsystem::param0 of subsystem s as the integrators read it: the baked value, or, with a table bound (`iv`: the
+// instance's row of it, instance_values) and the subsystem declared, the instance's.  Read once, in a kernel's prologue.
+__device__ __forceinline__ float subsystem_param(const DevProblem& p, const float* iv, int s) {
+  if (iv) {
+    const int c = p.inst_terms[2 * p.inst_count + s];
+    if (c >= 0) return iv[c];
+  }
+  return p.sub_param[s];
 }
 
 // arrays of a time step's image, as the row program's regions and the compact rows name them

@@ -34,6 +34,14 @@ __global__ void __launch_bounds__(64) strategy_costs_kernel(DevProblem p, Strate
   const size_t b = blockIdx.x;
   const int q = blockIdx.y;
   const int t = threadIdx.x;
+  // lane t < N: param0 of subsystem t and (Air3D's evader row) of the next one — the baked ones, or this instance's
+  T Lp = T(0), Lp_next = T(0);
+  if (t < p.N) {
+    const float* const iv = instance_values(p, int(blockIdx.x));
+    Lp = T(subsystem_param(p, iv, t));
+    // t + 1 < N: flatten_subsystems (ilqg_problem.hpp) admits the evader only as row 0 of the pair (evader, pursuer)
+    if (p.sub_kind[t] == ILQG_DYN_AIR_3D_EVADER) Lp_next = T(subsystem_param(p, iv, t + 1));
+  }
   // move q > 0: entry `ja` of the stacked alpha at step `kp`, lower (-) before upper (+)
   const int r = (q - 1) >> 1;
   const int kp = q > 0 ? r / m : -1, ja = q > 0 ? r % m : -1;
@@ -64,12 +72,12 @@ __global__ void __launch_bounds__(64) strategy_costs_kernel(DevProblem p, Strate
       for (int e = 0; e < kSubStatesMax; e++) xj[e] = e < xd ? sx[xo + e] : T(0);
       const bool dist = p.sub_kind[t] == ILQG_DYN_UNICYCLE_4D_DISTURBED;
       const bool air = p.sub_kind[t] == ILQG_DYN_AIR_3D_EVADER;  // d0 carries the pursuer's speed there
-      const T d0 = dist ? sx[n + uo + 2] : (air ? T(p.sub_param[t + 1]) : T(0)), d1 = dist ? sx[n + uo + 3] : T(0);
+      const T d0 = dist ? sx[n + uo + 2] : (air ? Lp_next : T(0)), d1 = dist ? sx[n + uo + 3] : T(0);
       if (a.euler) {  // multi_player_dynamical_system.cpp:57-58
-        sub_eval8<T>(p.sub_kind[t], T(p.sub_param[t]), xj, sx[n + uo], sx[n + uo + 1], f, d0, d1);
+        sub_eval8<T>(p.sub_kind[t], Lp, xj, sx[n + uo], sx[n + uo + 1], f, d0, d1);
         for (int e = 0; e < kSubStatesMax; e++) xj[e] += T(p.dt) * f[e];
       } else {
-        sub_integrate8<T>(p.sub_kind[t], T(p.sub_param[t]), p.dt, xj, sx[n + uo], sx[n + uo + 1], d0, d1);
+        sub_integrate8<T>(p.sub_kind[t], Lp, p.dt, xj, sx[n + uo], sx[n + uo + 1], d0, d1);
       }
       for (int e = 0; e < xd; e++) snx[xo + e] = xj[e];
     }

@@ -73,9 +73,11 @@ struct ilqg_problem {
   // the row program as built (ilqg_problem_row_program), with the term each op carries, and its device image
   ilqg::RowProgramHost row_prog;
   ilqg::DeviceBuffer<int> d_row_prog;
-  // Per-instance cost parameters (ilqg.h): the declared (term, field) list and its device table (DevProblem::inst_terms);
-  // dev.inst_values / inst_count are set while a table is bound, for `inst_batch` instances
+  // Per-instance parameters (ilqg.h): the declared (term, field) list, the declared subsystems (their columns follow the
+  // cost columns) and their device table (DevProblem::inst_terms); dev.inst_values / inst_count are set while a table is
+  // bound, for `inst_batch` instances
   std::vector<ilqg_instance_param> inst_params;
+  std::vector<int> inst_subs;
   ilqg::DeviceBuffer<int> d_inst_terms;
   int inst_batch = 0;
   int static_prog = 0;                // id of the registered structure it matches (ilqg_rowprog_static.hpp), 0: none
@@ -618,24 +620,84 @@ ilqg_status instance_params_check_terms(int num_terms, const ilqg_cost_term* ter
   }
   return ILQG_OK;
 }
-// A call that evaluates costs on `batch` instances while a table for another batch is bound would read past the table
-ilqg_status instance_batch_check(const ilqg_problem* p, int32_t batch) {
-  if (p->dev.inst_values && batch != p->inst_batch)
+// Per-instance subsystem parameters (ilqg.h): does a subsystem of this kind read its param0?
+const char* dyn_kind_name(int kind) {  // ilqg_dyn_kind without its prefix
+  static const char* const names[] = {"UNICYCLE_4D", "CAR_5D", "CAR_6D", "UNICYCLE_4D_DISTURBED", "PLANAR_DISTURBANCE",
+                                      "DUBINS_CAR", "AIR_3D_EVADER", "AIR_3D_PURSUER", "POINT_MASS_2D", "UNICYCLE_5D",
+                                      "CAR_7D", "DELAYED_DUBINS_CAR"};
+  static_assert(ILQG_DYN_UNICYCLE_4D == 1 && ILQG_DYN_DELAYED_DUBINS_CAR == sizeof(names) / sizeof(names[0]), "one name per kind");
+  return kind >= 1 && kind <= ILQG_DYN_DELAYED_DUBINS_CAR ? names[kind - 1] : "unknown kind";
+}
+bool subsystem_reads_param0(int kind) {
+  switch (kind) {
+    case ILQG_DYN_CAR_5D:
+    case ILQG_DYN_CAR_6D:
+    case ILQG_DYN_CAR_7D:              // inter-axle distance
+    case ILQG_DYN_DUBINS_CAR:
+    case ILQG_DYN_DELAYED_DUBINS_CAR:  // speed
+    case ILQG_DYN_AIR_3D_EVADER:
+    case ILQG_DYN_AIR_3D_PURSUER: return true;  // their speeds
+  }
+  return false;
+}
+ilqg_status instance_subsystems_check(int num_subsystems, const int* kinds, int32_t count, const int32_t* subsystems) {
+  if (count < 0 || count > ILQG_MAX_INSTANCE_PARAMS)
+    return fail(ILQG_ERR_INVALID, "instance subsystem parameters: count must be 0 .. ILQG_MAX_INSTANCE_PARAMS");
+  if (count > 0 && (!subsystems || !kinds)) return fail(ILQG_ERR_INVALID, "null argument");
+  for (int c = 0; c < count; c++) {
+    const int s = subsystems[c];
+    const std::string where = "instance parameter " + std::to_string(c) + " (subsystem " + std::to_string(s) + "): ";
+    if (s < 0 || s >= num_subsystems)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "row out of range (the problem has " + std::to_string(num_subsystems) + " subsystems)");
+    for (int q = 0; q < c; q++)
+      if (subsystems[q] == s) return fail(ILQG_ERR_UNSUPPORTED, where + "declared twice (also parameter " + std::to_string(q) + ")");
+    if (!subsystem_reads_param0(kinds[s]))
+      return fail(ILQG_ERR_UNSUPPORTED, where + dyn_kind_name(kinds[s]) + ": this kind reads no param0");
+  }
+  return ILQG_OK;
+}
+// One value table holds the cost columns and the subsystem columns
+ilqg_status instance_total_check(size_t cost_count, size_t subsystem_count) {
+  if (cost_count + subsystem_count > size_t(ILQG_MAX_INSTANCE_PARAMS))
+    return fail(ILQG_ERR_INVALID, "instance parameters: " + std::to_string(cost_count) + " cost columns + " +
+                                      std::to_string(subsystem_count) + " subsystem columns exceed ILQG_MAX_INSTANCE_PARAMS");
+  return ILQG_OK;
+}
+
+// A call that reads the table on `batch` instances while a table for another batch is bound would read past it: every
+// call that evaluates costs, and — `costs` false — with a subsystem column declared the ones that integrate or linearise
+ilqg_status instance_batch_check(const ilqg_problem* p, int32_t batch, bool costs = true) {
+  if (p->dev.inst_values && batch != p->inst_batch && (costs || !p->inst_subs.empty()))
     return fail(ILQG_ERR_INVALID, "per-instance parameter values are bound for a batch of " + std::to_string(p->inst_batch) +
                                       ", this call has " + std::to_string(batch) + " instances");
   return ILQG_OK;
 }
 
-// ilqg_problem_declare_instance_params: the checked list into the handle, its (term, field) table and the row stage's
-// side table (per op of the row program the column of its weight / value; the program is not touched) onto the device
-ilqg_status declare_instance_params(ilqg_problem* p, int32_t count, const ilqg_instance_param* params) {
-  const std::vector<int>& op_term = p->row_prog.op_term;
-  std::vector<int> cols(op_term.size() * 2 + 2, -1), terms(size_t(count) * 2 + 2, 0);
-  for (int c = 0; c < count; c++) {
+// ilqg_problem_declare_instance_params / _declare_instance_subsystem_params: the checked lists into the handle, and onto
+// the device the column table ((term, field) per cost column, then subsystem -> column: DevProblem::inst_terms) and the
+// row stage's side table (per op of the row program the column of its weight / value; the program is not touched).
+// Subsystem s's column goes to the weight word of its Jacobian op and, for the Air3D pursuer, to the value word of the
+// evader's, where build_row_program put the baked param0.
+ilqg_status declare_instance_columns(ilqg_problem* p, const std::vector<ilqg_instance_param>& params,
+                                     const std::vector<int>& subs) {
+  const std::vector<int>&op_term = p->row_prog.op_term, &op_sub = p->row_prog.op_sub;
+  const size_t count = params.size() + subs.size();
+  std::vector<int> cols(op_term.size() * 2 + 2, -1), terms(count * 2 + kMaxPlayers, -1);
+  for (size_t c = 0; c < params.size(); c++) {
     terms[2 * c] = params[c].term;
     terms[2 * c + 1] = params[c].field;
     for (size_t op = 0; op < op_term.size(); op++)
-      if (op_term[op] == params[c].term) cols[2 * op + (params[c].field == ILQG_PARAM_WEIGHT ? 0 : 1)] = c;
+      if (op_term[op] == params[c].term) cols[2 * op + (params[c].field == ILQG_PARAM_WEIGHT ? 0 : 1)] = int(c);
+  }
+  for (size_t q = 0; q < subs.size(); q++) {
+    const int c = int(params.size() + q), s = subs[q];
+    terms[2 * c] = -1;
+    terms[2 * c + 1] = s;
+    terms[2 * count + s] = c;
+    for (size_t op = 0; op < op_sub.size(); op++) {
+      if (op_sub[op] == s) cols[2 * op] = c;
+      if (op_sub[op] == s - 1 && op_sub[op] >= 0 && p->dev.sub_kind[s] == ILQG_DYN_AIR_3D_PURSUER) cols[2 * op + 1] = c;
+    }
   }
   const char* what = "instance parameter tables";
   // kernels of earlier calls on any stream may still read the old tables (unbound: they look at neither)
@@ -647,7 +709,8 @@ ilqg_status declare_instance_params(ilqg_problem* p, int32_t count, const ilqg_i
   e = copy_to_device(p->d_row_prog.get() + p->row_prog.words.size(), cols);
   if (e != hipSuccess) return hip_failed(what, e);
   p->d_inst_terms = std::move(d_terms);  // the old table goes only now that the new one is up
-  p->inst_params.assign(params, params + count);
+  p->inst_params = params;
+  p->inst_subs = subs;
   return ILQG_OK;
 }
 

@@ -33,6 +33,7 @@ struct PlanStepper {
   PlanRef<T> pl;
   T *sx, *su;
   int t;
+  T Lp, Lp_next;  // lane t < N: param0 of subsystem t and (Air3D's evader row) of the next one, this instance's (plan_stepper)
   __device__ __forceinline__ void controls(int k, bool interpolate, float frac_f) {
     const int n = p.n, m = p.m;
     if (t < m) {
@@ -59,8 +60,8 @@ struct PlanStepper {
       for (int e = 0; e < kSubStatesMax; e++) xj[e] = e < xd ? sx[xo + e] : T(0);
       const bool dist = p.sub_kind[t] == ILQG_DYN_UNICYCLE_4D_DISTURBED;  // the next player's (dx, dy)
       const bool air = p.sub_kind[t] == ILQG_DYN_AIR_3D_EVADER;           // the next row's parameter: pursuer speed
-      sub_integrate8<T>(p.sub_kind[t], T(p.sub_param[t]), interval, xj, su[uo], su[uo + 1],
-                       dist ? su[uo + 2] : (air ? T(p.sub_param[t + 1]) : T(0)), dist ? su[uo + 3] : T(0));
+      sub_integrate8<T>(p.sub_kind[t], Lp, interval, xj, su[uo], su[uo + 1], dist ? su[uo + 2] : (air ? Lp_next : T(0)),
+                       dist ? su[uo + 3] : T(0));
       for (int e = 0; e < xd; e++) sx[xo + e] = xj[e];
     }
     __syncthreads();
@@ -88,6 +89,20 @@ struct PlanStepper {
     integrate(rel - p.dt * ks);
   }
 };
+
+// The stepper of instance b: the subsystems' parameters are read here, once — the baked ones, or with per-instance
+// values bound (DevProblem::inst_values) and the subsystem declared, row b's
+template <typename T>
+__device__ __forceinline__ PlanStepper<T> plan_stepper(const DevProblem& p, const PlanRef<T>& pl, T* sx, T* su, int t, int b) {
+  const float* const iv = instance_values(p, b);
+  T Lp = T(0), Lp_next = T(0);
+  if (t < p.N) {
+    Lp = T(subsystem_param(p, iv, t));
+    // t + 1 < N: flatten_subsystems (ilqg_problem.hpp) admits the evader only as row 0 of the pair (evader, pursuer)
+    if (p.sub_kind[t] == ILQG_DYN_AIR_3D_EVADER) Lp_next = T(subsystem_param(p, iv, t + 1));
+  }
+  return PlanStepper<T>{p, pl, sx, su, t, Lp, Lp_next};
+}
 
 template <typename T>
 struct PlanBuffers {
@@ -134,7 +149,7 @@ __global__ void __launch_bounds__(64) plan_integrate_kernel(DevProblem p, PlanIn
   }
   if (t < p.n) sx[t] = a.x[b * p.n + t];
   __syncthreads();
-  PlanStepper<T> st{p, pl, sx, su, t};
+  PlanStepper<T> st = plan_stepper<T>(p, pl, sx, su, t, int(b));
   if (a.t_from > pl.t0) st.to_next_step(a.t_from);
   st.whole_steps(int(current) + 1, int(final_step));
   st.from_prior_step(a.t_to);
@@ -194,7 +209,7 @@ __global__ void __launch_bounds__(64) receding_sync_kernel(DevProblem p, Recedin
   }
   if (t < n) sx[t] = a.x[b * n + t];
   __syncthreads();
-  PlanStepper<T> st{p, pl, sx, su, t};
+  PlanStepper<T> st = plan_stepper<T>(p, pl, sx, su, t, int(b));
   st.to_next_step(a.t);
   st.whole_steps(int_begin, int_end);
   // nearest plan state in the first subsystem's metric (concatenated_dynamical_system.cpp:109-113: its position for

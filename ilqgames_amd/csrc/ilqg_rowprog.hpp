@@ -25,6 +25,8 @@ struct RowProgramHost {
   int compact_off = 0, compact_w = 0;  // the compact-row block (ilqg_rows.hpp: RP_OFF_COMPACT) and its row length
   std::vector<int> op_term;  // per op, beside the image: the term whose weight / value the op carries (TERM, EXT_EVAL,
                              // EXT_APPLY), -1 for the others — what a per-instance parameter of that term overrides
+  std::vector<int> op_sub;   // ... and the subsystem whose param0 a JACOBIAN op carries in its weight word (the next
+                             // subsystem's in its value word: the Air3D pair), -1 for the others
 };
 
 // `poly_off`: the problem's polyline offsets (points), host copy.
@@ -91,10 +93,11 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
   std::vector<int> passes, ops, sids, linit, regions, merit;
   std::vector<short> maps;
   int max_lslots = 0, max_gslots = 0;
-  std::vector<int> op_term;
+  std::vector<int> op_term, op_sub;
   auto emit_op = [&](int mode, int sid_begin, int nsid, int aux, const DevTerm& c, const DevTerm& owner, int poly_first,
                      int pattern_or_nseg, int term = -1) {
     op_term.push_back(term);
+    op_sub.push_back(mode == ROP_JACOBIAN ? aux : -1);
     // `owner`: the top-level term whose role / player / constraint slot / first step apply (c itself, or the
     // ExtremeValueCost c is a child of)
     int o[ROP_WORDS] = {0};
@@ -473,6 +476,7 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
   out->num_pslots = NPS;
   out->max_lslots = max_lslots;
   out->op_term = op_term;
+  out->op_sub = op_sub;
   out->max_gslots = max_gslots;
   out->maps_off = w[RP_OFF_MAPS];
   out->maps_words = w[RP_MAPS_WORDS];

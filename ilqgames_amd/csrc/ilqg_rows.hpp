@@ -546,7 +546,7 @@ struct OpStatic {
   }
   template <int F> __device__ __forceinline__ int param() const {
     constexpr int mode = S::w[S::w[RP_OFF_OPS] + OP * ROP_WORDS + RO_MODE];
-    if constexpr (BOUND && (F == RO_WEIGHT || F == RO_VALUE) && (mode == ROP_TERM || mode == ROP_EXT_EVAL || mode == ROP_EXT_APPLY)) {
+    if constexpr (BOUND && (F == RO_WEIGHT || F == RO_VALUE) && (mode == ROP_TERM || mode == ROP_EXT_EVAL || mode == ROP_EXT_APPLY || mode == ROP_JACOBIAN)) {
       const int c = cols[F == RO_WEIGHT ? 0 : 1];
       if (c >= 0) return iv[c];
     }

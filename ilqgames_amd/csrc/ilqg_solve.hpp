@@ -521,6 +521,7 @@ __device__ __forceinline__ void probe_roll_instance(const DevProblem& p, const S
   ra.alpha_scale = probe_step(sa, s, j);
   ra.xs = e + E.xs;
   ra.us = e + E.us;
+  ra.iv = instance_values(p, b);
   if constexpr (NX > 0)
     rollout_instance<T, NX, NP * MU, (NX == 4 && NP == 2), (MU == 1), (NX == 3 && NP == 2 && MU == 1),
                      (NX == 4 * NP && MU == 2 && NP <= 2), dims_use_plain_rk4(NX, NP, MU)>(p, ra, sm, int(threadIdx.x),
@@ -550,6 +551,7 @@ __device__ __forceinline__ void probe_roll_pair(const DevProblem& p, const Solve
     ra[q].alpha_scale = probe_step(sa, s, j);
     ra[q].xs = e + E.xs;
     ra[q].us = e + E.us;
+    ra[q].iv = instance_values(p, b);
   }
   rollout_pair<T, NX, NP * MU, (MU == 1)>(p, ra[0], ra[1], w0, w1, sm, int(threadIdx.x));
 }
@@ -578,6 +580,7 @@ __device__ __forceinline__ void probe_roll_lanes(const DevProblem& p, const Solv
   ra.alpha_scale = T(0);
   ra.xs = nullptr;
   ra.us = nullptr;
+  ra.iv = instance_values(p, b);
   rollout_lanes<T, NX, NP * MU, NP, (MU == 1)>(p, ra, probe_step(sa, s, j), e + E.xs, e + E.us, act, sm, t);
 }
 
@@ -812,6 +815,7 @@ __device__ __forceinline__ void roll_pair_instances(const DevProblem& p, const S
     s = trial_state_begin<T>(p, sa, ib, b, n, N, m);
     if (s.stage != ST_ROLLOUT) return false;
     trial_rollout_args<T>(sa, ib, b, n, s, r);
+    r.iv = instance_values(p, b);  // each half of the wavefront its own instance's row
     return true;
   };
   const bool g0 = enter(ib0, b0, s0, r0), g1 = enter(ib1, b1, s1, r1);
@@ -823,7 +827,11 @@ __device__ __forceinline__ void roll_pair_instances(const DevProblem& p, const S
 }
 
 // PROGID: 0 = the row stage interprets the problem's row program; k = straight-line code for registered structure k
-template <typename T, int NX, int NP, int MU, int W, int PHASE = TRIAL_FUSED, int PROGID = 0>
+// BOUND: the fused kernel of a problem with per-instance parameters bound — its rollout takes the subsystems' parameters
+// from the instance's row of the table.  Kernels of their own, as the bound straight-line row code is: the read costs the
+// unbound fused kernel two registers (and, n = 14 in fp64, a spill), so that one stays the code it was.  The one-wave
+// rollout kernel of the split pass (TRIAL_ROLL) has room for it and looks at run time.
+template <typename T, int NX, int NP, int MU, int W, int PHASE = TRIAL_FUSED, int PROGID = 0, bool BOUND = (PROGID >= kBoundProg)>
 __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const short* maps,
                                                     const SolveArgs<T>& sa, int b, T* sm) {
   static_assert(PHASE == TRIAL_FUSED || W == 1, "the split phases run one wave per instance");
@@ -861,7 +869,10 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
     __syncthreads();  // pass boundary: global-memory hand-off between waves
     const bool roll = PHASE != TRIAL_DECIDE && s.stage == ST_ROLLOUT;  // TRIAL_DECIDE: the pass's rollout is behind it
     RolloutArgs<T> ra;
-    if (roll) trial_rollout_args<T>(sa, ib, b, n, s, ra);
+    if (roll) {
+      trial_rollout_args<T>(sa, ib, b, n, s, ra);
+      if constexpr (BOUND || PHASE == TRIAL_ROLL) ra.iv = instance_values(p, b);
+    }
     if (t == 0) {
       flags[0] = roll ? 0 : Tn;
       flags[1] = 0;

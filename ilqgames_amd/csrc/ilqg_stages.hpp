@@ -30,6 +30,8 @@ struct RolloutArgs {
   T alpha_scale;
   T* xs;            // [T][n]
   T* us;            // [T][m]
+  const float* iv = nullptr;  // this instance's row of the bound per-instance parameters (instance_values) or nullptr:
+                              // param0 of a declared subsystem comes from it (subsystem_param)
 };
 
 // [x | dx | u] + two staged [P | alpha | u_ref | x_ref] blocks (the one in use, the one the DMA is filling)
@@ -102,10 +104,11 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
     xo = p.xoff[grp];
     uo = p.uoff[grp];
     xd = p.xoff[grp + 1] - xo;
-    Lp = T(p.sub_param[grp]);
+    Lp = T(subsystem_param(p, a.iv, grp));
 #pragma unroll
     for (int e = 0; e < XS; e++) xj[e] = (e < xd) ? a.x0[xo + e] : T(0);
   }
+  const T air_vp = AIR ? T(subsystem_param(p, a.iv, 1)) : T(0);  // Air3D: the pursuer's speed enters the evader's rows
   T* const gth = stg + 2 * WP;  // exchange scratch of the stage-parallel integrator
   const bool any_car = __any(integ && (kind == ILQG_DYN_CAR_5D || kind == ILQG_DYN_CAR_6D));
   issue(0, 0);
@@ -173,7 +176,7 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
       if constexpr (GEN) {
         if (integ) sub_integrate8<T>(kind, Lp, p.dt, xj, u0, u1);
       } else if constexpr (AIR) {
-        if (grp == 0) sub_integrate<T>(kind, Lp, p.dt, xj, u0, u1, T(p.sub_param[1]));  // every lane of the group keeps the state
+        if (grp == 0) sub_integrate<T>(kind, Lp, p.dt, xj, u0, u1, air_vp);  // every lane of the group keeps the state
       } else if constexpr (DIST) {
         const bool dist = integ && kind == ILQG_DYN_UNICYCLE_4D_DISTURBED;  // the next player's (dx, dy)
         const T d0 = dist ? su[uo + 2] : T(0), d1 = dist ? su[uo + 3] : T(0);
@@ -268,6 +271,7 @@ __device__ __forceinline__ void rollout_pair(const DevProblem& p, const RolloutA
   T* const xs_out = h ? a1.xs : a0.xs;
   T* const us_out = h ? a1.us : a0.us;
   const T alpha_scale = h ? a1.alpha_scale : a0.alpha_scale;
+  const float* const iv = h ? a1.iv : a0.iv;  // each half its own instance's row
 #pragma unroll
   for (int e = 0; e < XS; e++) xj[e] = T(0);
   if (integ) {
@@ -275,7 +279,7 @@ __device__ __forceinline__ void rollout_pair(const DevProblem& p, const RolloutA
     xo = p.xoff[grp];
     uo = p.uoff[grp];
     xd = p.xoff[grp + 1] - xo;
-    Lp = T(p.sub_param[grp]);
+    Lp = T(subsystem_param(p, iv, grp));
 #pragma unroll
     for (int e = 0; e < XS; e++) xj[e] = (e < xd) ? x0[xo + e] : T(0);
   }
@@ -370,7 +374,7 @@ __device__ __forceinline__ void rollout_lanes(const DevProblem& p, const Rollout
   T xj[XS];
   const int kind = p.sub_kind[i];
   const int xo = p.xoff[i], uo = p.uoff[i], xd = p.xoff[i + 1] - xo, ud = p.udim[i];
-  const T Lp = T(p.sub_param[i]);
+  const T Lp = T(subsystem_param(p, a.iv, i));
 #pragma unroll
   for (int e = 0; e < XS; e++) xj[e] = (e < xd) ? a.x0[xo + e] : T(0);
   const bool store = act && live;
@@ -509,6 +513,7 @@ __device__ __forceinline__ QuadTables<T> quad_tables_load(const DevProblem& p, v
     constexpr int TW = int(sizeof(DevTerm) / sizeof(int));
     for (int c = t; c < p.inst_count; c += NT) {
       const int term = p.inst_terms[2 * c], field = p.inst_terms[2 * c + 1];
+      if (term < 0) continue;  // a subsystem's column: the integrators read it (subsystem_param)
       const int word = int((field == ILQG_PARAM_WEIGHT ? offsetof(DevTerm, weight) : offsetof(DevTerm, value)) / sizeof(int));
       terms_i[term * TW + word] = __float_as_int(iv[c]);
     }

@@ -25,6 +25,7 @@ EXPORTS = [
     "ilqg_receding_horizon_shift_batch", "ilqg_default_solve_options", "ilqg_solve_batch_ex", "ilqg_solve_state_batch",
     "ilqg_set_scratch", "ilqg_problem_last_schedule", "ilqg_copy_bandwidth", "ilqg_problem_row_program", "ilqg_row_program_build",
     "ilqg_problem_declare_instance_params", "ilqg_problem_bind_instance_values", "ilqg_instance_params_check",
+    "ilqg_problem_declare_instance_subsystem_params", "ilqg_instance_subsystem_params_check",
 ]
 
 
@@ -181,6 +182,20 @@ def instance_params_check(spec, params, dtype=abi.F64):
     del keep
 
 
+def _instance_subsystems(rows):
+    rows = [int(r) for r in rows]
+    return (C.c_int32 * max(1, len(rows)))(*rows), len(rows)
+
+
+def instance_subsystem_params_check(spec, rows, dtype=abi.F64):
+    """ilqg_instance_subsystem_params_check: raises IlqgError where Problem.declare_instance_subsystem_params would —
+    host only, no device needed.  rows: rows of the spec's subsystems."""
+    desc, keep = spec.build(dtype)
+    arr, count = _instance_subsystems(rows)
+    _check(lib().ilqg_instance_subsystem_params_check(C.byref(desc), count, arr))
+    del keep
+
+
 class Problem:
     """Owns an ilqg_problem* (device tables of one reference `Problem`)."""
 
@@ -221,8 +236,16 @@ class Problem:
         _check(lib().ilqg_problem_declare_instance_params(self.h, count, arr))
         self.instance_params = [(int(arr[c].term), int(arr[c].field)) for c in range(count)]
 
+    def declare_instance_subsystem_params(self, rows):
+        """ilqg_problem_declare_instance_subsystem_params: rows of the spec's subsystems whose param0 (wheelbase, speed)
+        varies per instance; column cost_count + c of the table bind_instance_values binds overrides param0 of rows[c].
+        [] clears."""
+        arr, count = _instance_subsystems(rows)
+        _check(lib().ilqg_problem_declare_instance_subsystem_params(self.h, count, arr))
+        self.instance_subsystems = [int(arr[c]) for c in range(count)]
+
     def bind_instance_values(self, values):
-        """ilqg_problem_bind_instance_values: a float32 [B][count] table (uploaded if it is not a CUDA tensor), read by
+        """ilqg_problem_bind_instance_values: a float32 [B][count] table, count = cost columns + subsystem columns (uploaded if it is not a CUDA tensor), read by
         every later call on this problem until bind_instance_values(None); the tensor is kept alive while bound and
         returned — a CUDA float32 tensor passed in is bound as it is, so the caller may rewrite it between calls."""
         import torch
@@ -233,7 +256,7 @@ class Problem:
         if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float32 and
                 values.is_contiguous()):
             values = torch.as_tensor(np.ascontiguousarray(values, dtype=np.float32), device="cuda").contiguous()
-        count = len(getattr(self, "instance_params", []))
+        count = len(getattr(self, "instance_params", [])) + len(getattr(self, "instance_subsystems", []))
         if values.dim() != 2 or values.shape[1] != count:
             raise ValueError("instance values must be [batch][%d], got %s" % (count, tuple(values.shape)))
         _check(lib().ilqg_problem_bind_instance_values(self.h, values.shape[0], C.c_void_p(values.data_ptr())))

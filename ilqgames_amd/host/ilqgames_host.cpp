@@ -455,7 +455,7 @@ class Packer {
 }  // namespace
 
 bool ResolveInstanceParams(const ProblemDescription& description, const InstanceParams& params,
-                           std::vector<ilqg_instance_param>* out, std::string* why) {
+                           std::vector<ilqg_instance_param>* out, std::string* why, std::vector<int32_t>* subsystems_out) {
   std::string scratch;
   if (why == nullptr) why = &scratch;
   out->clear();
@@ -468,6 +468,28 @@ bool ResolveInstanceParams(const ProblemDescription& description, const Instance
       return false;
     }
     out->push_back(ilqg_instance_param{term, static_cast<int32_t>(params.params[c].field)});
+  }
+  if (subsystems_out != nullptr) subsystems_out->clear();
+  if (!params.subsystems.empty() && subsystems_out == nullptr) {
+    *why = "instance parameters name subsystems, the caller takes none";
+    return false;
+  }
+  for (size_t c = 0; c < params.subsystems.size(); c++) {
+    int row = params.subsystems[c].row;
+    if (params.subsystems[c].object != nullptr) {
+      row = -1;
+      for (size_t q = 0; q < description.subsystem_objects.size() && row < 0; q++)
+        if (description.subsystem_objects[q] == params.subsystems[c].object) row = static_cast<int>(q);
+      if (row < 0) {
+        *why = "instance subsystem parameter " + std::to_string(c) + " names an object that is no subsystem of the problem";
+        return false;
+      }
+    } else if (row < 0 || row >= description.desc.num_players) {
+      *why = "instance subsystem parameter " + std::to_string(c) + " names row " + std::to_string(row) + ", the problem has " +
+             std::to_string(description.desc.num_players) + " subsystems";
+      return false;
+    }
+    subsystems_out->push_back(row);
   }
   return true;
 }
@@ -516,6 +538,9 @@ bool DescribeProblem(const Problem& problem, const SolverParams& params, ilqg_dt
   ilqg_problem_desc& d = out->desc;
   if (!DescribeDynamics(*problem.Dynamics(), &d, why)) return false;
   const int N = d.num_players;
+  out->subsystem_objects.assign(N, nullptr);
+  if (const auto* dyn = dynamic_cast<const ConcatenatedDynamicalSystem*>(problem.Dynamics().get()))
+    for (int i = 0; i < N; i++) out->subsystem_objects[i] = dyn->Subsystems()[i].get();
   if (static_cast<size_t>(N) != problem.PlayerCosts().size()) {
     *why = "player count mismatch between dynamics and player costs";
     return false;
@@ -889,6 +914,7 @@ class DeviceSolve {
       if (!bound) return;
       (void)ilqg_problem_bind_instance_values(handle, 0, nullptr);
       (void)ilqg_problem_declare_instance_params(handle, 0, nullptr);
+      (void)ilqg_problem_declare_instance_subsystem_params(handle, 0, nullptr);
     }
     ilqg_problem* handle;
     bool bound = false;
@@ -932,13 +958,17 @@ class DeviceSolve {
     CHECK_GT(B, 0);
     // per-instance cost parameters: rows [first_row, first_row + B) of the caller's table, bound for this solve only
     InstanceBinding binding(handle_);
-    if (instance_params != nullptr && !instance_params->params.empty()) {
+    if (instance_params != nullptr && !(instance_params->params.empty() && instance_params->subsystems.empty())) {
       std::vector<ilqg_instance_param> declared;
+      std::vector<int32_t> rows_declared;
       std::string why;
-      CHECK(ResolveInstanceParams(description_, *instance_params, &declared, &why)) << why;
-      const size_t count = declared.size();
+      CHECK(ResolveInstanceParams(description_, *instance_params, &declared, &why, &rows_declared)) << why;
+      const size_t count = declared.size() + rows_declared.size();  // [cost params | subsystem params]
       CHECK_GE(instance_params->values.size(), (first_row + B) * count) << "instance parameter values: one row per instance";
-      CHECK_EQ(ilqg_problem_declare_instance_params(handle_, static_cast<int32_t>(count), declared.data()), ILQG_OK)
+      CHECK_EQ(ilqg_problem_declare_instance_params(handle_, static_cast<int32_t>(declared.size()), declared.data()), ILQG_OK)
+          << ilqg_last_error();
+      CHECK_EQ(ilqg_problem_declare_instance_subsystem_params(handle_, static_cast<int32_t>(rows_declared.size()),
+                                                              rows_declared.data()), ILQG_OK)
           << ilqg_last_error();
       const float* rows = instance_params->values.data() + first_row * count;
       HipCheck(hipMemcpy(d_instance_values_.Reserve(B * count * sizeof(float)), rows, B * count * sizeof(float),

@@ -309,7 +309,7 @@ typedef struct ilqg_problem ilqg_problem;
 ilqg_status ilqg_problem_create(const ilqg_problem_desc* desc, ilqg_problem** out);
 void ilqg_problem_destroy(ilqg_problem* p);
 
-/* ---- Per-instance cost parameters --------------------------------------------------------------------------------
+/* ---- Per-instance parameters -------------------------------------------------------------------------------------
  * A batch is thousands of games in one launch; by default they differ in x0 (and warm start) alone.  With a value table
  * bound to the handle, instance b of every later call evaluates the declared terms with row b of the table in place of
  * ilqg_cost_term::weight / value — different goals, nominal speeds, weights and thresholds in one batch.  The reference
@@ -321,7 +321,7 @@ void ilqg_problem_destroy(ilqg_problem* p);
  * ilqg_total_costs_batch, ilqg_strategy_costs_batch, ilqg_check_local_nash_batch, ilqg_check_sufficient_nash_batch; each
  * of them returns ILQG_ERR_INVALID, before anything is launched, when its `batch` is not the bound one.  Entry points
  * that evaluate no cost (rollout, linearize, the LQ sweeps, receding-horizon shift / sync / splice, plan integrate) are
- * unaffected.  No scheduling choice depends on a binding; the row program (ilqg_problem_row_program) and the static
+ * unaffected by cost columns (for subsystem columns see below).  No scheduling choice depends on a binding; the row program (ilqg_problem_row_program) and the static
  * structure it matched are those of the descriptor.
  *
  * Values are float, like the descriptor's, and are converted to the problem's arithmetic where the baked value is: an
@@ -347,7 +347,29 @@ void ilqg_problem_destroy(ilqg_problem* p);
  *   CONSTRAINT_AFFINE_SCALAR / _VECTOR     no       no  (dense coefficient blocks)
  * Anything else — a "no" above, a term index out of range, a field that is not an ilqg_param_field, the same (term,
  * field) twice — is ILQG_ERR_UNSUPPORTED with the term named in ilqg_last_error(); nothing is ever silently ignored.
- * Out of scope: value2, polyline geometry, subsystem parameters, regularisation, solver parameters. */
+ * Out of scope: value2, polyline geometry, regularisation, solver parameters.
+ *
+ * Per-instance SUBSYSTEM parameters (ilqg_problem_declare_instance_subsystem_params): ilqg_subsystem::param0 of the
+ * declared rows of ilqg_problem_desc::subsystems varies per instance too — fleets of cars with different wheelbases,
+ * the robustness of a plan to a Dubins or Air3D speed.  One value table serves both declarations: it is
+ * float [batch][cost_count + subsystem_count], the cost columns first in their declared order, and column
+ * cost_count + c replaces param0 of subsystems[c] for that instance.  Either declaration may be made first; together
+ * they hold at most ILQG_MAX_INSTANCE_PARAMS columns.
+ *   kind                                   param0
+ *   CAR_5D, CAR_6D, CAR_7D                 yes (inter-axle distance)
+ *   DUBINS_CAR, DELAYED_DUBINS_CAR         yes (speed)
+ *   AIR_3D_EVADER, AIR_3D_PURSUER          yes (their speeds)
+ *   UNICYCLE_4D, UNICYCLE_4D_DISTURBED,
+ *   PLANAR_DISTURBANCE, POINT_MASS_2D,
+ *   UNICYCLE_5D                            no  (the kind reads no param0)
+ * A "no", a row out of range or the same row twice is ILQG_ERR_UNSUPPORTED with "subsystem <row>" and the kind named in
+ * ilqg_last_error().  With a subsystem column declared and a table bound, the entry points that integrate or linearise
+ * read the table as well — ilqg_rollout_batch, ilqg_linearize_batch, ilqg_receding_horizon_shift_batch / _sync_batch,
+ * ilqg_plan_integrate_batch — and return ILQG_ERR_INVALID before any launch when their `batch` is not the bound one;
+ * the cost-evaluating entry points above honour both kinds of column.  The LQ sweeps and the splice read no parameter.
+ * The same bit-for-bit rule holds: an instance computes what a problem created with that float as param0 computes.
+ * VALUES ARE NOT VALIDATED: the table lives on the device and may be rewritten between calls, so a zero wheelbase gives
+ * what a descriptor with a zero wheelbase gives (a division by zero in the car models). */
 typedef enum { ILQG_PARAM_WEIGHT = 0, ILQG_PARAM_VALUE = 1 } ilqg_param_field;
 typedef struct {
   int32_t term;  /* index into ilqg_problem_desc::terms */
@@ -358,12 +380,19 @@ typedef struct {
 /* Which (term, field) pairs vary per instance: column c of the value table overrides params[c].  count = 0 clears the
  * declaration.  ILQG_ERR_INVALID while a table is bound (unbind first). */
 ilqg_status ilqg_problem_declare_instance_params(ilqg_problem* p, int32_t count, const ilqg_instance_param* params);
-/* values: device float [batch][count], or NULL to unbind.  The table is READ AT EVERY LATER CALL on this handle, not
+/* values: device float [batch][cost_count + subsystem_count], or NULL to unbind.  The table is READ AT EVERY LATER CALL on this handle, not
  * copied: the caller may rewrite it between calls (in stream order with them) and keeps it alive while it is bound.
  * ILQG_ERR_INVALID without a declaration, or with batch <= 0. */
 ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, const float* values);
 /* Host only, no device needed: the checks of the declare call against a descriptor. */
 ilqg_status ilqg_instance_params_check(const ilqg_problem_desc* desc, int32_t count, const ilqg_instance_param* params);
+/* Which subsystems' param0 vary per instance: subsystems[c] is a row of ilqg_problem_desc::subsystems, and column
+ * cost_count + c of the value table overrides its param0.  count = 0 clears the subsystem declaration.  ILQG_ERR_INVALID
+ * while a table is bound (unbind first), or when cost and subsystem columns together exceed ILQG_MAX_INSTANCE_PARAMS. */
+ilqg_status ilqg_problem_declare_instance_subsystem_params(ilqg_problem* p, int32_t count, const int32_t* subsystems);
+/* Host only, no device needed: the checks of the declare call against a descriptor (the total with the cost columns is
+ * the handle's to check). */
+ilqg_status ilqg_instance_subsystem_params_check(const ilqg_problem_desc* desc, int32_t count, const int32_t* subsystems);
 
 /* Bytes of device workspace a solve of `batch` instances needs: the per-instance iterates, linearisations and
  * loop states, the lists of back-tracking instances and the pool of the speculative line search.  A solve
@@ -734,6 +763,8 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
 /* Library / device introspection (used by the loader to fail loudly). */
 #define ILQG_ABI_VERSION 9 /* 9: per-instance cost parameters (ilqg_instance_param, ilqg_problem_declare_instance_params,
                                  ilqg_problem_bind_instance_values, ilqg_instance_params_check); still 9:
+                                 per-instance subsystem parameters (ilqg_problem_declare_instance_subsystem_params,
+                                 ilqg_instance_subsystem_params_check: two new calls, the table gains columns); still 9:
                                  ilqg_solve_options::sweep_forms (was reserved2 = 0 = AUTO: no layout or behaviour change);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;

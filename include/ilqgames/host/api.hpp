@@ -1052,12 +1052,17 @@ struct ProblemDescription {
   int num_constraints = 0;
   std::vector<float> dense_params;  // coefficient blocks of the affine constraints
   std::vector<const Cost*> term_objects;  // per term: the Cost / Constraint object it was flattened from
+  // per row of desc.subsystems: the subsystem object of a ConcatenatedDynamicalSystem (null for the row-pair systems)
+  std::vector<const SinglePlayerDynamicalSystem*> subsystem_objects;
 };
 
 // Per-instance cost parameters of a batched solve (include/ilqg.h; an EXTENSION: one reference Problem is one game).
 // `params` names what varies — the weight or the value (nominal / threshold) of a Cost or Constraint object of the
 // Problem, by address; the flattener resolves each to its term index — and `values` holds one row per instance,
-// column c overriding params[c]: [x0s.size()][params.size()], row-major.
+// column c overriding params[c]: [x0s.size()][params.size() + subsystems.size()], row-major.
+// `subsystems` names subsystems whose parameter (ilqg_subsystem::param0: a car's inter-axle distance, a Dubins or Air3D
+// speed) varies per instance — a subsystem of a ConcatenatedDynamicalSystem by address, or a row of the descriptor for the
+// row-pair systems (TwoPlayerUnicycle4D, Air3D); their columns follow the cost columns: [cost params | subsystem params].
 struct InstanceParams {
   struct Param {
     const Cost* term;        // a cost or constraint added to one of the Problem's PlayerCosts (or an ExtremeValueCost's child)
@@ -1067,11 +1072,23 @@ struct InstanceParams {
   std::vector<float> values;
   void Add(const Cost* term, ilqg_param_field field) { params.push_back(Param{term, field}); }
   void Add(const std::shared_ptr<const Cost>& term, ilqg_param_field field) { Add(term.get(), field); }
+  struct Subsystem {
+    const SinglePlayerDynamicalSystem* object;  // or null:
+    int row;                                    // ... a row of ilqg_problem_desc::subsystems
+  };
+  std::vector<Subsystem> subsystems;
+  void AddSubsystem(const SinglePlayerDynamicalSystem* subsystem) { subsystems.push_back(Subsystem{subsystem, -1}); }
+  void AddSubsystem(const std::shared_ptr<const SinglePlayerDynamicalSystem>& subsystem) { AddSubsystem(subsystem.get()); }
+  void AddSubsystem(int row) { subsystems.push_back(Subsystem{nullptr, row}); }
 };
 // The (term index, field) list of `params` in `description` (what ilqg_problem_declare_instance_params takes).
 // Returns false and sets *why when an object is not a term of the description.
+// `subsystems_out`: the rows of params.subsystems (what ilqg_problem_declare_instance_subsystem_params takes); also
+// false when an object is no subsystem of the description, a row is out of range, or subsystems are named and
+// subsystems_out is null (nothing is silently ignored).
 bool ResolveInstanceParams(const ProblemDescription& description, const InstanceParams& params,
-                           std::vector<ilqg_instance_param>* out, std::string* why);
+                           std::vector<ilqg_instance_param>* out, std::string* why,
+                           std::vector<int32_t>* subsystems_out = nullptr);
 
 // Walks Problem::Dynamics() and Problem::PlayerCosts() (after Initialize()) and fills the POD
 // descriptor of include/ilqg.h.  Returns false and sets *why when some object has no device kernel.

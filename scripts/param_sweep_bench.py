@@ -14,7 +14,11 @@ weight 0), and an iteration that rejects step sizes costs more passes.  So the l
 `baked_spread_vector_its`: ONE problem created with the first vector of the spread solving all B instances unbound, and
 the mean number of rejected step sizes per instance in the last iteration of (a), (c) and that run.
 
-Prints one JSON line: iterations/s of each.   python scripts/param_sweep_bench.py [--batch 1024] [--repeats 5] [--vectors 16]"""
+--subsystems: the same four legs for per-instance SUBSYSTEM parameters — the two cars' inter-axle distances (baked: 4.0 m):
+unbound; bound with every row the baked 4.0; bound with one wheelbase pair per instance drawn from [2.5, 5.0]; one problem
+per pair (V pairs, V solves of B / V instances).
+
+Prints one JSON line: iterations/s of each.   python scripts/param_sweep_bench.py [--batch 1024] [--repeats 5] [--vectors 16] [--subsystems]"""
 import argparse
 import copy
 import json
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--vectors", type=int, default=16)
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
+    ap.add_argument("--subsystems", action="store_true", help="the wheelbases of the two cars instead of cost parameters")
     args = ap.parse_args()
     import torch
     from ilqgames_amd import abi, examples, hip
@@ -72,6 +77,33 @@ def main():
             if rep > 0:
                 times.append(e0.elapsed_time(e1) * 1e-3)
         return float(np.median(times))
+
+    if args.subsystems:
+        rows = [0, 1]
+        wheelbases = (2.5 + 2.5 * rng.random((B, len(rows)))).astype(np.float32)
+        prob = hip.Problem(spec, dtype)
+        bufs = prob.alloc_solve_buffers(B)
+        out = dict(batch=B, iters=K, dtype=args.dtype, subsystems=rows, vectors=V)
+        out["unbound_its"] = B * K / timed([(prob, x0, bufs)])
+        prob.declare_instance_subsystem_params(rows)
+        prob.bind_instance_values(np.tile(np.array([spec.subsystems[r][3] for r in rows], dtype=np.float32), (B, 1)))
+        out["bound_identity_its"] = B * K / timed([(prob, x0, bufs)])
+        prob.bind_instance_values(wheelbases)
+        out["bound_spread_its"] = B * K / timed([(prob, x0, bufs)])
+        out["bound_spread_backtracks"] = float(prob.solve_state(bufs)["backtracks"].float().mean().item())
+        prob.bind_instance_values(None)
+        per = B // V
+        solves = []
+        for v in range(V):
+            s = copy.deepcopy(spec)
+            for r, val in zip(rows, wheelbases[v]):
+                kind, xd, ud, _ = s.subsystems[r]
+                s.subsystems[r] = (kind, xd, ud, float(val))
+            p = hip.Problem(s, dtype)
+            solves.append((p, x0[v * per:(v + 1) * per].contiguous(), p.alloc_solve_buffers(per)))
+        out["per_vector_problems_its"] = B * K / timed(solves)
+        print(json.dumps(out))
+        return
 
     prob = hip.Problem(spec, dtype)
     bufs = prob.alloc_solve_buffers(B)
