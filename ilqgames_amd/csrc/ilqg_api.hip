@@ -256,6 +256,7 @@ __device__ __forceinline__ QuadArgs<T> quad_args_of(const DevProblem& p, const Q
   a.merit_part = g.merit_part ? g.merit_part + b * Tn * N * 2 : nullptr;
   a.cost_part = g.cost_part ? g.cost_part + b * Tn * N : nullptr;
   a.iv = instance_values(p, int(b));
+  a.seg_off = instance_segs_offset(p, int(b));
   return a;
 }
 
@@ -1540,7 +1541,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
     sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), budget);
   }
   // (a problem with per-instance parameters bound runs fused kernels of its own, here and below: ilqg_solve.hpp)
-  auto k_trial = d.inst_values ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
+  auto k_trial = (d.inst_values || d.seg_inst_stride) ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
   const bool pw = C::USE_MFMA && !open_loop;  // one wave per player (MFMA feedback sweep)
   // Compact rows (ilqg_common.hpp) between the row stage and the sweep: the one-tile player-parallel sweep and the
   // open-loop sweep read them; the other sweeps take the dense arrays.  What the row stage writes and the sweep reads
@@ -1567,7 +1568,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
       if (p->static_prog == ID_) {                                                                             \
         static_id = ID_;                                                                                       \
         static_in_regs = static_prog_in_registers<StaticRowProg<ID_>>();                                       \
-        const bool bound = d.inst_values != nullptr; /* kernels of their own: the unbound ones are untouched */ \
+        const bool bound = d.inst_values != nullptr || d.seg_inst_stride != 0; /* kernels of their own */        \
         k_rows = bound ? ilq_rows_kernel<T, NX, NP, MU, kBoundProg + ID_> : ilq_rows_kernel<T, NX, NP, MU, ID_>; \
         k_prows = bound ? ilq_probe_rows_kernel<T, NX, NP, MU, kBoundProg + ID_>                               \
                         : ilq_probe_rows_kernel<T, NX, NP, MU, ID_>;                                           \
@@ -1947,6 +1948,32 @@ static const char* const kRouteProgressReceding =
     "receding horizon: the problem holds a RouteProgressCost, whose per-step nominals are tabulated for a first solve "
     "(initial time 0) only";
 
+// Per-instance routes (ilqg_problem_bind_instance_routes): the segment table of every instance, [batch][total_segs]
+// [kSegStride] in the layout of DevProblem::segs_f / segs_d.  One lane per (instance, segment).  A segment of a declared
+// polyline (cols[q] >= 0: its first point in the instance's row of `points`, float [batch][row_points][2]) is built from
+// the instance's points by the host builder's own function (ilqg_segment.hpp: the same roundings); a segment of any other
+// polyline is copied from the baked table, so that one base pointer serves every op of the row program.
+template <typename T>
+__global__ void __launch_bounds__(256) route_segments_kernel(const int* poly_off, int num_polylines, const int* cols,
+                                                             const float* points, int row_points, const T* baked,
+                                                             int total_segs, int batch, T* out) {
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(batch) * size_t(total_segs)) return;
+  const size_t b = gid / size_t(total_segs);
+  const int s = int(gid - b * size_t(total_segs));
+  T* const o = out + gid * kSegStride;
+  for (int q = 0; q < num_polylines; q++) {
+    const int first = poly_off[q] - q, nseg = poly_off[q + 1] - poly_off[q] - 1;  // (segment s of polyline q: DevProblem)
+    if (s < first || s >= first + nseg) continue;
+    if (cols[q] >= 0) {
+      segment_and_shortcuts(points + 2 * (b * size_t(row_points) + size_t(cols[q])), nseg, s - first, o);
+      return;
+    }
+    break;
+  }
+  for (int e = 0; e < kSegStride; e++) o[e] = baked[size_t(s) * kSegStride + e];
+}
+
 extern "C" {
 
 const char* ilqg_last_error(void) { return g_err.c_str(); }
@@ -2155,6 +2182,23 @@ ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words
   return s != ILQG_OK ? s : copy_row_program(tables.row_prog, tables.static_prog, words_out, capacity, num_words, static_id);
 }
 
+// The host half of creation alone, for the segment table (DevProblem::segs_f / segs_d: 21 scalars per segment)
+ilqg_status ilqg_segment_table_build(const ilqg_problem_desc* desc, int32_t dtype, void* out, int32_t capacity,
+                                     int32_t* num_elems) {
+  if (!num_elems || !desc) return fail(ILQG_ERR_INVALID, "null argument");
+  if (dtype != ILQG_F32 && dtype != ILQG_F64) return fail(ILQG_ERR_INVALID, "ilqg_segment_table_build: dtype");
+  ProblemTables tables;
+  const ilqg_status s = build_problem_tables(*desc, &tables);
+  if (s != ILQG_OK) return s;
+  *num_elems = int32_t(tables.segs.f.size());
+  if (out) {
+    if (capacity < *num_elems) return fail(ILQG_ERR_INVALID, "ilqg_segment_table_build: buffer too small");
+    if (dtype == ILQG_F32) std::memcpy(out, tables.segs.f.data(), sizeof(float) * tables.segs.f.size());
+    else std::memcpy(out, tables.segs.d.data(), sizeof(double) * tables.segs.d.size());
+  }
+  return ILQG_OK;
+}
+
 void ilqg_problem_destroy(ilqg_problem* p) { delete p; }
 
 // ---- per-instance cost parameters (ilqg.h) ----
@@ -2204,10 +2248,88 @@ ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, co
   if (p->inst_params.empty() && p->inst_subs.empty())
     return fail(ILQG_ERR_INVALID, "no instance parameters are declared (ilqg_problem_declare_instance_params)");
   if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance parameter values: batch must be positive");
+  if (p->route_batch && batch != p->route_batch)
+    return fail(ILQG_ERR_INVALID, "instance parameter values: per-instance routes are bound for a batch of " +
+                                      std::to_string(p->route_batch) + ", these values are for " + std::to_string(batch));
   d.inst_values = values;
   d.inst_terms = p->d_inst_terms.get();
   d.inst_count = int(p->inst_params.size() + p->inst_subs.size());
   p->inst_batch = batch;
+  return ILQG_OK;
+}
+
+// ---- per-instance routes (ilqg.h) ----
+ilqg_status ilqg_instance_routes_check(const ilqg_problem_desc* desc, int32_t count, const int32_t* polylines) {
+  if (!desc) return fail(ILQG_ERR_INVALID, "null argument");
+  return instance_routes_check_terms(desc->num_polylines, desc->num_terms, desc->terms, count, polylines);
+}
+
+ilqg_status ilqg_problem_declare_instance_routes(ilqg_problem* p, int32_t count, const int32_t* polylines) {
+  if (!p) return fail(ILQG_ERR_INVALID, "null argument");
+  if (p->route_batch)
+    return fail(ILQG_ERR_INVALID, "instance routes cannot be declared while a route table is bound: unbind first");
+  ilqg_status s = instance_routes_check_terms(p->dev.num_polylines, int(p->terms_host.size()), p->terms_host.data(), count, polylines);
+  if (s != ILQG_OK) return s;
+  // polyline -> its first point in a row of the caller's points (declaration order), -1: not declared
+  std::vector<int> cols(size_t(p->dev.num_polylines) + 1, -1), off(size_t(p->dev.num_polylines) + 1, 0);
+  if (count > 0) HIP_TRY(hipMemcpy(off.data(), p->d_poly_off.get(), sizeof(int) * off.size(), hipMemcpyDeviceToHost));
+  int points = 0;
+  for (int c = 0; c < count; c++) {
+    cols[polylines[c]] = points;
+    points += off[polylines[c] + 1] - off[polylines[c]];
+  }
+  DeviceBuffer<int> d_cols;
+  s = upload(cols, 0, "instance route tables", &d_cols);
+  if (s != ILQG_OK) return s;
+  p->d_route_cols = std::move(d_cols);
+  p->route_polys.assign(polylines, polylines + count);
+  p->route_points = points;
+  return ILQG_OK;
+}
+
+ilqg_status ilqg_problem_bind_instance_routes(ilqg_problem* p, int32_t batch, const float* points, void* stream) {
+  if (!p) return fail(ILQG_ERR_INVALID, "null argument");
+  DevProblem& d = p->dev;
+  if (!points) {  // (hipFree waits for the kernels that may still read the table)
+    d.segs_f = p->d_segs.f.get();
+    d.segs_d = p->d_segs.d.get();
+    d.seg_inst_stride = 0;
+    p->d_route_segs_f.reset();
+    p->d_route_segs_d.reset();
+    p->route_batch = 0;
+    return ILQG_OK;
+  }
+  if (p->route_polys.empty())
+    return fail(ILQG_ERR_INVALID, "no instance routes are declared (ilqg_problem_declare_instance_routes)");
+  if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance routes: batch must be positive");
+  if (d.inst_values && batch != p->inst_batch)
+    return fail(ILQG_ERR_INVALID, "instance routes: per-instance parameter values are bound for a batch of " +
+                                      std::to_string(p->inst_batch) + ", these routes are for " + std::to_string(batch));
+  const size_t count = size_t(batch) * size_t(d.total_segs);
+  const bool f32 = p->desc.dtype == ILQG_F32;
+  if (batch != p->route_batch) {  // a new table; one of the same size is rewritten in place, in stream order
+    const ilqg_status s = f32 ? upload(std::vector<float>(), count * kSegStride + 1, "instance route table", &p->d_route_segs_f)
+                              : upload(std::vector<double>(), count * kSegStride + 1, "instance route table", &p->d_route_segs_d);
+    if (s != ILQG_OK) {
+      (void)ilqg_problem_bind_instance_routes(p, 0, nullptr, stream);
+      return s;
+    }
+  }
+  if (count > 0) {
+    const dim3 grid((unsigned)((count + 255) / 256));
+    if (f32)
+      hipLaunchKernelGGL(route_segments_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, d.poly_off, d.num_polylines,
+                         p->d_route_cols.get(), points, p->route_points, p->d_segs.f.get(), d.total_segs, batch,
+                         p->d_route_segs_f.get());
+    else
+      hipLaunchKernelGGL(route_segments_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, d.poly_off, d.num_polylines,
+                         p->d_route_cols.get(), points, p->route_points, p->d_segs.d.get(), d.total_segs, batch,
+                         p->d_route_segs_d.get());
+    HIP_TRY(hipGetLastError());
+  }
+  if (f32) d.segs_f = p->d_route_segs_f.get(); else d.segs_d = p->d_route_segs_d.get();
+  d.seg_inst_stride = d.total_segs * kSegStride;
+  p->route_batch = batch;
   return ILQG_OK;
 }
 
@@ -2520,6 +2642,10 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
     const char* xs_c = (const char*)xs + size_t(b0) * d.T * d.n * esz;
     const char* us_c = (const char*)us + size_t(b0) * d.T * d.m * esz;
     if (p->dev.inst_values) full.inst_values = p->dev.inst_values + size_t(b0) * p->dev.inst_count;
+    if (p->dev.seg_inst_stride) {  // (the handle's precision: the other pointer is not read)
+      full.segs_f = p->dev.segs_f + size_t(b0) * p->dev.seg_inst_stride;
+      full.segs_d = p->dev.segs_d + size_t(b0) * p->dev.seg_inst_stride;
+    }
     s = launch_linquad(p, full, nb, xs_c, us_c, nullptr, nullptr, nullptr, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
                        nullptr, stream);
     if (s != ILQG_OK) break;

@@ -109,6 +109,10 @@ struct DevProblem {
   // (the row stage's table — per op of row_prog the column of its weight / value, or -1 — follows the program's
   // row_prog_words words in the device buffer `row_prog` points to)
   int inst_count;
+  // Per-instance routes (ilqg_problem_bind_instance_routes): while a route table is bound segs_f / segs_d point at the
+  // handle's [batch][total_segs][kSegStride] table and this is total_segs * kSegStride, the elements between two
+  // instances' tables; 0: every instance reads the one baked table.
+  int seg_inst_stride;
 };
 
 // Row b of the bound value table (null: nothing bound).  b is the instance a whole wavefront works on; the pointer is
@@ -147,6 +151,11 @@ constexpr int kSegStride = 21;
 template <typename T> __device__ __forceinline__ const T* problem_segs(const DevProblem& p);
 template <> __device__ __forceinline__ const float* problem_segs<float>(const DevProblem& p) { return p.segs_f; }
 template <> __device__ __forceinline__ const double* problem_segs<double>(const DevProblem& p) { return p.segs_d; }
+// Where instance b's segment table starts behind problem_segs (0 with no route table bound).  b is the instance a whole
+// wavefront works on (instance_values): scalar registers.
+__device__ __forceinline__ size_t instance_segs_offset(const DevProblem& p, int b) {
+  return size_t(unsigned(__builtin_amdgcn_readfirstlane(b))) * size_t(unsigned(p.seg_inst_stride));
+}
 template <typename T> __device__ __forceinline__ const T* problem_dense(const DevProblem& p);
 template <> __device__ __forceinline__ const float* problem_dense<float>(const DevProblem& p) { return p.dense_f; }
 template <> __device__ __forceinline__ const double* problem_dense<double>(const DevProblem& p) { return p.dense_d; }

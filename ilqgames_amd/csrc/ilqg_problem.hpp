@@ -14,6 +14,7 @@
 
 #include "ilqg_rowprog.hpp"         // RowProgramHost, build_row_program
 #include "ilqg_rowprog_static.hpp"  // the registered structures
+#include "ilqg_segment.hpp"         // line_segment2: the segment table's arithmetic
 #include "ilqg_stages.hpp"          // DevProblem, the models, dims_use_plain_rk4
 
 namespace ilqg {
@@ -80,6 +81,15 @@ struct ilqg_problem {
   std::vector<int> inst_subs;
   ilqg::DeviceBuffer<int> d_inst_terms;
   int inst_batch = 0;
+  // Per-instance routes (ilqg.h): the declared polylines, per polyline of the descriptor its first point in a row of the
+  // caller's points or -1 (device copy: route_segments_kernel), the points of a row, and while a table is bound the table
+  // (in the handle's precision; dev.segs_f / segs_d points at it, dev.seg_inst_stride is set) for `route_batch` instances
+  std::vector<int> route_polys;
+  ilqg::DeviceBuffer<int> d_route_cols;
+  int route_points = 0;
+  ilqg::DeviceBuffer<float> d_route_segs_f;
+  ilqg::DeviceBuffer<double> d_route_segs_d;
+  int route_batch = 0;
   int static_prog = 0;                // id of the registered structure it matches (ilqg_rowprog_static.hpp), 0: none
   ilqg::DeviceBuffer<int> d_unfinished;  // instances still running after an LQ-kernel launch
   ilqg::PinnedInts h_unfinished;  // pinned host mirror: [0..3] the counters, [8] the sequence number of read_round_counters
@@ -312,26 +322,17 @@ ilqg_status build_segments(const ilqg_problem_desc& desc, ProblemTables* t) {
     t->poly_off.assign(desc.polyline_offsets, desc.polyline_offsets + desc.num_polylines + 1);
     t->poly_pts.assign(desc.polyline_points, desc.polyline_points + 2 * size_t(t->poly_off.back()));
   }
-  auto emit = [&](auto& out, const float* a, const float* b) {
-    using S = typename std::decay<decltype(out)>::type::value_type;
-    const S ax = a[0], ay = a[1], bx = b[0], by = b[1];
-    const S dx = ax - bx, dy = ay - by;
-    const S len = std::sqrt(dx * dx + dy * dy);
-    out.push_back(ax); out.push_back(ay); out.push_back(bx); out.push_back(by);
-    out.push_back(len); out.push_back((bx - ax) / len); out.push_back((by - ay) / len);
-  };
   for (int q = 0; q < desc.num_polylines; q++) {
     const float* pts = desc.polyline_points + 2 * desc.polyline_offsets[q];
     const int nseg = desc.polyline_offsets[q + 1] - desc.polyline_offsets[q] - 1;
     for (int c = 0; c < nseg; c++) {
-      const int pm = c > 0 ? c - 1 : c, pn = c + 2 <= nseg ? c + 2 : c + 1;
-      auto segment_and_shortcuts = [&](auto& out) {
-        emit(out, pts + 2 * c, pts + 2 * (c + 1));
-        emit(out, pts + 2 * pm, pts + 2 * (c + 1));
-        emit(out, pts + 2 * c, pts + 2 * pn);
+      auto emit = [&](auto& out) {  // the arithmetic is ilqg_segment.hpp's, shared with route_segments_kernel
+        typename std::decay<decltype(out)>::type::value_type sg[kSegStride];
+        segment_and_shortcuts(pts, nseg, c, sg);
+        out.insert(out.end(), sg, sg + kSegStride);
       };
-      segment_and_shortcuts(t->segs.f);
-      segment_and_shortcuts(t->segs.d);
+      emit(t->segs.f);
+      emit(t->segs.d);
     }
   }
   t->dev.total_segs = int(t->segs.f.size() / kSegStride);
@@ -667,9 +668,33 @@ ilqg_status instance_total_check(size_t cost_count, size_t subsystem_count) {
 // A call that reads the table on `batch` instances while a table for another batch is bound would read past it: every
 // call that evaluates costs, and — `costs` false — with a subsystem column declared the ones that integrate or linearise
 ilqg_status instance_batch_check(const ilqg_problem* p, int32_t batch, bool costs = true) {
+  if (costs && p->route_batch && batch != p->route_batch)  // (only what evaluates costs reads a segment)
+    return fail(ILQG_ERR_INVALID, "per-instance routes are bound for a batch of " + std::to_string(p->route_batch) +
+                                      ", this call has " + std::to_string(batch) + " instances");
   if (p->dev.inst_values && batch != p->inst_batch && (costs || !p->inst_subs.empty()))
     return fail(ILQG_ERR_INVALID, "per-instance parameter values are bound for a batch of " + std::to_string(p->inst_batch) +
                                       ", this call has " + std::to_string(batch) + " instances");
+  return ILQG_OK;
+}
+
+// Per-instance routes (ilqg.h): may these polylines of the descriptor vary per instance?  A ROUTE_PROGRESS term's
+// per-step nominals are tabulated from the baked polyline at creation (build_time_nominals).
+ilqg_status instance_routes_check_terms(int num_polylines, int num_terms, const ilqg_cost_term* terms, int32_t count,
+                                        const int32_t* polylines) {
+  if (count < 0) return fail(ILQG_ERR_INVALID, "instance routes: count must not be negative");
+  if (count > 0 && !polylines) return fail(ILQG_ERR_INVALID, "null argument");
+  for (int c = 0; c < count; c++) {
+    const int q = polylines[c];
+    const std::string where = "instance route " + std::to_string(c) + " (polyline " + std::to_string(q) + "): ";
+    if (q < 0 || q >= num_polylines)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "index out of range (the problem has " + std::to_string(num_polylines) + " polylines)");
+    for (int e = 0; e < c; e++)
+      if (polylines[e] == q) return fail(ILQG_ERR_UNSUPPORTED, where + "declared twice (also route " + std::to_string(e) + ")");
+    for (int ti = 0; ti < num_terms; ti++)
+      if (terms[ti].kind == ILQG_COST_ROUTE_PROGRESS && terms[ti].polyline == q)
+        return fail(ILQG_ERR_UNSUPPORTED, where + "term " + std::to_string(ti) + " (" + cost_kind_name(terms[ti].kind) +
+                                              ") tabulates its per-step nominals from it when the problem is created");
+  }
   return ILQG_OK;
 }
 

@@ -507,7 +507,7 @@ constexpr int kStaticRowStride = 65;
 // descriptor it has fetched; the straight-line code exists in a second form, ProgStatic<ID, true>, whose ops read the
 // column table — kernels of their own, launched for a problem with a table bound, so that the unbound kernels are the
 // code they always were.
-struct ProgDynamic { static constexpr bool STATIC = false; };
+struct ProgDynamic { static constexpr bool STATIC = false; static constexpr bool kBound = true; };
 template <int ID> struct StaticRowProg;  // { static constexpr int kWords, w[kWords]; } per registered structure
 template <int ID, bool BOUND = false> struct ProgStatic {
   static constexpr bool STATIC = true;
@@ -548,7 +548,7 @@ struct OpStatic {
     constexpr int mode = S::w[S::w[RP_OFF_OPS] + OP * ROP_WORDS + RO_MODE];
     if constexpr (BOUND && (F == RO_WEIGHT || F == RO_VALUE) && (mode == ROP_TERM || mode == ROP_EXT_EVAL || mode == ROP_EXT_APPLY || mode == ROP_JACOBIAN)) {
       const int c = cols[F == RO_WEIGHT ? 0 : 1];
-      if (c >= 0) return iv[c];
+      if (c >= 0 && iv) return iv[c];  // (iv null: a route table alone is bound)
     }
     return rt[F];
   }
@@ -639,7 +639,9 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
   typedef typename std::conditional<XREG, MixArg<T>, RowArg<T>>::type Arg;
   const rp_cptr rp = (rp_cptr)p.row_prog;
   const rp_cptr iv = (rp_cptr) reinterpret_cast<const int*>(a.iv);
-  const typename ConstPtr<T>::type segs = (typename ConstPtr<T>::type)problem_segs<T>(p);
+  // (per-instance routes: the unbound straight-line code keeps the baked base, its bound twin runs when a table is bound)
+  const typename ConstPtr<T>::type segs =
+      (typename ConstPtr<T>::type)(PROG::kBound ? problem_segs<T>(p) + a.seg_off : problem_segs<T>(p));
   // table offsets: compile-time under ProgStatic (the run-time program has the same layout: it matched word for word)
   auto hdr = [&](auto f) -> int {
     if constexpr (ST) { constexpr int v = PROG::S::w[decltype(f)::value]; return v; } else return rp[decltype(f)::value];

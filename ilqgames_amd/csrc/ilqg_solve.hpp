@@ -409,7 +409,8 @@ __host__ __device__ inline size_t trial_phase_lds_bytes(const DevProblem& p, int
 }
 
 // What the rows of a pass are asked for, from the instance's state (the pass's rollout, if any, is done).
-template <typename T>
+// ROUTES false: the instance's segment table is not looked up (the unbound fused kernel: its bound twin does)
+template <typename T, bool ROUTES = true>
 __device__ __forceinline__ QuadArgs<T> trial_quad_args(const DevProblem& p, const InstanceBuffers<T>& ib,
                                                        const SolveState<T>& s, bool compact, int b) {
   const WsLayout& L = ib.L;
@@ -437,6 +438,7 @@ __device__ __forceinline__ QuadArgs<T> trial_quad_args(const DevProblem& p, cons
   qa.cost_part = (qmode == Q_COSTS || qmode == Q_TRIAL || qmode == Q_LIN) ? w + L.cpart : nullptr;
   qa.phacc = nullptr;
   qa.iv = instance_values(p, b);
+  if constexpr (ROUTES) qa.seg_off = instance_segs_offset(p, b);
   return qa;
 }
 
@@ -604,6 +606,7 @@ __device__ __forceinline__ void probe_rows_instance(const DevProblem& p, const s
   qa.cost_part = nullptr;
   qa.phacc = nullptr;
   qa.iv = instance_values(p, b);
+  qa.seg_off = instance_segs_offset(p, b);
   const int k0 = chunk * sa.rows_cw;
   const int nrows = p.T - k0 < sa.rows_cw ? p.T - k0 : sa.rows_cw;
   rows_chunk<T, NX, NP * MU, NP, rows_state_in_registers(NX, NP * MU), true, typename RowProgSel<PROGID>::type>(
@@ -905,7 +908,7 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
     // ---- linearise / quadraticise the trajectory: every wave claims rows as they become ready ----
     const int qmode = s.qmode;
     if constexpr (PHASE == TRIAL_FUSED) {
-    QuadArgs<T> qa = trial_quad_args<T>(p, ib, s, sa.compact != 0, b);
+    QuadArgs<T> qa = trial_quad_args<T, BOUND>(p, ib, s, sa.compact != 0, b);
     qa.phacc = (kProfile && sa.prof) ? qph : nullptr;
     qa.tl = kTimeline ? sa.prof : nullptr;
     qa.tl_b = b;

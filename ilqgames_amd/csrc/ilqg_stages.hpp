@@ -477,7 +477,7 @@ template <typename T>
 __device__ __forceinline__ QuadTables<T> quad_tables_load(const DevProblem& p, void* region, int inst) {
   const int t = threadIdx.x, NT = blockDim.x;
   T* segs = reinterpret_cast<T*>(region);
-  const T* gsegs = problem_segs<T>(p);
+  const T* gsegs = problem_segs<T>(p) + instance_segs_offset(p, inst);  // a bound route table: this instance's
   for (int e = t; e < p.total_segs * kSegStride; e += NT) segs[e] = gsegs[e];
   int* terms_i = reinterpret_cast<int*>(segs + size_t(p.total_segs) * kSegStride);
   const int* gterms = reinterpret_cast<const int*>(p.terms);
@@ -546,6 +546,8 @@ struct QuadArgs {
   T* merit_part;       // [T][N][2] = (|r_ii|^2, |l_i|^2) or nullptr
   T* cost_part;        // [T][N] PlayerCost::Evaluate or nullptr
   const float* iv = nullptr;  // this instance's row of the bound per-instance parameters (instance_values) or nullptr
+  size_t seg_off = 0;  // this instance's segment table behind problem_segs (instance_segs_offset), 0: the baked one.  Read
+                       // by the interpreter and the bound straight-line code only (rows_chunk)
   long long* phacc = nullptr;  // optional phase profile accumulators (registers of the caller)
   long long* tl = nullptr;     // optional timeline stamps (ilqg_common.hpp, -DILQG_TIMELINE=1): slots 40.. of instance tl_b
   int tl_b = 0;

@@ -26,6 +26,8 @@ EXPORTS = [
     "ilqg_set_scratch", "ilqg_problem_last_schedule", "ilqg_copy_bandwidth", "ilqg_problem_row_program", "ilqg_row_program_build",
     "ilqg_problem_declare_instance_params", "ilqg_problem_bind_instance_values", "ilqg_instance_params_check",
     "ilqg_problem_declare_instance_subsystem_params", "ilqg_instance_subsystem_params_check",
+    "ilqg_problem_declare_instance_routes", "ilqg_problem_bind_instance_routes", "ilqg_instance_routes_check",
+    "ilqg_segment_table_build",
 ]
 
 
@@ -196,6 +198,34 @@ def instance_subsystem_params_check(spec, rows, dtype=abi.F64):
     del keep
 
 
+def segment_table(spec, dtype=abi.F64):
+    """ilqg_segment_table_build: the [segments][21] table problem creation builds from the spec's polylines, in dtype's
+    arithmetic — host only, no device needed."""
+    desc, keep = spec.build(dtype)
+    count = C.c_int32(0)
+    _check(lib().ilqg_segment_table_build(C.byref(desc), dtype, None, 0, C.byref(count)))
+    out = np.zeros(count.value, dtype=np.float32 if dtype == abi.F32 else np.float64)
+    _check(lib().ilqg_segment_table_build(C.byref(desc), dtype, out.ctypes.data_as(C.c_void_p), count.value, C.byref(count)))
+    del keep
+    return out.reshape(-1, 21)
+
+
+def _instance_routes(spec, polylines):
+    """Polyline indices of the spec, or names given to them (ProblemSpec.polyline_names, where a scene sets it)."""
+    names = getattr(spec, "polyline_names", None) or []
+    rows = [names.index(q) if isinstance(q, str) else int(q) for q in polylines]
+    return (C.c_int32 * max(1, len(rows)))(*rows), len(rows)
+
+
+def instance_routes_check(spec, polylines, dtype=abi.F64):
+    """ilqg_instance_routes_check: raises IlqgError where Problem.declare_instance_routes would — host only, no device
+    needed.  polylines: indices of the spec's polylines."""
+    desc, keep = spec.build(dtype)
+    arr, count = _instance_routes(spec, polylines)
+    _check(lib().ilqg_instance_routes_check(C.byref(desc), count, arr))
+    del keep
+
+
 class Problem:
     """Owns an ilqg_problem* (device tables of one reference `Problem`)."""
 
@@ -243,6 +273,32 @@ class Problem:
         arr, count = _instance_subsystems(rows)
         _check(lib().ilqg_problem_declare_instance_subsystem_params(self.h, count, arr))
         self.instance_subsystems = [int(arr[c]) for c in range(count)]
+
+    def declare_instance_routes(self, polylines):
+        """ilqg_problem_declare_instance_routes: indices of the spec's polylines whose points vary per instance; a row of
+        the table bind_instance_routes binds holds their points one polyline after the other, in this order.  [] clears."""
+        arr, count = _instance_routes(self.spec, polylines)
+        _check(lib().ilqg_problem_declare_instance_routes(self.h, count, arr))
+        self.instance_routes = [int(arr[c]) for c in range(count)]
+
+    def bind_instance_routes(self, points, stream=None):
+        """ilqg_problem_bind_instance_routes: a float32 [B][P][2] table, P the declared polylines' point counts summed
+        (uploaded if it is not a CUDA tensor).  The points are consumed by this call — the handle builds its own segment
+        table from them on the stream — so rewriting them afterwards needs another bind; None unbinds.  Returns the
+        tensor that was read."""
+        import torch
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+        if points is None:
+            _check(lib().ilqg_problem_bind_instance_routes(self.h, 0, None, st))
+            return None
+        if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32 and
+                points.is_contiguous()):
+            points = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float32), device="cuda").contiguous()
+        P = sum(len(self.spec.polylines[q]) for q in getattr(self, "instance_routes", []))
+        if points.dim() != 3 or points.shape[1] != P or points.shape[2] != 2:
+            raise ValueError("instance routes must be [batch][%d][2], got %s" % (P, tuple(points.shape)))
+        _check(lib().ilqg_problem_bind_instance_routes(self.h, points.shape[0], C.c_void_p(points.data_ptr()), st))
+        return points
 
     def bind_instance_values(self, values):
         """ilqg_problem_bind_instance_values: a float32 [B][count] table, count = cost columns + subsystem columns (uploaded if it is not a CUDA tensor), read by

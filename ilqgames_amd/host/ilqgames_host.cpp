@@ -455,7 +455,8 @@ class Packer {
 }  // namespace
 
 bool ResolveInstanceParams(const ProblemDescription& description, const InstanceParams& params,
-                           std::vector<ilqg_instance_param>* out, std::string* why, std::vector<int32_t>* subsystems_out) {
+                           std::vector<ilqg_instance_param>* out, std::string* why, std::vector<int32_t>* subsystems_out,
+                           std::vector<int32_t>* routes_out) {
   std::string scratch;
   if (why == nullptr) why = &scratch;
   out->clear();
@@ -490,6 +491,39 @@ bool ResolveInstanceParams(const ProblemDescription& description, const Instance
       return false;
     }
     subsystems_out->push_back(row);
+  }
+  if (routes_out != nullptr) routes_out->clear();
+  if (!params.route_polylines.empty() && routes_out == nullptr) {
+    *why = "instance parameters name routes, the caller takes none";
+    return false;
+  }
+  const int num_polylines = static_cast<int>(description.polyline_offsets.size()) - 1;
+  for (size_t c = 0; c < params.route_polylines.size(); c++) {
+    int polyline = params.route_polylines[c].polyline;
+    if (params.route_polylines[c].object != nullptr) {
+      // (the costs copied their polylines and the flattener interned them by content: so is this one found)
+      std::vector<float> flat;
+      for (const auto& p : params.route_polylines[c].object->Points()) {
+        flat.push_back(p.x());
+        flat.push_back(p.y());
+      }
+      polyline = -1;
+      for (int q = 0; q < num_polylines && polyline < 0; q++) {
+        const int b = description.polyline_offsets[q], e = description.polyline_offsets[q + 1];
+        if (static_cast<size_t>(2 * (e - b)) == flat.size() &&
+            std::equal(flat.begin(), flat.end(), description.polyline_points.begin() + 2 * b))
+          polyline = q;
+      }
+      if (polyline < 0) {
+        *why = "instance route " + std::to_string(c) + " names an object that is no polyline of the problem";
+        return false;
+      }
+    } else if (polyline < 0 || polyline >= num_polylines) {
+      *why = "instance route " + std::to_string(c) + " names polyline " + std::to_string(polyline) + ", the problem has " +
+             std::to_string(num_polylines < 0 ? 0 : num_polylines) + " polylines";
+      return false;
+    }
+    routes_out->push_back(polyline);
   }
   return true;
 }
@@ -915,6 +949,8 @@ class DeviceSolve {
       (void)ilqg_problem_bind_instance_values(handle, 0, nullptr);
       (void)ilqg_problem_declare_instance_params(handle, 0, nullptr);
       (void)ilqg_problem_declare_instance_subsystem_params(handle, 0, nullptr);
+      (void)ilqg_problem_bind_instance_routes(handle, 0, nullptr, nullptr);
+      (void)ilqg_problem_declare_instance_routes(handle, 0, nullptr);
     }
     ilqg_problem* handle;
     bool bound = false;
@@ -958,25 +994,43 @@ class DeviceSolve {
     CHECK_GT(B, 0);
     // per-instance cost parameters: rows [first_row, first_row + B) of the caller's table, bound for this solve only
     InstanceBinding binding(handle_);
-    if (instance_params != nullptr && !(instance_params->params.empty() && instance_params->subsystems.empty())) {
+    if (instance_params != nullptr && !(instance_params->params.empty() && instance_params->subsystems.empty() &&
+                                        instance_params->route_polylines.empty())) {
       std::vector<ilqg_instance_param> declared;
-      std::vector<int32_t> rows_declared;
+      std::vector<int32_t> rows_declared, routes_declared;
       std::string why;
-      CHECK(ResolveInstanceParams(description_, *instance_params, &declared, &why, &rows_declared)) << why;
-      const size_t count = declared.size() + rows_declared.size();  // [cost params | subsystem params]
-      CHECK_GE(instance_params->values.size(), (first_row + B) * count) << "instance parameter values: one row per instance";
-      CHECK_EQ(ilqg_problem_declare_instance_params(handle_, static_cast<int32_t>(declared.size()), declared.data()), ILQG_OK)
-          << ilqg_last_error();
-      CHECK_EQ(ilqg_problem_declare_instance_subsystem_params(handle_, static_cast<int32_t>(rows_declared.size()),
-                                                              rows_declared.data()), ILQG_OK)
-          << ilqg_last_error();
-      const float* rows = instance_params->values.data() + first_row * count;
-      HipCheck(hipMemcpy(d_instance_values_.Reserve(B * count * sizeof(float)), rows, B * count * sizeof(float),
-                         hipMemcpyHostToDevice), "instance parameter values");
-      CHECK_EQ(ilqg_problem_bind_instance_values(handle_, static_cast<int32_t>(B),
-                                                 static_cast<const float*>(d_instance_values_.get())), ILQG_OK)
-          << ilqg_last_error();
+      CHECK(ResolveInstanceParams(description_, *instance_params, &declared, &why, &rows_declared, &routes_declared)) << why;
       binding.bound = true;
+      const size_t count = declared.size() + rows_declared.size();  // [cost params | subsystem params]
+      if (count > 0) {
+        CHECK_GE(instance_params->values.size(), (first_row + B) * count) << "instance parameter values: one row per instance";
+        CHECK_EQ(ilqg_problem_declare_instance_params(handle_, static_cast<int32_t>(declared.size()), declared.data()), ILQG_OK)
+            << ilqg_last_error();
+        CHECK_EQ(ilqg_problem_declare_instance_subsystem_params(handle_, static_cast<int32_t>(rows_declared.size()),
+                                                                rows_declared.data()), ILQG_OK)
+            << ilqg_last_error();
+        const float* rows = instance_params->values.data() + first_row * count;
+        HipCheck(hipMemcpy(d_instance_values_.Reserve(B * count * sizeof(float)), rows, B * count * sizeof(float),
+                           hipMemcpyHostToDevice), "instance parameter values");
+        CHECK_EQ(ilqg_problem_bind_instance_values(handle_, static_cast<int32_t>(B),
+                                                   static_cast<const float*>(d_instance_values_.get())), ILQG_OK)
+            << ilqg_last_error();
+      }
+      if (!routes_declared.empty()) {  // rows [first_row, first_row + B) of the caller's points, consumed by the bind
+        size_t row_floats = 0;
+        for (int32_t q : routes_declared)
+          row_floats += 2 * static_cast<size_t>(description_.polyline_offsets[q + 1] - description_.polyline_offsets[q]);
+        CHECK_GE(instance_params->routes.size(), (first_row + B) * row_floats) << "instance routes: one row per instance";
+        CHECK_EQ(ilqg_problem_declare_instance_routes(handle_, static_cast<int32_t>(routes_declared.size()),
+                                                      routes_declared.data()), ILQG_OK)
+            << ilqg_last_error();
+        const float* rows = instance_params->routes.data() + first_row * row_floats;
+        HipCheck(hipMemcpy(d_instance_routes_.Reserve(B * row_floats * sizeof(float)), rows, B * row_floats * sizeof(float),
+                           hipMemcpyHostToDevice), "instance routes");
+        CHECK_EQ(ilqg_problem_bind_instance_routes(handle_, static_cast<int32_t>(B),
+                                                   static_cast<const float*>(d_instance_routes_.get()), nullptr), ILQG_OK)
+            << ilqg_last_error();
+      }
     }
     const auto start = Clock::now();
     // pack the warm start once, replicate per instance
@@ -1174,7 +1228,7 @@ class DeviceSolve {
   int n_ = 0, m_ = 0, N_ = 0, T_ = 0;
   std::vector<int> udims_;
   bool solved_single_ = false, last_kind_ = false;
-  DeviceBuffer d_x0_, d_xs_, d_us_, d_P_, d_alpha_, d_costs_, d_iters_, d_status_, d_conv_, d_workspace_, d_instance_values_;
+  DeviceBuffer d_x0_, d_xs_, d_us_, d_P_, d_alpha_, d_costs_, d_iters_, d_status_, d_conv_, d_workspace_, d_instance_values_, d_instance_routes_;
   DeviceBuffer d_log_xs_, d_log_us_, d_log_costs_, d_log_P_, d_log_alpha_, d_log_count_;
 };
 

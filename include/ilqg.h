@@ -394,6 +394,33 @@ ilqg_status ilqg_problem_declare_instance_subsystem_params(ilqg_problem* p, int3
  * the handle's to check). */
 ilqg_status ilqg_instance_subsystem_params_check(const ilqg_problem_desc* desc, int32_t count, const int32_t* subsystems);
 
+/* Per-instance ROUTES: the points of the declared polylines of the descriptor — lanes, boundaries, the polygon of a
+ * signed-distance term — vary per instance — the same intersection with the turn lane bent differently in every game of
+ * a batch.  Only the coordinates vary: instance b's polyline q has the descriptor's number of points.  The row program,
+ * the static structure it matched and every scheduling choice are those of the descriptor.
+ *   declare   polylines[c] indexes the descriptor's polylines.  An index out of range, the same polyline twice, or a
+ *             polyline a ROUTE_PROGRESS term refers to (its per-step nominals are tabulated from the baked polyline by
+ *             ilqg_problem_create) is ILQG_ERR_UNSUPPORTED with the polyline (and the term) named in ilqg_last_error().
+ *             count = 0 clears the declaration.  ILQG_ERR_INVALID while a route table is bound (unbind first).
+ *   bind      points: device float [batch][P][2], P the sum of the declared polylines' point counts in declaration order;
+ *             row b holds instance b's points.  NULL unbinds.  ILQG_ERR_INVALID without a declaration or with batch <= 0.
+ * THE POINTS ARE CONSUMED BY THE BIND CALL, unlike the value table, which is read at every call: the call builds, on
+ * `stream`, a table the handle owns — every instance's segments with their derived scalars, batch * total segments * 21
+ * elements in the problem's precision, allocated here and freed at unbind or ilqg_problem_destroy — and later calls read
+ * that table, not `points`.  A caller who rewrites the points binds again (a table of the same batch is rewritten in
+ * place); later calls on the handle must run in stream order after the bind.  `points` may be released once the bind has
+ * run on its stream.
+ * Independent of ilqg_problem_bind_instance_values: either, both or neither may be bound, in any order; when both are
+ * bound their batches must agree (ILQG_ERR_INVALID from the second bind).  The calls that evaluate costs (the list
+ * above: the solves, quadraticize, total_costs, strategy costs, both Nash checks) read the table and return
+ * ILQG_ERR_INVALID before any launch when their `batch` is not the bound one; the others ignore a route binding.
+ * An instance computes, bit for bit, what a problem created with its points in the descriptor computes.  COORDINATES ARE
+ * NOT VALIDATED: a zero-length segment gives what a descriptor with one gives. */
+ilqg_status ilqg_problem_declare_instance_routes(ilqg_problem* p, int32_t count, const int32_t* polylines);
+ilqg_status ilqg_problem_bind_instance_routes(ilqg_problem* p, int32_t batch, const float* points, void* stream);
+/* Host only, no device needed: the checks of the declare call against a descriptor. */
+ilqg_status ilqg_instance_routes_check(const ilqg_problem_desc* desc, int32_t count, const int32_t* polylines);
+
 /* Bytes of device workspace a solve of `batch` instances needs: the per-instance iterates, linearisations and
  * loop states, the lists of back-tracking instances and the pool of the speculative line search.  A solve
  * allocates nothing. */
@@ -615,6 +642,12 @@ ilqg_status ilqg_problem_row_program(const ilqg_problem* p, int32_t* words_out, 
  * it uploads tables, without a device (the one entry point that works without one). */
 ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words_out, int32_t capacity, int32_t* num_words,
                                    int32_t* static_id);
+/* Host only, no device needed: the segment table ilqg_problem_create builds from the descriptor's polylines — per segment,
+ * in polyline order, 21 scalars [p1x p1y p2x p2y length ux uy | the shortcut prev.p1 -> p2 | the shortcut p1 -> next.p2] in
+ * the arithmetic of `dtype` (ILQG_F32 / ILQG_F64).  This is also the layout of one instance's block of a per-instance
+ * route table.  *num_elems is the element count; out may be NULL to query it. */
+ilqg_status ilqg_segment_table_build(const ilqg_problem_desc* desc, int32_t dtype, void* out, int32_t capacity,
+                                     int32_t* num_elems);
 
 /* Replaces AugmentedLagrangianSolver::Solve (src/augmented_lagrangian_solver.cpp:72-210) with
  * max_runtime = infinity: inner ilqg_ilq_solve_batch calls capped at
@@ -765,7 +798,9 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
                                  ilqg_problem_bind_instance_values, ilqg_instance_params_check); still 9:
                                  per-instance subsystem parameters (ilqg_problem_declare_instance_subsystem_params,
                                  ilqg_instance_subsystem_params_check: two new calls, the table gains columns); still 9:
-                                 ilqg_solve_options::sweep_forms (was reserved2 = 0 = AUTO: no layout or behaviour change);
+                                 ilqg_solve_options::sweep_forms (was reserved2 = 0 = AUTO: no layout or behaviour change); still 9:
+                                 per-instance routes (ilqg_problem_declare_instance_routes, ilqg_problem_bind_instance_routes,
+                                 ilqg_instance_routes_check, and the host-only ilqg_segment_table_build: four new calls);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;

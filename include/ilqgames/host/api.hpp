@@ -1080,15 +1080,31 @@ struct InstanceParams {
   void AddSubsystem(const SinglePlayerDynamicalSystem* subsystem) { subsystems.push_back(Subsystem{subsystem, -1}); }
   void AddSubsystem(const std::shared_ptr<const SinglePlayerDynamicalSystem>& subsystem) { AddSubsystem(subsystem.get()); }
   void AddSubsystem(int row) { subsystems.push_back(Subsystem{nullptr, row}); }
+  // Per-instance ROUTES (ilqg_problem_declare_instance_routes): polylines of the Problem whose points vary per instance —
+  // named by the address of a Polyline2 the caller built a cost from, or by the polyline's index in the descriptor.  A cost
+  // keeps its own copy of its polyline and the flattener interns polylines by their vertex lists, so the object named by
+  // address is found by its vertex list.  `routes` sits beside `values`: one row per instance,
+  // [x0s.size()][P][2] floats, P the named polylines' point counts summed in the order they were added.
+  struct Route {
+    const Polyline2* object;  // or null:
+    int polyline;             // ... an index into the descriptor's polylines
+  };
+  std::vector<Route> route_polylines;
+  std::vector<float> routes;
+  void AddRoute(const Polyline2* polyline) { route_polylines.push_back(Route{polyline, -1}); }
+  void AddRoute(int polyline) { route_polylines.push_back(Route{nullptr, polyline}); }
 };
 // The (term index, field) list of `params` in `description` (what ilqg_problem_declare_instance_params takes).
 // Returns false and sets *why when an object is not a term of the description.
 // `subsystems_out`: the rows of params.subsystems (what ilqg_problem_declare_instance_subsystem_params takes); also
 // false when an object is no subsystem of the description, a row is out of range, or subsystems are named and
 // subsystems_out is null (nothing is silently ignored).
+// `routes_out`: the descriptor's polylines of params.route_polylines (what ilqg_problem_declare_instance_routes takes),
+// under the same rules: false for an object that is no polyline of the description, an index out of range, or routes
+// named to a caller that takes none.
 bool ResolveInstanceParams(const ProblemDescription& description, const InstanceParams& params,
                            std::vector<ilqg_instance_param>* out, std::string* why,
-                           std::vector<int32_t>* subsystems_out = nullptr);
+                           std::vector<int32_t>* subsystems_out = nullptr, std::vector<int32_t>* routes_out = nullptr);
 
 // Walks Problem::Dynamics() and Problem::PlayerCosts() (after Initialize()) and fills the POD
 // descriptor of include/ilqg.h.  Returns false and sets *why when some object has no device kernel.

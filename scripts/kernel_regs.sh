@@ -1,5 +1,5 @@
 #!/bin/bash
-# Registers / LDS / scratch of the device kernels of one (n, N, m_i) instantiation:  scripts/kernel_regs.sh 24 4 2 [pattern]
+# Registers / scratch / static LDS of the device kernels of one (n, N, m_i) instantiation:  scripts/kernel_regs.sh 24 4 2 [pattern]
 # (also leaves the device assembly in /tmp/ilqg_regs_<n>_<N>_<mu>/dev.s)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -13,8 +13,9 @@ txt = open(sys.argv[1]).read()
 pat = re.compile(sys.argv[2], re.I)
 for blk in re.split(r"\n  - \.agpr_count:", txt)[1:]:
     blk = ".agpr_count:" + blk
-    f = dict(re.findall(r"\.(agpr_count|name|vgpr_count|sgpr_count|vgpr_spill_count|private_segment_fixed_size|max_flat_workgroup_size):\s+(\S+)", blk))
+    f = dict(re.findall(r"\.(agpr_count|name|vgpr_count|sgpr_count|vgpr_spill_count|private_segment_fixed_size|group_segment_fixed_size|max_flat_workgroup_size):\s+(\S+)", blk))
     if "name" in f and pat.search(f["name"]):
-        print("vgpr %4s agpr %4s sgpr %4s spill %4s scratch %5s wg %5s  %s" % (f.get("vgpr_count"), f.get("agpr_count"), f.get("sgpr_count"),
-              f.get("vgpr_spill_count"), f.get("private_segment_fixed_size"), f.get("max_flat_workgroup_size"), f["name"][:150]))
+        print("vgpr %4s agpr %4s sgpr %4s spill %4s scratch %5s lds %6s wg %5s  %s" % (f.get("vgpr_count"), f.get("agpr_count"), f.get("sgpr_count"),
+              f.get("vgpr_spill_count"), f.get("private_segment_fixed_size"), f.get("group_segment_fixed_size"),
+              f.get("max_flat_workgroup_size"), f["name"][:150]))
 PY

@@ -18,7 +18,12 @@ the mean number of rejected step sizes per instance in the last iteration of (a)
 unbound; bound with every row the baked 4.0; bound with one wheelbase pair per instance drawn from [2.5, 5.0]; one problem
 per pair (V pairs, V solves of B / V instances).
 
-Prints one JSON line: iterations/s of each.   python scripts/param_sweep_bench.py [--batch 1024] [--repeats 5] [--vectors 16] [--subsystems]"""
+--routes: the same four legs for per-instance ROUTES — the three bend points of player 2's turn lane displaced by up to
+1 m over V distinct layouts (instance b plays layout b % V): unbound; bound with every row the baked lane; bound with the V
+layouts; the same V layouts as V problems solved one after another, B / V instances each.
+
+Prints one JSON line: iterations/s of each.
+python scripts/param_sweep_bench.py [--batch 1024] [--repeats 5] [--vectors 16] [--subsystems | --routes]"""
 import argparse
 import copy
 import json
@@ -44,6 +49,7 @@ def main():
     ap.add_argument("--vectors", type=int, default=16)
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
     ap.add_argument("--subsystems", action="store_true", help="the wheelbases of the two cars instead of cost parameters")
+    ap.add_argument("--routes", action="store_true", help="the bend of player 2's turn lane instead of cost parameters")
     args = ap.parse_args()
     import torch
     from ilqgames_amd import abi, examples, hip
@@ -77,6 +83,35 @@ def main():
             if rep > 0:
                 times.append(e0.elapsed_time(e1) * 1e-3)
         return float(np.median(times))
+
+    if args.routes:
+        lane, bend = 1, [2, 3, 4]  # examples.py: lane2 and its three bend points
+        baked = np.array(spec.polylines[lane], dtype=np.float32)
+        layouts = np.tile(baked, (V, 1, 1))
+        layouts[:, bend] += (2.0 * rng.random((V, len(bend), 2)) - 1.0).astype(np.float32)
+        assert len({l.tobytes() for l in layouts}) == V
+        which = np.arange(B) % V
+        prob = hip.Problem(spec, dtype)
+        bufs = prob.alloc_solve_buffers(B)
+        out = dict(batch=B, iters=K, dtype=args.dtype, routes=[lane], layouts=V)
+        out["unbound_its"] = B * K / timed([(prob, x0, bufs)])
+        prob.declare_instance_routes([lane])
+        prob.bind_instance_routes(np.tile(baked, (B, 1, 1)))
+        out["bound_identity_its"] = B * K / timed([(prob, x0, bufs)])
+        prob.bind_instance_routes(layouts[which])
+        out["bound_layouts_its"] = B * K / timed([(prob, x0, bufs)])
+        out["bound_layouts_backtracks"] = float(prob.solve_state(bufs)["backtracks"].float().mean().item())
+        prob.bind_instance_routes(None)
+        solves = []
+        for v in range(V):
+            s = copy.deepcopy(spec)
+            s.polylines[lane] = [(float(x), float(y)) for x, y in layouts[v]]
+            p = hip.Problem(s, dtype)
+            sel = torch.as_tensor(np.nonzero(which == v)[0], device="cuda")
+            solves.append((p, x0[sel].contiguous(), p.alloc_solve_buffers(len(sel))))
+        out["per_layout_problems_its"] = B * K / timed(solves)
+        print(json.dumps(out))
+        return
 
     if args.subsystems:
         rows = [0, 1]
