@@ -257,6 +257,7 @@ __device__ __forceinline__ QuadArgs<T> quad_args_of(const DevProblem& p, const Q
   a.cost_part = g.cost_part ? g.cost_part + b * Tn * N : nullptr;
   a.iv = instance_values(p, int(b));
   a.seg_off = instance_segs_offset(p, int(b));
+  a.tnom_off = instance_tnom_offset(p, int(b));
   return a;
 }
 
@@ -1541,7 +1542,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
     sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), budget);
   }
   // (a problem with per-instance parameters bound runs fused kernels of its own, here and below: ilqg_solve.hpp)
-  auto k_trial = (d.inst_values || d.seg_inst_stride) ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
+  auto k_trial = (d.inst_values || d.seg_inst_stride || d.tnom_inst_stride) ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
   const bool pw = C::USE_MFMA && !open_loop;  // one wave per player (MFMA feedback sweep)
   // Compact rows (ilqg_common.hpp) between the row stage and the sweep: the one-tile player-parallel sweep and the
   // open-loop sweep read them; the other sweeps take the dense arrays.  What the row stage writes and the sweep reads
@@ -1568,7 +1569,8 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
       if (p->static_prog == ID_) {                                                                             \
         static_id = ID_;                                                                                       \
         static_in_regs = static_prog_in_registers<StaticRowProg<ID_>>();                                       \
-        const bool bound = d.inst_values != nullptr || d.seg_inst_stride != 0; /* kernels of their own */        \
+        const bool bound = d.inst_values != nullptr || d.seg_inst_stride != 0; /* kernels of their own (no        \
+           registered structure holds a time-dependent term: a table of time nominals never gets here) */      \
         k_rows = bound ? ilq_rows_kernel<T, NX, NP, MU, kBoundProg + ID_> : ilq_rows_kernel<T, NX, NP, MU, ID_>; \
         k_prows = bound ? ilq_probe_rows_kernel<T, NX, NP, MU, kBoundProg + ID_>                               \
                         : ilq_probe_rows_kernel<T, NX, NP, MU, ID_>;                                           \
@@ -1974,6 +1976,23 @@ __global__ void __launch_bounds__(256) route_segments_kernel(const int* poly_off
   for (int e = 0; e < kSegStride; e++) o[e] = baked[size_t(s) * kSegStride + e];
 }
 
+// Per-instance time nominals (ilqg_instance_time_nominals_build): [batch][tables][T][2] doubles in the layout of
+// DevProblem::time_nominal_f / _d per instance.  One lane per (instance, table, step): what build_time_nominals tabulates
+// for a descriptor whose term has the instance's (nominal speed, initial route position) — the host builder's own
+// function (ilqg_time_nominal.hpp: the same roundings) on the baked segment table of precision S.  `tables`: per table
+// (term, 1: a route, the polyline's first segment, its segments).
+template <typename S>
+__global__ void __launch_bounds__(256) time_nominals_kernel(const int* tables, int num_tables, int T, double dt,
+                                                            const float* speed_pos, const S* segs, int batch, double* out) {
+  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (gid >= size_t(batch) * size_t(num_tables) * size_t(T)) return;
+  const size_t bq = gid / size_t(T);  // (instance, table): a row of speed_pos
+  const int k = int(gid - bq * size_t(T));
+  const int* tab = tables + 4 * (bq % size_t(num_tables));
+  time_nominal<S>(tab[1] != 0, speed_pos[2 * bq], speed_pos[2 * bq + 1], k, dt, segs + size_t(tab[2]) * kSegStride, tab[3],
+                  out + 2 * gid);
+}
+
 extern "C" {
 
 const char* ilqg_last_error(void) { return g_err.c_str(); }
@@ -2199,6 +2218,24 @@ ilqg_status ilqg_segment_table_build(const ilqg_problem_desc* desc, int32_t dtyp
   return ILQG_OK;
 }
 
+// The host half of creation alone, for the per-step nominals of the time-dependent costs (DevProblem::time_nominal_f /
+// time_nominal_d: [tables][T][2] doubles in the geometry precision of `dtype`)
+ilqg_status ilqg_time_nominal_table_build(const ilqg_problem_desc* desc, int32_t dtype, double* out, int32_t capacity,
+                                          int32_t* num_elems) {
+  if (!num_elems || !desc) return fail(ILQG_ERR_INVALID, "null argument");
+  if (dtype != ILQG_F32 && dtype != ILQG_F64) return fail(ILQG_ERR_INVALID, "ilqg_time_nominal_table_build: dtype");
+  ProblemTables tables;
+  const ilqg_status s = build_problem_tables(*desc, &tables);
+  if (s != ILQG_OK) return s;
+  const std::vector<double>& table = dtype == ILQG_F32 ? tables.time_nominal.f : tables.time_nominal.d;
+  *num_elems = int32_t(table.size());
+  if (out) {
+    if (capacity < *num_elems) return fail(ILQG_ERR_INVALID, "ilqg_time_nominal_table_build: buffer too small");
+    if (!table.empty()) std::memcpy(out, table.data(), sizeof(double) * table.size());
+  }
+  return ILQG_OK;
+}
+
 void ilqg_problem_destroy(ilqg_problem* p) { delete p; }
 
 // ---- per-instance cost parameters (ilqg.h) ----
@@ -2251,6 +2288,9 @@ ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, co
   if (p->route_batch && batch != p->route_batch)
     return fail(ILQG_ERR_INVALID, "instance parameter values: per-instance routes are bound for a batch of " +
                                       std::to_string(p->route_batch) + ", these values are for " + std::to_string(batch));
+  if (p->tnom_batch && batch != p->tnom_batch)
+    return fail(ILQG_ERR_INVALID, "instance parameter values: per-instance time nominals are bound for a batch of " +
+                                      std::to_string(p->tnom_batch) + ", these values are for " + std::to_string(batch));
   d.inst_values = values;
   d.inst_terms = p->d_inst_terms.get();
   d.inst_count = int(p->inst_params.size() + p->inst_subs.size());
@@ -2305,6 +2345,9 @@ ilqg_status ilqg_problem_bind_instance_routes(ilqg_problem* p, int32_t batch, co
   if (d.inst_values && batch != p->inst_batch)
     return fail(ILQG_ERR_INVALID, "instance routes: per-instance parameter values are bound for a batch of " +
                                       std::to_string(p->inst_batch) + ", these routes are for " + std::to_string(batch));
+  if (p->tnom_batch && batch != p->tnom_batch)
+    return fail(ILQG_ERR_INVALID, "instance routes: per-instance time nominals are bound for a batch of " +
+                                      std::to_string(p->tnom_batch) + ", these routes are for " + std::to_string(batch));
   const size_t count = size_t(batch) * size_t(d.total_segs);
   const bool f32 = p->desc.dtype == ILQG_F32;
   if (batch != p->route_batch) {  // a new table; one of the same size is rewritten in place, in stream order
@@ -2330,6 +2373,66 @@ ilqg_status ilqg_problem_bind_instance_routes(ilqg_problem* p, int32_t batch, co
   if (f32) d.segs_f = p->d_route_segs_f.get(); else d.segs_d = p->d_route_segs_d.get();
   d.seg_inst_stride = d.total_segs * kSegStride;
   p->route_batch = batch;
+  return ILQG_OK;
+}
+
+// ---- per-instance time nominals (ilqg.h) ----
+ilqg_status ilqg_problem_time_nominal_terms(const ilqg_problem* p, int32_t* terms_out, int32_t capacity, int32_t* tables) {
+  if (!p || !tables) return fail(ILQG_ERR_INVALID, "null argument");
+  *tables = int32_t(p->tnom_tables.size() / 4);
+  if (terms_out) {
+    if (capacity < *tables) return fail(ILQG_ERR_INVALID, "ilqg_problem_time_nominal_terms: buffer too small");
+    for (int q = 0; q < *tables; q++) terms_out[q] = p->tnom_tables[size_t(4) * q];
+  }
+  return ILQG_OK;
+}
+
+ilqg_status ilqg_problem_bind_instance_time_nominals(ilqg_problem* p, int32_t batch, const double* nominals) {
+  if (!p) return fail(ILQG_ERR_INVALID, "null argument");
+  DevProblem& d = p->dev;
+  if (!nominals) {
+    d.time_nominal_f = p->d_time_nominal.f.get();
+    d.time_nominal_d = p->d_time_nominal.d.get();
+    d.tnom_inst_stride = 0;
+    p->tnom_batch = 0;
+    return ILQG_OK;
+  }
+  if (p->tnom_tables.empty())
+    return fail(ILQG_ERR_INVALID, "instance time nominals: the problem has no time-dependent term (NOMINAL_PATH_LENGTH, "
+                                  "ROUTE_PROGRESS)");
+  if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance time nominals: batch must be positive");
+  if (d.inst_values && batch != p->inst_batch)
+    return fail(ILQG_ERR_INVALID, "instance time nominals: per-instance parameter values are bound for a batch of " +
+                                      std::to_string(p->inst_batch) + ", these nominals are for " + std::to_string(batch));
+  if (p->route_batch && batch != p->route_batch)
+    return fail(ILQG_ERR_INVALID, "instance time nominals: per-instance routes are bound for a batch of " +
+                                      std::to_string(p->route_batch) + ", these nominals are for " + std::to_string(batch));
+  // (the handle's precision: the other pointer is not read)
+  if (p->desc.dtype == ILQG_F32) d.time_nominal_f = nominals; else d.time_nominal_d = nominals;
+  d.tnom_inst_stride = int(p->tnom_tables.size() / 4) * d.T * 2;
+  p->tnom_batch = batch;
+  return ILQG_OK;
+}
+
+ilqg_status ilqg_instance_time_nominals_build(const ilqg_problem* p, int32_t batch, const float* speed_pos, double* nominals,
+                                              void* stream) {
+  if (!p || !speed_pos || !nominals) return fail(ILQG_ERR_INVALID, "null argument");
+  if (p->tnom_tables.empty())
+    return fail(ILQG_ERR_INVALID, "instance time nominals: the problem has no time-dependent term (NOMINAL_PATH_LENGTH, "
+                                  "ROUTE_PROGRESS)");
+  if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance time nominals: batch must be positive");
+  const DevProblem& d = p->dev;
+  const int num_tables = int(p->tnom_tables.size() / 4);
+  const size_t count = size_t(batch) * size_t(num_tables) * size_t(d.T);
+  const dim3 grid((unsigned)((count + 255) / 256));
+  // the BAKED segment table (a ROUTE_PROGRESS term's polyline never varies per instance), in the handle's precision
+  if (p->desc.dtype == ILQG_F32)
+    hipLaunchKernelGGL(time_nominals_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, p->d_tnom_tables.get(),
+                       num_tables, d.T, d.dt, speed_pos, p->d_segs.f.get(), batch, nominals);
+  else
+    hipLaunchKernelGGL(time_nominals_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, p->d_tnom_tables.get(),
+                       num_tables, d.T, d.dt, speed_pos, p->d_segs.d.get(), batch, nominals);
+  HIP_TRY(hipGetLastError());
   return ILQG_OK;
 }
 
@@ -2645,6 +2748,10 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
     if (p->dev.seg_inst_stride) {  // (the handle's precision: the other pointer is not read)
       full.segs_f = p->dev.segs_f + size_t(b0) * p->dev.seg_inst_stride;
       full.segs_d = p->dev.segs_d + size_t(b0) * p->dev.seg_inst_stride;
+    }
+    if (p->dev.tnom_inst_stride) {
+      if (p->desc.dtype == ILQG_F32) full.time_nominal_f = p->dev.time_nominal_f + size_t(b0) * p->dev.tnom_inst_stride;
+      else full.time_nominal_d = p->dev.time_nominal_d + size_t(b0) * p->dev.tnom_inst_stride;
     }
     s = launch_linquad(p, full, nb, xs_c, us_c, nullptr, nullptr, nullptr, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
                        nullptr, stream);

@@ -72,6 +72,10 @@ struct DevProblem {
   const float* segs_f;
   const double* segs_d;
   int total_segs;
+  // Per-instance time nominals (ilqg_problem_bind_instance_time_nominals): while a table is bound time_nominal_f / _d (the
+  // handle's precision) points at the caller's [batch][tables][T][2] table and this is tables * T * 2, the elements
+  // between two instances' blocks; 0: every instance reads the one baked table.  (In the padding before the pointers.)
+  int tnom_inst_stride;
   // Per-step nominals of the time-dependent costs (NominalPathLengthCost: t_k * speed; RouteProgressCost: the route
   // point at pos0 + t_k * speed), [table][T][2] doubles, one copy per geometry precision; DevTerm::polyline of such a
   // term is its table.  Tabulated by ilqg_problem_create.
@@ -162,6 +166,12 @@ template <> __device__ __forceinline__ const double* problem_dense<double>(const
 template <typename T> __device__ __forceinline__ const double* problem_time_nominal(const DevProblem& p);
 template <> __device__ __forceinline__ const double* problem_time_nominal<float>(const DevProblem& p) { return p.time_nominal_f; }
 template <> __device__ __forceinline__ const double* problem_time_nominal<double>(const DevProblem& p) { return p.time_nominal_d; }
+// Where instance b's block starts behind problem_time_nominal (0 with no table of time nominals bound); b as in
+// instance_segs_offset.  Only the pointer of the handle's own precision is redirected to a bound table: add this to
+// problem_time_nominal<T> for the handle's T alone, the other precision's pointer stays the baked shared table.
+__device__ __forceinline__ size_t instance_tnom_offset(const DevProblem& p, int b) {
+  return size_t(unsigned(__builtin_amdgcn_readfirstlane(b))) * size_t(unsigned(p.tnom_inst_stride));
+}
 
 // user priority 0..3 of the calling wave (s_setprio takes an immediate)
 __device__ __forceinline__ void set_wave_prio(int pr) {

@@ -16,8 +16,13 @@
 #include "ilqg_rowprog_static.hpp"  // the registered structures
 #include "ilqg_segment.hpp"         // line_segment2: the segment table's arithmetic
 #include "ilqg_stages.hpp"          // DevProblem, the models, dims_use_plain_rk4
+#include "ilqg_time_nominal.hpp"    // time_nominal: the per-step nominals' arithmetic
 
 namespace ilqg {
+
+// build_time_nominals and time_nominals_kernel step to a polyline's first segment by kSegStride; the shared function then
+// strides by its own constant (ilqg_time_nominal.hpp includes no device header): one layout
+static_assert(kTimeNominalSegStride == kSegStride, "ilqg_time_nominal.hpp and ilqg_common.hpp disagree on a segment's scalars");
 
 // LoopTimer (include/ilqgames/utils/loop_timer.h:60-98, src/loop_timer.cpp:55-92): the last ten iteration times
 struct LoopTimer {
@@ -90,6 +95,12 @@ struct ilqg_problem {
   ilqg::DeviceBuffer<float> d_route_segs_f;
   ilqg::DeviceBuffer<double> d_route_segs_d;
   int route_batch = 0;
+  // Per-instance time nominals (ilqg.h): per table of the time-dependent costs (its term, 1: a route, its polyline's first
+  // segment, segments), the device copy time_nominals_kernel reads, and while a table is bound (dev.time_nominal_f / _d
+  // points at the caller's, dev.tnom_inst_stride is set) its batch
+  std::vector<int> tnom_tables;
+  ilqg::DeviceBuffer<int> d_tnom_tables;
+  int tnom_batch = 0;
   int static_prog = 0;                // id of the registered structure it matches (ilqg_rowprog_static.hpp), 0: none
   ilqg::DeviceBuffer<int> d_unfinished;  // instances still running after an LQ-kernel launch
   ilqg::PinnedInts h_unfinished;  // pinned host mirror: [0..3] the counters, [8] the sequence number of read_round_counters
@@ -158,6 +169,7 @@ struct ProblemTables {
   BothPrecisions<float, double> segs;           // DevProblem::segs_f / segs_d
   BothPrecisions<float, double> dense;          // DevProblem::dense_f / dense_d
   BothPrecisions<double, double> time_nominal;  // DevProblem::time_nominal_f / time_nominal_d
+  std::vector<int> tnom_tables;  // per table of time_nominal: (its term, 1: a route, its polyline's first segment, segments)
   std::vector<int> cost_order;
   RowProgramHost row_prog;
   int static_prog = 0;  // id of the registered structure the program matches (ilqg_rowprog_static.hpp), 0: none
@@ -339,24 +351,6 @@ ilqg_status build_segments(const ilqg_problem_desc& desc, ProblemTables* t) {
   return ILQG_OK;
 }
 
-// Polyline2::PointAt (src/polyline2.cpp:68-103) on the segment table of one precision: walks the cumulative lengths
-template <class S>
-void polyline_point_at(const ilqg_problem_desc& desc, int polyline, const std::vector<S>& segs, S route_pos, double* px,
-                       double* py) {
-  const int first = desc.polyline_offsets[polyline] - polyline;
-  const int nseg = desc.polyline_offsets[polyline + 1] - desc.polyline_offsets[polyline] - 1;
-  std::vector<S> cumulative(1, S(0));
-  for (int c = 0; c < nseg; c++) cumulative.push_back(cumulative.back() + segs[size_t(first + c) * kSegStride + 4]);
-  auto upper = std::upper_bound(cumulative.begin(), cumulative.end(), route_pos);
-  if (upper == cumulative.end()) upper--;
-  upper--;
-  const size_t idx = size_t(upper - cumulative.begin());
-  const S remaining = route_pos - cumulative[idx];
-  const S* sg = &segs[size_t(first + idx) * kSegStride];
-  *px = double(S(sg[0] + remaining * sg[5]));
-  *py = double(S(sg[1] + remaining * sg[6]));
-}
-
 // Per-step nominals of the time-dependent costs, one table per such term and geometry precision (doubles: the
 // path-length nominal is a double product in the reference, nominal_path_length_cost.cpp:53; the route point is a
 // pair of the geometry's scalars, exact in double).  t = RelativeTime(k) = double(k) * dt (relative_time_tracker.h:
@@ -384,19 +378,18 @@ ilqg_status build_time_nominals(const ilqg_problem_desc& desc, ProblemTables* t)
                                       "non-negative over the horizon (initial_route_pos, nominal_speed)");
       t->has_route_progress = true;
     }
+    const int first_seg = route ? desc.polyline_offsets[src_poly] - src_poly : 0;
+    const int nseg = route ? desc.polyline_offsets[src_poly + 1] - desc.polyline_offsets[src_poly] - 1 : 0;
     for (int k = 0; k < d.T; k++) {
-      const double tk = double(k) * d.dt;
-      const double pos = double(desc.terms[ti].value2) + (tk - 0.0) * double(o.value);
-      auto nominal = [&](const auto& segs, std::vector<double>& out) {
-        using S = typename std::decay<decltype(segs)>::type::value_type;
-        double x = tk * double(o.value), y = 0.0;
-        if (route) polyline_point_at(desc, src_poly, segs, S(pos), &x, &y);
-        out.push_back(x);
-        out.push_back(y);
+      auto nominal = [&](const auto& segs, std::vector<double>& out) {  // the arithmetic is ilqg_time_nominal.hpp's
+        double pair[2];
+        time_nominal(route, o.value, desc.terms[ti].value2, k, d.dt, segs.data() + size_t(first_seg) * kSegStride, nseg, pair);
+        out.insert(out.end(), pair, pair + 2);
       };
       nominal(t->segs.f, t->time_nominal.f);
       nominal(t->segs.d, t->time_nominal.d);
     }
+    t->tnom_tables.insert(t->tnom_tables.end(), {ti, route ? 1 : 0, first_seg, nseg});
     o.polyline = ntab++;
   }
   return ILQG_OK;
@@ -509,6 +502,7 @@ ilqg_status upload_problem(const ilqg_problem_desc& desc, const ProblemTables& t
   p->mu_uniform = t.mu_uniform;
   p->has_route_progress = t.has_route_progress;
   p->generic = t.generic;
+  p->tnom_tables = t.tnom_tables;
   // the row program's device image: the program, then per op the per-instance column of its weight / value (none: -1)
   std::vector<int> image = t.row_prog.words;
   image.resize(image.size() + 2 * t.row_prog.op_term.size() + 2, -1);
@@ -522,6 +516,7 @@ ilqg_status upload_problem(const ilqg_problem_desc& desc, const ProblemTables& t
   up(t.poly_pts, t.poly_pts.empty() ? 2 : 0, &p->d_poly_pts);
   up(t.segs, 1, &p->d_segs);
   up(t.time_nominal, 2, &p->d_time_nominal);
+  if (!t.tnom_tables.empty()) up(t.tnom_tables, 0, &p->d_tnom_tables);
   up(t.dense, 1, &p->d_dense);
   up(t.cost_order, 0, &p->d_cost_order);
   up(std::vector<int>(), 4, &p->d_unfinished);  // the four round counters: cleared by whoever counts
@@ -670,6 +665,9 @@ ilqg_status instance_total_check(size_t cost_count, size_t subsystem_count) {
 ilqg_status instance_batch_check(const ilqg_problem* p, int32_t batch, bool costs = true) {
   if (costs && p->route_batch && batch != p->route_batch)  // (only what evaluates costs reads a segment)
     return fail(ILQG_ERR_INVALID, "per-instance routes are bound for a batch of " + std::to_string(p->route_batch) +
+                                      ", this call has " + std::to_string(batch) + " instances");
+  if (costs && p->tnom_batch && batch != p->tnom_batch)  // (only what evaluates costs reads a nominal)
+    return fail(ILQG_ERR_INVALID, "per-instance time nominals are bound for a batch of " + std::to_string(p->tnom_batch) +
                                       ", this call has " + std::to_string(batch) + " instances");
   if (p->dev.inst_values && batch != p->inst_batch && (costs || !p->inst_subs.empty()))
     return fail(ILQG_ERR_INVALID, "per-instance parameter values are bound for a batch of " + std::to_string(p->inst_batch) +

@@ -876,7 +876,8 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
         TermOut<T> o;
         double tnom[2] = {0.0, 0.0};
         if (term_is_time_dependent(c.kind)) {  // this row's nominal; the op's RO_POLY_FIRST field is the term's table
-          const double* tn = problem_time_nominal<T>(p) + (size_t(od.template param<RO_POLY_FIRST>()) * p.T + row) * 2;
+          const double* tn = problem_time_nominal<T>(p) + (PROG::kBound ? a.tnom_off : size_t(0)) +
+                             (size_t(od.template param<RO_POLY_FIRST>()) * p.T + row) * 2;
           tnom[0] = tn[0];
           tnom[1] = tn[1];
         }

@@ -439,6 +439,7 @@ __device__ __forceinline__ QuadArgs<T> trial_quad_args(const DevProblem& p, cons
   qa.phacc = nullptr;
   qa.iv = instance_values(p, b);
   if constexpr (ROUTES) qa.seg_off = instance_segs_offset(p, b);
+  if constexpr (ROUTES) qa.tnom_off = instance_tnom_offset(p, b);
   return qa;
 }
 
@@ -607,6 +608,7 @@ __device__ __forceinline__ void probe_rows_instance(const DevProblem& p, const s
   qa.phacc = nullptr;
   qa.iv = instance_values(p, b);
   qa.seg_off = instance_segs_offset(p, b);
+  qa.tnom_off = instance_tnom_offset(p, b);
   const int k0 = chunk * sa.rows_cw;
   const int nrows = p.T - k0 < sa.rows_cw ? p.T - k0 : sa.rows_cw;
   rows_chunk<T, NX, NP * MU, NP, rows_state_in_registers(NX, NP * MU), true, typename RowProgSel<PROGID>::type>(

@@ -525,7 +525,7 @@ __device__ __forceinline__ QuadTables<T> quad_tables_load(const DevProblem& p, v
   tb.poly_off = poff;
   tb.order = order;
   tb.lc = lc;
-  tb.tnom = problem_time_nominal<T>(p);
+  tb.tnom = problem_time_nominal<T>(p) + instance_tnom_offset(p, inst);  // a bound table of time nominals: this instance's
   tb.tnom_T = p.T;
   tb.dense = problem_dense<T>(p);
   return tb;
@@ -548,6 +548,8 @@ struct QuadArgs {
   const float* iv = nullptr;  // this instance's row of the bound per-instance parameters (instance_values) or nullptr
   size_t seg_off = 0;  // this instance's segment table behind problem_segs (instance_segs_offset), 0: the baked one.  Read
                        // by the interpreter and the bound straight-line code only (rows_chunk)
+  size_t tnom_off = 0;  // this instance's block behind problem_time_nominal (instance_tnom_offset), 0: the baked table.
+                        // Read by the interpreter only: no registered straight-line program holds a time-dependent term
   long long* phacc = nullptr;  // optional phase profile accumulators (registers of the caller)
   long long* tl = nullptr;     // optional timeline stamps (ilqg_common.hpp, -DILQG_TIMELINE=1): slots 40.. of instance tl_b
   int tl_b = 0;

@@ -28,6 +28,8 @@ EXPORTS = [
     "ilqg_problem_declare_instance_subsystem_params", "ilqg_instance_subsystem_params_check",
     "ilqg_problem_declare_instance_routes", "ilqg_problem_bind_instance_routes", "ilqg_instance_routes_check",
     "ilqg_segment_table_build",
+    "ilqg_problem_bind_instance_time_nominals", "ilqg_instance_time_nominals_build", "ilqg_problem_time_nominal_terms",
+    "ilqg_time_nominal_table_build",
 ]
 
 
@@ -210,6 +212,19 @@ def segment_table(spec, dtype=abi.F64):
     return out.reshape(-1, 21)
 
 
+def time_nominal_table(spec, dtype=abi.F64):
+    """ilqg_time_nominal_table_build: the float64 [tables][T][2] per-step nominals problem creation tabulates for the spec's
+    time-dependent terms (nominal_path_length, route_progress), in dtype's geometry arithmetic — host only, no device
+    needed.  One instance's block of the table Problem.bind_instance_time_nominals binds."""
+    desc, keep = spec.build(dtype)
+    count = C.c_int32(0)
+    _check(lib().ilqg_time_nominal_table_build(C.byref(desc), dtype, None, 0, C.byref(count)))
+    out = np.zeros(count.value, dtype=np.float64)
+    _check(lib().ilqg_time_nominal_table_build(C.byref(desc), dtype, out.ctypes.data_as(C.c_void_p), count.value, C.byref(count)))
+    del keep
+    return out.reshape(-1, spec.T, 2)
+
+
 def _instance_routes(spec, polylines):
     """Polyline indices of the spec, or names given to them (ProblemSpec.polyline_names, where a scene sets it)."""
     names = getattr(spec, "polyline_names", None) or []
@@ -299,6 +314,60 @@ class Problem:
             raise ValueError("instance routes must be [batch][%d][2], got %s" % (P, tuple(points.shape)))
         _check(lib().ilqg_problem_bind_instance_routes(self.h, points.shape[0], C.c_void_p(points.data_ptr()), st))
         return points
+
+    # ---- per-instance time nominals (ilqg.h) ----
+    def time_nominal_terms(self):
+        """ilqg_problem_time_nominal_terms: the term index (in the spec) that owns table q, for every table."""
+        count = C.c_int32(0)
+        _check(lib().ilqg_problem_time_nominal_terms(self.h, None, 0, C.byref(count)))
+        arr = (C.c_int32 * max(1, count.value))()
+        _check(lib().ilqg_problem_time_nominal_terms(self.h, arr, count.value, C.byref(count)))
+        return [int(arr[q]) for q in range(count.value)]
+
+    def build_instance_time_nominals(self, speed_pos, out=None, stream=None):
+        """ilqg_instance_time_nominals_build: speed_pos is float32 [B][tables][2] = (nominal speed, initial route
+        position) (uploaded if it is not a CUDA tensor).  Returns the float64 CUDA tensor [B][tables][T][2] the kernel
+        wrote (`out`, when given, is written in place) — block b is what a problem created with those floats tabulates.
+        The result is not bound: pass it to bind_instance_time_nominals."""
+        import torch
+        st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
+        if not (isinstance(speed_pos, torch.Tensor) and speed_pos.is_cuda and speed_pos.dtype == torch.float32 and
+                speed_pos.is_contiguous()):
+            speed_pos = torch.as_tensor(np.ascontiguousarray(speed_pos, dtype=np.float32), device="cuda").contiguous()
+        tables = len(self.time_nominal_terms())
+        if speed_pos.dim() != 3 or speed_pos.shape[1] != tables or speed_pos.shape[2] != 2:
+            raise ValueError("speed_pos must be [batch][%d][2], got %s" % (tables, tuple(speed_pos.shape)))
+        B = speed_pos.shape[0]
+        if out is None:
+            out = torch.empty((B, tables, self.T, 2), dtype=torch.float64, device="cuda")
+        elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and
+                  tuple(out.shape) == (B, tables, self.T, 2)):
+            raise ValueError("out must be a contiguous CUDA float64 [%d][%d][%d][2]" % (B, tables, self.T))
+        _check(lib().ilqg_instance_time_nominals_build(self.h, B, C.c_void_p(speed_pos.data_ptr()),
+                                                       C.c_void_p(out.data_ptr()), st))
+        return out
+
+    def bind_instance_time_nominals(self, table):
+        """ilqg_problem_bind_instance_time_nominals: a float64 [B][tables][T][2] table (uploaded if it is not a CUDA
+        tensor), read by every later cost-evaluating call on this problem until bind_instance_time_nominals(None); the
+        tensor is kept alive while bound and returned — a CUDA float64 tensor passed in is bound as it is, so the caller
+        may rewrite it between calls."""
+        import torch
+        if table is None:
+            _check(lib().ilqg_problem_bind_instance_time_nominals(self.h, 0, None))
+            self._instance_time_nominals = None
+            return None
+        if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float64 and
+                table.is_contiguous()):
+            table = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float64), device="cuda").contiguous()
+        if table.dim() != 4 or table.shape[2] != self.T or table.shape[3] != 2:
+            raise ValueError("instance time nominals must be [batch][tables][%d][2], got %s" % (self.T, tuple(table.shape)))
+        tables = len(self.time_nominal_terms())
+        if tables and table.shape[1] != tables:
+            raise ValueError("instance time nominals must hold %d tables, got %s" % (tables, tuple(table.shape)))
+        _check(lib().ilqg_problem_bind_instance_time_nominals(self.h, table.shape[0], C.c_void_p(table.data_ptr())))
+        self._instance_time_nominals = table
+        return table
 
     def bind_instance_values(self, values):
         """ilqg_problem_bind_instance_values: a float32 [B][count] table, count = cost columns + subsystem columns (uploaded if it is not a CUDA tensor), read by

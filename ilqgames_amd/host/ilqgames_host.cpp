@@ -528,6 +528,67 @@ bool ResolveInstanceParams(const ProblemDescription& description, const Instance
   return true;
 }
 
+bool ResolveTimeNominalReferences(const ProblemDescription& description, const InstanceParams& params,
+                                  std::vector<int32_t>* tables_out, std::string* why, int32_t* tables) {
+  std::string scratch;
+  if (why == nullptr) why = &scratch;
+  tables_out->clear();
+  std::vector<int> table_of(description.terms.size(), -1);  // term -> its table (ilqg_problem_time_nominal_terms' order)
+  int32_t count = 0;
+  for (size_t q = 0; q < description.terms.size(); q++)
+    if (description.terms[q].kind == ILQG_COST_NOMINAL_PATH_LENGTH || description.terms[q].kind == ILQG_COST_ROUTE_PROGRESS)
+      table_of[q] = count++;
+  if (tables != nullptr) *tables = count;
+  for (size_t c = 0; c < params.references.size(); c++) {
+    int table = -1;
+    for (size_t q = 0; q < description.term_objects.size() && table < 0; q++)
+      if (description.term_objects[q] == params.references[c]) table = table_of[q];
+    if (table < 0) {
+      *why = "instance reference " + std::to_string(c) +
+             " names an object that is no NominalPathLengthCost or RouteProgressCost of the problem";
+      return false;
+    }
+    tables_out->push_back(table);
+  }
+  return true;
+}
+
+bool FillInstanceTimeNominals(const ProblemDescription& description, size_t instances, const std::vector<float>& speed_pos,
+                              InstanceParams* params, std::string* why) {
+  std::string scratch;
+  if (why == nullptr) why = &scratch;
+  std::vector<int32_t> tables;
+  int32_t count = 0;
+  if (!ResolveTimeNominalReferences(description, *params, &tables, why, &count)) return false;
+  if (speed_pos.size() < instances * tables.size() * 2) {
+    *why = "instance references: speed_pos holds fewer than [instances][references][2] floats";
+    return false;
+  }
+  std::vector<size_t> term_of_table;
+  for (size_t q = 0; q < description.terms.size(); q++)
+    if (description.terms[q].kind == ILQG_COST_NOMINAL_PATH_LENGTH || description.terms[q].kind == ILQG_COST_ROUTE_PROGRESS)
+      term_of_table.push_back(q);
+  const size_t block = static_cast<size_t>(count) * static_cast<size_t>(description.desc.T) * 2;
+  params->time_nominals.assign(instances * block, 0.0);
+  std::vector<ilqg_cost_term> terms = description.terms;  // a copy whose named terms take each row's floats
+  ilqg_problem_desc desc = description.desc;
+  desc.terms = terms.data();
+  for (size_t b = 0; b < instances; b++) {
+    for (size_t c = 0; c < tables.size(); c++) {
+      ilqg_cost_term& term = terms[term_of_table[tables[c]]];
+      term.value = speed_pos[(b * tables.size() + c) * 2];
+      if (term.kind == ILQG_COST_ROUTE_PROGRESS) term.value2 = speed_pos[(b * tables.size() + c) * 2 + 1];
+    }
+    int32_t elems = 0;
+    if (ilqg_time_nominal_table_build(&desc, desc.dtype, params->time_nominals.data() + b * block,
+                                      static_cast<int32_t>(block), &elems) != ILQG_OK || static_cast<size_t>(elems) != block) {
+      *why = "instance references, instance " + std::to_string(b) + ": " + ilqg_last_error();
+      return false;
+    }
+  }
+  return true;
+}
+
 bool DescribeDynamics(const MultiPlayerIntegrableSystem& dynamics, ilqg_problem_desc* d, std::string* why) {
   std::string scratch;
   if (why == nullptr) why = &scratch;
@@ -950,6 +1011,7 @@ class DeviceSolve {
       (void)ilqg_problem_declare_instance_params(handle, 0, nullptr);
       (void)ilqg_problem_declare_instance_subsystem_params(handle, 0, nullptr);
       (void)ilqg_problem_bind_instance_routes(handle, 0, nullptr, nullptr);
+      (void)ilqg_problem_bind_instance_time_nominals(handle, 0, nullptr);
       (void)ilqg_problem_declare_instance_routes(handle, 0, nullptr);
     }
     ilqg_problem* handle;
@@ -994,6 +1056,21 @@ class DeviceSolve {
     CHECK_GT(B, 0);
     // per-instance cost parameters: rows [first_row, first_row + B) of the caller's table, bound for this solve only
     InstanceBinding binding(handle_);
+    if (instance_params != nullptr && !instance_params->time_nominals.empty()) {
+      // blocks [first_row, first_row + B) of the caller's table, bound for this solve only
+      int32_t tables = 0;
+      CHECK_EQ(ilqg_problem_time_nominal_terms(handle_, nullptr, 0, &tables), ILQG_OK) << ilqg_last_error();
+      const size_t block = static_cast<size_t>(tables) * static_cast<size_t>(T_) * 2;
+      CHECK_GT(block, 0u) << "instance time nominals: the problem has no NominalPathLengthCost or RouteProgressCost";
+      CHECK_GE(instance_params->time_nominals.size(), (first_row + B) * block) << "instance time nominals: one block per instance";
+      const double* rows = instance_params->time_nominals.data() + first_row * block;
+      HipCheck(hipMemcpy(d_instance_time_nominals_.Reserve(B * block * sizeof(double)), rows, B * block * sizeof(double),
+                         hipMemcpyHostToDevice), "instance time nominals");
+      binding.bound = true;
+      CHECK_EQ(ilqg_problem_bind_instance_time_nominals(handle_, static_cast<int32_t>(B),
+                                                        static_cast<const double*>(d_instance_time_nominals_.get())), ILQG_OK)
+          << ilqg_last_error();
+    }
     if (instance_params != nullptr && !(instance_params->params.empty() && instance_params->subsystems.empty() &&
                                         instance_params->route_polylines.empty())) {
       std::vector<ilqg_instance_param> declared;
@@ -1228,7 +1305,8 @@ class DeviceSolve {
   int n_ = 0, m_ = 0, N_ = 0, T_ = 0;
   std::vector<int> udims_;
   bool solved_single_ = false, last_kind_ = false;
-  DeviceBuffer d_x0_, d_xs_, d_us_, d_P_, d_alpha_, d_costs_, d_iters_, d_status_, d_conv_, d_workspace_, d_instance_values_, d_instance_routes_;
+  DeviceBuffer d_x0_, d_xs_, d_us_, d_P_, d_alpha_, d_costs_, d_iters_, d_status_, d_conv_, d_workspace_, d_instance_values_, d_instance_routes_,
+      d_instance_time_nominals_;
   DeviceBuffer d_log_xs_, d_log_us_, d_log_costs_, d_log_P_, d_log_alpha_, d_log_count_;
 };
 

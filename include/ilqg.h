@@ -338,7 +338,8 @@ void ilqg_problem_destroy(ilqg_problem* p);
  *   SEMIQUADRATIC_NORM                     yes      yes
  *   QUADRATIC_DIFFERENCE, CURVATURE,
  *   RELATIVE_DISTANCE                      yes      no  (has none)
- *   NOMINAL_PATH_LENGTH, ROUTE_PROGRESS    yes      no  (tabulated per step by ilqg_problem_create)
+ *   NOMINAL_PATH_LENGTH, ROUTE_PROGRESS    yes      no  (tabulated per step by ilqg_problem_create; per instance:
+ *                                                       "Per-instance TIME NOMINALS" below)
  *   SIGNED_DISTANCE,
  *   POLYLINE2_SIGNED_DISTANCE              no       yes (the weight is not read)
  *   CONSTRAINT_PROXIMITY, _SINGLE_DIMENSION,
@@ -420,6 +421,45 @@ ilqg_status ilqg_problem_declare_instance_routes(ilqg_problem* p, int32_t count,
 ilqg_status ilqg_problem_bind_instance_routes(ilqg_problem* p, int32_t batch, const float* points, void* stream);
 /* Host only, no device needed: the checks of the declare call against a descriptor. */
 ilqg_status ilqg_instance_routes_check(const ilqg_problem_desc* desc, int32_t count, const int32_t* polylines);
+
+/* Per-instance TIME NOMINALS: a reference trajectory for each game.  The two time-dependent kinds track a per-step
+ * nominal — NOMINAL_PATH_LENGTH a scalar t_k * speed on one state dimension, ROUTE_PROGRESS the point of its polyline at
+ * pos0 + t_k * speed on a position pair — which ilqg_problem_create tabulates into [tables][T][2] doubles (the second
+ * entry of a NOMINAL_PATH_LENGTH pair is 0 and is not read).  `tables` is the number of time-dependent terms of the
+ * descriptor, and table q belongs to the q-th such term in ilqg_problem_desc::terms order
+ * (ilqg_problem_time_nominal_terms).  A bound table replaces the tabulated one per instance: K candidate ego
+ * trajectories against the same other agents, a speed profile per vehicle, a moving way-point per scene, the shifted
+ * reference of every replan.
+ *   bind      nominals: device double [batch][tables][T][2], or NULL to unbind; instance b tracks block b.  There is no
+ *             declaration step: the table covers every time-dependent term, and a caller who varies only some fills the
+ *             rest from the baked table (ilqg_time_nominal_table_build).  The table is READ AT EVERY LATER CALL on this
+ *             handle and never copied, like the value table: the caller keeps it alive while it is bound and may rewrite
+ *             it in place between calls, in stream order with them (a receding-horizon caller shifts its reference
+ *             between replans).  ILQG_ERR_INVALID when the problem has no time-dependent term, with batch <= 0, or when
+ *             a value table or a route table is bound with another batch (and likewise from those binds while this
+ *             table is bound): any of the three may be bound, in any order, with one batch.
+ *   build     ilqg_instance_time_nominals_build fills such a table on `stream` from speed_pos: device
+ *             float [batch][tables][2] = (nominal speed, initial route position); the second entry is ignored for a
+ *             NOMINAL_PATH_LENGTH term.  Block b is, bit for bit, what a problem created with those two floats as the
+ *             term's value / value2 tabulates, on the handle's baked polylines in the handle's precision; the caller
+ *             then binds `nominals` (it is not bound by this call).  Any other reference is the caller's to write.
+ * The calls that evaluate costs read the bound table — ilqg_solve_batch_ex and the three calls that are it (every mode),
+ * ilqg_solve_again_batch, ilqg_quadraticize_batch, ilqg_total_costs_batch, ilqg_strategy_costs_batch,
+ * ilqg_check_local_nash_batch, ilqg_check_sufficient_nash_batch — and return ILQG_ERR_INVALID before any launch when
+ * their `batch` is not the bound one.  Rollout, linearize, the LQ sweeps and the receding-horizon integration calls
+ * ignore the binding.  No scheduling choice looks at it; the row program and the static match stay the descriptor's.
+ * VALUES ARE NOT VALIDATED, on the device: where ilqg_problem_create returns ILQG_ERR_INVALID for a route position that
+ * turns negative over the horizon (and the host-only builder below does too), the device builder lets a negative or NaN
+ * route position take segment 0 — it extrapolates backwards along the first segment — and a position past the last
+ * segment extrapolates along the last, as the descriptor path does.
+ * Unchanged: a per-instance `value` column for these two kinds is still ILQG_ERR_UNSUPPORTED, and so is a per-instance
+ * route for a polyline that a ROUTE_PROGRESS term refers to (the device builder reads the baked polylines). */
+ilqg_status ilqg_problem_bind_instance_time_nominals(ilqg_problem* p, int32_t batch, const double* nominals);
+ilqg_status ilqg_instance_time_nominals_build(const ilqg_problem* p, int32_t batch, const float* speed_pos, double* nominals,
+                                              void* stream);
+/* Which term owns table q: terms_out[q] indexes ilqg_problem_desc::terms.  *tables is the table count (0: the problem
+ * has no time-dependent term); terms_out may be NULL to query it. */
+ilqg_status ilqg_problem_time_nominal_terms(const ilqg_problem* p, int32_t* terms_out, int32_t capacity, int32_t* tables);
 
 /* Bytes of device workspace a solve of `batch` instances needs: the per-instance iterates, linearisations and
  * loop states, the lists of back-tracking instances and the pool of the speculative line search.  A solve
@@ -648,6 +688,12 @@ ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words
  * route table.  *num_elems is the element count; out may be NULL to query it. */
 ilqg_status ilqg_segment_table_build(const ilqg_problem_desc* desc, int32_t dtype, void* out, int32_t capacity,
                                      int32_t* num_elems);
+/* Host only, no device needed: the per-step nominals ilqg_problem_create tabulates for the descriptor's time-dependent
+ * terms, double [tables][T][2] in the geometry arithmetic of `dtype` (ILQG_F32 / ILQG_F64) — one instance's block of a
+ * per-instance table of time nominals.  *num_elems is the element count (0 without such a term); out may be NULL to
+ * query it. */
+ilqg_status ilqg_time_nominal_table_build(const ilqg_problem_desc* desc, int32_t dtype, double* out, int32_t capacity,
+                                          int32_t* num_elems);
 
 /* Replaces AugmentedLagrangianSolver::Solve (src/augmented_lagrangian_solver.cpp:72-210) with
  * max_runtime = infinity: inner ilqg_ilq_solve_batch calls capped at
@@ -800,7 +846,10 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
                                  ilqg_instance_subsystem_params_check: two new calls, the table gains columns); still 9:
                                  ilqg_solve_options::sweep_forms (was reserved2 = 0 = AUTO: no layout or behaviour change); still 9:
                                  per-instance routes (ilqg_problem_declare_instance_routes, ilqg_problem_bind_instance_routes,
-                                 ilqg_instance_routes_check, and the host-only ilqg_segment_table_build: four new calls);
+                                 ilqg_instance_routes_check, and the host-only ilqg_segment_table_build: four new calls); still 9:
+                                 per-instance time nominals (ilqg_problem_bind_instance_time_nominals,
+                                 ilqg_instance_time_nominals_build, ilqg_problem_time_nominal_terms, and the host-only
+                                 ilqg_time_nominal_table_build: four new calls);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;

@@ -1093,6 +1093,15 @@ struct InstanceParams {
   std::vector<float> routes;
   void AddRoute(const Polyline2* polyline) { route_polylines.push_back(Route{polyline, -1}); }
   void AddRoute(int polyline) { route_polylines.push_back(Route{nullptr, polyline}); }
+  // Per-instance TIME NOMINALS (ilqg_problem_bind_instance_time_nominals): a reference trajectory for each game.
+  // `time_nominals` sits beside `values` and `routes`: one block per instance, [x0s.size()][tables][T][2] doubles, `tables`
+  // the NominalPathLengthCost / RouteProgressCost objects of the Problem in the flattener's term order — every one of
+  // them, named or not.  Any per-step reference may be written there; FillInstanceTimeNominals below writes the blocks
+  // of per-instance (nominal speed, initial route position) pairs for the costs named here by address.
+  std::vector<const Cost*> references;
+  std::vector<double> time_nominals;
+  void AddReference(const Cost* cost) { references.push_back(cost); }
+  void AddReference(const std::shared_ptr<const Cost>& cost) { AddReference(cost.get()); }
 };
 // The (term index, field) list of `params` in `description` (what ilqg_problem_declare_instance_params takes).
 // Returns false and sets *why when an object is not a term of the description.
@@ -1105,6 +1114,19 @@ struct InstanceParams {
 bool ResolveInstanceParams(const ProblemDescription& description, const InstanceParams& params,
                            std::vector<ilqg_instance_param>* out, std::string* why,
                            std::vector<int32_t>* subsystems_out = nullptr, std::vector<int32_t>* routes_out = nullptr);
+
+// The table (0 .. tables - 1: its place among the description's time-dependent terms) of each of params.references.
+// Returns false and sets *why when an object is no NominalPathLengthCost / RouteProgressCost of the description.
+bool ResolveTimeNominalReferences(const ProblemDescription& description, const InstanceParams& params,
+                                  std::vector<int32_t>* tables_out, std::string* why, int32_t* tables = nullptr);
+// Fills params->time_nominals for `instances` games from speed_pos, [instances][params->references.size()][2] floats =
+// (nominal speed, initial route position; the second is ignored for a NominalPathLengthCost): block b is, bit for bit,
+// what a Problem whose named costs were constructed with row b tabulates (ilqg_time_nominal_table_build on the
+// description with those floats, in the precision of description.desc.dtype); unnamed costs keep their own.  Host only.
+// Returns false and sets *why for an unresolved reference, a short speed_pos, or a row the library refuses (a route
+// position that turns negative over the horizon).
+bool FillInstanceTimeNominals(const ProblemDescription& description, size_t instances, const std::vector<float>& speed_pos,
+                              InstanceParams* params, std::string* why);
 
 // Walks Problem::Dynamics() and Problem::PlayerCosts() (after Initialize()) and fills the POD
 // descriptor of include/ilqg.h.  Returns false and sets *why when some object has no device kernel.

@@ -22,8 +22,15 @@ per pair (V pairs, V solves of B / V instances).
 1 m over V distinct layouts (instance b plays layout b % V): unbound; bound with every row the baked lane; bound with the V
 layouts; the same V layouts as V problems solved one after another, B / V instances each.
 
+--references: the same four legs for per-instance TIME NOMINALS — the scene gains a way-point for each car (a
+RouteProgressCost on its lane, weight 5; a scene with a time-dependent term runs the interpreted row stage, so leg (a) is
+this scene unbound, not bench.py's), and V reference vectors draw the cars' nominal speeds from [3, 8] m/s and their
+initial route positions from +-5 m about the baked ones (instance b tracks vector b % V): unbound; bound with every block
+the baked table; bound with the V references (tabulated on the device by ilqg_instance_time_nominals_build); the same V
+references as V problems solved one after another, B / V instances each.
+
 Prints one JSON line: iterations/s of each.
-python scripts/param_sweep_bench.py [--batch 1024] [--repeats 5] [--vectors 16] [--subsystems | --routes]"""
+python scripts/param_sweep_bench.py [--batch 1024] [--repeats 5] [--vectors 16] [--subsystems | --routes | --references]"""
 import argparse
 import copy
 import json
@@ -50,6 +57,7 @@ def main():
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
     ap.add_argument("--subsystems", action="store_true", help="the wheelbases of the two cars instead of cost parameters")
     ap.add_argument("--routes", action="store_true", help="the bend of player 2's turn lane instead of cost parameters")
+    ap.add_argument("--references", action="store_true", help="a way-point per car, its speed and start per instance")
     args = ap.parse_args()
     import torch
     from ilqgames_amd import abi, examples, hip
@@ -83,6 +91,40 @@ def main():
             if rep > 0:
                 times.append(e0.elapsed_time(e1) * 1e-3)
         return float(np.median(times))
+
+    if args.references:
+        baked = []  # (speed, pos0) of the two way-points: the cars start 970 m and 955 m along their lanes
+        for player, lane, xy, speed, pos0 in ((0, 0, (0, 1), 8.0, 970.0), (1, 1, (5, 6), 6.0, 955.0)):
+            spec.route_progress(player, 5.0, speed, lane, xy, pos0)
+            baked.append((speed, pos0))
+        terms = [ti for ti, t in enumerate(spec.terms) if t["kind"] == abi.COST_ROUTE_PROGRESS]
+        refs = np.tile(np.array(baked, dtype=np.float32), (V, 1, 1))
+        refs[:, :, 0] = (3.0 + 5.0 * rng.random((V, len(terms)))).astype(np.float32)
+        refs[:, :, 1] += (10.0 * rng.random((V, len(terms))) - 5.0).astype(np.float32)
+        assert len({r.tobytes() for r in refs}) == V
+        which = np.arange(B) % V
+        prob = hip.Problem(spec, dtype)
+        assert prob.time_nominal_terms() == terms
+        bufs = prob.alloc_solve_buffers(B)
+        out = dict(batch=B, iters=K, dtype=args.dtype, tables=len(terms), references=V)
+        out["unbound_its"] = B * K / timed([(prob, x0, bufs)])
+        prob.bind_instance_time_nominals(np.tile(hip.time_nominal_table(spec, dtype), (B, 1, 1, 1)))
+        out["bound_identity_its"] = B * K / timed([(prob, x0, bufs)])
+        prob.bind_instance_time_nominals(prob.build_instance_time_nominals(refs[which]))
+        out["bound_references_its"] = B * K / timed([(prob, x0, bufs)])
+        out["bound_references_backtracks"] = float(prob.solve_state(bufs)["backtracks"].float().mean().item())
+        prob.bind_instance_time_nominals(None)
+        solves = []
+        for v in range(V):
+            s = copy.deepcopy(spec)
+            for ti, (speed, pos0) in zip(terms, refs[v]):
+                s.terms[ti]["value"], s.terms[ti]["value2"] = float(speed), float(pos0)
+            p = hip.Problem(s, dtype)
+            sel = torch.as_tensor(np.nonzero(which == v)[0], device="cuda")
+            solves.append((p, x0[sel].contiguous(), p.alloc_solve_buffers(len(sel))))
+        out["per_reference_problems_its"] = B * K / timed(solves)
+        print(json.dumps(out))
+        return
 
     if args.routes:
         lane, bend = 1, [2, 3, 4]  # examples.py: lane2 and its three bend points
