@@ -829,6 +829,7 @@ void raise_lds_limit(const void* kern, size_t lds) {
 }  // namespace
 
 #include "ilqg_problem.hpp"  // the problem object: its host tables, its device buffers, the handle
+#include "ilqg_instances.hpp"  // per-instance declarations and bindings on it
 
 // Launchers of the kernels that are instantiated per (n, N, m_i).  Members are defined out of class (not inline),
 // so `extern template struct DimsLaunch<...>` in the main unit of a split build leaves their code — and the
@@ -1541,8 +1542,9 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
     const size_t budget = per_instance > fixed ? (per_instance - fixed) / trial_row_waves(W) : 0;
     sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), budget);
   }
-  // (a problem with per-instance parameters bound runs fused kernels of its own, here and below: ilqg_solve.hpp)
-  auto k_trial = (d.inst_values || d.seg_inst_stride || d.tnom_inst_stride) ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
+  // (a problem with per-instance tables bound runs fused kernels of its own, here and below: ilqg_solve.hpp)
+  const bool bound = p->bindings.any();
+  auto k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
   const bool pw = C::USE_MFMA && !open_loop;  // one wave per player (MFMA feedback sweep)
   // Compact rows (ilqg_common.hpp) between the row stage and the sweep: the one-tile player-parallel sweep and the
   // open-loop sweep read them; the other sweeps take the dense arrays.  What the row stage writes and the sweep reads
@@ -1569,8 +1571,6 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
       if (p->static_prog == ID_) {                                                                             \
         static_id = ID_;                                                                                       \
         static_in_regs = static_prog_in_registers<StaticRowProg<ID_>>();                                       \
-        const bool bound = d.inst_values != nullptr || d.seg_inst_stride != 0; /* kernels of their own (no        \
-           registered structure holds a time-dependent term: a table of time nominals never gets here) */      \
         k_rows = bound ? ilq_rows_kernel<T, NX, NP, MU, kBoundProg + ID_> : ilq_rows_kernel<T, NX, NP, MU, ID_>; \
         k_prows = bound ? ilq_probe_rows_kernel<T, NX, NP, MU, kBoundProg + ID_>                               \
                         : ilq_probe_rows_kernel<T, NX, NP, MU, ID_>;                                           \
@@ -1950,49 +1950,6 @@ static const char* const kRouteProgressReceding =
     "receding horizon: the problem holds a RouteProgressCost, whose per-step nominals are tabulated for a first solve "
     "(initial time 0) only";
 
-// Per-instance routes (ilqg_problem_bind_instance_routes): the segment table of every instance, [batch][total_segs]
-// [kSegStride] in the layout of DevProblem::segs_f / segs_d.  One lane per (instance, segment).  A segment of a declared
-// polyline (cols[q] >= 0: its first point in the instance's row of `points`, float [batch][row_points][2]) is built from
-// the instance's points by the host builder's own function (ilqg_segment.hpp: the same roundings); a segment of any other
-// polyline is copied from the baked table, so that one base pointer serves every op of the row program.
-template <typename T>
-__global__ void __launch_bounds__(256) route_segments_kernel(const int* poly_off, int num_polylines, const int* cols,
-                                                             const float* points, int row_points, const T* baked,
-                                                             int total_segs, int batch, T* out) {
-  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (gid >= size_t(batch) * size_t(total_segs)) return;
-  const size_t b = gid / size_t(total_segs);
-  const int s = int(gid - b * size_t(total_segs));
-  T* const o = out + gid * kSegStride;
-  for (int q = 0; q < num_polylines; q++) {
-    const int first = poly_off[q] - q, nseg = poly_off[q + 1] - poly_off[q] - 1;  // (segment s of polyline q: DevProblem)
-    if (s < first || s >= first + nseg) continue;
-    if (cols[q] >= 0) {
-      segment_and_shortcuts(points + 2 * (b * size_t(row_points) + size_t(cols[q])), nseg, s - first, o);
-      return;
-    }
-    break;
-  }
-  for (int e = 0; e < kSegStride; e++) o[e] = baked[size_t(s) * kSegStride + e];
-}
-
-// Per-instance time nominals (ilqg_instance_time_nominals_build): [batch][tables][T][2] doubles in the layout of
-// DevProblem::time_nominal_f / _d per instance.  One lane per (instance, table, step): what build_time_nominals tabulates
-// for a descriptor whose term has the instance's (nominal speed, initial route position) — the host builder's own
-// function (ilqg_time_nominal.hpp: the same roundings) on the baked segment table of precision S.  `tables`: per table
-// (term, 1: a route, the polyline's first segment, its segments).
-template <typename S>
-__global__ void __launch_bounds__(256) time_nominals_kernel(const int* tables, int num_tables, int T, double dt,
-                                                            const float* speed_pos, const S* segs, int batch, double* out) {
-  const size_t gid = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (gid >= size_t(batch) * size_t(num_tables) * size_t(T)) return;
-  const size_t bq = gid / size_t(T);  // (instance, table): a row of speed_pos
-  const int k = int(gid - bq * size_t(T));
-  const int* tab = tables + 4 * (bq % size_t(num_tables));
-  time_nominal<S>(tab[1] != 0, speed_pos[2 * bq], speed_pos[2 * bq + 1], k, dt, segs + size_t(tab[2]) * kSegStride, tab[3],
-                  out + 2 * gid);
-}
-
 extern "C" {
 
 const char* ilqg_last_error(void) { return g_err.c_str(); }
@@ -2246,7 +2203,7 @@ ilqg_status ilqg_instance_params_check(const ilqg_problem_desc* desc, int32_t co
 
 ilqg_status ilqg_problem_declare_instance_params(ilqg_problem* p, int32_t count, const ilqg_instance_param* params) {
   if (!p) return fail(ILQG_ERR_INVALID, "null argument");
-  if (p->dev.inst_values)
+  if (p->bindings.bound[kBindValues])
     return fail(ILQG_ERR_INVALID, "instance parameters cannot be declared while values are bound: unbind first");
   ilqg_status s = instance_params_check_terms(int(p->terms_host.size()), p->terms_host.data(), count, params);
   if (s == ILQG_OK) s = instance_total_check(size_t(count), p->inst_subs.size());
@@ -2265,7 +2222,7 @@ ilqg_status ilqg_instance_subsystem_params_check(const ilqg_problem_desc* desc, 
 
 ilqg_status ilqg_problem_declare_instance_subsystem_params(ilqg_problem* p, int32_t count, const int32_t* subsystems) {
   if (!p) return fail(ILQG_ERR_INVALID, "null argument");
-  if (p->dev.inst_values)
+  if (p->bindings.bound[kBindValues])
     return fail(ILQG_ERR_INVALID, "instance parameters cannot be declared while values are bound: unbind first");
   ilqg_status s = instance_subsystems_check(p->dev.N, p->dev.sub_kind, count, subsystems);
   if (s == ILQG_OK) s = instance_total_check(p->inst_params.size(), size_t(count));
@@ -2279,22 +2236,16 @@ ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, co
     d.inst_values = nullptr;
     d.inst_terms = nullptr;
     d.inst_count = 0;
-    p->inst_batch = 0;
+    p->bindings.bound[kBindValues] = false;
     return ILQG_OK;
   }
   if (p->inst_params.empty() && p->inst_subs.empty())
     return fail(ILQG_ERR_INVALID, "no instance parameters are declared (ilqg_problem_declare_instance_params)");
-  if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance parameter values: batch must be positive");
-  if (p->route_batch && batch != p->route_batch)
-    return fail(ILQG_ERR_INVALID, "instance parameter values: per-instance routes are bound for a batch of " +
-                                      std::to_string(p->route_batch) + ", these values are for " + std::to_string(batch));
-  if (p->tnom_batch && batch != p->tnom_batch)
-    return fail(ILQG_ERR_INVALID, "instance parameter values: per-instance time nominals are bound for a batch of " +
-                                      std::to_string(p->tnom_batch) + ", these values are for " + std::to_string(batch));
+  if (ilqg_status s = bind_batch_check(p, kBindValues, batch)) return s;
   d.inst_values = values;
   d.inst_terms = p->d_inst_terms.get();
   d.inst_count = int(p->inst_params.size() + p->inst_subs.size());
-  p->inst_batch = batch;
+  p->bindings.bind(kBindValues, batch);
   return ILQG_OK;
 }
 
@@ -2306,7 +2257,7 @@ ilqg_status ilqg_instance_routes_check(const ilqg_problem_desc* desc, int32_t co
 
 ilqg_status ilqg_problem_declare_instance_routes(ilqg_problem* p, int32_t count, const int32_t* polylines) {
   if (!p) return fail(ILQG_ERR_INVALID, "null argument");
-  if (p->route_batch)
+  if (p->bindings.bound[kBindRoutes])
     return fail(ILQG_ERR_INVALID, "instance routes cannot be declared while a route table is bound: unbind first");
   ilqg_status s = instance_routes_check_terms(p->dev.num_polylines, int(p->terms_host.size()), p->terms_host.data(), count, polylines);
   if (s != ILQG_OK) return s;
@@ -2334,25 +2285,20 @@ ilqg_status ilqg_problem_bind_instance_routes(ilqg_problem* p, int32_t batch, co
     d.segs_f = p->d_segs.f.get();
     d.segs_d = p->d_segs.d.get();
     d.seg_inst_stride = 0;
-    p->d_route_segs_f.reset();
-    p->d_route_segs_d.reset();
-    p->route_batch = 0;
+    p->d_route_segs.f.reset();
+    p->d_route_segs.d.reset();
+    p->bindings.bound[kBindRoutes] = false;
     return ILQG_OK;
   }
   if (p->route_polys.empty())
     return fail(ILQG_ERR_INVALID, "no instance routes are declared (ilqg_problem_declare_instance_routes)");
-  if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance routes: batch must be positive");
-  if (d.inst_values && batch != p->inst_batch)
-    return fail(ILQG_ERR_INVALID, "instance routes: per-instance parameter values are bound for a batch of " +
-                                      std::to_string(p->inst_batch) + ", these routes are for " + std::to_string(batch));
-  if (p->tnom_batch && batch != p->tnom_batch)
-    return fail(ILQG_ERR_INVALID, "instance routes: per-instance time nominals are bound for a batch of " +
-                                      std::to_string(p->tnom_batch) + ", these routes are for " + std::to_string(batch));
+  if (ilqg_status s = bind_batch_check(p, kBindRoutes, batch)) return s;
   const size_t count = size_t(batch) * size_t(d.total_segs);
-  const bool f32 = p->desc.dtype == ILQG_F32;
-  if (batch != p->route_batch) {  // a new table; one of the same size is rewritten in place, in stream order
-    const ilqg_status s = f32 ? upload(std::vector<float>(), count * kSegStride + 1, "instance route table", &p->d_route_segs_f)
-                              : upload(std::vector<double>(), count * kSegStride + 1, "instance route table", &p->d_route_segs_d);
+  // a new table; one of the same size is rewritten in place, in stream order
+  if (!p->bindings.bound[kBindRoutes] || batch != p->bindings.batch) {
+#define CALL(TY_) upload(std::vector<TY_>(), count * kSegStride + 1, "instance route table", &segs_of<TY_>(p->d_route_segs))
+    const ilqg_status s = DT_DISPATCH(p, CALL);
+#undef CALL
     if (s != ILQG_OK) {
       (void)ilqg_problem_bind_instance_routes(p, 0, nullptr, stream);
       return s;
@@ -2360,19 +2306,20 @@ ilqg_status ilqg_problem_bind_instance_routes(ilqg_problem* p, int32_t batch, co
   }
   if (count > 0) {
     const dim3 grid((unsigned)((count + 255) / 256));
-    if (f32)
-      hipLaunchKernelGGL(route_segments_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, d.poly_off, d.num_polylines,
-                         p->d_route_cols.get(), points, p->route_points, p->d_segs.f.get(), d.total_segs, batch,
-                         p->d_route_segs_f.get());
-    else
-      hipLaunchKernelGGL(route_segments_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, d.poly_off, d.num_polylines,
-                         p->d_route_cols.get(), points, p->route_points, p->d_segs.d.get(), d.total_segs, batch,
-                         p->d_route_segs_d.get());
-    HIP_TRY(hipGetLastError());
+#define CALL(TY_)                                                                                                           \
+  [&]() -> ilqg_status {                                                                                                    \
+    hipLaunchKernelGGL(route_segments_kernel<TY_>, grid, dim3(256), 0, (hipStream_t)stream, d.poly_off, d.num_polylines,    \
+                       p->d_route_cols.get(), points, p->route_points, segs_of<TY_>(p->d_segs).get(), d.total_segs, batch,  \
+                       segs_of<TY_>(p->d_route_segs).get());                                                                \
+    HIP_TRY(hipGetLastError());                                                                                             \
+    return ILQG_OK;                                                                                                         \
+  }()
+    if (ilqg_status s = DT_DISPATCH(p, CALL)) return s;
+#undef CALL
   }
-  if (f32) d.segs_f = p->d_route_segs_f.get(); else d.segs_d = p->d_route_segs_d.get();
+  if (p->desc.dtype == ILQG_F32) d.segs_f = p->d_route_segs.f.get(); else d.segs_d = p->d_route_segs.d.get();
   d.seg_inst_stride = d.total_segs * kSegStride;
-  p->route_batch = batch;
+  p->bindings.bind(kBindRoutes, batch);
   return ILQG_OK;
 }
 
@@ -2394,23 +2341,17 @@ ilqg_status ilqg_problem_bind_instance_time_nominals(ilqg_problem* p, int32_t ba
     d.time_nominal_f = p->d_time_nominal.f.get();
     d.time_nominal_d = p->d_time_nominal.d.get();
     d.tnom_inst_stride = 0;
-    p->tnom_batch = 0;
+    p->bindings.bound[kBindNominals] = false;
     return ILQG_OK;
   }
   if (p->tnom_tables.empty())
     return fail(ILQG_ERR_INVALID, "instance time nominals: the problem has no time-dependent term (NOMINAL_PATH_LENGTH, "
                                   "ROUTE_PROGRESS)");
-  if (batch <= 0) return fail(ILQG_ERR_INVALID, "instance time nominals: batch must be positive");
-  if (d.inst_values && batch != p->inst_batch)
-    return fail(ILQG_ERR_INVALID, "instance time nominals: per-instance parameter values are bound for a batch of " +
-                                      std::to_string(p->inst_batch) + ", these nominals are for " + std::to_string(batch));
-  if (p->route_batch && batch != p->route_batch)
-    return fail(ILQG_ERR_INVALID, "instance time nominals: per-instance routes are bound for a batch of " +
-                                      std::to_string(p->route_batch) + ", these nominals are for " + std::to_string(batch));
+  if (ilqg_status s = bind_batch_check(p, kBindNominals, batch)) return s;
   // (the handle's precision: the other pointer is not read)
   if (p->desc.dtype == ILQG_F32) d.time_nominal_f = nominals; else d.time_nominal_d = nominals;
   d.tnom_inst_stride = int(p->tnom_tables.size() / 4) * d.T * 2;
-  p->tnom_batch = batch;
+  p->bindings.bind(kBindNominals, batch);
   return ILQG_OK;
 }
 
@@ -2426,14 +2367,15 @@ ilqg_status ilqg_instance_time_nominals_build(const ilqg_problem* p, int32_t bat
   const size_t count = size_t(batch) * size_t(num_tables) * size_t(d.T);
   const dim3 grid((unsigned)((count + 255) / 256));
   // the BAKED segment table (a ROUTE_PROGRESS term's polyline never varies per instance), in the handle's precision
-  if (p->desc.dtype == ILQG_F32)
-    hipLaunchKernelGGL(time_nominals_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, p->d_tnom_tables.get(),
-                       num_tables, d.T, d.dt, speed_pos, p->d_segs.f.get(), batch, nominals);
-  else
-    hipLaunchKernelGGL(time_nominals_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, p->d_tnom_tables.get(),
-                       num_tables, d.T, d.dt, speed_pos, p->d_segs.d.get(), batch, nominals);
-  HIP_TRY(hipGetLastError());
-  return ILQG_OK;
+#define CALL(TY_)                                                                                                  \
+  [&]() -> ilqg_status {                                                                                           \
+    hipLaunchKernelGGL(time_nominals_kernel<TY_>, grid, dim3(256), 0, (hipStream_t)stream, p->d_tnom_tables.get(), \
+                       num_tables, d.T, d.dt, speed_pos, segs_of<TY_>(p->d_segs).get(), batch, nominals);          \
+    HIP_TRY(hipGetLastError());                                                                                    \
+    return ILQG_OK;                                                                                                \
+  }()
+  return DT_DISPATCH(p, CALL);
+#undef CALL
 }
 
 ilqg_status ilqg_problem_pairs(const ilqg_problem* p, ilqg_pair* pairs_host, int32_t* npairs) {
@@ -2722,10 +2664,8 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
   if (ilqg_status sb = instance_batch_check(p, batch)) return sb;
   // PlayerCost::Quadraticize of every player at every step (:168-172), whatever the player's time structure: the
   // quadraticisation kernel is launched on a copy of the problem whose players are all time-additive (the copy carries
-  // the declared per-instance parameters and the bound table; each chunk below starts at its own row of it)
-  DevProblem full = p->dev;
-  for (int i = 0; i < full.N; i++) full.structure[i] = ILQG_SUM;
-  const DevProblem& d = full;
+  // the declared per-instance parameters and the bound tables; each chunk below starts at its own rows of them)
+  const DevProblem& d = p->dev;
   const size_t esz = p->desc.dtype == ILQG_F32 ? 4 : 8;
   const size_t per_inst = size_t(d.T) * (size_t(d.N) * d.n * d.n + size_t(d.N) * d.n + d.pairs.Rsz + d.pairs.rsz) * esz;
   int chunk = int((size_t(256) << 20) / per_inst);
@@ -2744,21 +2684,14 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
     char* r = R + size_t(nb) * d.T * d.pairs.Rsz * esz;
     const char* xs_c = (const char*)xs + size_t(b0) * d.T * d.n * esz;
     const char* us_c = (const char*)us + size_t(b0) * d.T * d.m * esz;
-    if (p->dev.inst_values) full.inst_values = p->dev.inst_values + size_t(b0) * p->dev.inst_count;
-    if (p->dev.seg_inst_stride) {  // (the handle's precision: the other pointer is not read)
-      full.segs_f = p->dev.segs_f + size_t(b0) * p->dev.seg_inst_stride;
-      full.segs_d = p->dev.segs_d + size_t(b0) * p->dev.seg_inst_stride;
-    }
-    if (p->dev.tnom_inst_stride) {
-      if (p->desc.dtype == ILQG_F32) full.time_nominal_f = p->dev.time_nominal_f + size_t(b0) * p->dev.tnom_inst_stride;
-      else full.time_nominal_d = p->dev.time_nominal_d + size_t(b0) * p->dev.tnom_inst_stride;
-    }
+    DevProblem full = dev_from_instance(p, b0);
+    for (int i = 0; i < full.N; i++) full.structure[i] = ILQG_SUM;
     s = launch_linquad(p, full, nb, xs_c, us_c, nullptr, nullptr, nullptr, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
                        nullptr, stream);
     if (s != ILQG_OK) break;
 #define CALL(TY_)                                                                                                  \
   [&]() -> ilqg_status {                                                                                         \
-    hipLaunchKernelGGL(psd_check_kernel<TY_>, dim3(d.T, nb), dim3(64), 0, (hipStream_t)stream, d, (TY_*)Q, (TY_*)R, \
+    hipLaunchKernelGGL(psd_check_kernel<TY_>, dim3(d.T, nb), dim3(64), 0, (hipStream_t)stream, full, (TY_*)Q, (TY_*)R, \
                        is_psd + b0);                                                                               \
     HIP_TRY(hipGetLastError());                                                                                  \
     return ILQG_OK;                                                                                              \
@@ -2767,7 +2700,6 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
 #undef CALL
     if (s != ILQG_OK) break;
   }
-  // `full` is a shallow copy: it must not run the destructor logic of the handle it was copied from
   return s;
 }
 

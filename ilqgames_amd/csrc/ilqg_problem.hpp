@@ -5,6 +5,7 @@
 //   DeviceBuffer / upload  a table on the device, freed by whoever holds it (the two deleters: no other hipFree here).
 //   ilqg_problem           the handle: the device tables, the DevProblem that points at them and what the solves keep
 //                          between calls.  ilqg_problem_destroy is `delete`.
+// (What per-instance declarations and bindings do with the handle: ilqg_instances.hpp.)
 // Part of ilqg_api.hip, included once behind its fail() and ILQG_FOR_DIMS.  Every translation unit of the library sees the
 // handle and the buffers (the per-shape units reach into the handle); only the main unit the builder and the upload.
 #pragma once
@@ -23,6 +24,8 @@ namespace ilqg {
 // build_time_nominals and time_nominals_kernel step to a polyline's first segment by kSegStride; the shared function then
 // strides by its own constant (ilqg_time_nominal.hpp includes no device header): one layout
 static_assert(kTimeNominalSegStride == kSegStride, "ilqg_time_nominal.hpp and ilqg_common.hpp disagree on a segment's scalars");
+// the kernels take the DevProblem by value: its layout is part of every launch
+static_assert(sizeof(DevProblem) == 832, "DevProblem's size changed");
 
 // LoopTimer (include/ilqgames/utils/loop_timer.h:60-98, src/loop_timer.cpp:55-92): the last ten iteration times
 struct LoopTimer {
@@ -64,6 +67,21 @@ inline GenDims gen_dims_of(int n, int N, const int32_t* udim, int T) {
   return g;
 }
 
+// Per-instance tables bound on a handle (ilqg.h; the checks over the record: ilqg_instances.hpp).  Invariant: every
+// table bound on a handle is bound for the same batch, `batch` (which means nothing while none is bound): a bind of
+// another table for another batch is refused, so is a call that would read a bound table on another number of instances.
+// The kernels read the same state from the DevProblem: inst_values, seg_inst_stride, tnom_inst_stride, null / 0 unless bound.
+enum InstanceBinding { kBindValues, kBindRoutes, kBindNominals, kNumBindings };
+struct InstanceBindings {
+  bool bound[kNumBindings] = {false, false, false};
+  int batch = 0;
+  void bind(int table, int instances) { bound[table] = true; batch = instances; }
+  // Does a solve run the kernels that read per-instance tables (the bound twins, ilqg_solve.hpp)?  DimsLaunch::solve asks
+  // twice, the second time for a problem that matches a registered static structure: none of those holds a time-dependent
+  // term, so binding nominals to such a problem is refused and whether they count there cannot be observed.
+  bool any() const { return bound[kBindValues] || bound[kBindRoutes] || bound[kBindNominals]; }
+};
+
 }  // namespace ilqg
 
 struct ilqg_problem {
@@ -81,26 +99,23 @@ struct ilqg_problem {
   ilqg::DeviceBuffer<int> d_row_prog;
   // Per-instance parameters (ilqg.h): the declared (term, field) list, the declared subsystems (their columns follow the
   // cost columns) and their device table (DevProblem::inst_terms); dev.inst_values / inst_count are set while a table is
-  // bound, for `inst_batch` instances
+  // bound
   std::vector<ilqg_instance_param> inst_params;
   std::vector<int> inst_subs;
   ilqg::DeviceBuffer<int> d_inst_terms;
-  int inst_batch = 0;
   // Per-instance routes (ilqg.h): the declared polylines, per polyline of the descriptor its first point in a row of the
   // caller's points or -1 (device copy: route_segments_kernel), the points of a row, and while a table is bound the table
-  // (in the handle's precision; dev.segs_f / segs_d points at it, dev.seg_inst_stride is set) for `route_batch` instances
+  // (in the handle's precision; dev.segs_f / segs_d points at it, dev.seg_inst_stride is set)
   std::vector<int> route_polys;
   ilqg::DeviceBuffer<int> d_route_cols;
   int route_points = 0;
-  ilqg::DeviceBuffer<float> d_route_segs_f;
-  ilqg::DeviceBuffer<double> d_route_segs_d;
-  int route_batch = 0;
+  ilqg::DeviceBothPrecisions<float, double> d_route_segs;
   // Per-instance time nominals (ilqg.h): per table of the time-dependent costs (its term, 1: a route, its polyline's first
   // segment, segments), the device copy time_nominals_kernel reads, and while a table is bound (dev.time_nominal_f / _d
-  // points at the caller's, dev.tnom_inst_stride is set) its batch
+  // points at the caller's, dev.tnom_inst_stride is set)
   std::vector<int> tnom_tables;
   ilqg::DeviceBuffer<int> d_tnom_tables;
-  int tnom_batch = 0;
+  ilqg::InstanceBindings bindings;  // which of the three tables are bound, and for which batch
   int static_prog = 0;                // id of the registered structure it matches (ilqg_rowprog_static.hpp), 0: none
   ilqg::DeviceBuffer<int> d_unfinished;  // instances still running after an LQ-kernel launch
   ilqg::PinnedInts h_unfinished;  // pinned host mirror: [0..3] the counters, [8] the sequence number of read_round_counters
@@ -549,191 +564,6 @@ ilqg_status copy_row_program(const RowProgramHost& prog, int static_prog, int32_
     if (capacity < *num_words) return fail(ILQG_ERR_INVALID, "ilqg_problem_row_program: buffer too small");
     std::memcpy(words_out, prog.words.data(), sizeof(int32_t) * prog.words.size());
   }
-  return ILQG_OK;
-}
-
-// ---- per-instance cost parameters (ilqg.h) ----
-const char* cost_kind_name(int kind) {  // ilqg_cost_kind without its prefix
-  static const char* const names[] = {
-      "QUADRATIC", "QUADRATIC_POLYLINE2", "SEMIQUADRATIC", "SEMIQUADRATIC_POLYLINE2", "PROXIMITY", "SIGNED_DISTANCE",
-      "EXTREME_VALUE", "CONSTRAINT_PROXIMITY", "CONSTRAINT_SINGLE_DIMENSION", "POLYLINE2_SIGNED_DISTANCE",
-      "QUADRATIC_DIFFERENCE", "ORIENTATION", "QUADRATIC_NORM", "SEMIQUADRATIC_NORM", "RELATIVE_DISTANCE",
-      "LOCALLY_CONVEX_PROXIMITY", "CURVATURE", "CONSTRAINT_POLYLINE2_SIGNED_DISTANCE", "NOMINAL_PATH_LENGTH",
-      "ROUTE_PROGRESS", "WEIGHTED_CONVEX_PROXIMITY", "CONSTRAINT_AFFINE_SCALAR", "CONSTRAINT_AFFINE_VECTOR"};
-  static_assert(ILQG_COST_QUADRATIC == 1 && ILQG_CONSTRAINT_AFFINE_VECTOR == sizeof(names) / sizeof(names[0]), "one name per kind");
-  return kind >= 1 && kind <= ILQG_CONSTRAINT_AFFINE_VECTOR ? names[kind - 1] : "unknown kind";
-}
-// Does a term of this kind read the field (the table of ilqg.h; ilqg_models.hpp: term_evaluate_leaf_of and the row ops)?
-// Null: yes; else why not.
-const char* instance_param_refusal(int kind, int field) {
-  const bool weight = field == ILQG_PARAM_WEIGHT;
-  switch (kind) {
-    case ILQG_COST_EXTREME_VALUE: return "an EXTREME_VALUE term has no parameters of its own: declare its children";
-    case ILQG_CONSTRAINT_AFFINE_SCALAR:
-    case ILQG_CONSTRAINT_AFFINE_VECTOR: return "the affine constraints keep their coefficients in dense blocks";
-    case ILQG_COST_NOMINAL_PATH_LENGTH:
-    case ILQG_COST_ROUTE_PROGRESS:
-      return weight ? nullptr : "its nominal speed is tabulated per time step when the problem is created";
-    case ILQG_COST_SIGNED_DISTANCE:
-    case ILQG_COST_POLYLINE2_SIGNED_DISTANCE: return weight ? "this kind does not read its weight" : nullptr;
-    case ILQG_CONSTRAINT_PROXIMITY:
-    case ILQG_CONSTRAINT_SINGLE_DIMENSION:
-    case ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE: return weight ? "a constraint has no weight" : nullptr;
-    case ILQG_COST_QUADRATIC_POLYLINE2:
-    case ILQG_COST_QUADRATIC_DIFFERENCE:
-    case ILQG_COST_RELATIVE_DISTANCE:
-    case ILQG_COST_CURVATURE: return weight ? nullptr : "this kind has no nominal or threshold";
-    case ILQG_COST_QUADRATIC:
-    case ILQG_COST_SEMIQUADRATIC:
-    case ILQG_COST_SEMIQUADRATIC_POLYLINE2:
-    case ILQG_COST_PROXIMITY:
-    case ILQG_COST_ORIENTATION:
-    case ILQG_COST_QUADRATIC_NORM:
-    case ILQG_COST_SEMIQUADRATIC_NORM:
-    case ILQG_COST_LOCALLY_CONVEX_PROXIMITY:
-    case ILQG_COST_WEIGHTED_CONVEX_PROXIMITY: return nullptr;
-  }
-  return "unknown cost kind";
-}
-ilqg_status instance_params_check_terms(int num_terms, const ilqg_cost_term* terms, int32_t count,
-                                        const ilqg_instance_param* params) {
-  if (count < 0 || count > ILQG_MAX_INSTANCE_PARAMS)
-    return fail(ILQG_ERR_INVALID, "instance parameters: count must be 0 .. ILQG_MAX_INSTANCE_PARAMS");
-  if (count > 0 && (!params || !terms)) return fail(ILQG_ERR_INVALID, "null argument");
-  for (int c = 0; c < count; c++) {
-    const int term = params[c].term, field = params[c].field;
-    const std::string where = "instance parameter " + std::to_string(c) + " (term " + std::to_string(term) + ", " +
-                              (field == ILQG_PARAM_WEIGHT ? "weight" : field == ILQG_PARAM_VALUE ? "value" : "field " + std::to_string(field)) + "): ";
-    if (term < 0 || term >= num_terms)
-      return fail(ILQG_ERR_UNSUPPORTED, where + "term index out of range (the problem has " + std::to_string(num_terms) + " terms)");
-    if (field != ILQG_PARAM_WEIGHT && field != ILQG_PARAM_VALUE)
-      return fail(ILQG_ERR_UNSUPPORTED, where + "not an ilqg_param_field");
-    for (int q = 0; q < c; q++)
-      if (params[q].term == term && params[q].field == field)
-        return fail(ILQG_ERR_UNSUPPORTED, where + "declared twice (also parameter " + std::to_string(q) + ")");
-    if (const char* why = instance_param_refusal(terms[term].kind, field))
-      return fail(ILQG_ERR_UNSUPPORTED, where + cost_kind_name(terms[term].kind) + ": " + why);
-  }
-  return ILQG_OK;
-}
-// Per-instance subsystem parameters (ilqg.h): does a subsystem of this kind read its param0?
-const char* dyn_kind_name(int kind) {  // ilqg_dyn_kind without its prefix
-  static const char* const names[] = {"UNICYCLE_4D", "CAR_5D", "CAR_6D", "UNICYCLE_4D_DISTURBED", "PLANAR_DISTURBANCE",
-                                      "DUBINS_CAR", "AIR_3D_EVADER", "AIR_3D_PURSUER", "POINT_MASS_2D", "UNICYCLE_5D",
-                                      "CAR_7D", "DELAYED_DUBINS_CAR"};
-  static_assert(ILQG_DYN_UNICYCLE_4D == 1 && ILQG_DYN_DELAYED_DUBINS_CAR == sizeof(names) / sizeof(names[0]), "one name per kind");
-  return kind >= 1 && kind <= ILQG_DYN_DELAYED_DUBINS_CAR ? names[kind - 1] : "unknown kind";
-}
-bool subsystem_reads_param0(int kind) {
-  switch (kind) {
-    case ILQG_DYN_CAR_5D:
-    case ILQG_DYN_CAR_6D:
-    case ILQG_DYN_CAR_7D:              // inter-axle distance
-    case ILQG_DYN_DUBINS_CAR:
-    case ILQG_DYN_DELAYED_DUBINS_CAR:  // speed
-    case ILQG_DYN_AIR_3D_EVADER:
-    case ILQG_DYN_AIR_3D_PURSUER: return true;  // their speeds
-  }
-  return false;
-}
-ilqg_status instance_subsystems_check(int num_subsystems, const int* kinds, int32_t count, const int32_t* subsystems) {
-  if (count < 0 || count > ILQG_MAX_INSTANCE_PARAMS)
-    return fail(ILQG_ERR_INVALID, "instance subsystem parameters: count must be 0 .. ILQG_MAX_INSTANCE_PARAMS");
-  if (count > 0 && (!subsystems || !kinds)) return fail(ILQG_ERR_INVALID, "null argument");
-  for (int c = 0; c < count; c++) {
-    const int s = subsystems[c];
-    const std::string where = "instance parameter " + std::to_string(c) + " (subsystem " + std::to_string(s) + "): ";
-    if (s < 0 || s >= num_subsystems)
-      return fail(ILQG_ERR_UNSUPPORTED, where + "row out of range (the problem has " + std::to_string(num_subsystems) + " subsystems)");
-    for (int q = 0; q < c; q++)
-      if (subsystems[q] == s) return fail(ILQG_ERR_UNSUPPORTED, where + "declared twice (also parameter " + std::to_string(q) + ")");
-    if (!subsystem_reads_param0(kinds[s]))
-      return fail(ILQG_ERR_UNSUPPORTED, where + dyn_kind_name(kinds[s]) + ": this kind reads no param0");
-  }
-  return ILQG_OK;
-}
-// One value table holds the cost columns and the subsystem columns
-ilqg_status instance_total_check(size_t cost_count, size_t subsystem_count) {
-  if (cost_count + subsystem_count > size_t(ILQG_MAX_INSTANCE_PARAMS))
-    return fail(ILQG_ERR_INVALID, "instance parameters: " + std::to_string(cost_count) + " cost columns + " +
-                                      std::to_string(subsystem_count) + " subsystem columns exceed ILQG_MAX_INSTANCE_PARAMS");
-  return ILQG_OK;
-}
-
-// A call that reads the table on `batch` instances while a table for another batch is bound would read past it: every
-// call that evaluates costs, and — `costs` false — with a subsystem column declared the ones that integrate or linearise
-ilqg_status instance_batch_check(const ilqg_problem* p, int32_t batch, bool costs = true) {
-  if (costs && p->route_batch && batch != p->route_batch)  // (only what evaluates costs reads a segment)
-    return fail(ILQG_ERR_INVALID, "per-instance routes are bound for a batch of " + std::to_string(p->route_batch) +
-                                      ", this call has " + std::to_string(batch) + " instances");
-  if (costs && p->tnom_batch && batch != p->tnom_batch)  // (only what evaluates costs reads a nominal)
-    return fail(ILQG_ERR_INVALID, "per-instance time nominals are bound for a batch of " + std::to_string(p->tnom_batch) +
-                                      ", this call has " + std::to_string(batch) + " instances");
-  if (p->dev.inst_values && batch != p->inst_batch && (costs || !p->inst_subs.empty()))
-    return fail(ILQG_ERR_INVALID, "per-instance parameter values are bound for a batch of " + std::to_string(p->inst_batch) +
-                                      ", this call has " + std::to_string(batch) + " instances");
-  return ILQG_OK;
-}
-
-// Per-instance routes (ilqg.h): may these polylines of the descriptor vary per instance?  A ROUTE_PROGRESS term's
-// per-step nominals are tabulated from the baked polyline at creation (build_time_nominals).
-ilqg_status instance_routes_check_terms(int num_polylines, int num_terms, const ilqg_cost_term* terms, int32_t count,
-                                        const int32_t* polylines) {
-  if (count < 0) return fail(ILQG_ERR_INVALID, "instance routes: count must not be negative");
-  if (count > 0 && !polylines) return fail(ILQG_ERR_INVALID, "null argument");
-  for (int c = 0; c < count; c++) {
-    const int q = polylines[c];
-    const std::string where = "instance route " + std::to_string(c) + " (polyline " + std::to_string(q) + "): ";
-    if (q < 0 || q >= num_polylines)
-      return fail(ILQG_ERR_UNSUPPORTED, where + "index out of range (the problem has " + std::to_string(num_polylines) + " polylines)");
-    for (int e = 0; e < c; e++)
-      if (polylines[e] == q) return fail(ILQG_ERR_UNSUPPORTED, where + "declared twice (also route " + std::to_string(e) + ")");
-    for (int ti = 0; ti < num_terms; ti++)
-      if (terms[ti].kind == ILQG_COST_ROUTE_PROGRESS && terms[ti].polyline == q)
-        return fail(ILQG_ERR_UNSUPPORTED, where + "term " + std::to_string(ti) + " (" + cost_kind_name(terms[ti].kind) +
-                                              ") tabulates its per-step nominals from it when the problem is created");
-  }
-  return ILQG_OK;
-}
-
-// ilqg_problem_declare_instance_params / _declare_instance_subsystem_params: the checked lists into the handle, and onto
-// the device the column table ((term, field) per cost column, then subsystem -> column: DevProblem::inst_terms) and the
-// row stage's side table (per op of the row program the column of its weight / value; the program is not touched).
-// Subsystem s's column goes to the weight word of its Jacobian op and, for the Air3D pursuer, to the value word of the
-// evader's, where build_row_program put the baked param0.
-ilqg_status declare_instance_columns(ilqg_problem* p, const std::vector<ilqg_instance_param>& params,
-                                     const std::vector<int>& subs) {
-  const std::vector<int>&op_term = p->row_prog.op_term, &op_sub = p->row_prog.op_sub;
-  const size_t count = params.size() + subs.size();
-  std::vector<int> cols(op_term.size() * 2 + 2, -1), terms(count * 2 + kMaxPlayers, -1);
-  for (size_t c = 0; c < params.size(); c++) {
-    terms[2 * c] = params[c].term;
-    terms[2 * c + 1] = params[c].field;
-    for (size_t op = 0; op < op_term.size(); op++)
-      if (op_term[op] == params[c].term) cols[2 * op + (params[c].field == ILQG_PARAM_WEIGHT ? 0 : 1)] = int(c);
-  }
-  for (size_t q = 0; q < subs.size(); q++) {
-    const int c = int(params.size() + q), s = subs[q];
-    terms[2 * c] = -1;
-    terms[2 * c + 1] = s;
-    terms[2 * count + s] = c;
-    for (size_t op = 0; op < op_sub.size(); op++) {
-      if (op_sub[op] == s) cols[2 * op] = c;
-      if (op_sub[op] == s - 1 && op_sub[op] >= 0 && p->dev.sub_kind[s] == ILQG_DYN_AIR_3D_PURSUER) cols[2 * op + 1] = c;
-    }
-  }
-  const char* what = "instance parameter tables";
-  // kernels of earlier calls on any stream may still read the old tables (unbound: they look at neither)
-  hipError_t e = hipDeviceSynchronize();
-  if (e != hipSuccess) return hip_failed(what, e);
-  DeviceBuffer<int> d_terms;
-  const ilqg_status s = upload(terms, 0, what, &d_terms);
-  if (s != ILQG_OK) return s;
-  e = copy_to_device(p->d_row_prog.get() + p->row_prog.words.size(), cols);
-  if (e != hipSuccess) return hip_failed(what, e);
-  p->d_inst_terms = std::move(d_terms);  // the old table goes only now that the new one is up
-  p->inst_params = params;
-  p->inst_subs = subs;
   return ILQG_OK;
 }
 

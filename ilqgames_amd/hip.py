@@ -81,6 +81,16 @@ def _dev(a, dtype):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=torch_dtype(dtype), device="cuda").contiguous()
 
 
+def _table(a, torch_type):
+    """`a` as a contiguous CUDA tensor of this torch dtype: itself where it is one already (a bound table the caller
+    may then rewrite in place), uploaded where it is not."""
+    import torch
+    if isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch_type and a.is_contiguous():
+        return a
+    np_type = np.float32 if torch_type == torch.float32 else np.float64
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np_type), device="cuda").contiguous()
+
+
 def _stream():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -261,6 +271,9 @@ class Problem:
         # the library's choice, which depends on the batch size: tests that compare a slice with its batch bit for bit
         # pin it)
         self.single_wave_sweep = None
+        # per-instance bindings: what the declare calls recorded, and the bound tables, kept alive while bound
+        self.instance_params, self.instance_subsystems, self.instance_routes = [], [], []
+        self._instance_values = self._instance_time_nominals = None
 
     def __del__(self):
         try:
@@ -306,10 +319,8 @@ class Problem:
         if points is None:
             _check(lib().ilqg_problem_bind_instance_routes(self.h, 0, None, st))
             return None
-        if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32 and
-                points.is_contiguous()):
-            points = torch.as_tensor(np.ascontiguousarray(points, dtype=np.float32), device="cuda").contiguous()
-        P = sum(len(self.spec.polylines[q]) for q in getattr(self, "instance_routes", []))
+        points = _table(points, torch.float32)
+        P = sum(len(self.spec.polylines[q]) for q in self.instance_routes)
         if points.dim() != 3 or points.shape[1] != P or points.shape[2] != 2:
             raise ValueError("instance routes must be [batch][%d][2], got %s" % (P, tuple(points.shape)))
         _check(lib().ilqg_problem_bind_instance_routes(self.h, points.shape[0], C.c_void_p(points.data_ptr()), st))
@@ -331,9 +342,7 @@ class Problem:
         The result is not bound: pass it to bind_instance_time_nominals."""
         import torch
         st = C.c_void_p(stream if stream is not None else torch.cuda.current_stream().cuda_stream)
-        if not (isinstance(speed_pos, torch.Tensor) and speed_pos.is_cuda and speed_pos.dtype == torch.float32 and
-                speed_pos.is_contiguous()):
-            speed_pos = torch.as_tensor(np.ascontiguousarray(speed_pos, dtype=np.float32), device="cuda").contiguous()
+        speed_pos = _table(speed_pos, torch.float32)
         tables = len(self.time_nominal_terms())
         if speed_pos.dim() != 3 or speed_pos.shape[1] != tables or speed_pos.shape[2] != 2:
             raise ValueError("speed_pos must be [batch][%d][2], got %s" % (tables, tuple(speed_pos.shape)))
@@ -357,9 +366,7 @@ class Problem:
             _check(lib().ilqg_problem_bind_instance_time_nominals(self.h, 0, None))
             self._instance_time_nominals = None
             return None
-        if not (isinstance(table, torch.Tensor) and table.is_cuda and table.dtype == torch.float64 and
-                table.is_contiguous()):
-            table = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float64), device="cuda").contiguous()
+        table = _table(table, torch.float64)
         if table.dim() != 4 or table.shape[2] != self.T or table.shape[3] != 2:
             raise ValueError("instance time nominals must be [batch][tables][%d][2], got %s" % (self.T, tuple(table.shape)))
         tables = len(self.time_nominal_terms())
@@ -378,10 +385,8 @@ class Problem:
             _check(lib().ilqg_problem_bind_instance_values(self.h, 0, None))
             self._instance_values = None
             return None
-        if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float32 and
-                values.is_contiguous()):
-            values = torch.as_tensor(np.ascontiguousarray(values, dtype=np.float32), device="cuda").contiguous()
-        count = len(getattr(self, "instance_params", [])) + len(getattr(self, "instance_subsystems", []))
+        values = _table(values, torch.float32)
+        count = len(self.instance_params) + len(self.instance_subsystems)
         if values.dim() != 2 or values.shape[1] != count:
             raise ValueError("instance values must be [batch][%d], got %s" % (count, tuple(values.shape)))
         _check(lib().ilqg_problem_bind_instance_values(self.h, values.shape[0], C.c_void_p(values.data_ptr())))

@@ -1054,61 +1054,8 @@ class DeviceSolve {
                   size_t first_row = 0) {
     size_t B = x0s.size();
     CHECK_GT(B, 0);
-    // per-instance cost parameters: rows [first_row, first_row + B) of the caller's table, bound for this solve only
-    InstanceBinding binding(handle_);
-    if (instance_params != nullptr && !instance_params->time_nominals.empty()) {
-      // blocks [first_row, first_row + B) of the caller's table, bound for this solve only
-      int32_t tables = 0;
-      CHECK_EQ(ilqg_problem_time_nominal_terms(handle_, nullptr, 0, &tables), ILQG_OK) << ilqg_last_error();
-      const size_t block = static_cast<size_t>(tables) * static_cast<size_t>(T_) * 2;
-      CHECK_GT(block, 0u) << "instance time nominals: the problem has no NominalPathLengthCost or RouteProgressCost";
-      CHECK_GE(instance_params->time_nominals.size(), (first_row + B) * block) << "instance time nominals: one block per instance";
-      const double* rows = instance_params->time_nominals.data() + first_row * block;
-      HipCheck(hipMemcpy(d_instance_time_nominals_.Reserve(B * block * sizeof(double)), rows, B * block * sizeof(double),
-                         hipMemcpyHostToDevice), "instance time nominals");
-      binding.bound = true;
-      CHECK_EQ(ilqg_problem_bind_instance_time_nominals(handle_, static_cast<int32_t>(B),
-                                                        static_cast<const double*>(d_instance_time_nominals_.get())), ILQG_OK)
-          << ilqg_last_error();
-    }
-    if (instance_params != nullptr && !(instance_params->params.empty() && instance_params->subsystems.empty() &&
-                                        instance_params->route_polylines.empty())) {
-      std::vector<ilqg_instance_param> declared;
-      std::vector<int32_t> rows_declared, routes_declared;
-      std::string why;
-      CHECK(ResolveInstanceParams(description_, *instance_params, &declared, &why, &rows_declared, &routes_declared)) << why;
-      binding.bound = true;
-      const size_t count = declared.size() + rows_declared.size();  // [cost params | subsystem params]
-      if (count > 0) {
-        CHECK_GE(instance_params->values.size(), (first_row + B) * count) << "instance parameter values: one row per instance";
-        CHECK_EQ(ilqg_problem_declare_instance_params(handle_, static_cast<int32_t>(declared.size()), declared.data()), ILQG_OK)
-            << ilqg_last_error();
-        CHECK_EQ(ilqg_problem_declare_instance_subsystem_params(handle_, static_cast<int32_t>(rows_declared.size()),
-                                                                rows_declared.data()), ILQG_OK)
-            << ilqg_last_error();
-        const float* rows = instance_params->values.data() + first_row * count;
-        HipCheck(hipMemcpy(d_instance_values_.Reserve(B * count * sizeof(float)), rows, B * count * sizeof(float),
-                           hipMemcpyHostToDevice), "instance parameter values");
-        CHECK_EQ(ilqg_problem_bind_instance_values(handle_, static_cast<int32_t>(B),
-                                                   static_cast<const float*>(d_instance_values_.get())), ILQG_OK)
-            << ilqg_last_error();
-      }
-      if (!routes_declared.empty()) {  // rows [first_row, first_row + B) of the caller's points, consumed by the bind
-        size_t row_floats = 0;
-        for (int32_t q : routes_declared)
-          row_floats += 2 * static_cast<size_t>(description_.polyline_offsets[q + 1] - description_.polyline_offsets[q]);
-        CHECK_GE(instance_params->routes.size(), (first_row + B) * row_floats) << "instance routes: one row per instance";
-        CHECK_EQ(ilqg_problem_declare_instance_routes(handle_, static_cast<int32_t>(routes_declared.size()),
-                                                      routes_declared.data()), ILQG_OK)
-            << ilqg_last_error();
-        const float* rows = instance_params->routes.data() + first_row * row_floats;
-        HipCheck(hipMemcpy(d_instance_routes_.Reserve(B * row_floats * sizeof(float)), rows, B * row_floats * sizeof(float),
-                           hipMemcpyHostToDevice), "instance routes");
-        CHECK_EQ(ilqg_problem_bind_instance_routes(handle_, static_cast<int32_t>(B),
-                                                   static_cast<const float*>(d_instance_routes_.get()), nullptr), ILQG_OK)
-            << ilqg_last_error();
-      }
-    }
+    InstanceBinding binding(handle_);  // the per-instance tables are bound for this solve only
+    if (instance_params != nullptr) BindInstanceTables(*instance_params, first_row, B, &binding);
     const auto start = Clock::now();
     // pack the warm start once, replicate per instance
     std::vector<float> x0(B * n_), xs(B * T_ * n_), us(B * T_ * m_), P(B * T_ * m_ * n_), alpha(B * T_ * m_);
@@ -1298,6 +1245,56 @@ class DeviceSolve {
   }
 
  private:
+  // Rows [first_row, first_row + B) of each of the caller's per-instance tables onto the device, declared and bound on
+  // the handle until `binding` goes
+  void BindInstanceTables(const InstanceParams& instance_params, size_t first_row, size_t B, InstanceBinding* binding) {
+    // those rows of `table` (`row_elems` scalars each) in `buffer`; `what` names the table, `unit` an instance's part of it
+    auto rows_on_device = [&](const auto& table, size_t row_elems, DeviceBuffer* buffer, const char* what, const char* unit) {
+      using Scalar = typename std::decay_t<decltype(table)>::value_type;
+      CHECK_GE(table.size(), (first_row + B) * row_elems) << what << ": one " << unit << " per instance";
+      HipCheck(hipMemcpy(buffer->Reserve(B * row_elems * sizeof(Scalar)), table.data() + first_row * row_elems,
+                         B * row_elems * sizeof(Scalar), hipMemcpyHostToDevice), what);
+      return static_cast<const Scalar*>(buffer->get());
+    };
+    const int32_t batch = static_cast<int32_t>(B);
+    if (!instance_params.time_nominals.empty()) {
+      int32_t tables = 0;
+      CHECK_EQ(ilqg_problem_time_nominal_terms(handle_, nullptr, 0, &tables), ILQG_OK) << ilqg_last_error();
+      const size_t block = static_cast<size_t>(tables) * static_cast<size_t>(T_) * 2;
+      CHECK_GT(block, 0u) << "instance time nominals: the problem has no NominalPathLengthCost or RouteProgressCost";
+      const double* rows = rows_on_device(instance_params.time_nominals, block, &d_instance_time_nominals_,
+                                          "instance time nominals", "block");
+      binding->bound = true;
+      CHECK_EQ(ilqg_problem_bind_instance_time_nominals(handle_, batch, rows), ILQG_OK) << ilqg_last_error();
+    }
+    if (instance_params.params.empty() && instance_params.subsystems.empty() && instance_params.route_polylines.empty()) return;
+    std::vector<ilqg_instance_param> declared;
+    std::vector<int32_t> rows_declared, routes_declared;
+    std::string why;
+    CHECK(ResolveInstanceParams(description_, instance_params, &declared, &why, &rows_declared, &routes_declared)) << why;
+    binding->bound = true;
+    const size_t count = declared.size() + rows_declared.size();  // [cost params | subsystem params]
+    if (count > 0) {
+      const float* rows = rows_on_device(instance_params.values, count, &d_instance_values_, "instance parameter values", "row");
+      CHECK_EQ(ilqg_problem_declare_instance_params(handle_, static_cast<int32_t>(declared.size()), declared.data()), ILQG_OK)
+          << ilqg_last_error();
+      CHECK_EQ(ilqg_problem_declare_instance_subsystem_params(handle_, static_cast<int32_t>(rows_declared.size()),
+                                                              rows_declared.data()), ILQG_OK)
+          << ilqg_last_error();
+      CHECK_EQ(ilqg_problem_bind_instance_values(handle_, batch, rows), ILQG_OK) << ilqg_last_error();
+    }
+    if (!routes_declared.empty()) {  // (the points are consumed by the bind)
+      size_t row_floats = 0;
+      for (int32_t q : routes_declared)
+        row_floats += 2 * static_cast<size_t>(description_.polyline_offsets[q + 1] - description_.polyline_offsets[q]);
+      const float* rows = rows_on_device(instance_params.routes, row_floats, &d_instance_routes_, "instance routes", "row");
+      CHECK_EQ(ilqg_problem_declare_instance_routes(handle_, static_cast<int32_t>(routes_declared.size()),
+                                                    routes_declared.data()), ILQG_OK)
+          << ilqg_last_error();
+      CHECK_EQ(ilqg_problem_bind_instance_routes(handle_, batch, rows, nullptr), ILQG_OK) << ilqg_last_error();
+    }
+  }
+
   const ilqg_dtype dtype_;
   ProblemDescription description_;
   std::string fingerprint_;

@@ -6,108 +6,10 @@
 //   instance_routes_demo solve f64|f32 B out.bin  a batch of B games with the bend of player 2's turn lane displaced per
 //                                                 instance; writes [x0 | points | final xs | final us] as raw doubles
 // tests/test_instance_routes.py and tests/test_gpu_instance_routes.py replay both through the Python harness.
-#include <ilqgames/host/api.hpp>
-
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <iostream>
-#include <memory>
-#include <string>
-#include <vector>
+#include "instance_demo.h"
 
 namespace ilqgames {
 namespace {
-
-class HeadlineScene : public TopDownRenderableProblem {
- public:
-  using Car = SinglePlayerCar5D;
-  using Walker = SinglePlayerUnicycle4D;
-  static constexpr Dimension kP1 = 0, kP2 = 5, kP3 = 10;
-  // the objects a test declares as per-instance parameters
-  std::shared_ptr<QuadraticCost> p1_nominal_speed;
-  std::shared_ptr<QuadraticPolyline2Cost> p2_lane;
-  std::shared_ptr<ProximityCost> p1_proximity_p2;
-  // player 2's turn lane as the costs were built from it (they keep copies): what a test names as a per-instance route
-  Polyline2 lane2;
-
-  void ConstructDynamics() override {
-    dynamics_.reset(new ConcatenatedDynamicalSystem(
-        {std::make_shared<Car>(4.0f), std::make_shared<Car>(4.0f), std::make_shared<Walker>()}));
-  }
-  void ConstructInitialState() override {
-    x0_ = VectorXf::Zero(dynamics_->XDim());
-    x0_(kP1 + Car::kPxIdx) = -2.0f;
-    x0_(kP1 + Car::kPyIdx) = -30.0f;
-    x0_(kP1 + Car::kThetaIdx) = static_cast<float>(M_PI / 2);
-    x0_(kP1 + Car::kVIdx) = 4.0f;
-    x0_(kP2 + Car::kPxIdx) = -10.0f;
-    x0_(kP2 + Car::kPyIdx) = 45.0f;
-    x0_(kP2 + Car::kThetaIdx) = static_cast<float>(-M_PI / 2);
-    x0_(kP2 + Car::kVIdx) = 3.0f;
-    x0_(kP3 + Walker::kPxIdx) = -11.0f;
-    x0_(kP3 + Walker::kPyIdx) = 16.0f;
-    x0_(kP3 + Walker::kVIdx) = 1.25f;
-  }
-  void ConstructPlayerCosts() override {
-    for (const char* name : {"P1", "P2", "P3"}) player_costs_.emplace_back(name, 10.0f, 10.0f);
-    const Polyline2 lane1({Point2(-2.0f, -1000.0f), Point2(-2.0f, 1000.0f)});
-    lane2 = Polyline2({Point2(-10.0f, 1000.0f), Point2(-10.0f, 28.0f), Point2(-9.5f, 25.0f), Point2(-9.0f, 24.0f),
-                           Point2(-7.0f, 22.5f), Point2(-4.0f, 22.0f), Point2(1000.0f, 22.0f)});
-    const Polyline2 lane3({Point2(-1000.0f, 16.0f), Point2(1000.0f, 16.0f)});
-    const Polyline2* lanes[3] = {&lane1, &lane2, &lane3};
-    const Dimension base[3] = {kP1, kP2, kP3};
-    const Dimension vidx[3] = {kP1 + Car::kVIdx, kP2 + Car::kVIdx, kP3 + Walker::kVIdx};
-    const float vmax[3] = {12.0f, 12.0f, 2.0f}, vnom[3] = {8.0f, 6.0f, 1.5f};
-    const auto xy = [&](PlayerIndex ii) { return std::make_pair(base[ii], Dimension(base[ii] + 1)); };
-    for (PlayerIndex ii = 0; ii < 3; ii++) {
-      auto lane = std::make_shared<QuadraticPolyline2Cost>(25.0f, *lanes[ii], xy(ii), "lane");
-      if (ii == 1) p2_lane = lane;
-      player_costs_[ii].AddStateCost(lane);
-      player_costs_[ii].AddStateCost(std::make_shared<SemiquadraticPolyline2Cost>(100.0f, *lanes[ii], xy(ii), 2.5f, true, "right"));
-      player_costs_[ii].AddStateCost(std::make_shared<SemiquadraticPolyline2Cost>(100.0f, *lanes[ii], xy(ii), -2.5f, false, "left"));
-    }
-    for (PlayerIndex ii = 0; ii < 3; ii++) {
-      player_costs_[ii].AddStateCost(std::make_shared<SemiquadraticCost>(100.0f, vidx[ii], 1.0f, false, "min v"));
-      player_costs_[ii].AddStateCost(std::make_shared<SemiquadraticCost>(100.0f, vidx[ii], vmax[ii], true, "max v"));
-      auto nominal = std::make_shared<QuadraticCost>(10.0f, vidx[ii], vnom[ii], "nominal v");
-      if (ii == 0) p1_nominal_speed = nominal;
-      player_costs_[ii].AddStateCost(nominal);
-    }
-    for (PlayerIndex ii = 0; ii < 3; ii++) {
-      player_costs_[ii].AddControlCost(ii, std::make_shared<QuadraticCost>(0.1f, 0, 0.0f, "u0"));
-      player_costs_[ii].AddControlCost(ii, std::make_shared<QuadraticCost>(0.1f, 1, 0.0f, "u1"));
-    }
-    for (PlayerIndex ii = 0; ii < 3; ii++)
-      for (PlayerIndex jj = 0; jj < 3; jj++) {
-        if (jj == ii) continue;
-        auto gap = std::make_shared<ProximityCost>(0.0f, xy(ii), xy(jj), 6.0f, "proximity");
-        if (ii == 0 && jj == 1) p1_proximity_p2 = gap;
-        player_costs_[ii].AddStateCost(gap);
-      }
-  }
-  std::vector<float> Xs(const VectorXf& x) const override { return {x(kP1), x(kP2), x(kP3)}; }
-  std::vector<float> Ys(const VectorXf& x) const override { return {x(kP1 + 1), x(kP2 + 1), x(kP3 + 1)}; }
-  std::vector<float> Thetas(const VectorXf& x) const override { return {x(kP1 + 2), x(kP2 + 2), x(kP3 + 2)}; }
-};
-
-struct Lcg {  // [-1, 1), reproducible
-  uint32_t state;
-  float next() {
-    state = state * 1664525u + 1013904223u;
-    return static_cast<float>(static_cast<int32_t>(state >> 8) % 20001 - 10000) * 1e-4f;
-  }
-};
-
-SolverParams Params() {
-  SolverParams params;
-  params.max_backtracking_steps = 100;
-  params.initial_alpha_scaling = 0.1f;
-  params.convergence_tolerance = 1.0f;
-  params.expected_decrease_fraction = 0.001f;
-  params.max_solver_iters = 25;
-  return params;
-}
 
 // player 2's turn lane, named by address
 host::InstanceParams Declared(const HeadlineScene& scene) {
@@ -172,15 +74,7 @@ int main(int argc, char** argv) {
   host::Options().dtype = std::strcmp(argv[2], "f32") == 0 ? ILQG_F32 : ILQG_F64;
   const size_t B = static_cast<size_t>(std::atoi(argv[3]));
   Lcg rng{2024u};
-  std::vector<VectorXf> x0s;
-  for (size_t b = 0; b < B; b++) {
-    VectorXf x = scene->InitialState();
-    for (Dimension base : {HeadlineScene::kP1, HeadlineScene::kP2, HeadlineScene::kP3}) {
-      x(base) += rng.next();
-      x(base + 1) += rng.next();
-    }
-    x0s.push_back(x);
-  }
+  const std::vector<VectorXf> x0s = JitteredStates(*scene, {HeadlineScene::kP1, HeadlineScene::kP2, HeadlineScene::kP3}, 1.0f, B, &rng);
   const PointList2 lane = scene->lane2.Points();
   for (size_t b = 0; b < B; b++)
     for (size_t k = 0; k < lane.size(); k++) {  // the end of the straight and the bend move by up to 1.5 m
@@ -188,26 +82,5 @@ int main(int argc, char** argv) {
       ip.routes.push_back(lane[k].x() + (moves ? 1.5f * rng.next() : 0.0f));
       ip.routes.push_back(lane[k].y() + (moves ? 1.5f * rng.next() : 0.0f));
     }
-  ILQSolver solver(scene, params);
-  const host::BatchResult result = solver.SolveBatch(x0s, ip);
-  CHECK_EQ(result.logs.size(), B);
-  std::vector<double> out;
-  for (const auto& x : x0s)
-    for (Dimension e = 0; e < x.size(); e++) out.push_back(x(e));
-  for (float v : ip.routes) out.push_back(v);
-  for (size_t b = 0; b < B; b++)
-    for (const auto& x : result.logs[b]->FinalOperatingPoint().xs)
-      for (Dimension e = 0; e < x.size(); e++) out.push_back(x(e));
-  for (size_t b = 0; b < B; b++)
-    for (const auto& us : result.logs[b]->FinalOperatingPoint().us)
-      for (const auto& u : us)
-        for (Dimension e = 0; e < u.size(); e++) out.push_back(u(e));
-  FILE* f = std::fopen(argv[4], "wb");
-  CHECK(f != nullptr);
-  CHECK_EQ(std::fwrite(out.data(), sizeof(double), out.size(), f), out.size());
-  std::fclose(f);
-  // the solve unbinds what it bound: the plain call still runs, as before
-  const host::BatchResult plain = solver.SolveBatch(x0s);
-  CHECK_EQ(plain.logs.size(), B);
-  return 0;
+  return SolveAndWrite(scene, params, x0s, ip, std::vector<double>(ip.routes.begin(), ip.routes.end()), argv[4]);
 }

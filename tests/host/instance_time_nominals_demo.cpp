@@ -9,15 +9,7 @@
 //                                                        [x0 | speed_pos | time nominals | final xs | final us] as raw
 //                                                        doubles
 // tests/test_gpu_instance_time_nominals.py replays both through the Python harness.
-#include <ilqgames/host/api.hpp>
-
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <iostream>
-#include <memory>
-#include <string>
-#include <vector>
+#include "instance_demo.h"
 
 namespace ilqgames {
 namespace {
@@ -70,24 +62,6 @@ class TwoCarScene : public TopDownRenderableProblem {
   std::vector<float> Thetas(const VectorXf& x) const override { return {x(kP1 + 2), x(kP2 + 2)}; }
 };
 
-struct Lcg {  // [-1, 1), reproducible
-  uint32_t state;
-  float next() {
-    state = state * 1664525u + 1013904223u;
-    return static_cast<float>(static_cast<int32_t>(state >> 8) % 20001 - 10000) * 1e-4f;
-  }
-};
-
-SolverParams Params() {
-  SolverParams params;
-  params.max_backtracking_steps = 100;
-  params.initial_alpha_scaling = 0.1f;
-  params.convergence_tolerance = 0.1f;
-  params.expected_decrease_fraction = 0.001f;
-  params.max_solver_iters = 15;
-  return params;
-}
-
 // player 2's route first, then player 1's: not the tables' order
 host::InstanceParams Declared(const TwoCarScene& scene) {
   host::InstanceParams ip;
@@ -107,7 +81,7 @@ int main(int argc, char** argv) {
   }
   auto scene = std::make_shared<TwoCarScene>();
   scene->Initialize();
-  const SolverParams params = Params();
+  const SolverParams params = Params(0.1f, 15);
   host::InstanceParams ip = Declared(*scene);
   const ilqg_dtype dtype = (argc > 2 && std::strcmp(argv[2], "f32") == 0) ? ILQG_F32 : ILQG_F64;
   host::ProblemDescription description;
@@ -140,15 +114,7 @@ int main(int argc, char** argv) {
   host::Options().dtype = dtype;
   const size_t B = static_cast<size_t>(std::atoi(argv[3]));
   Lcg rng{2025u};
-  std::vector<VectorXf> x0s;
-  for (size_t b = 0; b < B; b++) {
-    VectorXf x = scene->InitialState();
-    for (Dimension base : {TwoCarScene::kP1, TwoCarScene::kP2}) {
-      x(base) += rng.next();
-      x(base + 1) += 0.5f * rng.next();
-    }
-    x0s.push_back(x);
-  }
+  const std::vector<VectorXf> x0s = JitteredStates(*scene, {TwoCarScene::kP1, TwoCarScene::kP2}, 0.5f, B, &rng);
   std::vector<float> speed_pos;  // [B][2 references][2]: player 2's route, then player 1's
   for (size_t b = 0; b < B; b++) {
     speed_pos.push_back(4.0f + 2.0f * rng.next());
@@ -157,27 +123,7 @@ int main(int argc, char** argv) {
     speed_pos.push_back(14.0f + 5.0f * rng.next());  // some pass the corner at route position 20
   }
   CHECK(host::FillInstanceTimeNominals(description, B, speed_pos, &ip, &why)) << why;
-  ILQSolver solver(scene, params);
-  const host::BatchResult result = solver.SolveBatch(x0s, ip);
-  CHECK_EQ(result.logs.size(), B);
-  std::vector<double> out;
-  for (const auto& x : x0s)
-    for (Dimension e = 0; e < x.size(); e++) out.push_back(x(e));
-  for (float v : speed_pos) out.push_back(v);
-  for (double v : ip.time_nominals) out.push_back(v);
-  for (size_t b = 0; b < B; b++)
-    for (const auto& x : result.logs[b]->FinalOperatingPoint().xs)
-      for (Dimension e = 0; e < x.size(); e++) out.push_back(x(e));
-  for (size_t b = 0; b < B; b++)
-    for (const auto& us : result.logs[b]->FinalOperatingPoint().us)
-      for (const auto& u : us)
-        for (Dimension e = 0; e < u.size(); e++) out.push_back(u(e));
-  FILE* f = std::fopen(argv[4], "wb");
-  CHECK(f != nullptr);
-  CHECK_EQ(std::fwrite(out.data(), sizeof(double), out.size(), f), out.size());
-  std::fclose(f);
-  // the solve unbinds what it bound: the plain call still runs, as before
-  const host::BatchResult plain = solver.SolveBatch(x0s);
-  CHECK_EQ(plain.logs.size(), B);
-  return 0;
+  std::vector<double> inputs(speed_pos.begin(), speed_pos.end());
+  inputs.insert(inputs.end(), ip.time_nominals.begin(), ip.time_nominals.end());
+  return SolveAndWrite(scene, params, x0s, ip, inputs, argv[4]);
 }

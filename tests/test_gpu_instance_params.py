@@ -12,10 +12,9 @@ import pytest
 
 from ilqgames_amd import abi, examples
 from helpers import rel_err
+from instance_harness import KEYS, check_baked_equals_bound, headline as _headline, same_bits as _same_bits, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
-
-KEYS = ("xs", "us", "P", "alpha", "costs", "iters", "status", "converged")
 
 
 @pytest.fixture(scope="module")
@@ -28,24 +27,7 @@ def hip():
     return h
 
 
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 # ---- scenes: what varies per instance, and the range each value is drawn from ----
-def _headline():
-    s = examples.modified_three_player_intersection()
-    s.params.initial_alpha_scaling = 0.1          # the bench's line-search parameters
-    s.params.expected_decrease_fraction = 0.001
-    s.params.max_solver_iters = 25
-    return s
-
-
 HEADLINE_DECL = [("p1_nominal_speed", "value", 6.0, 10.0), ("p2_nominal_speed", "value", 4.0, 8.0),
                  ("p3_nominal_speed", "weight", 5.0, 20.0), ("p1_lane", "weight", 15.0, 35.0),
                  ("p2_lane", "weight", 15.0, 35.0),
@@ -91,31 +73,10 @@ def _bound_problem(hip, spec, dtype, params, table):
     return prob
 
 
-def _check_baked_equals_bound(hip, spec, decl, dtype, B=12, BV=4, seed=5, whole_batch_partner=False, **solve_kw):
+def _check_baked_equals_bound(hip, spec, decl, dtype, BV=4, seed=5, **kw):
     params, vals = _draw(decl, BV, seed)
-    x0 = examples.jittered_x0(spec, B, seed=seed + 1)
-    which = np.arange(B) % BV
-    prob = _bound_problem(hip, spec, dtype, params, vals[which])
-    out = {k: _np(v) for k, v in prob.solve(x0, **solve_kw).items() if k in KEYS}
-    row_program = prob.row_program()
-    differ = False
-    for v in range(BV):
-        sel = np.nonzero(which == v)[0]
-        ref_prob = hip.Problem(_baked(spec, params, vals[v]), dtype)
-        # deterministic solves: an instance's bits do not depend on its batch, the partner solves its instances alone;
-        # otherwise the partner is a homogeneous batch of the same size (the same schedule)
-        ref = ref_prob.solve(x0 if whole_batch_partner else x0[sel], **solve_kw)
-        for k in KEYS:
-            r = _np(ref[k])
-            r = r[sel] if whole_batch_partner else r
-            assert _same_bits(out[k][sel], r), (k, v, np.nonzero(np.any((out[k][sel] != r).reshape(len(sel), -1), axis=1))[0])
-        if v > 0:
-            differ = differ or not _same_bits(out["xs"][sel[0]][1:], out["xs"][np.nonzero(which == 0)[0][0]][1:])
-    assert differ, "the drawn vectors should lead to different trajectories"
-    assert int(out["iters"].min()) > 0
-    # the declaration is a side table: the row program and the static structure it matched are the descriptor's
-    plain = hip.Problem(spec, dtype).row_program()
-    assert np.array_equal(row_program[0], plain[0]) and row_program[1] == plain[1]
+    check_baked_equals_bound(hip, spec, dtype, lambda table: _bound_problem(hip, spec, dtype, params, table),
+                             lambda row: _baked(spec, params, row), vals, seed=seed, **kw)
 
 
 # ---- 1. baked equals bound, bit for bit ----

@@ -12,10 +12,9 @@ import pytest
 
 from ilqgames_amd import abi, examples
 from helpers import rel_err
+from instance_harness import KEYS, check_baked_equals_bound, headline as _headline, same_bits as _same_bits, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
-
-KEYS = ("xs", "us", "P", "alpha", "costs", "iters", "status", "converged")
 
 
 @pytest.fixture(scope="module")
@@ -28,24 +27,7 @@ def hip():
     return h
 
 
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 # ---- scenes: which points of which polyline move, and by how much at most (metres, each coordinate) ----
-def _headline():
-    s = examples.modified_three_player_intersection()
-    s.params.initial_alpha_scaling = 0.1          # the bench's line-search parameters
-    s.params.expected_decrease_fraction = 0.001
-    s.params.max_solver_iters = 25
-    return s
-
-
 HEADLINE_ROUTES = [(1, (1, 2, 3, 4, 5), 1.5)]  # player 2's turn lane: the end of the straight and the bend
 ZOO_ROUTES = [(2, (1, 2, 3), 1.0)]             # the wall of the signed-distance constraint: its bulge into lane 1
 MIXED_ROUTES = [(0, (1, 2), 1.5)]              # the car's lane: its two inner vertices
@@ -95,38 +77,12 @@ def _bound_problem(hip, spec, dtype, polylines, table):
     return prob
 
 
-def _check_baked_equals_bound(hip, spec, routes, dtype, B=12, BV=4, seed=5, whole_batch_partner=False, **solve_kw):
+def _check_baked_equals_bound(hip, spec, routes, dtype, BV=4, **kw):
     """routes: (polylines, float32 [BV][P][2]); instance b takes route vector b % BV."""
     polylines, vecs = routes
     assert len(vecs) == BV
-    x0 = examples.jittered_x0(spec, B, seed=seed + 1)
-    which = np.arange(B) % BV
-    prob = _bound_problem(hip, spec, dtype, polylines, vecs[which])
-    out = {k: _np(v) for k, v in prob.solve(x0, **solve_kw).items() if k in KEYS}
-    row_program = prob.row_program()
-    differ = False
-    for v in range(BV):
-        sel = np.nonzero(which == v)[0]
-        ref_prob = hip.Problem(_baked(spec, polylines, vecs[v]), dtype)
-        # deterministic solves: an instance's bits do not depend on its batch, the partner solves its instances alone;
-        # otherwise the partner is a homogeneous batch of the same size (the same schedule)
-        ref = ref_prob.solve(x0 if whole_batch_partner else x0[sel], **solve_kw)
-        for k in KEYS:
-            r = _np(ref[k])
-            r = r[sel] if whole_batch_partner else r
-            assert _same_bits(out[k][sel], r), (k, v, np.nonzero(np.any((out[k][sel] != r).reshape(len(sel), -1), axis=1))[0])
-        if v == 0:
-            ref0_prob, ref0_xs = ref_prob, _np(ref["xs"])
-        else:  # the same instance, from the same x0, under route vector 0 and under vector v
-            b = sel[0]
-            under0 = ref0_xs[b] if whole_batch_partner else _np(ref0_prob.solve(x0[b:b + 1], **solve_kw)["xs"])[0]
-            differ = differ or not _same_bits(out["xs"][b], under0)
-    assert differ, "the route vectors should lead to different trajectories"
-    assert int(out["iters"].min()) > 0
-    # the declaration touches neither the row program nor the static structure it matched
-    plain = hip.Problem(spec, dtype).row_program()
-    assert np.array_equal(row_program[0], plain[0]) and row_program[1] == plain[1]
-    return prob, out, x0, which
+    return check_baked_equals_bound(hip, spec, dtype, lambda table: _bound_problem(hip, spec, dtype, polylines, table),
+                                    lambda row: _baked(spec, polylines, row), vecs, **kw)
 
 
 def _vertex_hits(oracle, pts, xy, dtype):

@@ -1,7 +1,7 @@
 """Per-instance subsystem parameters on the device (ilqg_problem_declare_instance_subsystem_params): a different
 wheelbase or speed for each game of a batch.
 
-As for the cost parameters (tests/test_gpu_instance_params.py, whose helpers are restated here), the core checks are
+As for the cost parameters (tests/test_gpu_instance_params.py; shared check: tests/instance_harness.py), the core checks are
 EXACT: an instance of a heterogeneous batch must return the bits of the same instance solved in a problem created with
 its param0 written into the descriptor — the values are floats on both paths and enter the arithmetic at the same place —
 over every instance and every output array.  Only the stage kernels against the oracle have tolerances, those of
@@ -18,10 +18,10 @@ import pytest
 
 from ilqgames_amd import abi, examples
 from helpers import rel_err
+from instance_harness import KEYS, check_baked_equals_bound, headline as _headline, same_bits as _same_bits, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("xs", "us", "P", "alpha", "costs", "iters", "status", "converged")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -33,23 +33,6 @@ def hip():
     name, _ = h.device_info()
     assert "gfx950" in name, name
     return h
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _headline():
-    s = examples.modified_three_player_intersection()
-    s.params.initial_alpha_scaling = 0.1          # the bench's line-search parameters
-    s.params.expected_decrease_fraction = 0.001
-    s.params.max_solver_iters = 25
-    return s
 
 
 WHEELBASE = (2.5, 5.0)
@@ -107,37 +90,11 @@ def _bound_problem(hip, spec, dtype, params, rows, table, subsystems_first=False
     return prob
 
 
-def _check_baked_equals_bound(hip, spec, rows, dtype, cost_decl=(), B=12, BV=4, seed=5, whole_batch_partner=False,
-                              subsystems_first=False, **solve_kw):
+def _check_baked_equals_bound(hip, spec, rows, dtype, cost_decl=(), BV=4, seed=5, subsystems_first=False, **kw):
     params, rows, vals = _draw(list(cost_decl), _sub_decl(spec, rows), BV, seed)
-    x0 = examples.jittered_x0(spec, B, seed=seed + 1)
-    which = np.arange(B) % BV
-    prob = _bound_problem(hip, spec, dtype, params, rows, vals[which], subsystems_first)
-    out = {k: _np(v) for k, v in prob.solve(x0, **solve_kw).items() if k in KEYS}
-    row_program = prob.row_program()
-    differ = False
-    for v in range(BV):
-        sel = np.nonzero(which == v)[0]
-        ref_prob = hip.Problem(_baked(spec, params, rows, vals[v]), dtype)
-        # deterministic solves: an instance's bits do not depend on its batch, the partner solves its instances alone;
-        # otherwise the partner is a homogeneous batch of the same size (the same schedule)
-        ref = ref_prob.solve(x0 if whole_batch_partner else x0[sel], **solve_kw)
-        for k in KEYS:
-            r = _np(ref[k])
-            r = r[sel] if whole_batch_partner else r
-            assert _same_bits(out[k][sel], r), (k, v, np.nonzero(np.any((out[k][sel] != r).reshape(len(sel), -1), axis=1))[0])
-        if v == 0:
-            ref0_prob, ref0_xs = ref_prob, _np(ref["xs"])
-        else:  # the same instance, from the same x0, under vector 0 and under vector v
-            b = sel[0]
-            under0 = ref0_xs[b] if whole_batch_partner else _np(ref0_prob.solve(x0[b:b + 1], **solve_kw)["xs"])[0]
-            differ = differ or not _same_bits(out["xs"][b], under0)
-    assert differ, "the drawn vectors should lead to different trajectories"
-    assert int(out["iters"].min()) > 0
-    # the declaration is a side table: the row program and the static structure it matched are the descriptor's
-    plain = hip.Problem(spec, dtype).row_program()
-    assert np.array_equal(row_program[0], plain[0]) and row_program[1] == plain[1]
-    return prob
+    return check_baked_equals_bound(hip, spec, dtype,
+                                    lambda table: _bound_problem(hip, spec, dtype, params, rows, table, subsystems_first),
+                                    lambda row: _baked(spec, params, rows, row), vals, seed=seed, **kw)[0]
 
 
 # ---- 1. bound equals baked, bit for bit ----

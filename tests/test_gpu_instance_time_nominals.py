@@ -16,10 +16,10 @@ import pytest
 from ilqgames_amd import abi, examples
 from test_instance_time_nominals import (MIXED_VECTORS, TWO_CAR_VECTORS, ZOO_VECTORS, mixed_route_scene, time_terms,
                                          two_car_scene, with_references, zoo20)
+from instance_harness import KEYS, check_baked_equals_bound, same_bits as _same_bits, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
 
-KEYS = ("xs", "us", "P", "alpha", "costs", "iters", "status", "converged")
 DTYPES = [abi.F64, abi.F32]
 
 
@@ -31,15 +31,6 @@ def hip():
     name, _ = h.device_info()
     assert "gfx950" in name, name
     return h
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def reach_scene():
@@ -89,36 +80,9 @@ def test_device_builder_equals_host_tables(hip, scene, dtype):
 
 
 # ---- 2. bound equals baked, bit for bit ----
-def _check_baked_equals_bound(hip, spec, vecs, dtype, B=12, seed=5, whole_batch_partner=False, **solve_kw):
-    BV = len(vecs)
-    x0 = examples.jittered_x0(spec, B, seed=seed + 1)
-    which = np.arange(B) % BV
-    prob = _bound_problem(hip, spec, dtype, vecs[which])
-    out = {k: _np(v) for k, v in prob.solve(x0, **solve_kw).items() if k in KEYS}
-    row_program = prob.row_program()
-    differ = False
-    for v in range(BV):
-        sel = np.nonzero(which == v)[0]
-        ref_prob = hip.Problem(with_references(spec, vecs[v]), dtype)
-        # deterministic solves: an instance's bits do not depend on its batch, the partner solves its instances alone;
-        # otherwise the partner is a homogeneous batch of the same size (the same schedule)
-        ref = ref_prob.solve(x0 if whole_batch_partner else x0[sel], **solve_kw)
-        for k in KEYS:
-            r = _np(ref[k])
-            r = r[sel] if whole_batch_partner else r
-            assert _same_bits(out[k][sel], r), (k, v, np.nonzero(np.any((out[k][sel] != r).reshape(len(sel), -1), axis=1))[0])
-        if v == 0:
-            ref0_prob, ref0_xs = ref_prob, _np(ref["xs"])
-        else:  # the same instance, from the same x0, under vector 0 and under vector v
-            b = sel[0]
-            under0 = ref0_xs[b] if whole_batch_partner else _np(ref0_prob.solve(x0[b:b + 1], **solve_kw)["xs"])[0]
-            differ = differ or not _same_bits(out["xs"][b], under0)
-    assert differ, "the reference vectors should lead to different trajectories"
-    assert int(out["iters"].min()) > 0
-    # the binding touches neither the row program nor the static structure it matched
-    plain = hip.Problem(spec, dtype).row_program()
-    assert np.array_equal(row_program[0], plain[0]) and row_program[1] == plain[1]
-    return prob, out, x0, which
+def _check_baked_equals_bound(hip, spec, vecs, dtype, **kw):
+    return check_baked_equals_bound(hip, spec, dtype, lambda speed_pos: _bound_problem(hip, spec, dtype, speed_pos),
+                                    lambda vec: with_references(spec, vec), vecs, **kw)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
