@@ -46,7 +46,8 @@ FLAG_ORIENTED, FLAG_IS_MIN, FLAG_EQUALITY = 1, 2, 4
 # ILQG_SCHEDULE_* (ilqg_problem_last_schedule)
 SCHEDULE_SINGLE_WAVE_SWEEP, SCHEDULE_ADJOINT_DECREASE, SCHEDULE_SPLIT_TRIAL, SCHEDULE_COMPACT_ROWS = 1, 2, 4, 8
 SCHEDULE_COUNTED, SCHEDULE_GENERIC, SCHEDULE_OPEN_LOOP, SCHEDULE_STATIC_ROWS = 16, 32, 64, 128
-SCHEDULE_PADDED_SWEEP = 256
+SCHEDULE_PADDED_SWEEP, SCHEDULE_CONSTANT_B = 256, 512
+B_ENTRY_LITERAL, B_ENTRY_DT, B_ENTRY_NEG_DT = 0, 1, 2  # ILQG_B_ENTRY_* (ilqg_sweep_b_structure_build)
 SUM, MAX, MIN = 0, 1, 2
 
 

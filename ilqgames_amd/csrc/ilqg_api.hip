@@ -505,7 +505,8 @@ __global__ void __launch_bounds__(256) ilq_exit_kernel(DevProblem p, SolveArgs<T
 // lets a CU hold instances (fp64: 20 KB -> eight per CU, two per SIMD; fp32: 10 KB -> sixteen, four per SIMD).
 // FORMS = false: the same sweep with the m x m solve's broadcasts through read-lanes (ilqg_solve_options::sweep_forms =
 // OFF), a second instantiation of the kinds that have the row-broadcast form: each step loop carries one of the two.
-template <typename T, int NX, int NP, int MU, int KIND, bool FORMS = true>
+// FORMS = 2: the player-parallel sweep with B's constant entries in registers as well (lq_part_instance).
+template <typename T, int NX, int NP, int MU, int KIND, int FORMS = 1>
 __global__ void __launch_bounds__((KIND == LQ_SINGLE_WAVE ? 64 : KIND == LQ_VALU_FEEDBACK ? LQCfg<T, NX, NP, MU>::NT : ((KIND == LQ_OPEN_LOOP || KIND == LQ_OPEN_LOOP_COMPACT) ? OLCfg<T, NX, NP, MU>::NT : 64 * NP)),
                                   (KIND == LQ_SINGLE_WAVE ? (sizeof(T) == 4 ? 4 : ILQG_1W_WAVES_F64) : KIND == LQ_PLAYER_WAVES_PACKED ? 4 : KIND == LQ_PLAYER_WAVES ? (NX <= 16 ? NP : 2) : ((KIND == LQ_OPEN_LOOP || KIND == LQ_OPEN_LOOP_COMPACT) ? 3 : 1)))
 ilq_lq_kernel(DevProblem p, SolveArgs<T> sa) {
@@ -1672,6 +1673,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   // over in (n = 24: 54 KB, three instances per CU; the feedback layout would take 85 KB).  fp32, one-tile sweep of
   // three player waves, many instances per CU: the 128-register build (see ilq_lq_kernel).
   constexpr bool has_packed = sizeof(T) == 4 && C::USE_MFMA && C::MFMA_ONE_TILE && NP == 3;
+  bool b_const = false;  // the sweep with B's constant entries in registers (ILQG_SCHEDULE_CONSTANT_B)
   if (open_loop) {
     plan.sweep = {ol_compact ? ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP_COMPACT> : ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP>,
                   O::NT, (O::LDS_ELEMS + 4) * sizeof(T)};
@@ -1683,20 +1685,29 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
     // ilqg_solve_options::sweep_forms = OFF: the read-lane instantiation of the same kind (only where the two differ)
     constexpr bool has_forms = C::MFMA_ONE_TILE && SolveRows<NP * MU, NX + 1>::FITS;
     const bool forms = choice(opt.sweep_forms, true);
+    // ... and with the forms on, a problem whose B is constant entries, at most one per row and column (ilqg_problem::
+    // b_constant), takes them from registers instead of the B tile — the solver's instantiation of the one-tile sweep with
+    // a spare tile column and two controls per player, i.e. compact rows and the forward pass in the trial kernel
+    constexpr bool has_bconst = has_forms && NX < 16 && MU == 2;
+    b_const = has_bconst && forms && p->b_constant && sa.compact && sa.defer_forward && !single_wave;
     if constexpr (has_forms)
-      if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES, false>;
+      if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES, 0>;
+    if constexpr (has_bconst)
+      if (b_const) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES, 2>;
     if constexpr (has_packed) {
       if (size_t(sched_batch) >= size_t(5) * 256) {
         plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED>;
         if constexpr (has_forms)
-          if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED, false>;
+          if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED, 0>;
+        if constexpr (has_bconst)
+          if (b_const) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED, 2>;
       }
     }
     if constexpr (has_1w) {
       if (single_wave) {
         plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_SINGLE_WAVE>, 64, size_t(W1Cfg<T, NX, NP, MU>::ELEMS + 4) * sizeof(T)};
         if constexpr (has_forms)
-          if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_SINGLE_WAVE, false>;
+          if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_SINGLE_WAVE, 0>;
       }
     }
   }
@@ -1738,7 +1749,8 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   p->last_schedule = (single_wave ? ILQG_SCHEDULE_SINGLE_WAVE_SWEEP : 0) | ((single_wave && adjoint) ? ILQG_SCHEDULE_ADJOINT_DECREASE : 0) |
                      (split ? ILQG_SCHEDULE_SPLIT_TRIAL : 0) | (sa.compact ? ILQG_SCHEDULE_COMPACT_ROWS : 0) |
                      (counted ? ILQG_SCHEDULE_COUNTED : 0) | (open_loop ? ILQG_SCHEDULE_OPEN_LOOP : 0) |
-                     ((static_prog || (static_id && split)) ? ILQG_SCHEDULE_STATIC_ROWS : 0);
+                     ((static_prog || (static_id && split)) ? ILQG_SCHEDULE_STATIC_ROWS : 0) |
+                     (b_const ? ILQG_SCHEDULE_CONSTANT_B : 0);
   return run_rounds(p, sa, tail, plan, opt, stream);
 }
 
@@ -2156,6 +2168,24 @@ ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words
   ProblemTables tables;
   const ilqg_status s = build_problem_tables(*desc, &tables);
   return s != ILQG_OK ? s : copy_row_program(tables.row_prog, tables.static_prog, words_out, capacity, num_words, static_id);
+}
+
+// The host half of creation alone, for what the feedback sweep may assume about B (ProblemTables::b_constant)
+ilqg_status ilqg_sweep_b_structure_build(const ilqg_problem_desc* desc, int32_t* constant_out, int32_t* entries_out,
+                                         int32_t capacity, int32_t* num_entries) {
+  static_assert(ILQG_B_ENTRY_LITERAL == RC_LITERAL && ILQG_B_ENTRY_DT == RC_DT && ILQG_B_ENTRY_NEG_DT == RC_NEG_DT, "ilqg.h");
+  if (!desc || !constant_out || !num_entries) return fail(ILQG_ERR_INVALID, "null argument");
+  ProblemTables tables;
+  const ilqg_status s = build_problem_tables(*desc, &tables);
+  if (s != ILQG_OK) return s;
+  const std::vector<int>& e = tables.row_prog.b_entries;
+  *constant_out = tables.b_constant ? 1 : 0;
+  *num_entries = int32_t(e.size() / 4);
+  if (entries_out) {
+    if (size_t(capacity) < e.size()) return fail(ILQG_ERR_INVALID, "ilqg_sweep_b_structure_build: buffer too small");
+    std::memcpy(entries_out, e.data(), sizeof(int32_t) * e.size());
+  }
+  return ILQG_OK;
 }
 
 // The host half of creation alone, for the segment table (DevProblem::segs_f / segs_d: 21 scalars per segment)

@@ -12,7 +12,8 @@
 // Two formulations (this is not the reference's loop nest):
 //   * n <= 16: lq_feedback_instance_mfma_pw — one wavefront per player, Z_i in MFMA accumulator-layout
 //     registers, every product a chain of v_mfma_*_16x16x4, operands DMA'd into zero-padded
-//     conflict-free LDS tiles (see the comment on that function and DESIGN.md §3.2);
+//     conflict-free LDS tiles (see the comment on that function and DESIGN.md §3.2); where B is constant entries, at
+//     most one per row and column, the solver's sweep multiplies by them from registers (BCONST);
 //   * larger n: lq_feedback_instance — lane t = i*NX + c owns COLUMN c of Z_i in registers;
 //     F^T Z_i F is two passes of "uniform matrix x private column" with broadcast LDS operands.
 // In both, the (m x m) Nash system with its n+1 right-hand sides lives one COLUMN PER LANE in wave 0
@@ -965,7 +966,20 @@ __device__ __forceinline__ void dma_tile(const T* g_, T* tile, int nrows, int nc
 // forward pass are not in its loop or its register allocation.
 // ROWBC: the m x m solve with row broadcasts (lu_solve_columns_rows) where its layout fits, else with read-lanes — a
 // compile-time choice, so that a kernel's step loop carries one of the two (ilqg_solve_options::sweep_forms).
-template <typename T, int NX, int NP, int MU, bool SOLVER = false, bool ROWBC = true>
+// BCONST: every non-zero of B is a constant of the compact rows' background, at most one per row and per column
+// (RowProgramHost::b_constant: B = dt x a selection matrix, every registered game).  The three places of a step that
+// multiply by B then take its entries from registers filled once per launch, and nothing reads the B tile:
+//   G[:, w MU + aa] = Z_w^T B    one multiply: b Z_w[row][j], on the lanes whose register holds that row of Z_w
+//   S = G_w^T B                  one LDS read of the G strip and one multiply per lane; Y = G_w^T A keeps its sums
+//   F = A - B [P | alpha]        fma(-b, P[col][j], A[row][j]) per accumulator row instead of two matrix instructions
+// Each replaced sum had one term that is not an exact zero, and the matrix pipe's accumulate is the vector unit's fma
+// (scripts/ubench/mfma_round.hip, both precisions), so the results are the bits of the dense form for finite operands
+// (a sum of exact zeros may come out -0 instead of +0; 0 x Inf no longer spreads a NaN).  A compile-time variant of
+// the SOLVER instantiation (SPARE, MU == 2), so that neither loop pays for the other: a problem whose B has a computed
+// entry runs the loop without it.  (A wave-uniform run-time flag around the three places instead, headline shape, fp64:
+// 168 VGPRs with a spill and 712 static instructions in the step loop, against 150 / none / 596 for this variant and
+// 150 / none / 620 for the dense one.)
+template <typename T, int NX, int NP, int MU, bool SOLVER = false, bool ROWBC = true, bool BCONST = false>
 __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a, const PairTable& pt, T* sm) {
   using C = LQCfg<T, NX, NP, MU>;
   using W = PWCfg<T, NX, NP, MU>;
@@ -1145,6 +1159,49 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
       sm[W::IMG + off] = v;
     }
   }
+  // BCONST: B's entries from the same list, loop invariant.  Per lane (g, j): for each accumulator row the negated
+  // entry of B in that row (0: none) and where the matching row of [P | alpha] is read (F); the entry in column j and
+  // its row in the G strip (S); the entries of the player's MU columns and which of the lane's registers holds their
+  // row of the Z_w tile (G; -1: a lane of another lane group — a per-lane value, so that the choice among the four
+  // registers is a select and not a scalar branch).
+  static_assert(!BCONST || (SOLVER && SPARE && MU == 2), "B's constant entries: the solver's sweep with a spare tile column");
+  T nbF[4] = {T(0), T(0), T(0), T(0)}, bS = T(0), bG[MU];
+  int oF[4] = {LD * j, LD * j, LD * j, LD * j}, oS = 0, selG[MU];
+#pragma unroll
+  for (int aa = 0; aa < MU; aa++) {
+    bG[aa] = T(0);
+    selG[aa] = g == 0 ? 0 : -1;  // a column without an entry: 0 x the first row
+  }
+  if constexpr (BCONST) {
+    const int nbg = a.compact_tab[RC_NBG];
+    const int* bg = a.compact_tab + RC_BASE + NP + 1 + CWD;
+    for (int e = 0; e < nbg; e++) {
+      const int code = bg[RC_BG_WORDS * e], kind = bg[RC_BG_WORDS * e + 1];
+      if ((code >> 24) != RA_B) continue;
+      const int col = (code & 0xffffff) / NX, row = (code & 0xffffff) - col * NX;
+      const T v = kind == RC_DT ? T(a.dt) : (kind == RC_NEG_DT ? T(-a.dt) : T(__int_as_float(bg[RC_BG_WORDS * e + 2])));
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        if (row == TL::row(g, r)) {
+          nbF[r] = -v;
+          oF[r] = col + LD * j;
+        }
+      }
+#pragma unroll
+      for (int aa = 0; aa < MU; aa++)
+        if (col == w * MU + aa) {
+          bG[aa] = v;
+          selG[aa] = -1;
+#pragma unroll
+          for (int r = 0; r < 4; r++)
+            if (row == TL::row(g, r)) selG[aa] = r;
+        }
+      if (col == j) {
+        bS = v;
+        oS = row * MU;
+      }
+    }
+  }
   // ---- terminal step: Z_w = Q_w[T-1], zeta_w = l_w[T-1]  (:102-105) ----
   if (cmp)
     stage_c_sync(Tn - 1, 0);
@@ -1224,7 +1281,8 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
     // Only this player's MU columns of G = Z_w^T B are needed, and of the MU x (M + NX) block G_w^T [B | A] that follows
     // two rows of a tile would be useful: neither is a job for the matrix pipe, which the SIMD's resident waves share
     // (an fp64 matrix instruction holds it for 64 cycles).
-    const vec Bd = ldD(tB);
+    vec Bd = zero4;
+    if constexpr (!BCONST) Bd = ldD(tB);
     constexpr bool kRowSums = MU == 2;  // the vector-unit forms below (rows_reduce4 packs (S, Y) x two controls)
     T ba[kRowSums ? 1 : NX];
     if constexpr (!kRowSums) {
@@ -1233,7 +1291,23 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
 #pragma unroll
       for (int kk = 0; kk < NX; kk++) ba[kk] = colp[kk];
     }
-    if constexpr (kRowSums) {
+    if constexpr (BCONST) {
+      // G[j][w MU + aa] = b Z_w[row][j], (row, b) the entry of B's column w MU + aa, on the lanes whose register selG[aa]
+      // holds that row of the Z_w tile (column JB: zeta_w, so entry JB is zeta_w^T B_w).
+#pragma unroll
+      for (int aa = 0; aa < MU; aa++) {
+        // (three plain selects on the two bits of the index: a nested chain of comparisons is compiled into divergent
+        // regions, and every comparison is a loop-invariant lane mask in a scalar register pair)
+        const bool lo = (selG[aa] & 1) != 0, hi = (selG[aa] & 2) != 0;
+        const T z01 = lo ? Zd[1] : Zd[0], z23 = lo ? Zd[3] : Zd[2];
+        const T z = hi ? z23 : z01;
+        const T gcol = z * bG[aa];
+        if (selG[aa] >= 0) {
+          sGw[j * MU + aa] = gcol;
+          if (j == JB) sYz[w * MU + aa] = gcol + sr[rg_ww + aa];  // y_zeta = B_w^T zeta_w + r_ww (:154-157)
+        }
+      }
+    } else if constexpr (kRowSums) {
       // G[:, w MU + aa] as two matrix-vector products: lane (g, j) multiplies its four rows of column j of the Z_w tile
       // with B[row][w MU + aa] (read from the B tile: the address depends on g only) and the four lane rows are summed on
       // the vector unit (v_permlane32_swap / v_permlane16_swap).  4 LDS reads + 8 FMA + 6 permlane / add instead of four
@@ -1302,14 +1376,26 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
 #pragma unroll
         for (int aa = 0; aa < MU; aa++) {
           const T gval = gp[aa];
-          pS[aa] += gval * Bd[r];
+          if constexpr (!BCONST) pS[aa] += gval * Bd[r];
           pY[aa] += gval * Ad2[r];
         }
       }
       // rows after the reduction: 0 = S(aa 0), 1 = Y(aa 0), 2 = S(aa 1), 3 = Y(aa 1)
-      const T tot = rows_reduce4<T>(pS[0], pS[MU - 1], pY[0], pY[MU - 1]);
       const int aa = g >> 1;
       const bool isY = (g & 1) != 0;
+      T tot;
+      if constexpr (BCONST) {
+        // S[aa][j] = G_w[row][aa] b, (row, b) the entry of B's column j; Y alone goes through the row sums, with the
+        // summation tree rows_reduce4 gives it: (r0 + r2) + (r1 + r3)
+        const T sval = sGw[oS + aa] * bS;
+        T sa, sb;
+        permlane32_swap(pY[0], pY[MU - 1], sa, sb);
+        const T u = sa + sb;  // rows: Y0(0+2), Y0(1+3), Y1(0+2), Y1(1+3)
+        permlane16_swap(u, u, sa, sb);
+        tot = isY ? sa + sb : sval;  // rows 0, 1: Y(aa 0); rows 2, 3: Y(aa 1)
+      } else {
+        tot = rows_reduce4<T>(pS[0], pS[MU - 1], pY[0], pY[MU - 1]);
+      }
       const int c = isY ? M + j : j;  // column of [S | Y]
       // + R_ww on this player's diagonal block of S (:148-150); every lane reads (a clamped address): no divergent region
       const bool diag = !isY && j / MU == w;
@@ -1450,10 +1536,20 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
 
     // ---- F = A - B P (:189-194), beta = -B alpha; every wave needs them, so every wave computes them ----
     const vec Pd = ldD(sPt);
-    vec nBT = ldDT(tB);  // B^T
+    vec Fraw;
+    if constexpr (BCONST) {
+      // row `row` of B [P | alpha] is b times row `col` of [P | alpha], (col, b) B's entry in that row; a row without an
+      // entry (b = 0, the rows >= NX among them) is A's.  Lane j = JB forms beta = -B alpha from the same line (column JB
+      // of the padded A is zero); a column 15 that is not JB is zero in both tiles, so it stays zero.
+      const vec Ad = ldD(tA);
 #pragma unroll
-    for (int r = 0; r < 4; r++) nBT[r] = -nBT[r];
-    const vec Fraw = tile_xty_blocks<T, kblock_mask<T>(0, M)>(nBT, Pd, ldD(tA));  // rows >= M of -B^T are zero
+      for (int r = 0; r < 4; r++) Fraw[r] = t_fma(nbF[r], sPt[oF[r]], Ad[r]);
+    } else {
+      vec nBT = ldDT(tB);  // B^T
+#pragma unroll
+      for (int r = 0; r < 4; r++) nBT[r] = -nBT[r];
+      Fraw = tile_xty_blocks<T, kblock_mask<T>(0, M)>(nBT, Pd, ldD(tA));  // rows >= M of -B^T are zero
+    }
     vec Fd, BetaD, zetaD;  // F proper; beta / zeta_w down the vector column, zero elsewhere
     if constexpr (SPARE) {
       // column JB of the padded A is zero and column JB of the P tile holds alpha: Fraw = [F | beta]

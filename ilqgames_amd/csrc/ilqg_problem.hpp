@@ -117,6 +117,7 @@ struct ilqg_problem {
   ilqg::DeviceBuffer<int> d_tnom_tables;
   ilqg::InstanceBindings bindings;  // which of the three tables are bound, and for which batch
   int static_prog = 0;                // id of the registered structure it matches (ilqg_rowprog_static.hpp), 0: none
+  bool b_constant = false;            // the feedback sweep may take B's entries from registers (ProblemTables::b_constant)
   ilqg::DeviceBuffer<int> d_unfinished;  // instances still running after an LQ-kernel launch
   ilqg::PinnedInts h_unfinished;  // pinned host mirror: [0..3] the counters, [8] the sequence number of read_round_counters
   int* h_unfinished_dev = nullptr;  // ... as the device addresses it
@@ -189,6 +190,8 @@ struct ProblemTables {
   RowProgramHost row_prog;
   int static_prog = 0;  // id of the registered structure the program matches (ilqg_rowprog_static.hpp), 0: none
   int mu_uniform = 0;   // the players' common control dimension, 0: they differ
+  bool b_constant = false;  // B is constant entries, at most one per row and column, and the solves read compact rows
+                            // (RowProgramHost::b_constant on a specialised instantiation): ilqg_sweep_b_structure_build
   bool has_route_progress = false;
   bool generic = false;  // no specialised instantiation holds the problem
 };
@@ -447,6 +450,7 @@ ilqg_status build_row_program_and_match(const ilqg_problem_desc& desc, ProblemTa
   d.rp_maps_words = rph.maps_words;
   d.rp_compact_off = rph.compact_off;
   d.rp_compact_w = rph.compact_w;
+  t->b_constant = rph.b_constant && rph.compact_w > 0 && !t->generic;
   std::vector<int> masked = rph.words;
   row_program_mask_parameters(&masked);
 #define X(ID_, NX_, NP_, MU_)                                                                                   \
@@ -514,6 +518,7 @@ ilqg_status upload_problem(const ilqg_problem_desc& desc, const ProblemTables& t
   p->terms_host.assign(desc.terms, desc.terms + desc.num_terms);
   p->row_prog = t.row_prog;
   p->static_prog = t.static_prog;
+  p->b_constant = t.b_constant;
   p->mu_uniform = t.mu_uniform;
   p->has_route_progress = t.has_route_progress;
   p->generic = t.generic;

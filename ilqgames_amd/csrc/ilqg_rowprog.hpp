@@ -25,6 +25,11 @@ struct RowProgramHost {
   int compact_off = 0, compact_w = 0;  // the compact-row block (ilqg_rows.hpp: RP_OFF_COMPACT) and its row length
   std::vector<int> op_term;  // per op, beside the image: the term whose weight / value the op carries (TERM, EXT_EVAL,
                              // EXT_APPLY), -1 for the others — what a per-instance parameter of that term overrides
+  // B for the feedback sweep (lq_feedback_instance_mfma_pw's BCONST): its constant entries as (row, column, RC_* kind,
+  // bits of a literal's float value), and whether they are all of B — compact rows, no computed entry — with at most
+  // one per row and per column
+  std::vector<int> b_entries;
+  bool b_constant = false;
   std::vector<int> op_sub;   // ... and the subsystem whose param0 a JACOBIAN op carries in its weight word (the next
                              // subsystem's in its value word: the Air3D pair), -1 for the others
 };
@@ -461,6 +466,16 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
       blk.insert(blk.end(), cbg.begin(), cbg.end());
     }
     w[RP_OFF_COMPACT] = put(blk);
+    out->b_constant = compact_ok;
+    for (int code : cdst)
+      if ((code >> 24) == RA_B) out->b_constant = false;
+    std::vector<int> in_row((size_t)n, 0), in_col((size_t)m, 0);
+    for (size_t e = 0; e + RC_BG_WORDS <= cbg.size(); e += RC_BG_WORDS) {
+      if ((cbg[e] >> 24) != RA_B) continue;
+      const int off = cbg[e] & 0xffffff, col = off / n, row = off - col * n;
+      out->b_entries.insert(out->b_entries.end(), {row, col, cbg[e + 1], cbg[e + 2]});
+      if (++in_row[row] > 1 || ++in_col[col] > 1) out->b_constant = false;
+    }
     out->compact_off = w[RP_OFF_COMPACT];
     out->compact_w = blk[0];
   }

@@ -1135,8 +1135,10 @@ __device__ __forceinline__ void deadline_part_instance(const DevProblem& p, cons
 enum { LQ_VALU_FEEDBACK = 0, LQ_PLAYER_WAVES = 1, LQ_OPEN_LOOP = 2, LQ_PLAYER_WAVES_PACKED = 3, LQ_OPEN_LOOP_COMPACT = 4,
        LQ_SINGLE_WAVE = 5 };  // _SINGLE_WAVE: the one-tile feedback sweep with one wave per instance (ilqg_lq_feedback1w.hpp)
 // _PACKED: ilqg_api.hip; _COMPACT: the open-loop sweep reading compact rows (its own instantiation: register budget)
-// FORMS: ilqg_solve_options::sweep_forms — the one-tile feedback sweeps' solve with row broadcasts (true) or read-lanes.
-template <typename T, int NX, int NP, int MU, int KIND, bool FORMS = true>
+// FORMS: ilqg_solve_options::sweep_forms — the one-tile feedback sweeps' solve with read-lanes (0) or row broadcasts (1),
+// and the player-parallel sweep with B's constant entries in registers on top of them (2: lq_feedback_instance_mfma_pw's
+// BCONST; the launcher picks it for a problem whose B qualifies, RowProgramHost::b_constant).
+template <typename T, int NX, int NP, int MU, int KIND, int FORMS = 1>
 __device__ __forceinline__ void lq_part_instance(const DevProblem& p, const SolveArgs<T>& sa, int b, T* sm) {
   const int Tn = p.T;
   const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
@@ -1194,7 +1196,7 @@ __device__ __forceinline__ void lq_part_instance(const DevProblem& p, const Solv
   if constexpr (KIND == LQ_PLAYER_WAVES) {
     if constexpr (LQCfg<T, NX, NP, MU>::MFMA_ONE_TILE) {
       if (la.compact != nullptr && defer)
-        lq_feedback_instance_mfma_pw<T, NX, NP, MU, true, FORMS>(la, p.pairs, sm);
+        lq_feedback_instance_mfma_pw<T, NX, NP, MU, true, FORMS != 0, FORMS == 2>(la, p.pairs, sm);
       else
         lq_feedback_instance_mfma<T, NX, NP, MU>(la, p.pairs, sm);
     } else
@@ -1204,7 +1206,7 @@ __device__ __forceinline__ void lq_part_instance(const DevProblem& p, const Solv
     // adjoint recursion of ilqg_lq_feedback1w.hpp — unless the forward pass is deferred to the trial kernel)
     if constexpr (W1Cfg<T, NX, NP, MU>::SUPPORTED) {
       la.dx = nullptr;
-      lq_feedback_instance_mfma_1w<T, NX, NP, MU, FORMS>(la, p.pairs, sm);
+      lq_feedback_instance_mfma_1w<T, NX, NP, MU, FORMS != 0>(la, p.pairs, sm);
     }
   } else if constexpr (KIND == LQ_OPEN_LOOP) {
     lq_openloop_instance<T, NX, NP, MU>(la, p.pairs, sm);  // SolverParams::open_loop (ilq_solver.h:76-81)

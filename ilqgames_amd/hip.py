@@ -29,7 +29,7 @@ EXPORTS = [
     "ilqg_problem_declare_instance_routes", "ilqg_problem_bind_instance_routes", "ilqg_instance_routes_check",
     "ilqg_segment_table_build",
     "ilqg_problem_bind_instance_time_nominals", "ilqg_instance_time_nominals_build", "ilqg_problem_time_nominal_terms",
-    "ilqg_time_nominal_table_build",
+    "ilqg_time_nominal_table_build", "ilqg_sweep_b_structure_build",
 ]
 
 
@@ -175,6 +175,20 @@ def row_program_build(spec, dtype=abi.F64):
     _check(lib().ilqg_row_program_build(C.byref(desc), w.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(sid)))
     del keep
     return w, int(sid.value)
+
+
+def sweep_b_structure(spec, dtype=abi.F64):
+    """ilqg_sweep_b_structure_build: (whether the feedback sweep may take B's entries from registers — B is constant
+    entries, at most one per row and per column, and the solves read compact rows —, B's constant entries as an int32
+    array [entries][4] of (row, column, abi.B_ENTRY_* kind, float bits of a literal)) — host only, no device needed."""
+    import numpy as np
+    desc, keep = spec.build(dtype)
+    ok, n = C.c_int32(0), C.c_int32(0)
+    _check(lib().ilqg_sweep_b_structure_build(C.byref(desc), C.byref(ok), None, 0, C.byref(n)))
+    e = np.zeros((n.value, 4), np.int32)
+    _check(lib().ilqg_sweep_b_structure_build(C.byref(desc), C.byref(ok), e.ctypes.data_as(C.c_void_p), e.size, C.byref(n)))
+    del keep
+    return bool(ok.value), e
 
 
 def _instance_params(spec, params):

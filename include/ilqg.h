@@ -613,10 +613,18 @@ typedef struct {
                                      m x m Nash solve of a step with DPP row broadcasts — the pivot columns replicated in
                                      every 16-lane row, values stay in vector registers — instead of read-lane broadcasts
                                      over the scalar unit (AUTO: on wherever the columns fit the rows: m < 16 and
-                                     n + 1 <= 4 (16 - m)).  The same operations in the same order: bit-identical.  OFF
-                                     keeps the read-lane instantiation selectable for A/B runs and the bit-for-bit test
-                                     (tests/test_gpu_sweep_forms.py).  (This field was reserved2 = 0 up to this release:
-                                     same layout, same ABI version.)                                                    */
+                                     n + 1 <= 4 (16 - m)).  The same operations in the same order: bit-identical.
+                                     With the forms on, the player-parallel sweep of a shape with n < 16 and two controls
+                                     per player also takes B's entries from registers instead of a tile wherever B is
+                                     constant entries with at most one per row and per column (dt x a selection matrix:
+                                     ilqg_sweep_b_structure_build says whether; ILQG_SCHEDULE_CONSTANT_B reports it): G, S
+                                     and F = A - B P are then one multiply or multiply-add per entry.  Every replaced
+                                     sum had a single term that is not an exact zero, so the results are the same bits
+                                     for finite operands, up to the sign of a zero; an infinite Z or P no longer turns
+                                     into NaN through 0 x Inf.  OFF keeps the read-lane, dense-B instantiation selectable
+                                     for A/B runs and the bit-for-bit tests (tests/test_gpu_sweep_forms.py,
+                                     tests/test_gpu_sweep_b_structure.py).  (This field was reserved2 = 0 up to ABI 9's
+                                     first release: same layout, same ABI version.)                                      */
   const struct ilqg_iterate_log* iterate_log; /* NULL, or where every logged iterate of the solve goes (below)          */
   double max_runtime;           /* > 0: the anytime exit of ILQSolver::Solve (src/ilq_solver.cpp:123-124) on the host's
                                      clock, seconds — once it has passed, instances leave the loop at their next
@@ -671,6 +679,7 @@ ilqg_status ilqg_solve_state_batch(const ilqg_problem* p, int32_t batch, const v
 #define ILQG_SCHEDULE_OPEN_LOOP 64          /* LQOpenLoopSolver's sweep                                           */
 #define ILQG_SCHEDULE_STATIC_ROWS 128       /* the row stage ran as straight-line code for a registered structure */
 #define ILQG_SCHEDULE_PADDED_SWEEP 256      /* run-time-dimensioned solve, its sweep on a specialised kernel (padded_sweep) */
+#define ILQG_SCHEDULE_CONSTANT_B 512        /* player-parallel sweep with B's constant entries in registers (sweep_forms)   */
 ilqg_status ilqg_problem_last_schedule(const ilqg_problem* p, int32_t* schedule_out);
 
 /* The row program ilqg_problem_create compiled the problem's dynamics and cost list into (csrc/ilqg_rowprog.hpp: passes,
@@ -682,6 +691,16 @@ ilqg_status ilqg_problem_row_program(const ilqg_problem* p, int32_t* words_out, 
  * it uploads tables, without a device (the one entry point that works without one). */
 ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words_out, int32_t capacity, int32_t* num_words,
                                    int32_t* static_id);
+/* Host only, no device needed: what the feedback sweep may assume about B (sweep_forms).  *constant_out is 1 when the
+ * problem's solves run on compact rows, every non-zero of B is a constant of the row program (no computed entry) and
+ * every row and every column of B holds at most one of them.  entries_out (capacity int32 words; may be NULL to query
+ * the count) receives B's constant entries, four words each: row, column, kind (ILQG_B_ENTRY_*), the bits of the float
+ * value of a literal; *num_entries is their number. */
+#define ILQG_B_ENTRY_LITERAL 0
+#define ILQG_B_ENTRY_DT 1      /* the time step */
+#define ILQG_B_ENTRY_NEG_DT 2  /* its negative  */
+ilqg_status ilqg_sweep_b_structure_build(const ilqg_problem_desc* desc, int32_t* constant_out, int32_t* entries_out,
+                                         int32_t capacity, int32_t* num_entries);
 /* Host only, no device needed: the segment table ilqg_problem_create builds from the descriptor's polylines — per segment,
  * in polyline order, 21 scalars [p1x p1y p2x p2y length ux uy | the shortcut prev.p1 -> p2 | the shortcut p1 -> next.p2] in
  * the arithmetic of `dtype` (ILQG_F32 / ILQG_F64).  This is also the layout of one instance's block of a per-instance
@@ -849,7 +868,8 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
                                  ilqg_instance_routes_check, and the host-only ilqg_segment_table_build: four new calls); still 9:
                                  per-instance time nominals (ilqg_problem_bind_instance_time_nominals,
                                  ilqg_instance_time_nominals_build, ilqg_problem_time_nominal_terms, and the host-only
-                                 ilqg_time_nominal_table_build: four new calls);
+                                 ilqg_time_nominal_table_build: four new calls); still 9:
+                                 ILQG_SCHEDULE_CONSTANT_B and the host-only ilqg_sweep_b_structure_build (one new call);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;
