@@ -226,10 +226,16 @@ __device__ __forceinline__ float div_by(float x, float c, float rc) {
 // RK4's up to the order of the roundings (a few ulp per step).  All 8 lanes return the new state in x[].
 // `gth` is LDS scratch of 64 + 128 elements (this wave's); any_car: some group of the wave holds a car model;
 // `group`: the lanes of this trajectory (ilqg_trig.hpp: the library fall-back is decided over them).
-template <typename T, bool DIST = false, bool DUB = false>
+// `qsel`: the value of q again, for the selects below whose condition is a lane role and nothing else (the second
+// sub-step's lanes, stage 0).  A caller with a step loop around this may hand in a copy it keeps opaque from step to
+// step: the compare is then formed where it is used (a compare into VCC) and not hoisted out of the loop as a lane mask
+// in a scalar register pair — in the fused trial kernel such pairs are spilled into lanes of a vector register and cost
+// two read-lanes and a wait state a use.  The VALUES that depend on q (aj, cq, bj) are taken from q and stay hoisted.
+// CHAINS: the trigonometry's polynomial steps in the spelled-out form (ilqg_trig.hpp, trig_poly_chains).
+template <typename T, bool DIST = false, bool DUB = false, bool CHAINS = true>
 __device__ __forceinline__ void sub_integrate_stages(int kind, T L, double interval, T* x, T u0, T u1, int q, int lane,
-                                                     T* gth, bool any_car, T d0 = T(0), T d1 = T(0),
-                                                     unsigned long long group = ~0ull) {
+                                                     T* gth, bool any_car, T d0, T d1, unsigned long long group,
+                                                     int qsel) {
   const T h = T(interval / 2.0);
   const T six = T(6.0), rsix = T(1.0) / T(6.0), rL = T(1.0) / L;
   const bool dubins = DUB && kind == ILQG_DYN_DUBINS_CAR;
@@ -251,7 +257,8 @@ __device__ __forceinline__ void sub_integrate_stages(int kind, T L, double inter
     const T a0 = x[5];
     const T a_1 = a0 + hj;
     const T v_1 = t_fma(T(0.5) * h, hj, t_fma(h, a0, v0));
-    const T vb = s1 ? v_1 : v0, ab = s1 ? a_1 : a0;
+    const bool s1v = qsel >= 4;
+    const T vb = s1v ? v_1 : v0, ab = s1v ? a_1 : a0;
     const T bj = j == 2 ? T(0.25) : (j == 3 ? T(0.5) : T(0));
     const T v6_q = t_fma(bj * h, hj, t_fma(aj * h, ab, vb));
     const T v6_end = t_fma(T(0.5) * h, hj, t_fma(h, a_1, v_1));
@@ -264,23 +271,26 @@ __device__ __forceinline__ void sub_integrate_stages(int kind, T L, double inter
   // ---- heading at this lane's stage ----
   T th_q = ang_q, th_end = ang_end;
   if (any_car) {  // wave-uniform
-    const T kth = car ? h * (div_by(v_q, L, rL) * fast_tan(ang_q, group)) : T(0);
+    const T kth = car ? h * (div_by(v_q, L, rL) * fast_tan<CHAINS>(ang_q, group)) : T(0);
     gth[lane] = kth;
     lds_sync(true);
     const T* g = gth + (lane & ~7);
     const T k0 = g[0], k1 = g[1], k2 = g[2], k3 = g[3], k4 = g[4], k5 = g[5], k6 = g[6], k7 = g[7];
     // the previous stage's derivative; stage 0 has none (aj = 0) and takes a zero — the neighbouring lane belongs to
     // another subsystem or, in rollout_pair, to the other trajectory, whose non-finite value 0 * would turn into a NaN here
-    const T kprev = (lane & 7) ? gth[lane - 1] : T(0);
+    // (read unconditionally and selected, no exec region around the read: stage 0 reads the slot in front of its group's —
+    // in front of gth itself on lane 0: the staged blocks lie there — and drops it)
+    const T kread = gth[lane - 1];
+    const T kprev = qsel ? kread : T(0);
     const T th1 = x[2] + div_by(t_fma(T(2), k1 + k2, k0) + k3, six, rsix);
     const T th2 = th1 + div_by(t_fma(T(2), k5 + k6, k4) + k7, six, rsix);
-    const T thb = s1 ? th1 : x[2];
+    const T thb = (qsel >= 4) ? th1 : x[2];
     th_q = car ? t_fma(aj, kprev, thb) : ang_q;
     th_end = car ? th2 : ang_end;
   }
   // ---- position rates of this lane's stage, then the two RK4 combinations ----
   T sn, cs;
-  fast_sincos(th_q, &sn, &cs, group);
+  fast_sincos<CHAINS>(th_q, &sn, &cs, group);
   const T kx = DIST ? h * t_fma(v_q, cs, d0) : h * (v_q * cs);
   const T ky = DIST ? h * t_fma(v_q, sn, d1) : h * (v_q * sn);
   T* gxy = gth + 64;

@@ -831,6 +831,19 @@ __device__ __forceinline__ void roll_pair_instances(const DevProblem& p, const S
   if (g1) state_store<T>(ib1.w, ib1.L, s1);
 }
 
+// Which fused kernels take the rollout's leaner step loop (rollout_instance's ROOM, ilqg_stages.hpp): it costs two vector
+// registers, and the fp64 kernels are at 254-256 of 256 — every one with the interpreted row stage, and the straight-line
+// ones of (16, 3, 2) and (24, 4, 2), where it was one more spilled pair (scripts/kernel_regs.sh: scratch 16 -> 32,
+// 320 -> 336 bytes).  The headline's (14, 3, 2) with straight-line rows has 22 registers to spare, fp32 sixty and more.
+// Results are the same bits either way; the list is a register-budget fact of one compiler and one row program, not of
+// the shapes.  To re-derive it after a compiler or row-program change: return true here for the shape in question, run
+// `scripts/kernel_regs.sh NX NP MU` on that build and on the previous one, and keep the shape only if the fused
+// kernels' (`ilq_trial_kernel<double, NX, NP, MU, 2, progid>`) scratch figure did not grow and the VGPR count stays at
+// 256 or below; a shape with no spill in either form belongs in the list.
+__host__ __device__ constexpr bool fused_rollout_room(int elem_bytes, int nx, int np, int mu, int progid) {
+  return elem_bytes == 4 || (progid != 0 && nx == 14 && np == 3 && mu == 2);
+}
+
 // PROGID: 0 = the row stage interprets the problem's row program; k = straight-line code for registered structure k
 // BOUND: the fused kernel of a problem with per-instance parameters bound — its rollout takes the subsystems' parameters
 // from the instance's row of the table.  Kernels of their own, as the bound straight-line row code is: the read costs the
@@ -890,7 +903,8 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
 #endif
       if constexpr (NX > 0)
         rollout_instance<T, NX, NP * MU, (NX == 4 && NP == 2), (MU == 1), (NX == 3 && NP == 2 && MU == 1),
-                         (NX == 4 * NP && MU == 2 && NP <= 2), dims_use_plain_rk4(NX, NP, MU)>(
+                         (NX == 4 * NP && MU == 2 && NP <= 2), dims_use_plain_rk4(NX, NP, MU),
+                         fused_rollout_room(int(sizeof(T)), NX, NP, MU, PROGID)>(
                                          p, ra, sm_roll, lane, W > 1 ? &flags[0] : nullptr,
                                          (kProfile && sa.prof) ? rph : nullptr, kTimeline ? sa.prof : nullptr, b);
       else

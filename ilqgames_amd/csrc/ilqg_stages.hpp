@@ -68,8 +68,30 @@ __device__ __forceinline__ int progress_observe(int* flag) {
 __host__ __device__ constexpr bool dims_use_plain_rk4(int nx, int np, int mu) {
   return (nx == 17 && np == 3 && mu == 2) || (nx == 8 && np == 2 && mu == 1);
 }
+// dma_g2l (4-byte pieces) for ONE wavefront inside a step loop: `lane` (0 .. 63) may be a copy the caller keeps opaque
+// from step to step.  Which lanes take part in a request is then a compare against a constant where the request is made
+// — hoisted, the masks of the requests are scalar register pairs the step loop has no room for — and the lane's offset
+// is formed beside the request, a 32-bit offset on a scalar base: the request takes the base from scalar registers
+// instead of a 64-bit per-lane address formed for every request.  Same bytes, same places as dma_g2l<64, false>.
+// `g2_`, `l2`: a second block of the same length, requested under the same lane compare (or none).
+__device__ __forceinline__ void dma_g2l_wave(const void* g_, void* l, int nbytes, int lane, const void* g2_ = nullptr,
+                                             void* l2 = nullptr) {
+  const char* g = (const char*)uniform_ptr(g_);
+  const char* g2 = g2_ ? (const char*)uniform_ptr(g2_) : nullptr;
+  const unsigned voff = unsigned(lane) << 2;
+  for (int off = 0; off < nbytes; off += 256) {
+    if (off + 256 <= nbytes || lane < ((nbytes - off) >> 2)) {
+      __builtin_amdgcn_global_load_lds((glb_vptr)((g + off) + voff), (lds_vptr)((char*)l + off), 4, 0, 0);
+      if (g2) __builtin_amdgcn_global_load_lds((glb_vptr)((g2 + off) + voff), (lds_vptr)((char*)l2 + off), 4, 0, 0);
+    }
+  }
+}
+
+// ROOM = false: the caller is at its register limit (fused_rollout_room, ilqg_solve.hpp) and its step loop keeps the form
+// the compiler gives it — no loop-carried copies of the lane roles (lane_roles_opaque below), the trigonometry's
+// polynomial steps as the compiler forms them: the two registers the leaner stream costs are a spilled pair there.
 template <typename T, int CN = 0, int CM = 0, bool DIST = false, bool DUB = false, bool AIR = false, bool PM = false,
-          bool GEN = false>
+          bool GEN = false, bool ROOM = true>
 __device__ __forceinline__ void rollout_instance(const DevProblem& p, const RolloutArgs<T>& a, T* sm, int t,
                                                  int* ready = nullptr, long long* phacc = nullptr,
                                                  long long* tl = nullptr, int tl_b = 0) {
@@ -83,12 +105,13 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
   constexpr int S = int(sizeof(T));
   // The step's gains and references go global -> LDS by DMA, one step ahead, into the block not in use:
   // no registers are held across the integration (the loop is the kernel's tightest spot for registers).
-  auto issue = [&](int k, int buf) {
+  // (The four blocks are rows of four arrays — gains and references of different iterates — so no two of them are
+  // contiguous in memory and each is a request of its own.)  `ln`: the lane, see dma_g2l_wave.
+  auto issue = [&](int k, int buf, int ln) {
     T* d = stg + buf * WP;
-    dma_g2l<NT, false>(a.P + size_t(k) * m * n, d, m * n * S, t);
-    dma_g2l<NT, false>(a.alpha + size_t(k) * m, d + m * n, m * S, t);
-    dma_g2l<NT, false>(a.us_ref + size_t(k) * m, d + m * n + m, m * S, t);
-    dma_g2l<NT, false>(a.xs_ref + size_t(k) * n, d + m * n + 2 * m, n * S, t);
+    dma_g2l_wave(a.P + size_t(k) * m * n, d, m * n * S, ln);
+    dma_g2l_wave(a.alpha + size_t(k) * m, d + m * n, m * S, ln, a.us_ref + size_t(k) * m, d + m * n + m);  // equal lengths
+    dma_g2l_wave(a.xs_ref + size_t(k) * n, d + m * n + 2 * m, n * S, ln);
   };
   // lane group g = t / 8 integrates subsystem g; lane q = t % 8 owns RK4 stage q of that group
   constexpr int XS = GEN ? kSubStatesMax : 6;
@@ -111,7 +134,12 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
   const T air_vp = AIR ? T(subsystem_param(p, a.iv, 1)) : T(0);  // Air3D: the pursuer's speed enters the evader's rows
   T* const gth = stg + 2 * WP;  // exchange scratch of the stage-parallel integrator
   const bool any_car = __any(integ && (kind == ILQG_DYN_CAR_5D || kind == ILQG_DYN_CAR_6D));
-  issue(0, 0);
+  issue(0, 0, t);
+  // The lane roles of the step loop — stage q, lane t — as per-lane VALUES the loop carries and the optimiser cannot
+  // see through (lane_roles_opaque below): a condition on them is a vector compare at the point of use.  Compared once
+  // in front of the loop they are lane masks in scalar register pairs, and the fused trial kernel has none to spare: it
+  // kept them in lanes of a spill register, two read-lanes and a wait state per use.
+  int qv = q, tv = t;
   long long rc0 = (kProfile && phacc) ? clock64() : 0, rc1;
 #define ILQG_RPH(i) do { if (kProfile && phacc) { __builtin_amdgcn_sched_barrier(0); rc1 = clock64(); __builtin_amdgcn_sched_barrier(0); phacc[i] += rc1 - rc0; rc0 = rc1; } } while (0)
 #pragma unroll 1
@@ -119,6 +147,7 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
     // Block k of [P | alpha | u_ref | x_ref] was requested a whole step ago, and the rows of step k - 1 were stored
     // then too: this wait finds nothing in flight, and with it the release below is free.
     dma_wait();
+    if constexpr (ROOM) asm volatile("" : "+v"(qv), "+v"(tv));  // lane_roles_opaque: no instruction, the same values every step
     if (kTimeline && (k & 31) == 0) tl_stamp(tl, tl_b, 20 + (k >> 5), t == 0);
     if (ready) progress_publish(ready, k);
     const T* sP = stg + (k & 1) * WP;  // [m*n] gains of this step
@@ -129,7 +158,7 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
       // every lane of a group holds the group's state: lane q publishes entry q (one LDS round trip for the row)
       T mine = xj[0];
 #pragma unroll
-      for (int e = 1; e < XS; e++) mine = (q == e) ? xj[e] : mine;
+      for (int e = 1; e < XS; e++) mine = (qv == e) ? xj[e] : mine;
       if (integ && q < xd) {
         sdx[xo + q] = mine - sxr[xo + q];
         a.xs[size_t(k) * n + xo + q] = mine;
@@ -139,7 +168,7 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
     ILQG_RPH(0);
     // (Measured and dropped, round 5: four lanes per control, each a quarter of the dot product, DPP quad sums —
     // -0.3 % on the headline: the chain is not what this phase costs.)
-    if (t < m) {
+    if (tv < m) {
       T s = T(0);
       if constexpr (CN > 0) {
         // loads in blocks of eight ahead of the reference's left-to-right accumulation (the whole row
@@ -170,9 +199,18 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
     // the next block's DMA (into the block step k - 1 read) is requested here, behind the controls — it still has most of
     // a step to land, and its dozen address / M0 instructions are off the chain publish -> u -> integrate (round 5:
     // +0.7 % on the headline; it used to follow the publication barrier)
-    if (k + 1 < Tn) issue(k + 1, (k + 1) & 1);
+    if (k + 1 < Tn) issue(k + 1, (k + 1) & 1, tv);
     if (t < 64 && k + 1 < Tn) {  // whole first wave: the exchanges inside need every group lane live
-      const T u0 = integ ? su[uo] : T(0), u1 = integ ? su[uo + 1] : T(0);
+      // Both controls in one unmasked read.  The lanes that integrate nothing (uo = 0) used to take zeros; they now
+      // take the first player's controls and carry a unicycle nobody reads: a lane's result depends on its own state
+      // alone, and what such a lane can do to the others is vote for the out-of-range trig branch (the PM and plain
+      // paths vote wave-wide too).  Its heading is its own start value plus the integral of player 0's heading rate, so
+      // it leaves the fast range when player 0's subsystem does, up to the difference of the two start headings; a
+      // vote cast early or late by that difference costs the wave a uniform branch and changes no result: a lane inside
+      // the range computes the fast form whatever its neighbours hold (fast_sincos, ilqg_trig.hpp).  With m = 1, su[uo + 1] is the word
+      // behind su: inside the LDS block, read and never used (u1 of a one-control subsystem), as it was for the
+      // integrating lanes before.
+      const T u0 = su[uo], u1 = su[uo + 1];
       if constexpr (GEN) {
         if (integ) sub_integrate8<T>(kind, Lp, p.dt, xj, u0, u1);
       } else if constexpr (AIR) {
@@ -180,11 +218,11 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
       } else if constexpr (DIST) {
         const bool dist = integ && kind == ILQG_DYN_UNICYCLE_4D_DISTURBED;  // the next player's (dx, dy)
         const T d0 = dist ? su[uo + 2] : T(0), d1 = dist ? su[uo + 3] : T(0);
-        sub_integrate_stages<T, true>(kind, Lp, p.dt, xj, u0, u1, q, t, gth, false, d0, d1);
+        sub_integrate_stages<T, true, false, ROOM>(kind, Lp, p.dt, xj, u0, u1, q, t, gth, false, d0, d1, ~0ull, qv);
       } else if (PM && p.sub_kind[0] == ILQG_DYN_POINT_MASS_2D) {
         sub_integrate<T>(kind, Lp, p.dt, xj, u0, u1);
       } else {
-        sub_integrate_stages<T, false, DUB>(kind, Lp, p.dt, xj, u0, u1, q, t, gth, any_car);
+        sub_integrate_stages<T, false, DUB, ROOM>(kind, Lp, p.dt, xj, u0, u1, q, t, gth, any_car, T(0), T(0), ~0ull, qv);
       }
     }
     ILQG_RPH(2);
@@ -327,7 +365,7 @@ __device__ __forceinline__ void rollout_pair(const DevProblem& p, const RolloutA
     if (k + 1 < Tn) {  // the whole wave: the exchanges inside need every group lane live
       const T u0 = integ ? su[uo] : T(0), u1 = integ ? su[uo + 1] : T(0);
       sub_integrate_stages<T, false, DUB>(kind, Lp, p.dt, xj, u0, u1, q, t, gth, any_car, T(0), T(0),
-                                          h ? 0xffffffff00000000ull : 0x00000000ffffffffull);
+                                          h ? 0xffffffff00000000ull : 0x00000000ffffffffull, q);
     }
   }
 }

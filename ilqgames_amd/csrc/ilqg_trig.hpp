@@ -53,24 +53,79 @@ __host__ __device__ __forceinline__ int trig_reduce(float x, float* r) {
   return int(n);
 }
 
-// sin and cos on [-pi/4, pi/4]
+// The two polynomials of the double kernels in z = r^2 (Horner, the sine's and the cosine's steps alternating):
+//   *ps = S2 + z (S3 + z (S4 + z (S5 + z (S6 + z S7)))),  *pc = C2 + z (C3 + z (C4 + z (C5 + z (C6 + z C7))))
+// On the device the ten steps are spelled out as three-operand instructions.  Left to itself the compiler forms the
+// two-operand accumulate (v_fmac_f64) on a COPY of each coefficient — the coefficients stay in registers across the
+// rollout's step loop, so every step was a move and a multiply-add, on a chain that pays for each instruction issued —
+// and, given the steps one by one, it puts a wait state between them that a multiply-add feeding the next does not need.
+// The two leading coefficients are asked for in scalar registers (a literal pair set up beside the call, as the compiler
+// did before), the other ten in vector registers.  The same fused multiply-adds, each rounding once, on the host as on
+// the device.
+__host__ __device__ __forceinline__ void trig_poly_chains(double z, double* ps, double* pc) {
+  constexpr double S2 = -1.66666666666666324348e-01, S3 = 8.33333333332248946124e-03, S4 = -1.98412698298579493134e-04,
+                   S5 = 2.75573137070700676789e-06, S6 = -2.50507602534068634195e-08, S7 = 1.58969099521155010221e-10;
+  constexpr double C2 = 4.16666666666666019037e-02, C3 = -1.38888888888741095749e-03, C4 = 2.48015872894767294178e-05,
+                   C5 = -2.75573143513906633035e-07, C6 = 2.08757232129817482790e-09, C7 = -1.13596475577881948265e-11;
+#if defined(__HIP_DEVICE_COMPILE__)
+  double s, c;
+  asm("v_fma_f64 %0, %2, %3, %4\n\t"
+      "v_fma_f64 %1, %2, %5, %6\n\t"
+      "v_fma_f64 %0, %2, %0, %7\n\t"
+      "v_fma_f64 %1, %2, %1, %8\n\t"
+      "v_fma_f64 %0, %2, %0, %9\n\t"
+      "v_fma_f64 %1, %2, %1, %10\n\t"
+      "v_fma_f64 %0, %2, %0, %11\n\t"
+      "v_fma_f64 %1, %2, %1, %12\n\t"
+      "v_fma_f64 %0, %2, %0, %13\n\t"
+      "v_fma_f64 %1, %2, %1, %14"
+      : "=&v"(s), "=&v"(c)
+      : "v"(z), "s"(S7), "v"(S6), "s"(C7), "v"(C6), "v"(S5), "v"(C5), "v"(S4), "v"(C4), "v"(S3), "v"(C3), "v"(S2), "v"(C2));
+  *ps = s;
+  *pc = c;
+#else
+  double s = __builtin_fma(z, S7, S6), c = __builtin_fma(z, C7, C6);
+  s = __builtin_fma(z, s, S5);
+  c = __builtin_fma(z, c, C5);
+  s = __builtin_fma(z, s, S4);
+  c = __builtin_fma(z, c, C4);
+  s = __builtin_fma(z, s, S3);
+  c = __builtin_fma(z, c, C3);
+  s = __builtin_fma(z, s, S2);
+  c = __builtin_fma(z, c, C2);
+  *ps = s;
+  *pc = c;
+#endif
+}
+
+// sin and cos on [-pi/4, pi/4].  CHAINS: the polynomial steps in the spelled-out form (trig_poly_chains) —
+// for the stage-parallel rollouts, one argument per lane on a latency-bound chain; the forms with many arguments per lane
+// keep the compiler's own (it may hold coefficients as literals there, and they have no registers for ten pairs at once).
+// The same operations either way.
+template <bool CHAINS = false>
 __host__ __device__ __forceinline__ void trig_kernels(double r, double* s, double* c) {
   const double z = r * r;
-  double ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
-  double pc = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
-  ps = __builtin_fma(z, ps, 2.75573137070700676789e-06);
-  pc = __builtin_fma(z, pc, -2.75573143513906633035e-07);
-  ps = __builtin_fma(z, ps, -1.98412698298579493134e-04);
-  pc = __builtin_fma(z, pc, 2.48015872894767294178e-05);
-  ps = __builtin_fma(z, ps, 8.33333333332248946124e-03);
-  pc = __builtin_fma(z, pc, -1.38888888888741095749e-03);
-  ps = __builtin_fma(z, ps, -1.66666666666666324348e-01);
-  pc = __builtin_fma(z, pc, 4.16666666666666019037e-02);
+  double ps, pc;
+  if constexpr (CHAINS) {
+    trig_poly_chains(z, &ps, &pc);
+  } else {
+    ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
+    pc = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
+    ps = __builtin_fma(z, ps, 2.75573137070700676789e-06);
+    pc = __builtin_fma(z, pc, -2.75573143513906633035e-07);
+    ps = __builtin_fma(z, ps, -1.98412698298579493134e-04);
+    pc = __builtin_fma(z, pc, 2.48015872894767294178e-05);
+    ps = __builtin_fma(z, ps, 8.33333333332248946124e-03);
+    pc = __builtin_fma(z, pc, -1.38888888888741095749e-03);
+    ps = __builtin_fma(z, ps, -1.66666666666666324348e-01);
+    pc = __builtin_fma(z, pc, 4.16666666666666019037e-02);
+  }
   *s = __builtin_fma(r * z, ps, r);
   // 1 - z/2 + z^2 pc, with the rounding error of (1 - z/2) put back (k_cos.c)
   const double hz = 0.5 * z, w = 1.0 - hz;
   *c = w + __builtin_fma(z * z, pc, (1.0 - w) - hz);
 }
+template <bool CHAINS = false>
 __host__ __device__ __forceinline__ void trig_kernels(float r, float* s, float* c) {
   const float z = r * r;
   float ps = __builtin_fmaf(z, 2.7183114939898219064e-06f, -1.98393348360966317347e-04f);
@@ -83,11 +138,11 @@ __host__ __device__ __forceinline__ void trig_kernels(float r, float* s, float* 
   *c = __builtin_fmaf(z, pc, 1.0f);
 }
 
-template <typename T>
+template <typename T, bool CHAINS = false>
 __host__ __device__ __forceinline__ void fast_sincos_core(T x, T* s, T* c) {
   T r, sr, cr;
   const int n = trig_reduce(x, &r);
-  trig_kernels(r, &sr, &cr);
+  trig_kernels<CHAINS>(r, &sr, &cr);
   const bool swap = n & 1;
   const T sv = swap ? cr : sr, cv = swap ? sr : cr;
   *s = (n & 2) ? -sv : sv;
@@ -218,6 +273,7 @@ __host__ __device__ inline void large_sincos(double x, double* s, double* c) {
 
 // (the branch is voted over the group on the device so that the common case is one uniform test; a lane inside the fast
 // range computes the fast form whatever its neighbours hold)
+template <bool CHAINS = false>
 __host__ __device__ __forceinline__ void fast_sincos(double x, double* s, double* c, unsigned long long group = ~0ull) {
   const bool mine = !(__builtin_fabs(x) <= kTrigFastLimit);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -232,8 +288,9 @@ __host__ __device__ __forceinline__ void fast_sincos(double x, double* s, double
       return;
     }
   }
-  fast_sincos_core<double>(x, s, c);
+  fast_sincos_core<double, CHAINS>(x, s, c);
 }
+template <bool CHAINS = false>  // (the float kernels take their coefficients as literals: one form)
 __host__ __device__ __forceinline__ void fast_sincos(float x, float* s, float* c, unsigned long long group = ~0ull) {
   const bool mine = !(__builtin_fabsf(x) <= kTrigFastLimitF);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -277,11 +334,11 @@ __host__ __device__ __forceinline__ float trig_div(float a, float b) {
   const float q = a * rc;
   return __builtin_fmaf(__builtin_fmaf(-q, b, a), rc, q);
 }
-template <typename T>
+template <typename T, bool CHAINS = false>
 __host__ __device__ __forceinline__ T fast_tan_core(T x) {
   T r, sr, cr;
   const int n = trig_reduce(x, &r);
-  trig_kernels(r, &sr, &cr);
+  trig_kernels<CHAINS>(r, &sr, &cr);
   const bool odd = n & 1;
   return trig_div(odd ? -cr : sr, odd ? sr : cr);
 }
@@ -298,6 +355,7 @@ __host__ __device__ inline double large_tan(double x) {
   large_sincos(x, &s, &c);
   return s / c;
 }
+template <bool CHAINS = false>
 __host__ __device__ __forceinline__ double fast_tan(double x, unsigned long long group = ~0ull) {
   const bool mine = !(__builtin_fabs(x) <= kTrigFastLimit);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -309,8 +367,9 @@ __host__ __device__ __forceinline__ double fast_tan(double x, unsigned long long
   if (__builtin_expect(any, 0)) {
     if (mine) return large_tan(x);
   }
-  return fast_tan_core<double>(x);
+  return fast_tan_core<double, CHAINS>(x);
 }
+template <bool CHAINS = false>
 __host__ __device__ __forceinline__ float fast_tan(float x, unsigned long long group = ~0ull) {
   const bool mine = !(__builtin_fabsf(x) <= kTrigFastLimitF);
 #if defined(__HIP_DEVICE_COMPILE__)
