@@ -1031,6 +1031,27 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
     rg_ww = (w == e) ? pr.rg[e][e] : rg_ww;
   }
 
+  // PAIRS (the solver's spare-column sweep with the forms on): the C-term product [P | alpha]^T [H | q] over the k blocks
+  // that hold a row of a present pair (w, jj).  Row jj MU + aa of [H | q] is an exact zero for an absent pair, so any
+  // other block adds 0 x p to every entry and is not issued.  kPairMask: the blocks of this wave, wave-uniform (a
+  // scalar: the branch around a 64-cycle matrix instruction is a scalar one).  [H | q] itself is formed as before —
+  // what selects a row's pair is loop invariant and the compiler keeps it out of the loop; moving the chains behind
+  // the branch as well changed how they are vectorised in fp32 (packed multiplies and adds for fused multiply-adds),
+  // and with that the bits.  fp64 only, for the same reason: with the branch in the fp32 loop the compiler sinks the
+  // chains behind it in some instantiations and not in others, and the fused and the split trial schedules, which run
+  // different instantiations, stopped agreeing bit for bit (tests/test_gpu_parity.py, cost_zoo_scene).  fp64 has no
+  // packed arithmetic to choose: every chain is the same fused multiply-adds wherever it stands.
+  constexpr bool PAIRS = SOLVER && SPARE && ROWBC && sizeof(T) == 8;
+  int kPairMask = 0;
+  if constexpr (PAIRS) {
+#pragma unroll
+    for (int e = 0; e < NP; e++)
+#pragma unroll
+      for (int f = 0; f < NP; f++)
+        if (w == e && pr.q[e][f] >= 0) kPairMask |= kblock_mask_rt<T>(0, f * MU, f * MU + MU);
+    kPairMask = __builtin_amdgcn_readfirstlane(kPairMask);
+  }
+
   T* img = sm;  // image of the step being processed
   T *tA, *tB, *tQ, *sl, *sR, *sr;
   auto set_img = [&](int which) {
@@ -1122,10 +1143,12 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
       }
     }
   };
-  // the same for a step whose compact row is not staged yet (before the loop): straight from global memory
+  // the same for a step whose compact row is not staged yet (before the loop): straight from global memory.  Where a
+  // word goes is read from sCD — thread t decoded the words t, t + NT, ... itself (below), so no barrier lies between —
+  // and the table is not fetched and decoded again.
   auto stage_c_sync = [&](int k, int which) {
     T* dst = sm + which * W::IMG;
-    for (int c = t; c < CWD; c += NT) dst[cdecode(a.compact_tab[RC_BASE + NP + 1 + c])] = a.compact[size_t(k) * CWD + c];
+    for (int c = t; c < CWD; c += NT) dst[sCD[c]] = a.compact[size_t(k) * CWD + c];
   };
 
   // (Q_i l_i) of the staged step -> scratch, for ExpectedDecrease
@@ -1152,9 +1175,10 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
     const int nbg = a.compact_tab[RC_NBG];
     const int* bg = a.compact_tab + RC_BASE + NP + 1 + CWD;
     for (int e = t; e < nbg; e += NT) {
-      const int off = cdecode(bg[RC_BG_WORDS * e]);
-      const int kind = bg[RC_BG_WORDS * e + 1];
-      const T v = kind == RC_DT ? T(a.dt) : (kind == RC_NEG_DT ? T(-a.dt) : T(__int_as_float(bg[RC_BG_WORDS * e + 2])));
+      // the entry's three words requested together: one round trip, not one per word
+      const int code = bg[RC_BG_WORDS * e], kind = bg[RC_BG_WORDS * e + 1], bits = bg[RC_BG_WORDS * e + 2];
+      const int off = cdecode(code);
+      const T v = kind == RC_DT ? T(a.dt) : (kind == RC_NEG_DT ? T(-a.dt) : T(__int_as_float(bits)));
       sm[off] = v;
       sm[W::IMG + off] = v;
     }
@@ -1175,30 +1199,40 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
   if constexpr (BCONST) {
     const int nbg = a.compact_tab[RC_NBG];
     const int* bg = a.compact_tab + RC_BASE + NP + 1 + CWD;
-    for (int e = 0; e < nbg; e++) {
-      const int code = bg[RC_BG_WORDS * e], kind = bg[RC_BG_WORDS * e + 1];
-      if ((code >> 24) != RA_B) continue;
-      const int col = (code & 0xffffff) / NX, row = (code & 0xffffff) - col * NX;
-      const T v = kind == RC_DT ? T(a.dt) : (kind == RC_NEG_DT ? T(-a.dt) : T(__int_as_float(bg[RC_BG_WORDS * e + 2])));
+    // Lane e reads entry e — the three words of 64 entries in one round trip, not one dependent trip per word and entry
+    // on every lane — and the wave then visits B's entries in list order through a ballot and read-lanes.
+    for (int e0 = 0; e0 < nbg; e0 += 64) {
+      const bool has = e0 + lane < nbg;
+      const int* ent = bg + RC_BG_WORDS * (has ? e0 + lane : e0);
+      const int codeL = ent[0], kindL = ent[1], bitsL = ent[2];
+      unsigned long long todo = __builtin_amdgcn_ballot_w64(has && (codeL >> 24) == RA_B);
+      while (todo != 0) {
+        const int src = __builtin_amdgcn_readfirstlane(__builtin_ctzll(todo));
+        todo &= todo - 1;
+        const int code = __builtin_amdgcn_readlane(codeL, src), kind = __builtin_amdgcn_readlane(kindL, src);
+        const int bits = __builtin_amdgcn_readlane(bitsL, src);
+        const int col = (code & 0xffffff) / NX, row = (code & 0xffffff) - col * NX;
+        const T v = kind == RC_DT ? T(a.dt) : (kind == RC_NEG_DT ? T(-a.dt) : T(__int_as_float(bits)));
 #pragma unroll
-      for (int r = 0; r < 4; r++) {
-        if (row == TL::row(g, r)) {
-          nbF[r] = -v;
-          oF[r] = col + LD * j;
+        for (int r = 0; r < 4; r++) {
+          if (row == TL::row(g, r)) {
+            nbF[r] = -v;
+            oF[r] = col + LD * j;
+          }
         }
-      }
 #pragma unroll
-      for (int aa = 0; aa < MU; aa++)
-        if (col == w * MU + aa) {
-          bG[aa] = v;
-          selG[aa] = -1;
+        for (int aa = 0; aa < MU; aa++)
+          if (col == w * MU + aa) {
+            bG[aa] = v;
+            selG[aa] = -1;
 #pragma unroll
-          for (int r = 0; r < 4; r++)
-            if (row == TL::row(g, r)) selG[aa] = r;
+            for (int r = 0; r < 4; r++)
+              if (row == TL::row(g, r)) selG[aa] = r;
+          }
+        if (col == j) {
+          bS = v;
+          oS = row * MU;
         }
-      if (col == j) {
-        bS = v;
-        oS = row * MU;
       }
     }
   }
@@ -1681,7 +1715,10 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_pw(const LQArgs<T>& a,
           Qy[r] += (in && qw >= 0) ? h * mCols : T(0);
         }
       }
-      Cd = tile_xty_blocks<T, kblock_mask<T>(0, M)>(Pm, Qy, Cd);
+      if constexpr (PAIRS)
+        Cd = tile_xty_blocks_rt<T, kblock_mask<T>(0, M)>(Pm, Qy, Cd, kPairMask);
+      else
+        Cd = tile_xty_blocks<T, kblock_mask<T>(0, M)>(Pm, Qy, Cd);
     }
     if constexpr (!(SOLVER && SPARE))
     static_for<NP>([&](auto JJ) {  // jj is a compile-time constant: it selects the k blocks of the product

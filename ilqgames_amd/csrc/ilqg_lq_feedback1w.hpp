@@ -191,6 +191,25 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_1w(const LQArgs<T>& a,
     }
   };
 
+  // PAIRS: the C-term product [P | alpha]^T [H | q] of player w over the k blocks that hold a row of a present pair
+  // (w, jj), as in the player-parallel sweep (ilqg_lq.hpp, PAIRS): one scalar mask per player, from the pair table.
+  // fp64 only: in fp32 the compiler moves the chains that form [H | q] behind the branch and vectorises them there with
+  // packed multiplies and adds where the full product has fused multiply-adds — other bits (alpha, three ulp) — so the
+  // fp32 form keeps the full product.
+  // (Nothing of it is instantiated there: the fp32 kernel's packed arithmetic moved with as little as an unused mask.)
+  constexpr bool PAIRS = ROWBC && sizeof(T) == 8;
+  [[maybe_unused]] int kPairMask[PAIRS ? NP : 1];
+  if constexpr (PAIRS) {
+#pragma unroll
+    for (int w = 0; w < NP; w++) {
+      int km = 0;
+#pragma unroll
+      for (int f = 0; f < NP; f++)
+        if (pr.q[w][f] >= 0) km |= kblock_mask_rt<T>(0, f * MU, f * MU + MU);
+      kPairMask[w] = __builtin_amdgcn_readfirstlane(km);
+    }
+  }
+
   // ---- zero the tile padding (and everything else the scatter does not write), once; the constants of the image ----
   for (int e = lane; e < W::ELEMS; e += 64) sm[e] = T(0);
   lds_sync(true);
@@ -451,7 +470,10 @@ __device__ __forceinline__ void lq_feedback_instance_mfma_1w(const LQArgs<T>& a,
         const int srow = row < NX ? row : 0;
         Cd[r] += (row < NX ? sl[w * NX + srow] : T(0)) * mVecCol;
       }
-      Cd = tile_xty_blocks<T, kblock_mask<T>(0, M)>(Pd, Qy, Cd);
+      if constexpr (PAIRS)  // rows of an absent pair are exact zeros in Qy: their blocks add 0 x p and are not issued
+        Cd = tile_xty_blocks_rt<T, kblock_mask<T>(0, M)>(Pd, Qy, Cd, kPairMask[w]);
+      else
+        Cd = tile_xty_blocks<T, kblock_mask<T>(0, M)>(Pd, Qy, Cd);
       const vec Wd = tile_xty<T>(Zd[w], Fd, zero4);  // Z_w [F | beta] (Z_w symmetric: its own transpose)
       vec Wz;
 #pragma unroll
