@@ -72,6 +72,14 @@ class InstanceParam(C.Structure):
 
 PARAM_WEIGHT, PARAM_VALUE = 0, 1
 PARAM_FIELDS = {"weight": PARAM_WEIGHT, "value": PARAM_VALUE}
+# ilqg_solver_field: the members of ilqg_solver_params in their order ("linesearch" and "open_loop" are named to be refused)
+SOLVER_FIELD_NAMES = ("convergence_tolerance", "max_solver_iters", "linesearch", "initial_alpha_scaling",
+                      "geometric_alpha_scaling", "max_backtracking_steps", "expected_decrease_fraction", "open_loop",
+                      "unconstrained_solver_max_iters", "geometric_mu_scaling", "geometric_mu_downscaling",
+                      "geometric_lambda_downscaling", "constraint_error_tolerance")
+SOLVER_FIELDS = {name: q for q, name in enumerate(SOLVER_FIELD_NAMES)}
+SOLVER_INT_FIELDS = ("max_solver_iters", "max_backtracking_steps", "unconstrained_solver_max_iters")
+MAX_INSTANCE_PARAMS = 256
 
 
 class IterateLog(C.Structure):

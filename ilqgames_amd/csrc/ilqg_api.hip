@@ -404,7 +404,11 @@ __global__ void __launch_bounds__(64) ilq_rows_kernel(DevProblem p, SolveArgs<T>
   rows_part_instance<T, NX, NP, MU, PROGID>(p, maps, sa, b, int(blockIdx.x), sm);
 }
 
-template <typename T, int NX, int NP, int MU>
+// SOLVER: the kernel of a problem with per-instance solver columns bound (solver_params_of).  A twin, as the fused trial
+// kernel has one for bound problems: this kernel is a chain of dependent loads per instance, and the test of
+// DevProblem::inst_solver with its wait cost the unbound fp32 batch of 8192 0.4-0.55 % — the unbound
+// twin is the code it was.
+template <typename T, int NX, int NP, int MU, bool SOLVER = true>
 __global__ void __launch_bounds__(64) ilq_decide_kernel(DevProblem p, SolveArgs<T> sa) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = sa.ids ? sa.ids[blockIdx.x] : int(blockIdx.x);
@@ -413,7 +417,7 @@ __global__ void __launch_bounds__(64) ilq_decide_kernel(DevProblem p, SolveArgs<
     const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
     if (stage != ST_ROLLOUT && stage != ST_QUAD) return;
   }
-  trial_part_instance<T, NX, NP, MU, 1, TRIAL_DECIDE>(p, nullptr, sa, b, reinterpret_cast<T*>(smem_raw));
+  trial_part_instance<T, NX, NP, MU, 1, TRIAL_DECIDE, 0, false, SOLVER>(p, nullptr, sa, b, reinterpret_cast<T*>(smem_raw));
 }
 
 // Speculative line search of the listed instances (ilqg_solve.hpp): candidate j of list entry `slot`.
@@ -454,7 +458,7 @@ __global__ void __launch_bounds__(64, sizeof(T) == 8 ? 4 : 1) ilq_probe_rows_ker
   {  // leave before the table load if this candidate is not wanted
     const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
     const SolveState<T> s = state_load<T>(sa.ws + size_t(b) * sa.ws_stride, L);
-    if (!probe_wanted(sa, s, j)) return;
+    if (!probe_wanted(sa, solver_params_of(p, sa.prm, b), s, j)) return;
   }
   const short* maps = sa.compact ? nullptr : rows_maps_load(p, smem_raw);  // merit only: no dense image either way
   T* sm = reinterpret_cast<T*>(smem_raw + (sa.compact ? 0 : rows_maps_bytes(p)));
@@ -737,7 +741,7 @@ padded_lq_kernel(DevProblem p, SolveArgs<T> sa, PadArgs<T> pa) {
     st->expected_decrease = sm[PS::ED_SLOT];
     st->num_iterations += 1;
     st->step = sa.forced_steps ? sa.forced_steps[size_t(b) * sa.fixed_iters + (st->num_iterations - 1)]
-                               : T(sa.prm.initial_alpha_scaling);
+                               : T(solver_real_of(p, b, ILQG_SOLVER_INITIAL_ALPHA_SCALING, sa.prm.initial_alpha_scaling));
     st->bt = 0;
     st->stage = ST_ROLLOUT;
   }
@@ -1725,7 +1729,8 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
     const bool regs = static_id && static_in_regs;
     plan.roll = {ilq_roll_kernel<T, NX, NP, MU>, 64, lds_proll};
     plan.rows = {k_rows, 64, regs ? static_regs_lds : split_maps_bytes + split_rows_elems(d, NX, rows_cw) * sizeof(T)};
-    plan.decide = {ilq_decide_kernel<T, NX, NP, MU>, 64, trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw)};
+    plan.decide = {d.inst_solver ? ilq_decide_kernel<T, NX, NP, MU, true> : ilq_decide_kernel<T, NX, NP, MU, false>, 64,
+                   trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw)};
     plan.prows = {k_prows, 64, regs ? static_regs_lds : split_maps_bytes + probe_rows_elems(d, NX, rows_cw) * sizeof(T)};
     plan.proll = {ilq_probe_roll_kernel<T, NX, NP, MU>, 64, lds_proll};
     plan.proll_fat = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8>, 64, lds_proll};  // (fp32: the same kernel)
@@ -2236,8 +2241,9 @@ ilqg_status ilqg_problem_declare_instance_params(ilqg_problem* p, int32_t count,
   if (p->bindings.bound[kBindValues])
     return fail(ILQG_ERR_INVALID, "instance parameters cannot be declared while values are bound: unbind first");
   ilqg_status s = instance_params_check_terms(int(p->terms_host.size()), p->terms_host.data(), count, params);
-  if (s == ILQG_OK) s = instance_total_check(size_t(count), p->inst_subs.size());
-  return s != ILQG_OK ? s : declare_instance_columns(p, std::vector<ilqg_instance_param>(params, params + count), p->inst_subs);
+  if (s == ILQG_OK) s = instance_total_check(size_t(count), p->inst_subs.size(), p->inst_solver.size());
+  return s != ILQG_OK ? s : declare_instance_columns(p, std::vector<ilqg_instance_param>(params, params + count), p->inst_subs,
+                                                     p->inst_solver);
 }
 
 // ---- per-instance subsystem parameters (ilqg.h) ----
@@ -2255,8 +2261,24 @@ ilqg_status ilqg_problem_declare_instance_subsystem_params(ilqg_problem* p, int3
   if (p->bindings.bound[kBindValues])
     return fail(ILQG_ERR_INVALID, "instance parameters cannot be declared while values are bound: unbind first");
   ilqg_status s = instance_subsystems_check(p->dev.N, p->dev.sub_kind, count, subsystems);
-  if (s == ILQG_OK) s = instance_total_check(p->inst_params.size(), size_t(count));
-  return s != ILQG_OK ? s : declare_instance_columns(p, p->inst_params, std::vector<int>(subsystems, subsystems + count));
+  if (s == ILQG_OK) s = instance_total_check(p->inst_params.size(), size_t(count), p->inst_solver.size());
+  return s != ILQG_OK ? s : declare_instance_columns(p, p->inst_params, std::vector<int>(subsystems, subsystems + count),
+                                                     p->inst_solver);
+}
+
+// ---- per-instance solver parameters (ilqg.h) ----
+ilqg_status ilqg_instance_solver_params_check(const ilqg_problem_desc* desc, int32_t count, const int32_t* fields) {
+  if (!desc) return fail(ILQG_ERR_INVALID, "null argument");
+  return instance_solver_check(count, fields);
+}
+
+ilqg_status ilqg_problem_declare_instance_solver_params(ilqg_problem* p, int32_t count, const int32_t* fields) {
+  if (!p) return fail(ILQG_ERR_INVALID, "null argument");
+  if (p->bindings.bound[kBindValues])
+    return fail(ILQG_ERR_INVALID, "instance parameters cannot be declared while values are bound: unbind first");
+  ilqg_status s = instance_solver_check(count, fields);
+  if (s == ILQG_OK) s = instance_total_check(p->inst_params.size(), p->inst_subs.size(), size_t(count));
+  return s != ILQG_OK ? s : declare_instance_columns(p, p->inst_params, p->inst_subs, std::vector<int>(fields, fields + count));
 }
 
 ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, const float* values) {
@@ -2266,15 +2288,17 @@ ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, co
     d.inst_values = nullptr;
     d.inst_terms = nullptr;
     d.inst_count = 0;
+    d.inst_solver = 0;
     p->bindings.bound[kBindValues] = false;
     return ILQG_OK;
   }
-  if (p->inst_params.empty() && p->inst_subs.empty())
+  if (p->inst_params.empty() && p->inst_subs.empty() && p->inst_solver.empty())
     return fail(ILQG_ERR_INVALID, "no instance parameters are declared (ilqg_problem_declare_instance_params)");
   if (ilqg_status s = bind_batch_check(p, kBindValues, batch)) return s;
   d.inst_values = values;
   d.inst_terms = p->d_inst_terms.get();
-  d.inst_count = int(p->inst_params.size() + p->inst_subs.size());
+  d.inst_count = int(p->inst_params.size() + p->inst_subs.size() + p->inst_solver.size());
+  d.inst_solver = int(p->inst_solver.size());
   p->bindings.bind(kBindValues, batch);
   return ILQG_OK;
 }

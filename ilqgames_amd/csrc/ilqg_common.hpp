@@ -109,10 +109,13 @@ struct DevProblem {
   // unless a table is bound: every reader then takes the baked parameters.  Read-only on the device.
   const float* inst_values;  // [batch][inst_count], the caller's buffer
   const int* inst_terms;     // [inst_count][2]: (term index, ilqg_param_field) (quad_tables_load), (-1, subsystem) for a
-                             // subsystem column; then [kMaxPlayers]: subsystem -> its column or -1 (subsystem_param)
+                             // subsystem column, (-1, -1 - ilqg_solver_field) for a solver column; then [kMaxPlayers]:
+                             // subsystem -> its column or -1 (subsystem_param); then [ILQG_NUM_SOLVER_FIELDS]:
+                             // ilqg_solver_field -> its column or -1 (solver_params_of)
   // (the row stage's table — per op of row_prog the column of its weight / value, or -1 — follows the program's
   // row_prog_words words in the device buffer `row_prog` points to)
   int inst_count;
+  int inst_solver;  // how many of the columns are solver columns (the last ones); 0: the solves read ilqg_solver_params alone
   // Per-instance routes (ilqg_problem_bind_instance_routes): while a route table is bound segs_f / segs_d point at the
   // handle's [batch][total_segs][kSegStride] table and this is total_segs * kSegStride, the elements between two
   // instances' tables; 0: every instance reads the one baked table.
@@ -134,6 +137,79 @@ __device__ __forceinline__ float subsystem_param(const DevProblem& p, const floa
     if (c >= 0) return iv[c];
   }
   return p.sub_param[s];
+}
+
+// Per-instance solver parameters (ilqg.h): a member of the descriptor's ilqg_solver_params, or, with solver columns
+// bound, instance b's float of the declared member's column.  b is the instance a whole workgroup works on.
+// The field -> column map and the instance's row are read through CONSTANT-ADDRESS-SPACE views of the two tables (both
+// are read-only for the length of a kernel: the map is the handle's, the row the caller's, rewritten between calls
+// only).  A plain global pointer in a kernel that also stores is loaded through the vector memory path even at a uniform
+// address — the value then sits in a VGPR and every member is a chain of two vector loads with a full wait each; the
+// constant view makes them s_loads, and a member lives in scalar registers like the kernel argument it replaces.  The
+// map's entries of one call site merge into wide scalar loads.  A FLOAT member's value load is unconditional (an
+// undeclared member reads column 0 and keeps the baked value by a select); an integer member's sits behind a uniform
+// branch on its column, with the ceiling test.
+// Called WHERE A MEMBER IS USED (the decision section, the exit path, a sweep's last lines), not at kernel entry.  No
+// table bound, or one without a solver column: the one uniform test of a kernel argument, then the baked value.
+typedef const __attribute__((address_space(4))) float* ConstFloats;
+typedef const __attribute__((address_space(4))) int* ConstInts;
+struct SolverRow {  // null row: no solver column is bound
+  ConstFloats row;
+  ConstInts col;
+};
+__device__ __forceinline__ SolverRow solver_row(const DevProblem& p, int b) {
+  SolverRow r;
+  r.row = nullptr;
+  r.col = nullptr;
+  if (p.inst_solver != 0) {
+    r.row = (ConstFloats)(p.inst_values + size_t(__builtin_amdgcn_readfirstlane(b)) * size_t(p.inst_count));
+    r.col = (ConstInts)(p.inst_terms + 2 * p.inst_count + kMaxPlayers);
+  }
+  return r;
+}
+__device__ __forceinline__ float solver_real(const SolverRow& r, int field, float baked) {
+  if (!r.row) return baked;
+  const int c = r.col[field];
+  const float v = r.row[c >= 0 ? c : 0];
+  return c >= 0 ? v : baked;
+}
+// An integer member travels as a float: truncated, and limited to [0, the descriptor's value] whatever it holds — the
+// host sized its round plans and the iterate log by the descriptor's value (a NaN fails the first test).
+__device__ __forceinline__ int solver_int_member(float v, int ceiling) {
+  if (!(v < float(ceiling))) return ceiling;
+  if (!(v > 0.0f)) return 0;
+  const int i = int(v);
+  return i < ceiling ? i : ceiling;  // (a ceiling above 2^24 may round up as a float)
+}
+__device__ __forceinline__ int solver_whole(const SolverRow& r, int field, int baked) {
+  if (!r.row) return baked;
+  const int c = r.col[field];
+  const float v = r.row[c >= 0 ? c : 0];
+  // (gfx950 compares and converts floats on the vector ALU: the result goes back to a scalar register)
+  return c >= 0 ? __builtin_amdgcn_readfirstlane(solver_int_member(v, baked)) : baked;
+}
+// One member for a site that reads one (the sweeps' first step)
+__device__ __forceinline__ float solver_real_of(const DevProblem& p, int b, int field, float baked) {
+  return solver_real(solver_row(p, b), field, baked);
+}
+// ... and the descriptor's `prm` with every declared member replaced, for the sites that read several: the members a
+// site does not read are dead code (the register tables of DESIGN.md 3.14 were taken with this form)
+__device__ __forceinline__ ilqg_solver_params solver_params_of(const DevProblem& p, const ilqg_solver_params& prm, int b) {
+  ilqg_solver_params o = prm;
+  const SolverRow r = solver_row(p, b);
+  if (!r.row) return o;
+  o.convergence_tolerance = solver_real(r, ILQG_SOLVER_CONVERGENCE_TOLERANCE, prm.convergence_tolerance);
+  o.max_solver_iters = solver_whole(r, ILQG_SOLVER_MAX_SOLVER_ITERS, prm.max_solver_iters);
+  o.initial_alpha_scaling = solver_real(r, ILQG_SOLVER_INITIAL_ALPHA_SCALING, prm.initial_alpha_scaling);
+  o.geometric_alpha_scaling = solver_real(r, ILQG_SOLVER_GEOMETRIC_ALPHA_SCALING, prm.geometric_alpha_scaling);
+  o.max_backtracking_steps = solver_whole(r, ILQG_SOLVER_MAX_BACKTRACKING_STEPS, prm.max_backtracking_steps);
+  o.expected_decrease_fraction = solver_real(r, ILQG_SOLVER_EXPECTED_DECREASE_FRACTION, prm.expected_decrease_fraction);
+  o.unconstrained_solver_max_iters = solver_whole(r, ILQG_SOLVER_UNCONSTRAINED_SOLVER_MAX_ITERS, prm.unconstrained_solver_max_iters);
+  o.geometric_mu_scaling = solver_real(r, ILQG_SOLVER_GEOMETRIC_MU_SCALING, prm.geometric_mu_scaling);
+  o.geometric_mu_downscaling = solver_real(r, ILQG_SOLVER_GEOMETRIC_MU_DOWNSCALING, prm.geometric_mu_downscaling);
+  o.geometric_lambda_downscaling = solver_real(r, ILQG_SOLVER_GEOMETRIC_LAMBDA_DOWNSCALING, prm.geometric_lambda_downscaling);
+  o.constraint_error_tolerance = solver_real(r, ILQG_SOLVER_CONSTRAINT_ERROR_TOLERANCE, prm.constraint_error_tolerance);
+  return o;
 }
 
 // arrays of a time step's image, as the row program's regions and the compact rows name them

@@ -110,11 +110,39 @@ ilqg_status instance_subsystems_check(int num_subsystems, const int* kinds, int3
   }
   return ILQG_OK;
 }
-// One value table holds the cost columns and the subsystem columns
-ilqg_status instance_total_check(size_t cost_count, size_t subsystem_count) {
-  if (cost_count + subsystem_count > size_t(ILQG_MAX_INSTANCE_PARAMS))
+// Per-instance solver parameters (ilqg.h): the members of ilqg_solver_params by ilqg_solver_field
+const char* solver_field_name(int field) {
+  static const char* const names[] = {"convergence_tolerance", "max_solver_iters", "linesearch", "initial_alpha_scaling",
+                                      "geometric_alpha_scaling", "max_backtracking_steps", "expected_decrease_fraction",
+                                      "open_loop", "unconstrained_solver_max_iters", "geometric_mu_scaling",
+                                      "geometric_mu_downscaling", "geometric_lambda_downscaling", "constraint_error_tolerance"};
+  static_assert(ILQG_NUM_SOLVER_FIELDS == sizeof(names) / sizeof(names[0]) &&
+                    ILQG_SOLVER_CONSTRAINT_ERROR_TOLERANCE + 1 == ILQG_NUM_SOLVER_FIELDS, "one name per member");
+  return field >= 0 && field < ILQG_NUM_SOLVER_FIELDS ? names[field] : "unknown field";
+}
+ilqg_status instance_solver_check(int32_t count, const int32_t* fields) {
+  if (count < 0 || count > ILQG_MAX_INSTANCE_PARAMS)
+    return fail(ILQG_ERR_INVALID, "instance solver parameters: count must be 0 .. ILQG_MAX_INSTANCE_PARAMS");
+  if (count > 0 && !fields) return fail(ILQG_ERR_INVALID, "null argument");
+  for (int c = 0; c < count; c++) {
+    const int f = fields[c];
+    if (f < 0 || f >= ILQG_NUM_SOLVER_FIELDS)
+      return fail(ILQG_ERR_UNSUPPORTED, "instance parameter " + std::to_string(c) + " (solver field " + std::to_string(f) +
+                                            "): not an ilqg_solver_field");
+    const std::string where = "instance parameter " + std::to_string(c) + " (solver field " + solver_field_name(f) + "): ";
+    if (f == ILQG_SOLVER_LINESEARCH || f == ILQG_SOLVER_OPEN_LOOP)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "it selects kernels and the host's schedule and cannot vary per instance");
+    for (int q = 0; q < c; q++)
+      if (fields[q] == f) return fail(ILQG_ERR_UNSUPPORTED, where + "declared twice (also parameter " + std::to_string(q) + ")");
+  }
+  return ILQG_OK;
+}
+// One value table holds the cost columns, the subsystem columns and the solver columns
+ilqg_status instance_total_check(size_t cost_count, size_t subsystem_count, size_t solver_count) {
+  if (cost_count + subsystem_count + solver_count > size_t(ILQG_MAX_INSTANCE_PARAMS))
     return fail(ILQG_ERR_INVALID, "instance parameters: " + std::to_string(cost_count) + " cost columns + " +
-                                      std::to_string(subsystem_count) + " subsystem columns exceed ILQG_MAX_INSTANCE_PARAMS");
+                                      std::to_string(subsystem_count) + " subsystem columns + " + std::to_string(solver_count) +
+                                      " solver columns exceed ILQG_MAX_INSTANCE_PARAMS");
   return ILQG_OK;
 }
 
@@ -140,16 +168,17 @@ ilqg_status instance_routes_check_terms(int num_polylines, int num_terms, const 
   return ILQG_OK;
 }
 
-// ilqg_problem_declare_instance_params / _declare_instance_subsystem_params: the checked lists into the handle, and onto
-// the device the column table ((term, field) per cost column, then subsystem -> column: DevProblem::inst_terms) and the
+// ilqg_problem_declare_instance_params / _declare_instance_subsystem_params / _declare_instance_solver_params: the
+// checked lists into the handle, and onto the device the column table ((term, field) per cost column, then subsystem ->
+// column, then ilqg_solver_field -> column: DevProblem::inst_terms; the solver columns come last) and the
 // row stage's side table (per op of the row program the column of its weight / value; the program is not touched).
 // Subsystem s's column goes to the weight word of its Jacobian op and, for the Air3D pursuer, to the value word of the
 // evader's, where build_row_program put the baked param0.
 ilqg_status declare_instance_columns(ilqg_problem* p, const std::vector<ilqg_instance_param>& params,
-                                     const std::vector<int>& subs) {
+                                     const std::vector<int>& subs, const std::vector<int>& solver) {
   const std::vector<int>&op_term = p->row_prog.op_term, &op_sub = p->row_prog.op_sub;
-  const size_t count = params.size() + subs.size();
-  std::vector<int> cols(op_term.size() * 2 + 2, -1), terms(count * 2 + kMaxPlayers, -1);
+  const size_t count = params.size() + subs.size() + solver.size();
+  std::vector<int> cols(op_term.size() * 2 + 2, -1), terms(count * 2 + kMaxPlayers + ILQG_NUM_SOLVER_FIELDS, -1);
   for (size_t c = 0; c < params.size(); c++) {
     terms[2 * c] = params[c].term;
     terms[2 * c + 1] = params[c].field;
@@ -166,6 +195,12 @@ ilqg_status declare_instance_columns(ilqg_problem* p, const std::vector<ilqg_ins
       if (op_sub[op] == s - 1 && op_sub[op] >= 0 && p->dev.sub_kind[s] == ILQG_DYN_AIR_3D_PURSUER) cols[2 * op + 1] = c;
     }
   }
+  for (size_t q = 0; q < solver.size(); q++) {
+    const int c = int(params.size() + subs.size() + q);
+    terms[2 * c] = -1;
+    terms[2 * c + 1] = -1 - solver[q];
+    terms[2 * count + kMaxPlayers + solver[q]] = c;
+  }
   const char* what = "instance parameter tables";
   // kernels of earlier calls on any stream may still read the old tables (unbound: they look at neither)
   hipError_t e = hipDeviceSynchronize();
@@ -178,6 +213,7 @@ ilqg_status declare_instance_columns(ilqg_problem* p, const std::vector<ilqg_ins
   p->d_inst_terms = std::move(d_terms);  // the old table goes only now that the new one is up
   p->inst_params = params;
   p->inst_subs = subs;
+  p->inst_solver = solver;
   return ILQG_OK;
 }
 

@@ -25,7 +25,7 @@ namespace ilqg {
 // strides by its own constant (ilqg_time_nominal.hpp includes no device header): one layout
 static_assert(kTimeNominalSegStride == kSegStride, "ilqg_time_nominal.hpp and ilqg_common.hpp disagree on a segment's scalars");
 // the kernels take the DevProblem by value: its layout is part of every launch
-static_assert(sizeof(DevProblem) == 832, "DevProblem's size changed");
+static_assert(sizeof(DevProblem) == 840, "DevProblem's size changed");
 
 // LoopTimer (include/ilqgames/utils/loop_timer.h:60-98, src/loop_timer.cpp:55-92): the last ten iteration times
 struct LoopTimer {
@@ -98,10 +98,11 @@ struct ilqg_problem {
   ilqg::RowProgramHost row_prog;
   ilqg::DeviceBuffer<int> d_row_prog;
   // Per-instance parameters (ilqg.h): the declared (term, field) list, the declared subsystems (their columns follow the
-  // cost columns) and their device table (DevProblem::inst_terms); dev.inst_values / inst_count are set while a table is
-  // bound
+  // cost columns), the declared ilqg_solver_fields (theirs come last) and their device table (DevProblem::inst_terms);
+  // dev.inst_values / inst_count / inst_solver are set while a table is bound
   std::vector<ilqg_instance_param> inst_params;
   std::vector<int> inst_subs;
+  std::vector<int> inst_solver;
   ilqg::DeviceBuffer<int> d_inst_terms;
   // Per-instance routes (ilqg.h): the declared polylines, per polyline of the descriptor its first point in a row of the
   // caller's points or -1 (device copy: route_segments_kernel), the points of a row, and while a table is bound the table

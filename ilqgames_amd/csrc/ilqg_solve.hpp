@@ -188,11 +188,10 @@ struct InstanceBuffers {
 };
 
 template <typename T>
-__device__ __forceinline__ int solve_max_iters(const SolveArgs<T>& sa) {
+__device__ __forceinline__ int solve_max_iters(const SolveArgs<T>& sa, const ilqg_solver_params& prm) {
   // AugmentedLagrangianSolver builds its inner ILQSolver with unconstrained_solver_max_iters
-  // (augmented_lagrangian_solver.h:80-84)
-  return sa.fixed_iters > 0 ? sa.fixed_iters
-                            : (sa.al_mode ? sa.prm.unconstrained_solver_max_iters : sa.prm.max_solver_iters);
+  // (augmented_lagrangian_solver.h:80-84).  `prm`: the instance's (solver_params_of)
+  return sa.fixed_iters > 0 ? sa.fixed_iters : (sa.al_mode ? prm.unconstrained_solver_max_iters : prm.max_solver_iters);
 }
 
 // Row waves of a fused trial kernel of W wavefronts: wave 0 integrates, the others take the chunks of rows as they
@@ -235,7 +234,6 @@ __device__ __forceinline__ void solve_exit_path(const DevProblem& p, const QuadT
                                                 const InstanceBuffers<T>& ib, SolveState<T>& s, int b, T* sm) {
   const int n = NX > 0 ? NX : p.n, m = NX > 0 ? NP * MU : p.m;  // NX = 0: the run-time-dimensioned path
   const int Tn = p.T;
-  const ilqg_solver_params& prm = sa.prm;
   const WsLayout& L = ib.L;
   T* const w = ib.w;
   T *const xs0 = ib.xs0, *const us0 = ib.us0, *const P0 = ib.P0, *const al0 = ib.al0;
@@ -271,6 +269,8 @@ __device__ __forceinline__ void solve_exit_path(const DevProblem& p, const QuadT
       copy(al0, ib.AL(s.sacc), Tn * m, s.acc_scale, true);
       __syncthreads();
       s.stage = ST_DONE;
+      // the instance's solver parameters, read here where the bookkeeping needs them (uniform per workgroup)
+      const ilqg_solver_params prm = solver_params_of(p, sa.prm, b);
       if (sa.al_mode) {  // AugmentedLagrangianSolver::Solve, src/augmented_lagrangian_solver.cpp:72-210
         s.logged += 1 + s.accepted_iters;  // SolverLog entries of this inner call (:94, :185)
         s.al_success = s.al_success && s.ok;
@@ -494,15 +494,18 @@ struct ProbeEntry {
 
 // Is instance state `s` in a line search that has already rejected a step, and is candidate j one the sequential
 // loop would reach (ILQSolver::ModifyLQStrategies gives up after max_backtracking_steps rejections)?
+// `prm`: instance b's solver parameters (solver_params_of).  Every probing kernel works on ONE instance per wavefront —
+// a workgroup's candidates, the two halves of a paired rollout and the lanes of rollout_lanes are all candidates of
+// sa.ids[blockIdx.x] — so the members are uniform there too and are read through scalar loads.
 template <typename T>
-__device__ __forceinline__ bool probe_wanted(const SolveArgs<T>& sa, const SolveState<T>& s, int j) {
+__device__ __forceinline__ bool probe_wanted(const SolveArgs<T>& sa, const ilqg_solver_params& prm, const SolveState<T>& s, int j) {
   return (s.stage == ST_ROLLOUT || s.stage == ST_PROBE) && !s.initial && sa.prm.linesearch && s.bt > 0 &&
-         s.bt + j < sa.prm.max_backtracking_steps;
+         s.bt + j < prm.max_backtracking_steps;
 }
 template <typename T>
-__device__ __forceinline__ T probe_step(const SolveArgs<T>& sa, const SolveState<T>& s, int j) {
+__device__ __forceinline__ T probe_step(const ilqg_solver_params& prm, const SolveState<T>& s, int j) {
   T step = s.step;
-  for (int i = 0; i < j; i++) step *= T(sa.prm.geometric_alpha_scaling);  // the products the loop forms, in order
+  for (int i = 0; i < j; i++) step *= T(prm.geometric_alpha_scaling);  // the products the loop forms, in order
   return step;
 }
 
@@ -511,7 +514,8 @@ __device__ __forceinline__ void probe_roll_instance(const DevProblem& p, const S
                                                     T* sm) {
   const InstanceBuffers<T> ib(p, sa, b);
   const SolveState<T> s = state_load<T>(ib.w, ib.L);
-  if (!probe_wanted(sa, s, j)) return;
+  const ilqg_solver_params prm = solver_params_of(p, sa.prm, b);
+  if (!probe_wanted(sa, prm, s, j)) return;
   const ProbeEntry E(p.n, p.m, p.N, p.T);
   T* const e = sa.probe_pool + (size_t(slot) * sa.probe_k + j) * E.total;
   const int snew = 1 - s.sacc;
@@ -521,7 +525,7 @@ __device__ __forceinline__ void probe_roll_instance(const DevProblem& p, const S
   ra.us_ref = ib.US(s.cur);
   ra.P = ib.PB(snew);
   ra.alpha = ib.AL(snew);
-  ra.alpha_scale = probe_step(sa, s, j);
+  ra.alpha_scale = probe_step(prm, s, j);
   ra.xs = e + E.xs;
   ra.us = e + E.us;
   ra.iv = instance_values(p, b);
@@ -538,7 +542,8 @@ template <typename T, int NX, int NP, int MU>
 __device__ __forceinline__ void probe_roll_pair(const DevProblem& p, const SolveArgs<T>& sa, int b, int slot, int j0, T* sm) {
   const InstanceBuffers<T> ib(p, sa, b);
   const SolveState<T> s = state_load<T>(ib.w, ib.L);
-  const bool w0 = probe_wanted(sa, s, j0), w1 = j0 + 1 < sa.probe_k && probe_wanted(sa, s, j0 + 1);
+  const ilqg_solver_params prm = solver_params_of(p, sa.prm, b);
+  const bool w0 = probe_wanted(sa, prm, s, j0), w1 = j0 + 1 < sa.probe_k && probe_wanted(sa, prm, s, j0 + 1);
   if (!w0 && !w1) return;
   const ProbeEntry E(p.n, p.m, p.N, p.T);
   const int snew = 1 - s.sacc;
@@ -551,7 +556,7 @@ __device__ __forceinline__ void probe_roll_pair(const DevProblem& p, const Solve
     ra[q].us_ref = ib.US(s.cur);
     ra[q].P = ib.PB(snew);
     ra[q].alpha = ib.AL(snew);
-    ra[q].alpha_scale = probe_step(sa, s, j);
+    ra[q].alpha_scale = probe_step(prm, s, j);
     ra[q].xs = e + E.xs;
     ra[q].us = e + E.us;
     ra[q].iv = instance_values(p, b);
@@ -566,12 +571,13 @@ template <typename T, int NX, int NP, int MU>
 __device__ __forceinline__ void probe_roll_lanes(const DevProblem& p, const SolveArgs<T>& sa, int b, int slot, int j0, T* sm) {
   const InstanceBuffers<T> ib(p, sa, b);
   const SolveState<T> s = state_load<T>(ib.w, ib.L);
-  if (j0 >= sa.probe_k || !probe_wanted(sa, s, j0)) return;
+  const ilqg_solver_params prm = solver_params_of(p, sa.prm, b);
+  if (j0 >= sa.probe_k || !probe_wanted(sa, prm, s, j0)) return;
   const ProbeEntry E(p.n, p.m, p.N, p.T);
   const int snew = 1 - s.sacc;
   const int t = int(threadIdx.x);
   const int c = t / NP;
-  const bool act = c < rollout_lanes_per_wave(NP) && j0 + c < sa.probe_k && probe_wanted(sa, s, j0 + c);
+  const bool act = c < rollout_lanes_per_wave(NP) && j0 + c < sa.probe_k && probe_wanted(sa, prm, s, j0 + c);
   const int j = act ? j0 + c : j0;
   T* const e = sa.probe_pool + (size_t(slot) * sa.probe_k + j) * E.total;
   RolloutArgs<T> ra;
@@ -584,7 +590,7 @@ __device__ __forceinline__ void probe_roll_lanes(const DevProblem& p, const Solv
   ra.xs = nullptr;
   ra.us = nullptr;
   ra.iv = instance_values(p, b);
-  rollout_lanes<T, NX, NP * MU, NP, (MU == 1)>(p, ra, probe_step(sa, s, j), e + E.xs, e + E.us, act, sm, t);
+  rollout_lanes<T, NX, NP * MU, NP, (MU == 1)>(p, ra, probe_step(prm, s, j), e + E.xs, e + E.us, act, sm, t);
 }
 
 template <typename T, int NX, int NP, int MU, int PROGID = 0>
@@ -592,7 +598,7 @@ __device__ __forceinline__ void probe_rows_instance(const DevProblem& p, const s
                                                     int b, int slot, int j, int chunk, T* sm) {
   const InstanceBuffers<T> ib(p, sa, b);
   const SolveState<T> s = state_load<T>(ib.w, ib.L);
-  if (!probe_wanted(sa, s, j)) return;
+  if (!probe_wanted(sa, solver_params_of(p, sa.prm, b), s, j)) return;
   const ProbeEntry E(p.n, p.m, p.N, p.T);
   T* const e = sa.probe_pool + (size_t(slot) * sa.probe_k + j) * E.total;
   QuadArgs<T> qa;
@@ -625,8 +631,8 @@ __device__ __forceinline__ void probe_pick_instance(const DevProblem& p, const S
                                                     T* merits = nullptr) {
   const InstanceBuffers<T> ib(p, sa, b);
   SolveState<T> s = state_load<T>(ib.w, ib.L);
-  if (!probe_wanted(sa, s, 0)) return;
-  const ilqg_solver_params& prm = sa.prm;
+  const ilqg_solver_params prm = solver_params_of(p, sa.prm, b);
+  if (!probe_wanted(sa, prm, s, 0)) return;
   const ProbeEntry E(p.n, p.m, p.N, p.T);
   const T* const e0 = sa.probe_pool + size_t(slot) * sa.probe_k * E.total;
   if (merits) {
@@ -849,14 +855,17 @@ __host__ __device__ constexpr bool fused_rollout_room(int elem_bytes, int nx, in
 // from the instance's row of the table.  Kernels of their own, as the bound straight-line row code is: the read costs the
 // unbound fused kernel two registers (and, n = 14 in fp64, a spill), so that one stays the code it was.  The one-wave
 // rollout kernel of the split pass (TRIAL_ROLL) has room for it and looks at run time.
-template <typename T, int NX, int NP, int MU, int W, int PHASE = TRIAL_FUSED, int PROGID = 0, bool BOUND = (PROGID >= kBoundProg)>
+// SOLVER_COLS: the decision section reads the instance's solver parameters (solver_params_of).  False only in the
+// decision kernel's twin for problems with no solver column bound (ilq_decide_kernel's SOLVER, ilqg_api.hip), which reads
+// the descriptor alone; independent of BOUND, which is about the rollout's and the rows' tables.
+template <typename T, int NX, int NP, int MU, int W, int PHASE = TRIAL_FUSED, int PROGID = 0, bool BOUND = (PROGID >= kBoundProg),
+          bool SOLVER_COLS = true>
 __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const short* maps,
                                                     const SolveArgs<T>& sa, int b, T* sm) {
   static_assert(PHASE == TRIAL_FUSED || W == 1, "the split phases run one wave per instance");
   static_assert(NX > 0 || PHASE != TRIAL_FUSED, "the run-time-dimensioned path (NX = 0) runs the split passes");
   const int n = NX > 0 ? NX : p.n, N = NX > 0 ? NP : p.N, m = NX > 0 ? NP * MU : p.m;
   const int Tn = p.T;
-  const ilqg_solver_params& prm = sa.prm;
   const InstanceBuffers<T> ib(p, sa, b);
   const WsLayout& L = ib.L;
   T* const w = ib.w;
@@ -876,7 +885,6 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
   T* const ed_slot = reinterpret_cast<T*>(flags + 2);  // deferred ExpectedDecrease, from the first row wave to everyone
 
   SolveState<T> s = trial_state_begin<T>(p, sa, ib, b, n, N, m);
-  const int max_iters = solve_max_iters(sa);
   tl_stamp(sa.prof, b, 0, t == 0);
   const long long pr_start = clock64();
   long long qph[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // linquad phase profile of this wave (diagnostics)
@@ -1010,6 +1018,12 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
     }
     // ---- reductions and the line-search decision (wave-uniform, identical on every wave) ----
     tl_stamp(sa.prof, b, 12, t == 0);
+    // The instance's solver parameters (solver_params_of), read HERE and not at kernel entry: they are uniform per
+    // workgroup and scalar, and nothing of them is live across the rollout and the row stage, where the fp64 kernels
+    // have no register to spare.
+    ilqg_solver_params prm = sa.prm;
+    if constexpr (SOLVER_COLS) prm = solver_params_of(p, sa.prm, b);
+    const int max_iters = solve_max_iters(sa, prm);
     if (qmode == Q_COSTS) {
       costs_reduce<T>(p, w + L.cpart, costs, t_extreme, sm_quad0, int(qe));
       s.qmode = Q_INIT;
@@ -1238,7 +1252,7 @@ __device__ __forceinline__ void lq_part_instance(const DevProblem& p, const Solv
       st->expected_decrease = sm[ed_slot];
     st->num_iterations += 1;
     st->step = sa.forced_steps ? sa.forced_steps[size_t(b) * sa.fixed_iters + (st->num_iterations - 1)]
-                               : T(sa.prm.initial_alpha_scaling);
+                               : T(solver_real_of(p, b, ILQG_SOLVER_INITIAL_ALPHA_SCALING, sa.prm.initial_alpha_scaling));
     st->bt = 0;
     st->stage = ST_ROLLOUT;
     if (kProfile && sa.prof) sa.prof[size_t(b) * 96 + 2] += clock64() - pr_start;
@@ -1282,7 +1296,7 @@ __device__ __forceinline__ void lq_part_generic(const DevProblem& p, const Solve
     st->expected_decrease = *la.ed_out;
     st->num_iterations += 1;
     st->step = sa.forced_steps ? sa.forced_steps[size_t(b) * sa.fixed_iters + (st->num_iterations - 1)]
-                               : T(sa.prm.initial_alpha_scaling);
+                               : T(solver_real_of(p, b, ILQG_SOLVER_INITIAL_ALPHA_SCALING, sa.prm.initial_alpha_scaling));
     st->bt = 0;
     st->stage = ST_ROLLOUT;
   }

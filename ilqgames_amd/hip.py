@@ -26,6 +26,7 @@ EXPORTS = [
     "ilqg_set_scratch", "ilqg_problem_last_schedule", "ilqg_copy_bandwidth", "ilqg_problem_row_program", "ilqg_row_program_build",
     "ilqg_problem_declare_instance_params", "ilqg_problem_bind_instance_values", "ilqg_instance_params_check",
     "ilqg_problem_declare_instance_subsystem_params", "ilqg_instance_subsystem_params_check",
+    "ilqg_problem_declare_instance_solver_params", "ilqg_instance_solver_params_check",
     "ilqg_problem_declare_instance_routes", "ilqg_problem_bind_instance_routes", "ilqg_instance_routes_check",
     "ilqg_segment_table_build",
     "ilqg_problem_bind_instance_time_nominals", "ilqg_instance_time_nominals_build", "ilqg_problem_time_nominal_terms",
@@ -224,6 +225,21 @@ def instance_subsystem_params_check(spec, rows, dtype=abi.F64):
     del keep
 
 
+def _instance_solver_fields(fields):
+    """Members of ilqg_solver_params by name (abi.SOLVER_FIELDS) or as ilqg_solver_field numbers."""
+    fields = [abi.SOLVER_FIELDS[f] if isinstance(f, str) else int(f) for f in fields]
+    return (C.c_int32 * max(1, len(fields)))(*fields), len(fields)
+
+
+def instance_solver_params_check(spec, fields, dtype=abi.F64, count=None):
+    """ilqg_instance_solver_params_check: raises IlqgError where Problem.declare_instance_solver_params would — host
+    only, no device needed.  `count`: passed instead of len(fields) (the refusals of a count out of range)."""
+    desc, keep = spec.build(dtype)
+    arr, n = _instance_solver_fields(fields)
+    _check(lib().ilqg_instance_solver_params_check(C.byref(desc), n if count is None else int(count), arr))
+    del keep
+
+
 def segment_table(spec, dtype=abi.F64):
     """ilqg_segment_table_build: the [segments][21] table problem creation builds from the spec's polylines, in dtype's
     arithmetic — host only, no device needed."""
@@ -287,6 +303,7 @@ class Problem:
         self.single_wave_sweep = None
         # per-instance bindings: what the declare calls recorded, and the bound tables, kept alive while bound
         self.instance_params, self.instance_subsystems, self.instance_routes = [], [], []
+        self.instance_solver_fields = []
         self._instance_values = self._instance_time_nominals = None
 
     def __del__(self):
@@ -315,6 +332,14 @@ class Problem:
         arr, count = _instance_subsystems(rows)
         _check(lib().ilqg_problem_declare_instance_subsystem_params(self.h, count, arr))
         self.instance_subsystems = [int(arr[c]) for c in range(count)]
+
+    def declare_instance_solver_params(self, fields):
+        """ilqg_problem_declare_instance_solver_params: members of ilqg_solver_params, by name or as ilqg_solver_field
+        numbers, that vary per instance; column cost_count + subsystem_count + c of the table bind_instance_values binds
+        overrides fields[c] in every later solve.  An integer member is limited to [0, the spec's value].  [] clears."""
+        arr, count = _instance_solver_fields(fields)
+        _check(lib().ilqg_problem_declare_instance_solver_params(self.h, count, arr))
+        self.instance_solver_fields = [int(arr[c]) for c in range(count)]
 
     def declare_instance_routes(self, polylines):
         """ilqg_problem_declare_instance_routes: indices of the spec's polylines whose points vary per instance; a row of
@@ -391,7 +416,7 @@ class Problem:
         return table
 
     def bind_instance_values(self, values):
-        """ilqg_problem_bind_instance_values: a float32 [B][count] table, count = cost columns + subsystem columns (uploaded if it is not a CUDA tensor), read by
+        """ilqg_problem_bind_instance_values: a float32 [B][count] table, count = cost columns + subsystem columns + solver columns (uploaded if it is not a CUDA tensor), read by
         every later call on this problem until bind_instance_values(None); the tensor is kept alive while bound and
         returned — a CUDA float32 tensor passed in is bound as it is, so the caller may rewrite it between calls."""
         import torch
@@ -400,7 +425,7 @@ class Problem:
             self._instance_values = None
             return None
         values = _table(values, torch.float32)
-        count = len(self.instance_params) + len(self.instance_subsystems)
+        count = len(self.instance_params) + len(self.instance_subsystems) + len(self.instance_solver_fields)
         if values.dim() != 2 or values.shape[1] != count:
             raise ValueError("instance values must be [batch][%d], got %s" % (count, tuple(values.shape)))
         _check(lib().ilqg_problem_bind_instance_values(self.h, values.shape[0], C.c_void_p(values.data_ptr())))

@@ -456,7 +456,7 @@ class Packer {
 
 bool ResolveInstanceParams(const ProblemDescription& description, const InstanceParams& params,
                            std::vector<ilqg_instance_param>* out, std::string* why, std::vector<int32_t>* subsystems_out,
-                           std::vector<int32_t>* routes_out) {
+                           std::vector<int32_t>* routes_out, std::vector<int32_t>* solver_out) {
   std::string scratch;
   if (why == nullptr) why = &scratch;
   out->clear();
@@ -525,6 +525,12 @@ bool ResolveInstanceParams(const ProblemDescription& description, const Instance
     }
     routes_out->push_back(polyline);
   }
+  if (solver_out != nullptr) solver_out->clear();
+  if (!params.solver_fields.empty() && solver_out == nullptr) {
+    *why = "instance parameters name solver fields, the caller takes none";
+    return false;
+  }
+  for (ilqg_solver_field field : params.solver_fields) solver_out->push_back(static_cast<int32_t>(field));
   return true;
 }
 
@@ -1010,6 +1016,7 @@ class DeviceSolve {
       (void)ilqg_problem_bind_instance_values(handle, 0, nullptr);
       (void)ilqg_problem_declare_instance_params(handle, 0, nullptr);
       (void)ilqg_problem_declare_instance_subsystem_params(handle, 0, nullptr);
+      (void)ilqg_problem_declare_instance_solver_params(handle, 0, nullptr);
       (void)ilqg_problem_bind_instance_routes(handle, 0, nullptr, nullptr);
       (void)ilqg_problem_bind_instance_time_nominals(handle, 0, nullptr);
       (void)ilqg_problem_declare_instance_routes(handle, 0, nullptr);
@@ -1267,19 +1274,25 @@ class DeviceSolve {
       binding->bound = true;
       CHECK_EQ(ilqg_problem_bind_instance_time_nominals(handle_, batch, rows), ILQG_OK) << ilqg_last_error();
     }
-    if (instance_params.params.empty() && instance_params.subsystems.empty() && instance_params.route_polylines.empty()) return;
+    if (instance_params.params.empty() && instance_params.subsystems.empty() && instance_params.route_polylines.empty() &&
+        instance_params.solver_fields.empty())
+      return;
     std::vector<ilqg_instance_param> declared;
-    std::vector<int32_t> rows_declared, routes_declared;
+    std::vector<int32_t> rows_declared, routes_declared, solver_declared;
     std::string why;
-    CHECK(ResolveInstanceParams(description_, instance_params, &declared, &why, &rows_declared, &routes_declared)) << why;
+    CHECK(ResolveInstanceParams(description_, instance_params, &declared, &why, &rows_declared, &routes_declared, &solver_declared))
+        << why;
     binding->bound = true;
-    const size_t count = declared.size() + rows_declared.size();  // [cost params | subsystem params]
+    const size_t count = declared.size() + rows_declared.size() + solver_declared.size();  // [cost | subsystem | solver params]
     if (count > 0) {
       const float* rows = rows_on_device(instance_params.values, count, &d_instance_values_, "instance parameter values", "row");
       CHECK_EQ(ilqg_problem_declare_instance_params(handle_, static_cast<int32_t>(declared.size()), declared.data()), ILQG_OK)
           << ilqg_last_error();
       CHECK_EQ(ilqg_problem_declare_instance_subsystem_params(handle_, static_cast<int32_t>(rows_declared.size()),
                                                               rows_declared.data()), ILQG_OK)
+          << ilqg_last_error();
+      CHECK_EQ(ilqg_problem_declare_instance_solver_params(handle_, static_cast<int32_t>(solver_declared.size()),
+                                                           solver_declared.data()), ILQG_OK)
           << ilqg_last_error();
       CHECK_EQ(ilqg_problem_bind_instance_values(handle_, batch, rows), ILQG_OK) << ilqg_last_error();
     }

@@ -348,7 +348,8 @@ void ilqg_problem_destroy(ilqg_problem* p);
  *   CONSTRAINT_AFFINE_SCALAR / _VECTOR     no       no  (dense coefficient blocks)
  * Anything else — a "no" above, a term index out of range, a field that is not an ilqg_param_field, the same (term,
  * field) twice — is ILQG_ERR_UNSUPPORTED with the term named in ilqg_last_error(); nothing is ever silently ignored.
- * Out of scope: value2, polyline geometry, regularisation, solver parameters.
+ * Out of scope: value2, regularisation, ilqg_solver_params::linesearch and ::open_loop (polyline geometry: "Per-instance
+ * ROUTES" below; the other solver parameters: "Per-instance SOLVER parameters" below).
  *
  * Per-instance SUBSYSTEM parameters (ilqg_problem_declare_instance_subsystem_params): ilqg_subsystem::param0 of the
  * declared rows of ilqg_problem_desc::subsystems varies per instance too — fleets of cars with different wheelbases,
@@ -370,7 +371,46 @@ void ilqg_problem_destroy(ilqg_problem* p);
  * the cost-evaluating entry points above honour both kinds of column.  The LQ sweeps and the splice read no parameter.
  * The same bit-for-bit rule holds: an instance computes what a problem created with that float as param0 computes.
  * VALUES ARE NOT VALIDATED: the table lives on the device and may be rewritten between calls, so a zero wheelbase gives
- * what a descriptor with a zero wheelbase gives (a division by zero in the car models). */
+ * what a descriptor with a zero wheelbase gives (a division by zero in the car models).
+ *
+ * Per-instance SOLVER parameters (ilqg_problem_declare_instance_solver_params): the declared members of
+ * ilqg_problem_desc::params vary per instance — a sweep over (initial step, geometric scaling, Armijo fraction,
+ * back-tracking depth), over the stopping rule, or over the augmented-Lagrangian schedule in ONE batch, with success,
+ * iteration and back-tracking statistics per vector from one solve.  The solver columns are a third group of the same
+ * value table: it is float [batch][cost_count + subsystem_count + solver_count], the solver columns last in their
+ * declared order.  The three declarations may be made in any order; together they hold at most
+ * ILQG_MAX_INSTANCE_PARAMS columns.  Every member may be declared but `linesearch` and `open_loop`, which select kernels
+ * and the host's schedule: they, a number that is no ilqg_solver_field and the same field twice are
+ * ILQG_ERR_UNSUPPORTED with the field named in ilqg_last_error().
+ * The same bit-for-bit rule holds: an instance computes what a problem created with that float in
+ * ilqg_problem_desc::params computes; a float member is converted to the handle's arithmetic where the baked one is.
+ * The table is READ AT EVERY LATER SOLVE on the handle — ilqg_solve_batch_ex and the three calls that are it, in every
+ * mode, and ilqg_solve_again_batch — and may be rewritten between calls in stream order.  ONLY THE SOLVES read solver
+ * columns: every other entry point ignores them.  The "bound for a batch of N" refusals are what they are without
+ * solver columns: a cost-evaluating call on another batch is refused while a value table is bound, whatever columns it
+ * holds.  No scheduling choice depends on a binding — the host cannot see the device table — so the round plans, the
+ * probing heuristics and the capacity of the iterate log keep using the descriptor's values, and therefore:
+ * THE DESCRIPTOR'S VALUE OF AN INTEGER MEMBER IS A CEILING.  max_solver_iters, max_backtracking_steps and
+ * unconstrained_solver_max_iters travel as floats; an instance's value is the float truncated to an integer and limited
+ * on the device to [0, the descriptor's value] whatever the float holds (a NaN or anything at or above the descriptor's
+ * value gives the descriptor's value, anything negative 0).  A caller sets the ceiling in the descriptor and sweeps
+ * below it.  Everything else follows VALUES ARE NOT VALIDATED above. */
+typedef enum {
+  ILQG_SOLVER_CONVERGENCE_TOLERANCE = 0,
+  ILQG_SOLVER_MAX_SOLVER_ITERS = 1,
+  ILQG_SOLVER_LINESEARCH = 2, /* not declarable: named so that it is refused by name */
+  ILQG_SOLVER_INITIAL_ALPHA_SCALING = 3,
+  ILQG_SOLVER_GEOMETRIC_ALPHA_SCALING = 4,
+  ILQG_SOLVER_MAX_BACKTRACKING_STEPS = 5,
+  ILQG_SOLVER_EXPECTED_DECREASE_FRACTION = 6,
+  ILQG_SOLVER_OPEN_LOOP = 7, /* not declarable: named so that it is refused by name */
+  ILQG_SOLVER_UNCONSTRAINED_SOLVER_MAX_ITERS = 8,
+  ILQG_SOLVER_GEOMETRIC_MU_SCALING = 9,
+  ILQG_SOLVER_GEOMETRIC_MU_DOWNSCALING = 10,
+  ILQG_SOLVER_GEOMETRIC_LAMBDA_DOWNSCALING = 11,
+  ILQG_SOLVER_CONSTRAINT_ERROR_TOLERANCE = 12
+} ilqg_solver_field; /* the members of ilqg_solver_params, in their order */
+#define ILQG_NUM_SOLVER_FIELDS 13
 typedef enum { ILQG_PARAM_WEIGHT = 0, ILQG_PARAM_VALUE = 1 } ilqg_param_field;
 typedef struct {
   int32_t term;  /* index into ilqg_problem_desc::terms */
@@ -381,7 +421,7 @@ typedef struct {
 /* Which (term, field) pairs vary per instance: column c of the value table overrides params[c].  count = 0 clears the
  * declaration.  ILQG_ERR_INVALID while a table is bound (unbind first). */
 ilqg_status ilqg_problem_declare_instance_params(ilqg_problem* p, int32_t count, const ilqg_instance_param* params);
-/* values: device float [batch][cost_count + subsystem_count], or NULL to unbind.  The table is READ AT EVERY LATER CALL on this handle, not
+/* values: device float [batch][cost_count + subsystem_count + solver_count], or NULL to unbind.  The table is READ AT EVERY LATER CALL on this handle, not
  * copied: the caller may rewrite it between calls (in stream order with them) and keeps it alive while it is bound.
  * ILQG_ERR_INVALID without a declaration, or with batch <= 0. */
 ilqg_status ilqg_problem_bind_instance_values(ilqg_problem* p, int32_t batch, const float* values);
@@ -394,6 +434,13 @@ ilqg_status ilqg_problem_declare_instance_subsystem_params(ilqg_problem* p, int3
 /* Host only, no device needed: the checks of the declare call against a descriptor (the total with the cost columns is
  * the handle's to check). */
 ilqg_status ilqg_instance_subsystem_params_check(const ilqg_problem_desc* desc, int32_t count, const int32_t* subsystems);
+/* Which members of ilqg_problem_desc::params vary per instance: fields[c] is an ilqg_solver_field, and column
+ * cost_count + subsystem_count + c of the value table overrides it.  count = 0 clears the solver declaration.
+ * ILQG_ERR_INVALID while a table is bound (unbind first), or when the three groups together exceed
+ * ILQG_MAX_INSTANCE_PARAMS. */
+ilqg_status ilqg_problem_declare_instance_solver_params(ilqg_problem* p, int32_t count, const int32_t* fields);
+/* Host only, no device needed: the checks of the declare call (the total with the other columns is the handle's). */
+ilqg_status ilqg_instance_solver_params_check(const ilqg_problem_desc* desc, int32_t count, const int32_t* fields);
 
 /* Per-instance ROUTES: the points of the declared polylines of the descriptor — lanes, boundaries, the polygon of a
  * signed-distance term — vary per instance — the same intersection with the turn lane bent differently in every game of
@@ -869,7 +916,9 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
                                  per-instance time nominals (ilqg_problem_bind_instance_time_nominals,
                                  ilqg_instance_time_nominals_build, ilqg_problem_time_nominal_terms, and the host-only
                                  ilqg_time_nominal_table_build: four new calls); still 9:
-                                 ILQG_SCHEDULE_CONSTANT_B and the host-only ilqg_sweep_b_structure_build (one new call);
+                                 ILQG_SCHEDULE_CONSTANT_B and the host-only ilqg_sweep_b_structure_build (one new call); still 9:
+                                 per-instance solver parameters (ilqg_solver_field, ilqg_problem_declare_instance_solver_params,
+                                 ilqg_instance_solver_params_check: two new calls, the table gains columns);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;

@@ -1059,7 +1059,7 @@ struct ProblemDescription {
 // Per-instance cost parameters of a batched solve (include/ilqg.h; an EXTENSION: one reference Problem is one game).
 // `params` names what varies — the weight or the value (nominal / threshold) of a Cost or Constraint object of the
 // Problem, by address; the flattener resolves each to its term index — and `values` holds one row per instance,
-// column c overriding params[c]: [x0s.size()][params.size() + subsystems.size()], row-major.
+// column c overriding params[c]: [x0s.size()][params.size() + subsystems.size() + solver_fields.size()], row-major.
 // `subsystems` names subsystems whose parameter (ilqg_subsystem::param0: a car's inter-axle distance, a Dubins or Air3D
 // speed) varies per instance — a subsystem of a ConcatenatedDynamicalSystem by address, or a row of the descriptor for the
 // row-pair systems (TwoPlayerUnicycle4D, Air3D); their columns follow the cost columns: [cost params | subsystem params].
@@ -1080,6 +1080,12 @@ struct InstanceParams {
   void AddSubsystem(const SinglePlayerDynamicalSystem* subsystem) { subsystems.push_back(Subsystem{subsystem, -1}); }
   void AddSubsystem(const std::shared_ptr<const SinglePlayerDynamicalSystem>& subsystem) { AddSubsystem(subsystem.get()); }
   void AddSubsystem(int row) { subsystems.push_back(Subsystem{nullptr, row}); }
+  // Per-instance SOLVER parameters (ilqg_problem_declare_instance_solver_params): members of the SolverParams the solver
+  // was built with that vary per instance — a line-search or stopping-rule sweep in one batch.  Their columns come last:
+  // [cost params | subsystem params | solver params].  An integer member travels as a float and is limited on the device
+  // to [0, the SolverParams' own value], which is the ceiling the sweep stays below; linesearch and open_loop are refused.
+  std::vector<ilqg_solver_field> solver_fields;
+  void AddSolverParam(ilqg_solver_field field) { solver_fields.push_back(field); }
   // Per-instance ROUTES (ilqg_problem_declare_instance_routes): polylines of the Problem whose points vary per instance —
   // named by the address of a Polyline2 the caller built a cost from, or by the polyline's index in the descriptor.  A cost
   // keeps its own copy of its polyline and the flattener interns polylines by their vertex lists, so the object named by
@@ -1111,9 +1117,12 @@ struct InstanceParams {
 // `routes_out`: the descriptor's polylines of params.route_polylines (what ilqg_problem_declare_instance_routes takes),
 // under the same rules: false for an object that is no polyline of the description, an index out of range, or routes
 // named to a caller that takes none.
+// `solver_out`: params.solver_fields as ilqg_problem_declare_instance_solver_params takes them, under the same rule:
+// false for solver fields named to a caller that takes none (what may be declared is the library's to check).
 bool ResolveInstanceParams(const ProblemDescription& description, const InstanceParams& params,
                            std::vector<ilqg_instance_param>* out, std::string* why,
-                           std::vector<int32_t>* subsystems_out = nullptr, std::vector<int32_t>* routes_out = nullptr);
+                           std::vector<int32_t>* subsystems_out = nullptr, std::vector<int32_t>* routes_out = nullptr,
+                           std::vector<int32_t>* solver_out = nullptr);
 
 // The table (0 .. tables - 1: its place among the description's time-dependent terms) of each of params.references.
 // Returns false and sets *why when an object is no NominalPathLengthCost / RouteProgressCost of the description.

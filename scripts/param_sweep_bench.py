@@ -29,8 +29,18 @@ initial route positions from +-5 m about the baked ones (instance b tracks vecto
 the baked table; bound with the V references (tabulated on the device by ilqg_instance_time_nominals_build); the same V
 references as V problems solved one after another, B / V instances each.
 
+--solver-params: the same four legs for per-instance SOLVER parameters, on FREE-RUNNING solves (the stopping rule and the
+line search are what varies, so nothing is fixed: --iters is not used and iterations/s counts the iterations the
+instances report) of the scene created with the example's OWN line-search parameters (initial_alpha_scaling 1.0,
+expected_decrease_fraction 0.9 — the descriptor's integer members are the sweep's ceilings): unbound; bound with every
+row the baked values; bound with V = 16 line-search vectors, initial step {1, 0.5, 0.25, 0.1} x Armijo fraction
+{0.9, 0.1, 0.01, 0.001} (instance b takes vector b % V); the same V vectors as V problems solved one after another,
+B / V instances each.  Before the JSON line it prints, per vector, the share of its instances that succeeded and their
+mean iterations and rejected steps — the table a user runs the feature for.
+
 Prints one JSON line: iterations/s of each.
-python scripts/param_sweep_bench.py [--batch 1024] [--repeats 5] [--vectors 16] [--subsystems | --routes | --references]"""
+python scripts/param_sweep_bench.py [--batch 1024] [--repeats 5] [--vectors 16]
+                                    [--subsystems | --routes | --references | --solver-params]"""
 import argparse
 import copy
 import json
@@ -58,6 +68,7 @@ def main():
     ap.add_argument("--subsystems", action="store_true", help="the wheelbases of the two cars instead of cost parameters")
     ap.add_argument("--routes", action="store_true", help="the bend of player 2's turn lane instead of cost parameters")
     ap.add_argument("--references", action="store_true", help="a way-point per car, its speed and start per instance")
+    ap.add_argument("--solver-params", action="store_true", help="a line search per instance, free-running solves")
     args = ap.parse_args()
     import torch
     from ilqgames_amd import abi, examples, hip
@@ -91,6 +102,69 @@ def main():
             if rep > 0:
                 times.append(e0.elapsed_time(e1) * 1e-3)
         return float(np.median(times))
+
+    if args.solver_params:
+        spec = examples.modified_three_player_intersection()  # its own 1.0 / 0.9: the descriptor is the ceiling
+        fields = ["initial_alpha_scaling", "geometric_alpha_scaling", "expected_decrease_fraction", "max_backtracking_steps"]
+        own = np.array([getattr(spec.params, f) for f in fields], dtype=np.float32)
+        grid = [(a0, fr) for a0 in (1.0, 0.5, 0.25, 0.1) for fr in (0.9, 0.1, 0.01, 0.001)]
+        assert V == len(grid), "--solver-params sweeps %d vectors" % len(grid)
+        vectors = np.array([[a0, own[1], fr, own[3]] for a0, fr in grid], dtype=np.float32)
+        which = np.arange(B) % V
+
+        def timed_free(solves):
+            """-> (median device time of the free-running `solves`, the iterations their instances reported)."""
+            times = []
+            for rep in range(args.repeats + 1):  # the first pass is the warm-up
+                for _, _, bufs in solves:
+                    for k in ("xs", "us", "P", "alpha"):
+                        bufs[k].zero_()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                for prob, x, bufs in solves:
+                    prob.solve(x, bufs)
+                e1.record()
+                torch.cuda.synchronize()
+                if rep > 0:
+                    times.append(e0.elapsed_time(e1) * 1e-3)
+            return float(np.median(times)), sum(int(bufs["iters"].sum().item()) for _, _, bufs in solves)
+
+        def its(solves):
+            t, iters = timed_free(solves)
+            return iters / t
+
+        prob = hip.Problem(spec, dtype)
+        bufs = prob.alloc_solve_buffers(B)
+        out = dict(batch=B, dtype=args.dtype, fields=fields, vectors=V)
+        out["unbound_its"] = its([(prob, x0, bufs)])
+        prob.declare_instance_solver_params(fields)
+        prob.bind_instance_values(np.tile(own, (B, 1)))
+        out["bound_identity_its"] = its([(prob, x0, bufs)])
+        prob.bind_instance_values(vectors[which])
+        out["bound_vectors_its"] = its([(prob, x0, bufs)])
+        status, iters = bufs["status"].cpu().numpy(), bufs["iters"].cpu().numpy()
+        rejected = prob.solve_state(bufs)["backtracks"].cpu().numpy()
+        print("vector  alpha0  fraction  success  mean_iters  mean_rejected")
+        table = []
+        for v, (a0, fr) in enumerate(grid):
+            sel = which == v
+            row = (float(status[sel].mean()), float(iters[sel].mean()), float(rejected[sel].mean()))
+            table.append([a0, fr] + [round(r, 3) for r in row])
+            print("%6d  %6.2f  %8.3f  %6.1f%%  %10.2f  %13.2f" % (v, a0, fr, 100.0 * row[0], row[1], row[2]))
+        out["per_vector"] = table
+        prob.bind_instance_values(None)
+        solves = []
+        for v in range(V):
+            s = copy.deepcopy(spec)
+            for f, val in zip(fields, vectors[v]):
+                setattr(s.params, f, int(val) if f in abi.SOLVER_INT_FIELDS else float(val))
+            p = hip.Problem(s, dtype)
+            sel = torch.as_tensor(np.nonzero(which == v)[0], device="cuda")
+            solves.append((p, x0[sel].contiguous(), p.alloc_solve_buffers(len(sel))))
+        out["per_vector_problems_its"] = its(solves)
+        print(json.dumps(out))
+        return
 
     if args.references:
         baked = []  # (speed, pos0) of the two way-points: the cars start 970 m and 955 m along their lanes
