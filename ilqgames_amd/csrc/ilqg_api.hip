@@ -1716,7 +1716,15 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
     }
   }
   sa.clear_counters = 1;
-  plan.trial = {k_trial, 64 * W, lds_trial};
+  // The fused kernel with a register-held static row stage keeps the per-row partials of a trial's reductions in LDS as
+  // well (trial_part_instance's running reductions) — where four instances still fit a CU with that block behind theirs.
+  size_t lds_part_bytes = 0;
+  if (static_prog && static_in_regs && W == 2 && fused_partials_room(int(sizeof(T)), NX, NP, MU)) {
+    const size_t extra = partials_lds_elems(d.T, d.N) * sizeof(T);
+    if (4 * (lds_trial + extra) <= size_t(160) * 1024) lds_part_bytes = extra;
+  }
+  sa.lds_part = lds_part_bytes ? 1 : 0;
+  plan.trial = {k_trial, 64 * W, lds_trial + lds_part_bytes};
   plan.exit = {ilq_exit_kernel<T, NX, NP, MU>, nt_exit, quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T)};
   plan.read_restarts = counted && al_mode;
   constexpr bool pairs = rollout_pairs(NX, NP, MU);  // two rollouts per wavefront (ilqg_stages.hpp)

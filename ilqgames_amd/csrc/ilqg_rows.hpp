@@ -623,7 +623,10 @@ template <class PROG> struct ProgInRegisters<PROG, true> {
 // laid out with the fixed strides of kStaticRowStride whatever `cw`: size it for cw = 64).
 // pass_mask: bit ps = run pass ps of the program (the passes are independent of each other: the Jacobians, then one per
 // player, each with its own slots and outputs).
-template <typename T, int CN_, int CM_, int CNP_, bool XREG = false, bool GRAD_ONLY = false, class PROG = ProgDynamic>
+// LDSP: the partials go to the workgroup's LDS block as well (QuadArgs::lds_merit / lds_cost, when set), for the fused
+// kernel's running reductions (partials_extend, ilqg_stages.hpp); the global copies are written all the same.
+template <typename T, int CN_, int CM_, int CNP_, bool XREG = false, bool GRAD_ONLY = false, class PROG = ProgDynamic,
+          bool LDSP = false>
 __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* maps, const QuadArgs<T>& a, int k0,
                                            int nrows, int cw, T* sm, int lane, unsigned pass_mask = ~0u) {
   constexpr bool RT = CN_ == 0;
@@ -939,6 +942,8 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
       }
       if (pkind == RPASS_PLAYER && valid) {
         if (want_cost) a.cost_part[size_t(row) * CNP + player] = ctot;
+        if constexpr (LDSP)
+          if (want_cost && a.lds_cost) a.lds_cost[row * CNP + player] = ctot;
         if (a.merit_part) {
           // pieces of ILQSolver::MeritFunction (:419-430): |r_ii|^2 and |l_i|^2 of this lane's row.  Entries no term
           // touches are exact zeros, so the sums over the touched slots (in index order) are the reference's sums.
@@ -970,6 +975,11 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
           }
           a.merit_part[(size_t(row) * CNP + player) * 2 + 0] = s1;
           a.merit_part[(size_t(row) * CNP + player) * 2 + 1] = s2;
+          if constexpr (LDSP)
+            if (a.lds_merit) {
+              a.lds_merit[(row * CNP + player) * 2 + 0] = s1;
+              a.lds_merit[(row * CNP + player) * 2 + 1] = s2;
+            }
         }
       }
     }

@@ -64,6 +64,8 @@ struct SolveArgs {
   int clear_counters;   // 1: the sweep kernel's first workgroup clears the round counters — nothing counts between a
                         //    round's sweep and the next round's first kernel, and the next round then needs no fill
                         //    command in front of it (~5 us of every round of a free-running solve)
+  int lds_part;         // 1: the fused trial kernel's LDS ends with a block of partials_lds_elems for the per-row merit and
+                        //    cost partials (trial_part_instance's running reductions); set only for the kernels that read it
 };
 
 
@@ -850,6 +852,26 @@ __host__ __device__ constexpr bool fused_rollout_room(int elem_bytes, int nx, in
   return elem_bytes == 4 || (progid != 0 && nx == 14 && np == 3 && mu == 2);
 }
 
+// Which of the fused kernels with a register-held static row stage keep running reductions over partials in LDS
+// (trial_part_instance's LDS_RED; the launcher adds the LDS block for exactly these): a register-budget fact like
+// fused_rollout_room above, taken the same way.  fp64 (14, 3, 2): 233 -> 252 registers (bound: 235 -> 255), no scratch;
+// (15, 3, 2): 243 -> 255 and 16 bytes of scratch where there were none (bound: 32), (16, 3, 2): scratch 0 -> 32 (bound
+// 16 -> 32) — those two keep merit_costs_reduce.  fp32 has sixty registers and more to spare in every shape.
+__host__ __device__ constexpr bool fused_partials_room(int elem_bytes, int nx, int np, int mu) {
+  return elem_bytes == 4 || (nx == 14 && np == 3 && mu == 2);
+}
+
+// Chunk order of the fused kernel whose two waves share the last chunk (trial_part_instance's SHARE_LAST): 1 = in row
+// order with the chunk that is not full LAST, 0 = that chunk first.
+#ifndef ILQG_SHORT_CHUNK_LAST
+#define ILQG_SHORT_CHUNK_LAST 1
+#endif
+// first row of that kernel's last chunk
+__device__ __forceinline__ int trial_last_chunk_begin(int Tn, int cw) {
+  if (Tn <= cw) return 0;
+  return ILQG_SHORT_CHUNK_LAST ? ((Tn + cw - 1) / cw - 1) * cw : Tn - cw;
+}
+
 // PROGID: 0 = the row stage interprets the problem's row program; k = straight-line code for registered structure k
 // BOUND: the fused kernel of a problem with per-instance parameters bound — its rollout takes the subsystems' parameters
 // from the instance's row of the table.  Kernels of their own, as the bound straight-line row code is: the read costs the
@@ -883,9 +905,13 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
   T* const sm_quad0 = sm + re;  // the first row wave's scratch doubles as reduction scratch between passes
   int* const flags = reinterpret_cast<int*>(sm + re + size_t(RW) * qe);  // [0] rows ready, [1] next chunk to claim
   T* const ed_slot = reinterpret_cast<T*>(flags + 2);  // deferred ExpectedDecrease, from the first row wave to everyone
+  T* const part_lds = reinterpret_cast<T*>(flags + 4);  // SolveArgs::lds_part: the per-row partials and their running values
 
   SolveState<T> s = trial_state_begin<T>(p, sa, ib, b, n, N, m);
   tl_stamp(sa.prof, b, 0, t == 0);
+  if (kTimeline && PHASE == TRIAL_FUSED && sa.prof && lane == 0 && wave < 2)  // where this wave sits, as the sweep's waves say it (ilqg_lq.hpp): slots 30, 31
+    sa.prof[size_t(b) * 96 + 32 + 30 + wave] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+                                               ((long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
   const long long pr_start = clock64();
   long long qph[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // linquad phase profile of this wave (diagnostics)
   long long rph[4] = {0, 0, 0, 0};              // rollout phase profile (wave 0)
@@ -931,8 +957,20 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
 
     // ---- linearise / quadraticise the trajectory: every wave claims rows as they become ready ----
     const int qmode = s.qmode;
+    // Running reductions (partials_extend, ilqg_stages.hpp): a line-search trial of the fused kernel whose static row
+    // stage keeps a chunk in registers — the row scratch is free, both waves end in the shared last chunk — leaves its
+    // merit and cost partials in LDS as well; the row wave carries the sums over each chunk it has finished while the
+    // rollout still integrates, and only the last chunk's rows are added behind it.  The other passes (Q_COSTS,
+    // Q_INIT, Q_LIN: a few per solve) and every other kernel reduce from global memory as before.
+    constexpr bool LDS_RED = PHASE == TRIAL_FUSED && PROGID != 0 && W == 2 && fused_partials_room(int(sizeof(T)), NX, NP, MU) &&
+                             ProgInRegisters<typename RowProgSel<PROGID>::type>::value && rows_state_in_registers(NX, NP * MU);
+    const bool lds_red = LDS_RED && sa.lds_part != 0 && qmode == Q_TRIAL;
     if constexpr (PHASE == TRIAL_FUSED) {
     QuadArgs<T> qa = trial_quad_args<T, BOUND>(p, ib, s, sa.compact != 0, b);
+    if (lds_red) {
+      qa.lds_merit = part_lds;
+      qa.lds_cost = part_lds + size_t(Tn) * N * 2;
+    }
     qa.phacc = (kProfile && sa.prof) ? qph : nullptr;
     qa.tl = kTimeline ? sa.prof : nullptr;
     qa.tl_b = b;
@@ -972,14 +1010,19 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
       if (wave == 0) qa.tl = nullptr;
 #pragma unroll 1
       for (int c = (wave == 0 ? nchunks - 1 : 0); c < nchunks; c++) {
-        const int k0 = rem == 0 ? c * cw : (c == 0 ? 0 : rem + (c - 1) * cw);  // the chunk that is not full comes first
-        const int nrows = (rem != 0 && c == 0) ? rem : cw;
+        // ILQG_SHORT_CHUNK_LAST 0: the chunk that is not full comes first, as in the other form below; 1: last, which
+        // leaves fewer rows' partials behind the rollout for the running reductions (trial_last_chunk_begin)
+        constexpr bool SHORT_LAST = ILQG_SHORT_CHUNK_LAST && LDS_RED;  // (measured with the running reductions only)
+        const int k0 = (SHORT_LAST || rem == 0) ? c * cw : (c == 0 ? 0 : rem + (c - 1) * cw);
+        const int nrows = SHORT_LAST ? (Tn - k0 < cw ? Tn - k0 : cw) : ((rem != 0 && c == 0) ? rem : cw);
         if (wave != 0)
           while (progress_observe(&flags[0]) < k0 + nrows) __builtin_amdgcn_s_sleep(8);
         tl_stamp(sa.prof, b, 4 + 2 * (c < 3 ? c : 3), wave != 0 && lane == 0);
         const unsigned mask = c == nchunks - 1 ? (wave == 0 ? first_half : ~first_half) : ~0u;
-        rows_chunk<T, NX, NP * MU, NP, true, false, RowProg>(p, maps, qa, k0, nrows, cw, sm_quad, lane, mask);
+        rows_chunk<T, NX, NP * MU, NP, true, false, RowProg, LDS_RED>(p, maps, qa, k0, nrows, cw, sm_quad, lane, mask);
         tl_stamp(sa.prof, b, 5 + 2 * (c < 3 ? c : 3), wave != 0 && lane == 0);
+        // (the chunks come in row order and all but the last are this wave's alone: its own LDS stores, in order)
+        if (lds_red && c < nchunks - 1) partials_extend<T>(p, part_lds, t_extreme, k0, k0 + nrows, c == 0, 64, 65);
       }
     } else
     if (rwave >= 0) {
@@ -1010,6 +1053,15 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
     }
     }
 
+    if (lds_red) {
+      // one LDS barrier for the last chunk's partials and the expected decrease alike: nothing below reads what the
+      // chunk stored to global memory, so those stores drain behind the reduction instead of in front of it
+      lds_sync(false);
+      if (s.ed_pending) {
+        s.expected_decrease = uniform(*ed_slot);
+        s.ed_pending = 0;
+      }
+    } else
     if (PHASE == TRIAL_FUSED && s.ed_pending) {
       __syncthreads();
       s.expected_decrease = uniform(*ed_slot);
@@ -1036,6 +1088,14 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
       bool costs_ready = false;  // the cost totals were reduced beside the merit value and wait in LDS
       if (qmode == Q_TRIAL) {
         T merit_v = T(0);
+        if (lds_red) {
+          // what is left of both chains: the last chunk's rows (all of them where the horizon is one chunk), the merit
+          // on the workgroup's first lane and the costs beside it on the row wave
+          partials_extend<T>(p, part_lds, t_extreme, trial_last_chunk_begin(Tn, sa.rows_cw), Tn, Tn <= sa.rows_cw, 0, 64);
+          lds_sync(false);
+          merit_v = T(0.5) * part_lds[size_t(Tn) * N * 3];
+          costs_ready = true;
+        } else
         costs_ready = merit_costs_reduce<T>(p, w + L.mpart, w + L.cpart, t_extreme, sm_quad0, int(qe), &merit_v);
         const T merit = costs_ready ? uniform(merit_v) : uniform(merit_reduce<T>(p, w + L.mpart, sm_quad0, int(qe)));
         tl_stamp(sa.prof, b, 14, t == 0);
@@ -1055,7 +1115,9 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
         s.sacc = 1 - s.sacc;
         s.acc_scale = s.step;
         s.accepted_iters++;
-        if (costs_ready)  // TotalCosts of the accepted iterate (:158)
+        if (lds_red)  // (an accepted trial ends the launch's passes: no barrier behind the stores)
+          costs_commit<T, false>(p, part_lds, costs, t_extreme);
+        else if (costs_ready)  // TotalCosts of the accepted iterate (:158)
           costs_commit<T>(p, sm_quad0, costs, t_extreme);
         else
           costs_reduce<T>(p, w + L.cpart, costs, t_extreme, sm_quad0, int(qe));

@@ -583,6 +583,8 @@ struct QuadArgs {
   bool compact_lin = false, compact_quad = false;  // ... of the linearisation (A, Bm) / of the quadraticisation (Q, l, R, r)
   T* merit_part;       // [T][N][2] = (|r_ii|^2, |l_i|^2) or nullptr
   T* cost_part;        // [T][N] PlayerCost::Evaluate or nullptr
+  T* lds_merit = nullptr;  // the fused kernel's LDS copy of merit_part / cost_part (partials_extend below), read by
+  T* lds_cost = nullptr;   // rows_chunk's LDSP form only
   const float* iv = nullptr;  // this instance's row of the bound per-instance parameters (instance_values) or nullptr
   size_t seg_off = 0;  // this instance's segment table behind problem_segs (instance_segs_offset), 0: the baked one.  Read
                        // by the interpreter and the bound straight-line code only (rows_chunk)
@@ -636,6 +638,34 @@ __device__ __forceinline__ void lds_ordered_visit(const T* v, int count, F&& vis
       for (int u = 0; u < U; u++) visit(e + u, x[u]);
 #pragma unroll
       for (int u = 0; u < U; u++) x[u] = y[u];
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) visit(e + u, x[u]);
+    e += U;
+  }
+  for (; e < count; e++) visit(e, v[e]);
+}
+
+// The same visit order with two register batches taken in turn, so that no batch is copied into the other's registers
+// between trips (lds_ordered_visit moves eight values per eight visited: for a chain of fp64 adds that is as many
+// instructions again as the chain itself).
+template <typename T, typename F>
+__device__ __forceinline__ void lds_ordered_visit2(const T* v, int count, F&& visit) {
+  constexpr int U = 8;
+  int e = 0;
+  if (count >= 2 * U) {
+    T x[U], y[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) x[u] = v[u];
+    for (; e + 3 * U <= count; e += 2 * U) {  // x holds v[e .. e + U)
+#pragma unroll
+      for (int u = 0; u < U; u++) y[u] = v[e + U + u];
+#pragma unroll
+      for (int u = 0; u < U; u++) visit(e + u, x[u]);
+#pragma unroll
+      for (int u = 0; u < U; u++) x[u] = v[e + 2 * U + u];
+#pragma unroll
+      for (int u = 0; u < U; u++) visit(e + U + u, y[u]);
     }
 #pragma unroll
     for (int u = 0; u < U; u++) visit(e + u, x[u]);
@@ -739,7 +769,8 @@ __device__ __forceinline__ bool merit_costs_reduce(const DevProblem& p, const T*
   return true;
 }
 // The cost totals merit_costs_reduce left in `sm`, written out (TotalCosts of an accepted iterate).
-template <typename T>
+// SYNC false: the caller reuses neither `sm` nor the outputs before its next workgroup barrier.
+template <typename T, bool SYNC = true>
 __device__ __forceinline__ void costs_commit(const DevProblem& p, const T* sm, T* costs_out, int* t_extreme) {
   const T* const res = sm + p.T * p.N * 3;
   const int i = threadIdx.x;
@@ -747,7 +778,70 @@ __device__ __forceinline__ void costs_commit(const DevProblem& p, const T* sm, T
     costs_out[i] = res[1 + i];
     if (t_extreme) t_extreme[i] = int(res[1 + kMaxPlayers + i]);
   }
-  __syncthreads();
+  if constexpr (SYNC) __syncthreads();
+}
+
+// The same two reductions as running values over per-row partials that the row stage left in LDS (the fused trial
+// kernel with a register-held static row stage, ilqg_solve.hpp): `pl` is merit_costs_reduce's block, [T][N][2] merit
+// pieces | [T][N] costs | res, and a call carries res over the rows [k0, k1) — the merit sum on thread `merit_thread`,
+// player i's total (or extreme and its time step) on thread `cost_thread0 + i`.  `first` starts them as
+// merit_costs_reduce does, t_extreme included; calls over consecutive row ranges then perform that function's sequence
+// of additions and comparisons, cut at the range boundaries, so the values are its values bit for bit.  res[0] is the
+// merit sum BEFORE its factor 0.5; res[1..] is what costs_commit reads.  No barrier in here: the caller orders the
+// partials before the call and res after it.
+__host__ __device__ inline size_t partials_lds_elems(int T, int N) {
+  return (size_t(T) * N * 3 + 2 * kMaxPlayers + 4 + 3) & ~size_t(3);
+}
+template <typename T>
+__device__ __forceinline__ void partials_extend(const DevProblem& p, T* pl, const int* t_extreme, int k0, int k1,
+                                                bool first, int merit_thread, int cost_thread0) {
+  const int cm = p.T * p.N * 2, cc = p.T * p.N;
+  T* const smc = pl + cm;
+  T* const res = smc + cc;
+  if (int(threadIdx.x) == merit_thread) {
+    T merit = first ? T(0) : res[0];
+    int e0 = k0 * p.N * 2;
+    const int e1 = k1 * p.N * 2;
+    if (k0 == 0) {  // the |l_i|^2 terms of k = 0 do not enter (:421)
+      const int skip = p.N * 2;
+      for (int e = 0; e < skip && e < e1; e += 2) merit += pl[e];
+      e0 = skip;
+    }
+    if (e1 > e0) lds_ordered_visit2<T>(pl + e0, e1 - e0, [&](int, T x) { merit += x; });
+    res[0] = merit;
+  }
+  const int i = int(threadIdx.x) - cost_thread0;
+  if (i >= 0 && i < p.N) {
+    const int st = p.structure[i];
+    T c = st == ILQG_SUM ? T(0) : (st == ILQG_MAX ? -dinf<T>() : dinf<T>());
+    int te = t_extreme ? t_extreme[i] : 0;
+    if (!first) {
+      c = res[1 + i];
+      te = int(res[1 + kMaxPlayers + i]);
+    }
+    auto visit = [&](int k, T v) {
+      if (st == ILQG_SUM)
+        c += v;
+      else if (st == ILQG_MAX && v > c) {
+        c = v;
+        te = k;
+      } else if (st == ILQG_MIN && v < c) {
+        c = v;
+        te = k;
+      }
+    };
+    int k = k0;
+    for (; k + 8 <= k1; k += 8) {
+      T x[8];
+#pragma unroll
+      for (int u = 0; u < 8; u++) x[u] = smc[(k + u) * p.N + i];
+#pragma unroll
+      for (int u = 0; u < 8; u++) visit(k + u, x[u]);
+    }
+    for (; k < k1; k++) visit(k, smc[k * p.N + i]);
+    res[1 + i] = c;
+    res[1 + kMaxPlayers + i] = T(te);
+  }
 }
 
 // ILQSolver::TotalCosts reduction (:220-257): sum / max / min over time per player, and

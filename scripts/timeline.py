@@ -43,6 +43,39 @@ for name, i, j in (("chunk start -> (x, u) staged", 6, 40), ("persistent slot in
                    ("player 0: ops", 43, 44), ("player 0: write-out", 44, 45), ("player 1: ops", 45, 46), ("player 1: write-out", 46, 47),
                    ("player 2: ops", 47, 48), ("player 2: write-out", 48, 49)):
     print("  %-44s %s" % (name, d(i, j)))
+# the trial kernel's tail over the batch: a slow population, placement (HW_ID of its two waves, slots 30 / 31), or entry order?
+ok = (tl[:, 0] > 0) & (tl[:, 13] > 0)
+tpass = np.where(ok, tl[:, 13] - tl[:, 0], np.nan)
+print("trial pass over the batch: max - p90 %.1f us (p50 %.1f p90 %.1f max %.1f); last end - last entry %.1f us" %
+      (np.nanmax(tpass) - np.nanpercentile(tpass, 90), np.nanpercentile(tpass, 50), np.nanpercentile(tpass, 90), np.nanmax(tpass),
+       tl[ok, 13].max() - tl[ok, 0].max()))
+thw = prof[:, 32 + 30:32 + 32].cpu().numpy()
+if (thw[ok, 0] != 0).any():
+    simd_of = lambda v: ((int(v) >> 32) & 15, (int(v) >> 13) & 7, (int(v) >> 12) & 1, (int(v) >> 8) & 15, (int(v) >> 4) & 3)  # noqa: E731
+    roll_on, rows_on = {}, {}
+    for b in np.where(ok)[0]:
+        roll_on.setdefault(simd_of(thw[b, 0]), []).append(b)
+        rows_on.setdefault(simd_of(thw[b, 1]), []).append(b)
+    share = {}
+    for key, bs in roll_on.items():
+        share.setdefault(len(bs), []).extend(tpass[bs])
+    print("  mean pass by rollout waves sharing the rollout wave's SIMD:",
+          "  ".join("%d: %.1f us (%d)" % (c, np.mean(v), len(v)) for c, v in sorted(share.items())))
+    both = {}
+    for key, bs in roll_on.items():
+        for b in bs:
+            both.setdefault(len(bs) + len(rows_on.get(key, [])), []).append(tpass[b])
+    print("  ... by waves of either kind on that SIMD:", "  ".join("%d: %.1f us (%d)" % (c, np.mean(v), len(v)) for c, v in sorted(both.items())))
+    same = np.array([simd_of(thw[b, 0]) == simd_of(thw[b, 1]) for b in np.where(ok)[0]])
+    print("  instances with both waves on one SIMD: %d, mean pass %.1f us; on two: %d, mean pass %.1f us" %
+          (same.sum(), np.mean(tpass[ok][same]) if same.any() else 0, (~same).sum(), np.mean(tpass[ok][~same]) if (~same).any() else 0))
+else:
+    print("  (no HW_ID stamps of the trial waves in this build)")
+order_t = np.argsort(tl[:, 0])
+qt = B // 4
+print("  pass us by launch-order quartile:", " ".join("%.1f" % np.nanmean(tpass[order_t[i * qt:(i + 1) * qt]]) for i in range(4)),
+      "; entry us (from the first):", " ".join("%.1f" % np.mean(tl[order_t[i * qt:(i + 1) * qt], 0] - t0) for i in range(4)),
+      "; end us:", " ".join("%.1f" % np.mean(tl[order_t[i * qt:(i + 1) * qt], 13] - t0) for i in range(4)))
 print("last sweep launch:")
 for name, i, j in (("entry -> loop", 16, 17), ("loop (T-1 steps)", 17, 18), ("loop end -> exit", 18, 19), ("whole", 16, 19)):
     print("  %-44s %s" % (name, d(i, j)))
