@@ -297,7 +297,7 @@ struct WsTail {
 };
 inline WsTail ws_tail(const DevProblem& d, int batch, size_t elem, int ol_row) {
   auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-  const WsLayout L(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, ol_row, d.num_constraints, 1);
+  const WsLayout L = ws_layout_of(d, ol_row, 1);  // the augmented-Lagrangian layout, the larger one: for either al_mode
   WsTail t;
   t.ids_off = up(size_t(L.total) * elem * size_t(batch));
   t.pool_off = up(t.ids_off + size_t(2) * batch * sizeof(int));
@@ -346,13 +346,10 @@ __global__ void __launch_bounds__(64 * W, (sizeof(T) == 4 && W == 2) ? ILQG_TRIA
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = blockIdx.x;
   if (!sa.first) {  // instances that are done (or waiting for the LQ kernel) leave without touching LDS
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
-    const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
+    const int stage = instance_stage<T>(p, sa, b);
     if (stage != ST_ROLLOUT && stage != ST_QUAD) return;
-  } else if (sa.active && !sa.active[b]) {  // skipped instance: done before it starts, outputs untouched
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
-    if (threadIdx.x == 0)
-      reinterpret_cast<SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage = ST_DONE;
+  } else if (sa.active && !sa.active[b]) {  // skipped instance
+    instance_mark_done<T>(p, sa, b);
     return;
   }
   const short* maps = rows_maps_load(p, smem_raw);
@@ -377,13 +374,9 @@ __global__ void __launch_bounds__(64, sizeof(T) == 8 ? ILQG_ROLL_WAVES : 1) ilq_
   }
   const int b = sa.ids ? sa.ids[blockIdx.x] : int(blockIdx.x);
   if (!sa.first) {
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
-    const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
-    if (stage != ST_ROLLOUT) return;
+    if (instance_stage<T>(p, sa, b) != ST_ROLLOUT) return;
   } else if (sa.active && !sa.active[b]) {
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
-    if (threadIdx.x == 0)
-      reinterpret_cast<SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage = ST_DONE;
+    instance_mark_done<T>(p, sa, b);
     return;
   }
   trial_part_instance<T, NX, NP, MU, 1, TRIAL_ROLL>(p, nullptr, sa, b, reinterpret_cast<T*>(smem_raw));
@@ -393,11 +386,7 @@ template <typename T, int NX, int NP, int MU, int PROGID = 0>
 __global__ void __launch_bounds__(64) ilq_rows_kernel(DevProblem p, SolveArgs<T> sa) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = sa.ids ? sa.ids[blockIdx.y] : int(blockIdx.y);
-  {
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
-    const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
-    if (stage != ST_ROLLOUT && stage != ST_QUAD) return;
-  }
+  if (const int stage = instance_stage<T>(p, sa, b); stage != ST_ROLLOUT && stage != ST_QUAD) return;
   // compact rows: nothing dense is written, so the word maps of the dense images are not needed (nor their LDS)
   const short* maps = sa.compact ? nullptr : rows_maps_load(p, smem_raw);
   T* sm = reinterpret_cast<T*>(smem_raw + (sa.compact ? 0 : rows_maps_bytes(p)));
@@ -412,11 +401,7 @@ template <typename T, int NX, int NP, int MU, bool SOLVER = true>
 __global__ void __launch_bounds__(64) ilq_decide_kernel(DevProblem p, SolveArgs<T> sa) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = sa.ids ? sa.ids[blockIdx.x] : int(blockIdx.x);
-  {
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
-    const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
-    if (stage != ST_ROLLOUT && stage != ST_QUAD) return;
-  }
+  if (const int stage = instance_stage<T>(p, sa, b); stage != ST_ROLLOUT && stage != ST_QUAD) return;
   trial_part_instance<T, NX, NP, MU, 1, TRIAL_DECIDE, 0, false, SOLVER>(p, nullptr, sa, b, reinterpret_cast<T*>(smem_raw));
 }
 
@@ -456,8 +441,7 @@ __global__ void __launch_bounds__(64, sizeof(T) == 8 ? 4 : 1) ilq_probe_rows_ker
   const int slot = blockIdx.y / sa.probe_k, j = blockIdx.y % sa.probe_k;
   const int b = sa.ids[slot];
   {  // leave before the table load if this candidate is not wanted
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
-    const SolveState<T> s = state_load<T>(sa.ws + size_t(b) * sa.ws_stride, L);
+    const SolveState<T> s = state_load<T>(sa.ws + size_t(b) * sa.ws_stride, ws_layout_of(p, sa));
     if (!probe_wanted(sa, solver_params_of(p, sa.prm, b), s, j)) return;
   }
   const short* maps = sa.compact ? nullptr : rows_maps_load(p, smem_raw);  // merit only: no dense image either way
@@ -487,11 +471,7 @@ template <typename T, int NX, int NP, int MU>
 __global__ void __launch_bounds__(256) ilq_exit_kernel(DevProblem p, SolveArgs<T> sa) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = blockIdx.x;
-  {
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
-    const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
-    if (stage != ST_INNER_DONE) return;
-  }
+  if (instance_stage<T>(p, sa, b) != ST_INNER_DONE) return;
   const QuadTables<T> tb = quad_tables_load<T>(p, smem_raw, b);
   T* sm = reinterpret_cast<T*>(smem_raw + quad_tables_bytes(p, sizeof(T)));
   exit_part_instance<T, NX, NP, MU>(p, tb, sa, b, sm);
@@ -517,8 +497,8 @@ ilq_lq_kernel(DevProblem p, SolveArgs<T> sa) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = blockIdx.x;
   if (sa.clear_counters && b == 0 && threadIdx.x < 4) sa.unfinished[threadIdx.x] = 0;  // (SolveArgs::clear_counters)
-  {
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
+  {  // instance_stage, written out: through the helper the compiler schedules this kernel's whole sweep differently
+    const WsLayout L = ws_layout_of(p, sa);
     const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
     if (stage != ST_LQ) return;
   }
@@ -717,10 +697,10 @@ padded_lq_kernel(DevProblem p, SolveArgs<T> sa, PadArgs<T> pa) {
   using PS = PadSweep<T, NX, NP, MU, OL>;
   const int b = blockIdx.x;
   const int Tn = p.T;
-  const WsLayout L(p.n, p.m, p.N, Tn, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
+  if (instance_stage<T>(p, sa, b) != ST_LQ) return;
+  const WsLayout L = ws_layout_of(p, sa);
   T* const w = sa.ws + size_t(b) * sa.ws_stride;
   SolveState<T>* const st = reinterpret_cast<SolveState<T>*>(w + L.state);
-  if (st->stage != ST_LQ) return;
   const int sacc = __builtin_amdgcn_readfirstlane(st->sacc);
   PadGame<T> g;
   g.n = p.n; g.m = p.m; g.N = p.N; g.T_steps = Tn;
@@ -779,11 +759,7 @@ template <typename T>
 __global__ void __launch_bounds__(256) gen_lq_kernel(DevProblem p, SolveArgs<T> sa) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = blockIdx.x;
-  {
-    const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
-    const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
-    if (stage != ST_LQ) return;
-  }
+  if (instance_stage<T>(p, sa, b) != ST_LQ) return;
   lq_part_generic<T>(p, sa, b, reinterpret_cast<T*>(smem_raw));
 }
 
@@ -829,6 +805,13 @@ void raise_lds_limit(const void* kern, size_t lds) {
 #include ILQG_DIMS_HEADER  // experiment builds: a generated subset of the list below (__graft_entry__.build_hip_library)
 #else
 #define ILQG_FOR_DIMS(X) X(14, 3, 2) X(16, 3, 2) X(15, 3, 2) X(24, 4, 2) X(18, 3, 2) X(12, 2, 2) X(10, 2, 2) X(4, 2, 2) X(6, 2, 1) X(3, 2, 1) X(3, 1, 1) X(2, 2, 1) X(6, 3, 2) X(2, 1, 2) X(8, 2, 2) X(17, 3, 2) X(8, 2, 1)
+#endif
+
+#if !defined(ILQG_PART_NX)
+// The list as a table, one entry per shape with DimsLaunch's members in both precisions (kShapes, below DimsLaunch):
+// the entry of (n, N, m_i), or nullptr where the shape has no instantiation.
+struct ShapeEntry;
+const ShapeEntry* find_shape(int n, int N, int mu);
 #endif
 
 }  // namespace
@@ -1187,7 +1170,7 @@ SolveArgs<T> solve_args_of(const ilqg_problem* p, int32_t batch, const void* x0,
   sa.x0 = (const T*)x0; sa.xs = (T*)xs; sa.us = (T*)us; sa.P = (T*)P; sa.alpha = (T*)alpha;
   sa.total_costs = (T*)total_costs; sa.iters = iters; sa.status = status; sa.converged = converged;
   sa.ws = (T*)workspace;
-  sa.ws_stride = WsLayout(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, sa.ol_row, d.num_constraints, sa.al_mode).total;
+  sa.ws_stride = ws_layout_of(d, sa.ol_row, sa.al_mode).total;
   sa.fixed_iters = opt.fixed_iters;
   sa.batch = batch;
   sa.prm = p->desc.params;
@@ -1513,6 +1496,11 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
 
 #define DT_DISPATCH(p, CALL) ((p)->desc.dtype == ILQG_F32 ? CALL(float) : CALL(double))
 
+// The LDS of a CU (gfx950: 160 KB): the most one workgroup can be given, and what the workgroups resident on a CU share
+static constexpr size_t kLdsPerCu = size_t(160) * 1024;
+// ... among the four instances per CU of the headline batch, which the fused trial kernel's LDS is sized for
+static constexpr size_t kTrialInstancesPerCu = 4;
+
 template <typename T, int NX, int NP, int MU>
 ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, const void* x0, void* xs, void* us,
                                              void* P, void* alpha, void* total_costs, int32_t* iters, int32_t* status,
@@ -1528,12 +1516,12 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   SolveTail<T> tail;
   SolveArgs<T> sa = solve_args_of<T>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, opt, &tail);
   const int al_mode = sa.al_mode;
-  const WsLayout L(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, sa.ol_row, d.num_constraints, al_mode);
+  const WsLayout L = ws_layout_of(d, sa.ol_row, al_mode);
 #if ILQG_DIAGNOSTIC_BUILD
   sa.prof = g_prof;
 #endif
   // ws_tail places the lists behind the augmented-Lagrangian layout (the larger one): whatever al_mode this solve runs in
-  if (WsLayout(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, sa.ol_row, d.num_constraints, 1).total < L.total)
+  if (ws_layout_of(d, sa.ol_row, 1).total < L.total)
     return fail(ILQG_ERR_INVALID, "workspace layout: the tail offset does not cover this solve's per-instance blocks");
 
   // The schedule: every AUTO decision, into `plan` and `sa`.  Nothing is launched here but the mask count.
@@ -1543,7 +1531,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   // (the headline batch is four instances per CU); the split row kernels get the same width.
   {
     const size_t fixed = rows_maps_bytes(d) + ((rollout_lds_elems(d.n, d.m) + 3) & ~size_t(3)) * sizeof(T) + 16;
-    const size_t per_instance = size_t(160) * 1024 / 4;
+    const size_t per_instance = kLdsPerCu / kTrialInstancesPerCu;
     const size_t budget = per_instance > fixed ? (per_instance - fixed) / trial_row_waves(W) : 0;
     sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), budget);
   }
@@ -1579,7 +1567,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
         k_rows = bound ? ilq_rows_kernel<T, NX, NP, MU, kBoundProg + ID_> : ilq_rows_kernel<T, NX, NP, MU, ID_>; \
         k_prows = bound ? ilq_probe_rows_kernel<T, NX, NP, MU, kBoundProg + ID_>                               \
                         : ilq_probe_rows_kernel<T, NX, NP, MU, ID_>;                                           \
-        if (rows_state_in_registers(NX, NP * MU) && trial_lds_bytes<T>(d, W, 64, true) <= size_t(160) * 1024 / 4) { \
+        if (rows_state_in_registers(NX, NP * MU) && trial_lds_bytes<T>(d, W, 64, true) <= kLdsPerCu / kTrialInstancesPerCu) { \
           k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, kBoundProg + ID_>                               \
                           : ilq_trial_kernel<T, NX, NP, MU, W, ID_>;                                           \
           static_prog = ID_;                                                                                   \
@@ -1630,7 +1618,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   // (round 3, with compact rows: n = 14 fp32, B = 8192: 1.97 M fused vs 1.79 M split; fp64: 1.34 M vs 1.27 M).  The
   // host then counts every round: an instance may ask for another pass (back-tracking) before its sweep.
   // ilqg_solve_options::split_trial overrides the choice.
-  bool split = choice(opt.split_trial, 4 * lds_trial > size_t(160) * 1024 || (big_batch && NX > 16) || want_1w);
+  bool split = choice(opt.split_trial, kTrialInstancesPerCu * lds_trial > kLdsPerCu || (big_batch && NX > 16) || want_1w);
   if (kProfile || opt.forced_steps) split = false;  // the phase profile reads the fused kernel's counters
   if (split) {  // the split row kernels interpret the program: their chunk width is the interpreter's
     static_prog = 0;
@@ -1721,7 +1709,7 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   size_t lds_part_bytes = 0;
   if (static_prog && static_in_regs && W == 2 && fused_partials_room(int(sizeof(T)), NX, NP, MU)) {
     const size_t extra = partials_lds_elems(d.T, d.N) * sizeof(T);
-    if (4 * (lds_trial + extra) <= size_t(160) * 1024) lds_part_bytes = extra;
+    if (kTrialInstancesPerCu * (lds_trial + extra) <= kLdsPerCu) lds_part_bytes = extra;
   }
   sa.lds_part = lds_part_bytes ? 1 : 0;
   plan.trial = {k_trial, 64 * W, lds_trial + lds_part_bytes};
@@ -1773,12 +1761,48 @@ template struct DimsLaunch<float, ILQG_PART_NX, ILQG_PART_NP, ILQG_PART_MU>;
 template struct DimsLaunch<double, ILQG_PART_NX, ILQG_PART_NP, ILQG_PART_MU>;
 #else
 #if defined(ILQG_SPLIT_BUILD)
+// The list's one expansion besides the table: without these declarations the table's addresses would instantiate every
+// shape's launchers, and the kernels behind them, in this unit as well.
 #define X(NX_, NP_, MU_)                                   \
   extern template struct DimsLaunch<float, NX_, NP_, MU_>; \
   extern template struct DimsLaunch<double, NX_, NP_, MU_>;
 ILQG_FOR_DIMS(X)
 #undef X
 #endif
+
+namespace {
+
+// Index of a precision in a ShapeEntry's pairs
+inline int dtype_index(int32_t dtype) { return dtype == ILQG_F32 ? 0 : 1; }
+
+struct ShapeEntry {
+  int nx, np, mu;
+  // DimsLaunch<float, nx, np, mu>'s member at [0], DimsLaunch<double, nx, np, mu>'s at [1]
+  decltype(&DimsLaunch<float, 0, 0, 0>::lq) lq[2];
+  decltype(&DimsLaunch<float, 0, 0, 0>::lq_openloop) lq_openloop[2];
+  decltype(&DimsLaunch<float, 0, 0, 0>::solve) solve[2];
+  decltype(&DimsLaunch<float, 0, 0, 0>::rows) rows[2];
+  PaddedSweep lq_padded[2];
+  decltype(&DimsLaunch<float, 0, 0, 0>::lq_padded_batch) lq_padded_batch[2];
+};
+template <int NX, int NP, int MU>
+constexpr ShapeEntry shape_entry() {
+  using F = DimsLaunch<float, NX, NP, MU>;
+  using D = DimsLaunch<double, NX, NP, MU>;
+  return {NX, NP, MU, {F::lq, D::lq}, {F::lq_openloop, D::lq_openloop}, {F::solve, D::solve}, {F::rows, D::rows},
+          {F::lq_padded, D::lq_padded}, {F::lq_padded_batch, D::lq_padded_batch}};
+}
+#define X(NX_, NP_, MU_) shape_entry<NX_, NP_, MU_>(),
+const ShapeEntry kShapes[] = {ILQG_FOR_DIMS(X)};
+#undef X
+
+const ShapeEntry* find_shape(int n, int N, int mu) {
+  for (const ShapeEntry& e : kShapes)
+    if (e.nx == n && e.np == N && e.mu == mu) return &e;
+  return nullptr;
+}
+
+}  // namespace
 
 // `d`: the problem as the kernels get it, p->dev or a variant of it
 static ilqg_status launch_linquad(const ilqg_problem* p, const DevProblem& d, int32_t batch, const void* xs, const void* us,
@@ -1789,31 +1813,21 @@ static ilqg_status launch_linquad(const ilqg_problem* p, const DevProblem& d, in
   if (p->generic)  // the row stage with run-time dimensions (rows_chunk<T, 0, 0, 0>)
     return p->desc.dtype == ILQG_F32 ? DimsLaunch<float, 0, 0, 0>::rows(d, batch, ptrs, (hipStream_t)stream)
                                      : DimsLaunch<double, 0, 0, 0>::rows(d, batch, ptrs, (hipStream_t)stream);
-#define X(NX_, NP_, MU_)                                                                          \
-  if (d.n == NX_ && d.N == NP_ && p->mu_uniform == MU_)                                           \
-    return p->desc.dtype == ILQG_F32                                                              \
-               ? DimsLaunch<float, NX_, NP_, MU_>::rows(d, batch, ptrs, (hipStream_t)stream)      \
-               : DimsLaunch<double, NX_, NP_, MU_>::rows(d, batch, ptrs, (hipStream_t)stream);
-  ILQG_FOR_DIMS(X)
-#undef X
+  if (const ShapeEntry* e = find_shape(d.n, d.N, p->mu_uniform))
+    return e->rows[dtype_index(p->desc.dtype)](d, batch, ptrs, (hipStream_t)stream);
   return fail(ILQG_ERR_UNSUPPORTED, "no device kernel instantiated for this problem's dimensions");
 }
 
 // The smallest instantiated shape a game embeds in (same player count, at least its states and its widest control), for
-// the padded sweeps (padded_lq_kernel / padded_lq_batch_kernel); false: none.
-static bool pick_padded_shape(int n, int N, const int32_t* udim, int* nx, int* mu) {
-  int mumax = 0, best_nx = 0, best_mu = 0;
+// the padded sweeps (padded_lq_kernel / padded_lq_batch_kernel); nullptr: none.
+static const ShapeEntry* pick_padded_shape(int n, int N, const int32_t* udim) {
+  int mumax = 0;
   for (int i = 0; i < N; i++) mumax = udim[i] > mumax ? udim[i] : mumax;
-#define X(NX_, NP_, MU_)                                                                                                 \
-  if (NP_ == N && NX_ >= n && MU_ >= mumax && (best_nx == 0 || NX_ < best_nx || (NX_ == best_nx && MU_ < best_mu))) { \
-    best_nx = NX_;                                                                                                       \
-    best_mu = MU_;                                                                                                       \
-  }
-  ILQG_FOR_DIMS(X)
-#undef X
-  *nx = best_nx;
-  *mu = best_mu;
-  return best_nx != 0;
+  const ShapeEntry* best = nullptr;
+  for (const ShapeEntry& e : kShapes)
+    if (e.np == N && e.nx >= n && e.mu >= mumax && (!best || e.nx < best->nx || (e.nx == best->nx && e.mu < best->mu)))
+      best = &e;
+  return best;
 }
 
 // The game's control blocks at mu x mu each (the padded shape's PairTable)
@@ -1829,9 +1843,6 @@ static bool padded_pairs(const PairTable& pt, int N, int mu, PairTable* ptp, std
 // Threads of a workgroup of the run-time-dimensioned sweeps (ilqg_lq_generic.hpp: every phase strides its entries over
 // the workgroup and ends with a barrier; lq_generic_kernel's launch bound).
 static constexpr int kGenSweepThreads = 256;
-
-// LDS a CU can give one workgroup (gfx950: 160 KB)
-static constexpr size_t kLdsPerWorkgroup = size_t(160) * 1024;
 
 // The whole solve on the run-time-dimensioned kernels: the split trial pass (integrate / rows / decide, ilqg_solve.hpp)
 // over the whole batch in a round without back-tracking instances, the host counting rounds; the sweeps of
@@ -1851,7 +1862,7 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
   const size_t lds_roll = trial_phase_lds_bytes<T>(d, TRIAL_ROLL, sa.rows_cw);
   const size_t lds_rows = rows_maps_bytes(d) + trial_rows_elems(d, sa.rows_cw) * sizeof(T);
   const size_t lds_lq = ((p->desc.params.open_loop ? gen_openloop_lds_elems(d.n, d.N, d.m) : gen_feedback_lds_elems(d.n, d.N, d.m)) + 4) * sizeof(T);
-  if (lds_lq > kLdsPerWorkgroup || lds_rows > kLdsPerWorkgroup)
+  if (lds_lq > kLdsPerCu || lds_rows > kLdsPerCu)
     return fail(ILQG_ERR_UNSUPPORTED, "the game does not fit a CU's LDS");
   // Back-tracking instances are listed and their next step sizes probed side by side, as in the specialised solve
   // (DimsLaunch::solve): without it a single failing line search of 100 steps costs the whole batch 100 serial passes
@@ -1878,18 +1889,14 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
   // ilqg_solve_options::generic_kernels keeps the run-time-dimensioned sweeps unless padded_sweep = ON.
   PairTable ptp;
   if (opt.padded_sweep == ILQG_CHOICE_ON || (opt.padded_sweep == ILQG_CHOICE_AUTO && p->generic)) {
-    int pad_nx = 0, pad_mu = 0;
-    pick_padded_shape(d.n, d.N, d.udim, &pad_nx, &pad_mu);
-    if (pad_nx == 0 && opt.padded_sweep == ILQG_CHOICE_ON)
+    const ShapeEntry* const shape = pick_padded_shape(d.n, d.N, d.udim);
+    if (!shape && opt.padded_sweep == ILQG_CHOICE_ON)
       return fail(ILQG_ERR_UNSUPPORTED, "padded_sweep = ON: no instantiated shape holds this game (same player count, at "
                                         "least its states and its widest control)");
-    if (pad_nx) {
-#define X(NX_, NP_, MU_) \
-      if (pad_nx == NX_ && d.N == NP_ && pad_mu == MU_) plan.padded = DimsLaunch<T, NX_, NP_, MU_>::lq_padded;
-      ILQG_FOR_DIMS(X)
-#undef X
+    if (shape) {
+      plan.padded = shape->lq_padded[dtype_index(p->desc.dtype)];
       std::string err;
-      if (!padded_pairs(d.pairs, d.N, pad_mu, &ptp, &err)) return fail(ILQG_ERR_INVALID, err);
+      if (!padded_pairs(d.pairs, d.N, shape->mu, &ptp, &err)) return fail(ILQG_ERR_INVALID, err);
       size_t elems = 0;
       ilqg_status s = plan.padded(d, &sa, ptp, nullptr, &elems, p->desc.params.open_loop != 0, stream);
       if (s != ILQG_OK) return s;
@@ -1903,20 +1910,14 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
   return run_rounds(p, sa, tail, plan, opt, stream);
 }
 
-// ilqg_lq_feedback_batch / ilqg_lq_openloop_batch of a shape without an instantiation on the padded sweep of (nx, N, mu)
-template <typename T>
-static ilqg_status launch_lq_padded(const ilqg_dims* d, const PairTable& pt, int nx, int mu, bool open_loop, const void* A,
-                                    const void* Bm, const void* Q, const void* l, const void* R, const void* r,
-                                    const void* x0, void* P, void* alpha, void* dx, hipStream_t stream) {
+// ilqg_lq_feedback_batch / ilqg_lq_openloop_batch of a shape without an instantiation on the padded sweep of `shape`
+static ilqg_status launch_lq_padded(const ilqg_dims* d, const PairTable& pt, const ShapeEntry& shape, bool open_loop,
+                                    const void* A, const void* Bm, const void* Q, const void* l, const void* R,
+                                    const void* r, const void* x0, void* P, void* alpha, void* dx, hipStream_t stream) {
   PairTable ptp;
   std::string err;
-  if (!padded_pairs(pt, d->num_players, mu, &ptp, &err)) return fail(ILQG_ERR_INVALID, err);
-#define X(NX_, NP_, MU_)                                                                                                  \
-  if (nx == NX_ && d->num_players == NP_ && mu == MU_)                                                                     \
-    return DimsLaunch<T, NX_, NP_, MU_>::lq_padded_batch(d, pt, ptp, open_loop, A, Bm, Q, l, R, r, x0, P, alpha, dx, stream);
-  ILQG_FOR_DIMS(X)
-#undef X
-  return fail(ILQG_ERR_UNSUPPORTED, "no shape to embed the game in");
+  if (!padded_pairs(pt, d->num_players, shape.mu, &ptp, &err)) return fail(ILQG_ERR_INVALID, err);
+  return shape.lq_padded_batch[dtype_index(d->dtype)](d, pt, ptp, open_loop, A, Bm, Q, l, R, r, x0, P, alpha, dx, stream);
 }
 
 // ilqg_lq_feedback_batch / ilqg_lq_openloop_batch for a shape without a specialised instantiation (or when the caller
@@ -1928,7 +1929,7 @@ static ilqg_status launch_lq_generic(const ilqg_dims* d, const PairTable& pt, bo
   const GenDims gd = gen_dims_of(d->n, d->num_players, d->udim, d->T);
   if (gd.m > ILQG_MAX_UDIM_TOTAL) return fail(ILQG_ERR_UNSUPPORTED, "more than ILQG_MAX_UDIM_TOTAL controls in total");
   const size_t lds = (open_loop ? gen_openloop_lds_elems(gd.n, gd.N, gd.m) : gen_feedback_lds_elems(gd.n, gd.N, gd.m)) * sizeof(T);
-  if (lds > kLdsPerWorkgroup) return fail(ILQG_ERR_UNSUPPORTED, "the game's value functions do not fit a CU's LDS");
+  if (lds > kLdsPerCu) return fail(ILQG_ERR_UNSUPPORTED, "the game's value functions do not fit a CU's LDS");
   LQBatchArgs<T> g(d, A, Bm, Q, l, R, r, x0, P, alpha, dx);
   const int row = open_loop ? gen_ol_row_elems(gd.n, gd.m, gd.N, costates != nullptr) : 0;
   if (open_loop) {
@@ -1941,6 +1942,46 @@ static ilqg_status launch_lq_generic(const ilqg_dims* d, const PairTable& pt, bo
   auto kern = lq_generic_kernel<T>;
   raise_lds_limit((const void*)kern, lds);
   hipLaunchKernelGGL(kern, dim3(d->batch), dim3(kGenSweepThreads), lds, stream, g, gd, pt, open_loop ? 1 : 0, row);
+  HIP_TRY(hipGetLastError());
+  return ILQG_OK;
+}
+
+// The sweep of ilqg_lq_feedback_batch / ilqg_lq_openloop_batch on the first route that takes the game: its shape's own
+// instantiation (`uniform`: one m_i, `mu`, for all players), the smallest instantiated shape that holds it, the
+// run-time-dimensioned sweep (also when the caller asks for it: ilqg_dims::sweep_formulation = ILQG_SWEEP_GENERIC).
+// `costates`: the open-loop sweeps carry them out themselves, the padded one excepted: with them it is passed over.
+// (The feedback sweeps carry none: ilqg_lq_feedback_batch runs a kernel of its own behind whichever ran.)
+static ilqg_status launch_lq_route(const ilqg_dims* d, const PairTable& pt, bool uniform, int mu, bool open_loop,
+                                   const void* A, const void* Bm, const void* Q, const void* l, const void* R,
+                                   const void* r, const void* x0, void* P, void* alpha, void* dx, void* costates,
+                                   hipStream_t st) {
+  const int ty = dtype_index(d->dtype);
+  const bool specialised = d->sweep_formulation != ILQG_SWEEP_GENERIC;
+  if (!open_loop) costates = nullptr;
+  if (const ShapeEntry* own = uniform && specialised ? find_shape(d->n, d->num_players, mu) : nullptr)
+    return open_loop ? own->lq_openloop[ty](d, pt, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, st)
+                     : own->lq[ty](d, pt, A, Bm, Q, l, R, r, x0, P, alpha, dx, st);
+  if (const ShapeEntry* holds = specialised && !costates ? pick_padded_shape(d->n, d->num_players, d->udim) : nullptr)
+    return launch_lq_padded(d, pt, *holds, open_loop, A, Bm, Q, l, R, r, x0, P, alpha, dx, st);
+  return ty ? launch_lq_generic<double>(d, pt, open_loop, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, st)
+            : launch_lq_generic<float>(d, pt, open_loop, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, st);
+}
+
+// The costates of a feedback sweep's results, behind it on the stream; `zs`: costates_scratch_elems per instance
+template <typename T>
+static ilqg_status launch_feedback_costates(const ilqg_dims* d, const PairTable& pt, const void* A, const void* Bm,
+                                            const void* Q, const void* l, const void* R, const void* r, const void* P,
+                                            const void* alpha, const void* dx, void* zs, void* costates, hipStream_t st) {
+  CostateDims cd;
+  cd.n = d->n; cd.N = d->num_players; cd.T = d->T;
+  cd.uoff[0] = 0;
+  for (int i = 0; i < cd.N; i++) cd.uoff[i + 1] = cd.uoff[i] + d->udim[i];
+  cd.m = cd.uoff[cd.N];
+  const size_t lds = costates_lds_elems(cd.n, cd.N) * sizeof(T);
+  auto kern = lq_feedback_costates_kernel<T>;
+  raise_lds_limit((const void*)kern, lds);
+  hipLaunchKernelGGL(kern, dim3(d->batch), dim3(256), lds, st, cd, pt, (const T*)A, (const T*)Bm, (const T*)Q, (const T*)l,
+                     (const T*)R, (const T*)r, (const T*)P, (const T*)alpha, (const T*)dx, (T*)zs, (T*)costates);
   HIP_TRY(hipGetLastError());
   return ILQG_OK;
 }
@@ -2075,59 +2116,17 @@ ilqg_status ilqg_lq_feedback_batch(const ilqg_dims* d, const void* A, const void
   if (s != ILQG_OK) return s;
   if (d->batch == 0) return ILQG_OK;
   hipStream_t st = (hipStream_t)stream;
-  const size_t elem = d->dtype == ILQG_F32 ? 4 : 8;
-  const int N = d->num_players;
-  int m = 0;
-  for (int i = 0; i < N; i++) m += d->udim[i];
   // costates: Z_i, zeta_i of every step (this translation unit's scratch; the sweep's launcher has its own)
   if (costates) {
-    s = Scratch().reserve(size_t(d->batch) * costates_scratch_elems(d->n, N, d->T) * elem);
+    const size_t elem = d->dtype == ILQG_F32 ? 4 : 8;
+    s = Scratch().reserve(size_t(d->batch) * costates_scratch_elems(d->n, d->num_players, d->T) * elem);
     if (s != ILQG_OK) return s;
   }
-  auto finish = [&](ilqg_status launched) -> ilqg_status {
-    if (launched != ILQG_OK || !costates) return launched;
-    CostateDims cd;
-    cd.n = d->n; cd.N = N; cd.m = m; cd.T = d->T;
-    cd.uoff[0] = 0;
-    for (int i = 0; i < N; i++) cd.uoff[i + 1] = cd.uoff[i] + d->udim[i];
-    const size_t lds = costates_lds_elems(d->n, N) * elem;
-    void* zs = ilqg_shared::scratch_state().ptr;
-    if (d->dtype == ILQG_F32) {
-      auto kern = lq_feedback_costates_kernel<float>;
-      raise_lds_limit((const void*)kern, lds);
-      hipLaunchKernelGGL(kern, dim3(d->batch), dim3(256), lds, st, cd, pt, (const float*)A, (const float*)Bm,
-                         (const float*)Q, (const float*)l, (const float*)R, (const float*)r, (const float*)P,
-                         (const float*)alpha, (const float*)dx, (float*)zs, (float*)costates);
-    } else {
-      auto kern = lq_feedback_costates_kernel<double>;
-      raise_lds_limit((const void*)kern, lds);
-      hipLaunchKernelGGL(kern, dim3(d->batch), dim3(256), lds, st, cd, pt, (const double*)A, (const double*)Bm,
-                         (const double*)Q, (const double*)l, (const double*)R, (const double*)r, (const double*)P,
-                         (const double*)alpha, (const double*)dx, (double*)zs, (double*)costates);
-    }
-    HIP_TRY(hipGetLastError());
-    return ILQG_OK;
-  };
-#define X(NX_, NP_, MU_)                                                                              \
-  if (uniform && d->sweep_formulation != ILQG_SWEEP_GENERIC && d->n == NX_ && d->num_players == NP_ && mu == MU_) { \
-    return finish(d->dtype == ILQG_F32                                                                \
-               ? DimsLaunch<float, NX_, NP_, MU_>::lq(d, pt, A, Bm, Q, l, R, r, x0, P, alpha, dx, st)      \
-               : DimsLaunch<double, NX_, NP_, MU_>::lq(d, pt, A, Bm, Q, l, R, r, x0, P, alpha, dx, st));   \
-  }
-  ILQG_FOR_DIMS(X)
-#undef X
-  // no specialised instantiation (or players with different control dimensions): the game embedded in the smallest
-  // instantiated shape that holds it, on that shape's sweep (padded_lq_batch_kernel) ...
-  {
-    int nx = 0, pmu = 0;
-    if (d->sweep_formulation != ILQG_SWEEP_GENERIC && pick_padded_shape(d->n, N, d->udim, &nx, &pmu))
-      return finish(d->dtype == ILQG_F32 ? launch_lq_padded<float>(d, pt, nx, pmu, false, A, Bm, Q, l, R, r, x0, P, alpha, dx, st)
-                                         : launch_lq_padded<double>(d, pt, nx, pmu, false, A, Bm, Q, l, R, r, x0, P, alpha, dx, st));
-  }
-  // ... or, where there is none (or the caller asks for it), the run-time-dimensioned sweep
-  return finish(d->dtype == ILQG_F32
-                    ? launch_lq_generic<float>(d, pt, false, A, Bm, Q, l, R, r, x0, P, alpha, dx, nullptr, st)
-                    : launch_lq_generic<double>(d, pt, false, A, Bm, Q, l, R, r, x0, P, alpha, dx, nullptr, st));
+  s = launch_lq_route(d, pt, uniform, mu, false, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, st);
+  if (s != ILQG_OK || !costates) return s;
+  void* zs = ilqg_shared::scratch_state().ptr;
+  return dtype_index(d->dtype) ? launch_feedback_costates<double>(d, pt, A, Bm, Q, l, R, r, P, alpha, dx, zs, costates, st)
+                               : launch_feedback_costates<float>(d, pt, A, Bm, Q, l, R, r, P, alpha, dx, zs, costates, st);
 }
 
 ilqg_status ilqg_lq_openloop_batch(const ilqg_dims* d, const void* A, const void* Bm, const void* Q, const void* l,
@@ -2140,23 +2139,7 @@ ilqg_status ilqg_lq_openloop_batch(const ilqg_dims* d, const void* A, const void
                                        "lq_open_loop_solver.cpp:83-84", &pt, &uniform, &mu);
   if (s != ILQG_OK) return s;
   if (d->batch == 0) return ILQG_OK;
-  hipStream_t st = (hipStream_t)stream;
-#define X(NX_, NP_, MU_)                                                                                      \
-  if (uniform && d->sweep_formulation != ILQG_SWEEP_GENERIC && d->n == NX_ && d->num_players == NP_ && mu == MU_) { \
-    return d->dtype == ILQG_F32                                                                               \
-               ? DimsLaunch<float, NX_, NP_, MU_>::lq_openloop(d, pt, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, st)     \
-               : DimsLaunch<double, NX_, NP_, MU_>::lq_openloop(d, pt, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, st);   \
-  }
-  ILQG_FOR_DIMS(X)
-#undef X
-  {
-    int nx = 0, pmu = 0;  // (the padded sweep does not carry costates out: with them, the run-time-dimensioned sweep)
-    if (!costates && d->sweep_formulation != ILQG_SWEEP_GENERIC && pick_padded_shape(d->n, d->num_players, d->udim, &nx, &pmu))
-      return d->dtype == ILQG_F32 ? launch_lq_padded<float>(d, pt, nx, pmu, true, A, Bm, Q, l, R, r, x0, P, alpha, dx, st)
-                                  : launch_lq_padded<double>(d, pt, nx, pmu, true, A, Bm, Q, l, R, r, x0, P, alpha, dx, st);
-  }
-  return d->dtype == ILQG_F32 ? launch_lq_generic<float>(d, pt, true, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, st)
-                              : launch_lq_generic<double>(d, pt, true, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, st);
+  return launch_lq_route(d, pt, uniform, mu, true, A, Bm, Q, l, R, r, x0, P, alpha, dx, costates, (hipStream_t)stream);
 }
 
 // ---- the problem object (ilqg_problem.hpp) ----
@@ -2552,16 +2535,9 @@ ilqg_status ilqg_solve_batch_ex(ilqg_problem* p, int32_t batch, const void* x0, 
     return p->desc.dtype == ILQG_F32
                ? generic_solve<float>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, o, st)
                : generic_solve<double>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, o, st);
-#define X(NX_, NP_, MU_)                                                                                        \
-  if (d.n == NX_ && d.N == NP_ && p->mu_uniform == MU_) {                                                       \
-    return p->desc.dtype == ILQG_F32                                                                            \
-               ? DimsLaunch<float, NX_, NP_, MU_>::solve(p, batch, x0, xs, us, P, alpha, total_costs, iters, status,  \
-                                                         converged, workspace, o, st)                            \
-               : DimsLaunch<double, NX_, NP_, MU_>::solve(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, \
-                                                          converged, workspace, o, st);                          \
-  }
-  ILQG_FOR_DIMS(X)
-#undef X
+  if (const ShapeEntry* e = find_shape(d.n, d.N, p->mu_uniform))
+    return e->solve[dtype_index(p->desc.dtype)](p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged,
+                                                workspace, o, st);
   return fail(ILQG_ERR_UNSUPPORTED, "no device kernel instantiated for this problem's dimensions");
 }
 
@@ -2602,7 +2578,7 @@ ilqg_status ilqg_solve_state_batch(const ilqg_problem* p, int32_t batch, const v
   if (batch <= 0) return ILQG_OK;
   const DevProblem& d = p->dev;
   const int ol_row = p->desc.params.open_loop ? ol_row_elems(d.n, d.m, d.N) : 0;
-  const WsLayout L(d.n, d.m, d.N, d.T, d.pairs.Rsz, d.pairs.rsz, ol_row, d.num_constraints, augmented_lagrangian ? 1 : 0);
+  const WsLayout L = ws_layout_of(d, ol_row, augmented_lagrangian ? 1 : 0);
 #define CALL(TY_)                                                                                                  \
   [&]() -> ilqg_status {                                                                                         \
     hipLaunchKernelGGL(solve_state_kernel<TY_>, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream,        \

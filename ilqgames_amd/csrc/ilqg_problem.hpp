@@ -6,7 +6,7 @@
 //   ilqg_problem           the handle: the device tables, the DevProblem that points at them and what the solves keep
 //                          between calls.  ilqg_problem_destroy is `delete`.
 // (What per-instance declarations and bindings do with the handle: ilqg_instances.hpp.)
-// Part of ilqg_api.hip, included once behind its fail() and ILQG_FOR_DIMS.  Every translation unit of the library sees the
+// Part of ilqg_api.hip, included once behind its fail() and find_shape().  Every translation unit of the library sees the
 // handle and the buffers (the per-shape units reach into the handle); only the main unit the builder and the upload.
 #pragma once
 
@@ -240,11 +240,9 @@ ilqg_status flatten_subsystems(const ilqg_problem_desc& desc, ProblemTables* t) 
   // too), the whole block where it does not (the two Dubins cars: single_player_dynamical_system.h:69-71)
   d.sync_dist_dims = d.sub_kind[0] == ILQG_DYN_DUBINS_CAR ? 3 : (d.sub_kind[0] == ILQG_DYN_DELAYED_DUBINS_CAR ? 4 : 2);
   if (!uniform_udim(d.udim, d.N, &t->mu_uniform)) t->mu_uniform = 0;
-  bool plain = false, instantiated = false;
+  bool plain = false;
   for (int i = 0; i < d.N; i++) plain = plain || is_plain_rk4_kind(d.sub_kind[i]);
-#define X(NX_, NP_, MU_) instantiated = instantiated || (d.n == NX_ && d.N == NP_ && t->mu_uniform == MU_);
-  ILQG_FOR_DIMS(X)
-#undef X
+  const bool instantiated = find_shape(d.n, d.N, t->mu_uniform) != nullptr;
   // Unicycle5D / Car7D / DelayedDubinsCar rows need an instantiation that carries the plain RK4 (dims_use_plain_rk4,
   // ilqg_stages.hpp); in any other shape they run on the run-time-dimensioned path, which picks its integrator by model
   t->generic = !instantiated || (plain && !dims_use_plain_rk4(d.n, d.N, d.udim[0]));

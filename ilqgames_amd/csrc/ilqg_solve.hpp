@@ -169,12 +169,35 @@ __device__ __forceinline__ void state_store(T* w, const WsLayout& L, const Solve
   if (threadIdx.x == 0) *reinterpret_cast<SolveState<T>*>(w + L.state) = s;
 }
 
+// The layout of a solve's per-instance blocks.  Kernels and host build it here and nowhere else: a copy of the nine
+// arguments that leaves out ol_row or al_mode still compiles, and reads a wrong SolveState slot.
+__host__ __device__ __forceinline__ WsLayout ws_layout_of(const DevProblem& p, int ol_row, int al_mode) {
+  return WsLayout(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, ol_row, p.num_constraints, al_mode);
+}
+template <typename T>
+__device__ __forceinline__ WsLayout ws_layout_of(const DevProblem& p, const SolveArgs<T>& sa) {
+  return ws_layout_of(p, sa.ol_row, sa.al_mode);
+}
+// The gate of the per-instance solve kernels: the stage instance b is in (a kernel leaves, before it touches LDS, unless
+// the stage is one of its own) ...
+template <typename T>
+__device__ __forceinline__ int instance_stage(const DevProblem& p, const SolveArgs<T>& sa, int b) {
+  const WsLayout L = ws_layout_of(p, sa);
+  return reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
+}
+// ... and an instance the caller's mask switches off on a solve's first launch: done before it starts, outputs untouched
+template <typename T>
+__device__ __forceinline__ void instance_mark_done(const DevProblem& p, const SolveArgs<T>& sa, int b) {
+  const WsLayout L = ws_layout_of(p, sa);
+  if (threadIdx.x == 0) reinterpret_cast<SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage = ST_DONE;
+}
+
 template <typename T>
 struct InstanceBuffers {
   T *w, *xs0, *us0, *P0, *al0;
   const WsLayout L;
   __device__ InstanceBuffers(const DevProblem& p, const SolveArgs<T>& sa, int b)
-      : L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode) {
+      : L(ws_layout_of(p, sa)) {
     w = sa.ws + size_t(b) * sa.ws_stride;
     // two operating-point buffers and two strategy buffers; buffer 0 is the caller's
     xs0 = sa.xs + size_t(b) * p.T * p.n;
@@ -1206,7 +1229,7 @@ __device__ __forceinline__ void log_part_instance(const DevProblem& p, const Sol
 // stays true, has_converged is whatever the last accepted step left.
 template <typename T>
 __device__ __forceinline__ void deadline_part_instance(const DevProblem& p, const SolveArgs<T>& sa, int b) {
-  const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
+  const WsLayout L = ws_layout_of(p, sa);
   SolveState<T>* const st = reinterpret_cast<SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state);
   if (threadIdx.x == 0 && st->stage == ST_LQ) {
     st->stage = ST_INNER_DONE;
@@ -1231,7 +1254,7 @@ enum { LQ_VALU_FEEDBACK = 0, LQ_PLAYER_WAVES = 1, LQ_OPEN_LOOP = 2, LQ_PLAYER_WA
 template <typename T, int NX, int NP, int MU, int KIND, int FORMS = 1>
 __device__ __forceinline__ void lq_part_instance(const DevProblem& p, const SolveArgs<T>& sa, int b, T* sm) {
   const int Tn = p.T;
-  const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
+  const WsLayout L = ws_layout_of(p, sa);
   T* const w = sa.ws + size_t(b) * sa.ws_stride;
   SolveState<T>* const st = reinterpret_cast<SolveState<T>*>(w + L.state);
   const int sacc = __builtin_amdgcn_readfirstlane(st->sacc);
@@ -1326,7 +1349,7 @@ __device__ __forceinline__ void lq_part_instance(const DevProblem& p, const Solv
 template <typename T>
 __device__ __forceinline__ void lq_part_generic(const DevProblem& p, const SolveArgs<T>& sa, int b, T* sm) {
   const int Tn = p.T;
-  const WsLayout L(p.n, p.m, p.N, p.T, p.pairs.Rsz, p.pairs.rsz, sa.ol_row, p.num_constraints, sa.al_mode);
+  const WsLayout L = ws_layout_of(p, sa);
   T* const w = sa.ws + size_t(b) * sa.ws_stride;
   SolveState<T>* const st = reinterpret_cast<SolveState<T>*>(w + L.state);
   const int sacc = __builtin_amdgcn_readfirstlane(st->sacc);

@@ -53,8 +53,12 @@ def test_lq_feedback_matches_reference_python_golden(hip, name):
     assert np.all(_np(P)[:, -1] == 0) and np.all(_np(alpha)[:, -1] == 0)
 
 
+# `dims` of this test and of test_lq_openloop_matches_oracle_random: every shape the library instantiates (ILQG_FOR_DIMS,
+# csrc/ilqg_api.hip) — tests/test_host_boundary.py::test_every_instantiated_shape_has_its_sweep_tests holds them to it.
+# (A new shape goes to the end of each: the ids of the cases are their positions.)
 @pytest.mark.parametrize("dims", [(14, 3, 2), (16, 3, 2), (15, 3, 2), (24, 4, 2), (18, 3, 2), (10, 2, 2), (6, 3, 2),
-                                  (4, 2, 2), (6, 2, 1), (3, 2, 1), (3, 1, 1), (2, 2, 1), (17, 3, 2), (8, 2, 1)])
+                                  (4, 2, 2), (6, 2, 1), (3, 2, 1), (3, 1, 1), (2, 2, 1), (17, 3, 2), (8, 2, 1),
+                                  (12, 2, 2), (2, 1, 2), (8, 2, 2)])
 @pytest.mark.parametrize("dtype", [abi.F64, abi.F32])
 def test_lq_feedback_matches_oracle_random(hip, oracle, dims, dtype):
     n, N, mu = dims
@@ -105,7 +109,8 @@ def test_stand_alone_entry_points_run_in_caller_owned_scratch(hip, oracle):
 
 
 @pytest.mark.parametrize("dims", [(14, 3, 2), (16, 3, 2), (24, 4, 2), (18, 3, 2), (10, 2, 2), (6, 3, 2), (2, 2, 1),
-                                  (17, 3, 2), (8, 2, 1)])
+                                  (17, 3, 2), (8, 2, 1),
+                                  (15, 3, 2), (12, 2, 2), (4, 2, 2), (6, 2, 1), (3, 2, 1), (3, 1, 1), (2, 1, 2), (8, 2, 2)])
 @pytest.mark.parametrize("dtype", [abi.F64, abi.F32])
 def test_lq_openloop_matches_oracle_random(hip, oracle, dims, dtype):
     """ilqg_lq_openloop_batch vs the oracle's LQOpenLoopSolver restatement (alpha, delta_xs; P == 0)."""

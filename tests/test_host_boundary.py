@@ -44,6 +44,22 @@ def test_library_has_no_dangling_internal_symbol():
     assert not own, own
 
 
+def test_every_instantiated_shape_has_its_sweep_tests():
+    """The (n, N, m_i) list of the library — the `#define ILQG_FOR_DIMS(X)` line of csrc/ilqg_api.hip, read the way
+    __graft_entry__.build_hip_library reads it — is the `dims` parametrisation of the two stand-alone sweep tests of
+    tests/test_gpu_parity.py: a shape added to the library cannot go without them."""
+    import test_gpu_parity
+    src = os.path.join(ROOT, "ilqgames_amd", "csrc", "ilqg_api.hip")
+    line = next(l for l in open(src) if l.startswith("#define ILQG_FOR_DIMS(X)"))
+    shapes = [tuple(int(v) for v in m) for m in re.findall(r"X\((\d+), (\d+), (\d+)\)", line)]
+    assert shapes and len(set(shapes)) == len(shapes)
+    for test in (test_gpu_parity.test_lq_feedback_matches_oracle_random,
+                 test_gpu_parity.test_lq_openloop_matches_oracle_random):
+        tested = [tuple(v) for mark in test.pytestmark if mark.name == "parametrize" and mark.args[0] == "dims"
+                  for v in mark.args[1]]
+        assert set(tested) == set(shapes) and len(tested) == len(shapes), test.__name__
+
+
 def test_struct_layouts_match_the_c_header():
     """Compile a tiny C program against include/ilqg.h and compare sizeof/offsetof with ctypes."""
     from ilqgames_amd import abi
