@@ -40,6 +40,11 @@ COST_ROUTE_PROGRESS = 20       # time-dependent: quadratic about the polyline po
 COST_WEIGHTED_CONVEX_PROXIMITY = 21  # idx = (x1, y1, x2, y2), idx_extra = (v1, v2)
 CONSTRAINT_AFFINE_SCALAR = 22  # g = a^T v - b over the whole argument vector; `polyline` = offset of [a | b] in dense_params
 CONSTRAINT_AFFINE_VECTOR = 23  # g = |A v - b|; `polyline` = offset of [A (column-major) | b]
+COST_EXPRESSION = 24  # a postfix program over idx[0] (x) and idx[1] (y, or -1); `polyline` = offset of [L, (op, imm) x L]
+# ilqg_expr_op
+(EXPR_PUSH_X, EXPR_PUSH_Y, EXPR_PUSH_CONST, EXPR_PUSH_WEIGHT, EXPR_PUSH_VALUE, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_DIV,
+ EXPR_NEG, EXPR_SQUARE, EXPR_SQRT, EXPR_EXP, EXPR_LOG, EXPR_SIN, EXPR_COS, EXPR_HINGE) = range(1, 18)
+EXPR_MAX_OPS, EXPR_MAX_DEPTH = 64, 4
 # ilqg_cost_role
 ROLE_STATE_COST, ROLE_CONTROL_COST, ROLE_STATE_CONSTRAINT, ROLE_CONTROL_CONSTRAINT, ROLE_CHILD = range(5)
 FLAG_ORIENTED, FLAG_IS_MIN, FLAG_EQUALITY = 1, 2, 4
@@ -49,6 +54,56 @@ SCHEDULE_COUNTED, SCHEDULE_GENERIC, SCHEDULE_OPEN_LOOP, SCHEDULE_STATIC_ROWS = 1
 SCHEDULE_PADDED_SWEEP, SCHEDULE_CONSTANT_B = 256, 512
 B_ENTRY_LITERAL, B_ENTRY_DT, B_ENTRY_NEG_DT = 0, 1, 2  # ILQG_B_ENTRY_* (ilqg_sweep_b_structure_build)
 SUM, MAX, MIN = 0, 1, 2
+
+
+class Expr:
+    """An expression tree for ProblemSpec.expression: Expr.x(), Expr.y(), Expr.const(c), Expr.weight(), Expr.value(),
+    + - * / and unary minus between them (numbers become constants), and the functions square / sqrt / exp / log / sin /
+    cos / hinge.  program() is its postfix form [(opcode, imm), ...], operands left to right."""
+
+    def __init__(self, op, imm=0.0, kids=()):
+        self.op, self.imm, self.kids = op, float(imm), tuple(kids)
+
+    x = staticmethod(lambda: Expr(EXPR_PUSH_X))
+    y = staticmethod(lambda: Expr(EXPR_PUSH_Y))
+    const = staticmethod(lambda c: Expr(EXPR_PUSH_CONST, c))
+    weight = staticmethod(lambda: Expr(EXPR_PUSH_WEIGHT))
+    value = staticmethod(lambda: Expr(EXPR_PUSH_VALUE))
+
+    @staticmethod
+    def of(v):
+        return v if isinstance(v, Expr) else Expr.const(v)
+
+    def __add__(self, o): return Expr(EXPR_ADD, kids=(self, Expr.of(o)))
+    def __radd__(self, o): return Expr(EXPR_ADD, kids=(Expr.of(o), self))
+    def __sub__(self, o): return Expr(EXPR_SUB, kids=(self, Expr.of(o)))
+    def __rsub__(self, o): return Expr(EXPR_SUB, kids=(Expr.of(o), self))
+    def __mul__(self, o): return Expr(EXPR_MUL, kids=(self, Expr.of(o)))
+    def __rmul__(self, o): return Expr(EXPR_MUL, kids=(Expr.of(o), self))
+    def __truediv__(self, o): return Expr(EXPR_DIV, kids=(self, Expr.of(o)))
+    def __rtruediv__(self, o): return Expr(EXPR_DIV, kids=(Expr.of(o), self))
+    def __neg__(self): return Expr(EXPR_NEG, kids=(self,))
+    square = lambda self: Expr(EXPR_SQUARE, kids=(self,))
+    sqrt = lambda self: Expr(EXPR_SQRT, kids=(self,))
+    exp = lambda self: Expr(EXPR_EXP, kids=(self,))
+    log = lambda self: Expr(EXPR_LOG, kids=(self,))
+    sin = lambda self: Expr(EXPR_SIN, kids=(self,))
+    cos = lambda self: Expr(EXPR_COS, kids=(self,))
+    hinge = lambda self: Expr(EXPR_HINGE, kids=(self,))
+
+    def program(self):
+        out = []
+        for k in self.kids:
+            out += k.program()
+        return out + [(self.op, self.imm)]
+
+
+def expr_block(program):
+    """The dense_params block of a postfix program [(opcode, imm), ...]: [L, opcode_0, imm_0, ...] as floats."""
+    out = [float(len(program))]
+    for op, imm in program:
+        out += [float(op), float(imm)]
+    return out
 
 
 class Pair(C.Structure):
@@ -363,6 +418,18 @@ class ProblemSpec:
         return self._term(CONSTRAINT_AFFINE_VECTOR, role, player, arg, (0,), 1.0, 0.0,
                           FLAG_EQUALITY if is_equality else 0, off, constraint=True)
 
+    def expression(self, player, program_or_tree, dims, weight=1.0, value=0.0, control_of=None, role=None):
+        """An ILQG_COST_EXPRESSION term (include/ilqg.h): `program_or_tree` is an Expr or a postfix list [(opcode, imm), ...],
+        `dims` the one or two entries (x, y) of the state — or of the control vector of player `control_of` — it reads.
+        Nothing is checked here: the library refuses a malformed term (`role` overrides the role, for those tests)."""
+        r, arg = (ROLE_STATE_COST, -1) if control_of is None else (ROLE_CONTROL_COST, control_of)
+        dims = tuple(dims)
+        program = program_or_tree.program() if isinstance(program_or_tree, Expr) else list(program_or_tree)
+        off = len(self.dense_params)
+        self.dense_params += expr_block(program)
+        return self._term(COST_EXPRESSION, r if role is None else role, player, arg,
+                          (dims[0], dims[1] if len(dims) > 1 else -1, -1, -1), weight, value, 0, off)
+
     @property
     def num_constraints(self):
         return self._num_constraints
@@ -422,6 +489,9 @@ class ProblemSpec:
             if t["kind"] in (CONSTRAINT_AFFINE_SCALAR, CONSTRAINT_AFFINE_VECTOR):  # its coefficient block, by content
                 dim = self.n if t["arg"] < 0 else self.udims[t["arg"]]
                 cnt = dim + 1 if t["kind"] == CONSTRAINT_AFFINE_SCALAR else dim * dim + dim
+                poly = tuple(f32(v) for v in self.dense_params[t["polyline"]:t["polyline"] + cnt])
+            elif t["kind"] == COST_EXPRESSION:  # its program, by content
+                cnt = 1 + 2 * int(self.dense_params[t["polyline"]])
                 poly = tuple(f32(v) for v in self.dense_params[t["polyline"]:t["polyline"] + cnt])
             else:
                 poly = tuple((float('%.6g' % x), float('%.6g' % y)) for x, y in self.polylines[t["polyline"]]) \

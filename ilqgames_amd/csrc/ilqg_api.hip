@@ -263,7 +263,8 @@ __device__ __forceinline__ QuadArgs<T> quad_args_of(const DevProblem& p, const Q
 
 // Linearise / quadraticise / cost stage on its own (ilqg_rows.hpp): grid = (ceil(T / cw), B), one wavefront takes cw
 // consecutive rows of one instance.
-template <typename T, int NX, int NP, int MU>
+// EXPR: the interpreter that also evaluates expression costs (ProgDynamicExpr, ilqg_rows.hpp), for the problems that hold one
+template <typename T, int NX, int NP, int MU, bool EXPR = false>
 __global__ void __launch_bounds__(64) rows_kernel(DevProblem p, QuadBatchArgs<T> g, int cw) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const size_t b = blockIdx.y;
@@ -273,7 +274,8 @@ __global__ void __launch_bounds__(64) rows_kernel(DevProblem p, QuadBatchArgs<T>
   const QuadArgs<T> a = quad_args_of<T>(p, g, b);
   const int k0 = int(blockIdx.x) * cw;
   const int nrows = p.T - k0 < cw ? p.T - k0 : cw;
-  rows_chunk<T, NX, NP * MU, NP>(p, maps, a, k0, nrows, cw, sm, int(threadIdx.x));
+  rows_chunk<T, NX, NP * MU, NP, false, false, typename std::conditional<EXPR, ProgDynamicExpr, ProgDynamic>::type>(
+      p, maps, a, k0, nrows, cw, sm, int(threadIdx.x));
 }
 
 // ilqg_solve_state_batch: the loop state of every instance out of the workspace
@@ -834,7 +836,8 @@ struct __attribute__((visibility("hidden"))) DimsLaunch {
                            void* total_costs, int32_t* iters, int32_t* status, int32_t* converged, void* workspace,
                            const ilqg_solve_options& opt, hipStream_t stream);
   // pointers in QuadBatchArgs' order: xs us lambdas mu t_extreme A Bm Q l R r merit_part cost_part active
-  static ilqg_status rows(const DevProblem& d, int32_t batch, const void* const* ptrs, hipStream_t stream);
+  // expr: the problem holds an expression cost (ilqg_problem::has_expression)
+  static ilqg_status rows(const DevProblem& d, int32_t batch, const void* const* ptrs, bool expr, hipStream_t stream);
   // the sweep of a run-time-dimensioned solve whose game is embedded in this shape (padded_lq_kernel);
   // pad_elems_out != nullptr: only report the scratch elements one instance needs
   static ilqg_status lq_padded(const DevProblem& d, const void* solve_args, const PairTable& ptp, void* pad,
@@ -847,14 +850,14 @@ struct __attribute__((visibility("hidden"))) DimsLaunch {
 };
 
 template <typename T, int NX, int NP, int MU>
-ilqg_status DimsLaunch<T, NX, NP, MU>::rows(const DevProblem& d, int32_t batch, const void* const* q,
+ilqg_status DimsLaunch<T, NX, NP, MU>::rows(const DevProblem& d, int32_t batch, const void* const* q, bool expr,
                                             hipStream_t stream) {
   const QuadBatchArgs<T> g{(const T*)q[0], (const T*)q[1], (const T*)q[2], (const T*)q[3], (const int*)q[4], (T*)q[5],
                            (T*)q[6], (T*)q[7], (T*)q[8], (T*)q[9], (T*)q[10], (T*)q[11], (T*)q[12], (const int*)q[13]};
   // the widest chunk that leaves a CU three workgroups of this kernel
   const int cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), size_t(48) * 1024);
   const size_t lds = rows_maps_bytes(d) + rows_lds_elems(d.n, d.m, d.rp_pslots, d.rp_lslots, cw) * sizeof(T);
-  auto kern = rows_kernel<T, NX, NP, MU>;
+  auto kern = expr ? rows_kernel<T, NX, NP, MU, true> : rows_kernel<T, NX, NP, MU>;
   raise_lds_limit((const void*)kern, lds);
   hipLaunchKernelGGL(kern, dim3((d.T + cw - 1) / cw, batch), dim3(64), lds, stream, d, g, cw);
   HIP_TRY(hipGetLastError());
@@ -1537,7 +1540,11 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   }
   // (a problem with per-instance tables bound runs fused kernels of its own, here and below: ilqg_solve.hpp)
   const bool bound = p->bindings.any();
+  // (... and so does a problem that holds an expression cost: the interpreter with the evaluator in it, kExprProg — in
+  // the fused kernel, the split row kernel and the merit-only one; it matches no registered structure)
+  const bool expr = p->has_expression;
   auto k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
+  if (expr) k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, kExprProg, true> : ilq_trial_kernel<T, NX, NP, MU, W, kExprProg, false>;
   const bool pw = C::USE_MFMA && !open_loop;  // one wave per player (MFMA feedback sweep)
   // Compact rows (ilqg_common.hpp) between the row stage and the sweep: the one-tile player-parallel sweep and the
   // open-loop sweep read them; the other sweeps take the dense arrays.  What the row stage writes and the sweep reads
@@ -1553,8 +1560,8 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   // in the merit-only row kernel of the speculative line search.  Same results, bit for bit.
   int static_id = 0;    // the structure the split / probing row kernels are compiled for (0: they interpret)
   int static_prog = 0;  // ... and the fused kernel
-  auto k_rows = ilq_rows_kernel<T, NX, NP, MU>;
-  auto k_prows = ilq_probe_rows_kernel<T, NX, NP, MU>;
+  auto k_rows = expr ? ilq_rows_kernel<T, NX, NP, MU, kExprProg> : ilq_rows_kernel<T, NX, NP, MU>;
+  auto k_prows = expr ? ilq_probe_rows_kernel<T, NX, NP, MU, kExprProg> : ilq_probe_rows_kernel<T, NX, NP, MU>;
   // (the static kernels exist for solves on compact rows: they write nothing dense)
   const bool will_compact = (pw && C::MFMA_ONE_TILE && compact_on) || ol_compact;
   bool static_in_regs = false;  // ... with the slots of a chunk in registers (ilqg_rows.hpp: no row scratch in LDS)
@@ -1811,10 +1818,10 @@ static ilqg_status launch_linquad(const ilqg_problem* p, const DevProblem& d, in
                                   const int32_t* active, void* stream) {
   const void* const ptrs[14] = {xs, us, lambdas, mu, t_extreme, A, Bm, Q, l, R, r, merit_part, cost_part, active};
   if (p->generic)  // the row stage with run-time dimensions (rows_chunk<T, 0, 0, 0>)
-    return p->desc.dtype == ILQG_F32 ? DimsLaunch<float, 0, 0, 0>::rows(d, batch, ptrs, (hipStream_t)stream)
-                                     : DimsLaunch<double, 0, 0, 0>::rows(d, batch, ptrs, (hipStream_t)stream);
+    return p->desc.dtype == ILQG_F32 ? DimsLaunch<float, 0, 0, 0>::rows(d, batch, ptrs, p->has_expression, (hipStream_t)stream)
+                                     : DimsLaunch<double, 0, 0, 0>::rows(d, batch, ptrs, p->has_expression, (hipStream_t)stream);
   if (const ShapeEntry* e = find_shape(d.n, d.N, p->mu_uniform))
-    return e->rows[dtype_index(p->desc.dtype)](d, batch, ptrs, (hipStream_t)stream);
+    return e->rows[dtype_index(p->desc.dtype)](d, batch, ptrs, p->has_expression, (hipStream_t)stream);
   return fail(ILQG_ERR_UNSUPPORTED, "no device kernel instantiated for this problem's dimensions");
 }
 
@@ -1870,10 +1877,10 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
   // candidate: the probing rollout has a single form, so "fat" is the same kernel.
   RoundPlan<T> plan;
   plan.roll = {ilq_roll_kernel<T, 0, 0, 0>, 64, lds_roll};
-  plan.rows = {ilq_rows_kernel<T, 0, 0, 0>, 64, lds_rows};
+  plan.rows = {p->has_expression ? ilq_rows_kernel<T, 0, 0, 0, kExprProg> : ilq_rows_kernel<T, 0, 0, 0>, 64, lds_rows};
   plan.decide = {ilq_decide_kernel<T, 0, 0, 0>, 64, trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw)};
   plan.proll = plan.proll_fat = {ilq_probe_roll_kernel<T, 0, 0, 0>, 64, lds_roll};
-  plan.prows = {ilq_probe_rows_kernel<T, 0, 0, 0>, 64, rows_maps_bytes(d) + probe_rows_elems(d, 0, sa.rows_cw) * sizeof(T)};
+  plan.prows = {p->has_expression ? ilq_probe_rows_kernel<T, 0, 0, 0, kExprProg> : ilq_probe_rows_kernel<T, 0, 0, 0>, 64, rows_maps_bytes(d) + probe_rows_elems(d, 0, sa.rows_cw) * sizeof(T)};
   plan.sweep = {gen_lq_kernel<T>, kGenSweepThreads, lds_lq};
   plan.exit = {ilq_exit_kernel<T, 0, 0, 0>, 64, quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T)};
   plan.exit_fill_first = true; plan.read_restarts = sa.al_mode != 0;
@@ -2164,6 +2171,20 @@ ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words
   ProblemTables tables;
   const ilqg_status s = build_problem_tables(*desc, &tables);
   return s != ILQG_OK ? s : copy_row_program(tables.row_prog, tables.static_prog, words_out, capacity, num_words, static_id);
+}
+
+// The host half of creation up to the term table, then the checks of one expression cost (check_expression_term)
+ilqg_status ilqg_expression_check(const ilqg_problem_desc* desc, int32_t term) {
+  if (!desc) return fail(ILQG_ERR_INVALID, "null argument");
+  if (term < 0 || term >= desc->num_terms || !desc->terms)
+    return fail(ILQG_ERR_INVALID, "ilqg_expression_check: term index out of range (the problem has " + std::to_string(desc->num_terms) + " terms)");
+  if (desc->terms[term].kind != ILQG_COST_EXPRESSION)
+    return fail(ILQG_ERR_INVALID, "ilqg_expression_check: term " + std::to_string(term) + " is not an ILQG_COST_EXPRESSION term");
+  ProblemTables tables;
+  using Step = ilqg_status (*)(const ilqg_problem_desc&, ProblemTables*);
+  for (Step step : {check_problem_sizes, flatten_subsystems, build_term_table})
+    if (ilqg_status s = step(*desc, &tables)) return s;
+  return check_expression_term(*desc, term, tables.terms[term].arg_dim);
 }
 
 // The host half of creation alone, for what the feedback sweep may assume about B (ProblemTables::b_constant)

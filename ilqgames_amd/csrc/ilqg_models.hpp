@@ -8,6 +8,9 @@
 
 #include "ilqg_common.hpp"
 #include "ilqg_trig.hpp"
+// an expression cost's SIN / COS on the device: the rollout's pair (ilqg_expr.hpp takes the C library's anywhere else)
+#define ILQG_EXPR_SINCOS(x, s, c) ::ilqg::fast_sincos(x, s, c)
+#include "ilqg_expr.hpp"
 
 namespace ilqg {
 
@@ -507,7 +510,8 @@ struct QuadTables {
   // The per-step nominals of the time-dependent costs (DevProblem::time_nominal of this precision), [table][T][2].
   const double* tnom;
   int tnom_T;
-  const T* dense = nullptr;  // coefficient blocks of the affine constraints (DevProblem::dense_f / dense_d)
+  const T* dense = nullptr;  // coefficient blocks of the affine constraints and programs of the expression costs
+                             // (DevProblem::dense_f / dense_d)
 };
 __host__ __device__ inline bool term_is_affine(int kind) {
   return kind == ILQG_CONSTRAINT_AFFINE_SCALAR || kind == ILQG_CONSTRAINT_AFFINE_VECTOR;
@@ -776,6 +780,8 @@ __device__ __forceinline__ T term_evaluate_leaf_of(const QuadTables<T>& tb, cons
     case ILQG_CONSTRAINT_AFFINE_SCALAR:
     case ILQG_CONSTRAINT_AFFINE_VECTOR:
       return tb.dense ? affine_evaluate<T, V>(c.kind, tb.dense + c.polyline, v, dim) : T(0);
+    case ILQG_COST_EXPRESSION:  // ilqg_expr.hpp: the program's value alone
+      return tb.dense ? expr_eval_value<T>(tb.dense + c.polyline, w, val, v[c.idx[0]], c.idx[1] >= 0 ? v[c.idx[1]] : T(0)) : T(0);
   }
   return T(0);
 }

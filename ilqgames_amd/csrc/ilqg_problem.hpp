@@ -126,6 +126,7 @@ struct ilqg_problem {
   bool counters_clean = false;  // d_unfinished was cleared by the last thing that touched it (read_round_counters)
   int mu_uniform = 0;
   bool has_route_progress = false;  // a RouteProgressCost term: its tables are a first solve's (initial time 0)
+  bool has_expression = false;  // an expression cost: the row kernels with its evaluator in them run (kExprProg, ilqg_solve.hpp)
   int last_schedule = 0;  // ILQG_SCHEDULE_* of the last solve (ilqg_problem_last_schedule)
   bool generic = false;  // no specialised instantiation holds this problem: every entry point runs the run-time-dimensioned kernels
   // The solver object's LoopTimer over its iterations, kept across solves as the reference's member is (only solves with a
@@ -194,6 +195,7 @@ struct ProblemTables {
   bool b_constant = false;  // B is constant entries, at most one per row and column, and the solves read compact rows
                             // (RowProgramHost::b_constant on a specialised instantiation): ilqg_sweep_b_structure_build
   bool has_route_progress = false;
+  bool has_expression = false;  // an expression cost (build_expression_blocks)
   bool generic = false;  // no specialised instantiation holds the problem
 };
 
@@ -344,6 +346,65 @@ ilqg_status build_affine_blocks(const ilqg_problem_desc& desc, ProblemTables* t)
   return ILQG_OK;
 }
 
+// What creation checks about one ILQG_COST_EXPRESSION term (ilqg.h; the program's own rules: expr_validate,
+// ilqg_expr.hpp).  arg_dim: the length of the term's argument vector.
+ilqg_status check_expression_term(const ilqg_problem_desc& desc, int ti, int arg_dim) {
+  const ilqg_cost_term& c = desc.terms[ti];
+  const std::string where = "expression term " + std::to_string(ti) + ": ";
+  if (c.role == ILQG_ROLE_STATE_CONSTRAINT || c.role == ILQG_ROLE_CONTROL_CONSTRAINT)
+    return fail(ILQG_ERR_UNSUPPORTED, where + "an expression is a cost: a constraint role is not supported");
+  bool child = c.role == ILQG_ROLE_CHILD;
+  for (int q = 0; q < desc.num_terms; q++)
+    if (desc.terms[q].kind == ILQG_COST_EXTREME_VALUE && ti >= desc.terms[q].child_begin &&
+        ti < desc.terms[q].child_begin + desc.terms[q].child_count)
+      child = true;
+  if (child) return fail(ILQG_ERR_UNSUPPORTED, where + "an expression cannot be an EXTREME_VALUE child");
+  if (c.role != ILQG_ROLE_STATE_COST && c.role != ILQG_ROLE_CONTROL_COST)
+    return fail(ILQG_ERR_INVALID, where + "its role must be a top-level state or control cost");
+  if (c.idx[0] < 0 || c.idx[0] >= arg_dim)
+    return fail(ILQG_ERR_INVALID, where + "idx[0] = " + std::to_string(c.idx[0]) + " is outside its argument vector (dimension " +
+                                      std::to_string(arg_dim) + ")");
+  if (c.idx[1] != -1 && (c.idx[1] < 0 || c.idx[1] >= arg_dim))
+    return fail(ILQG_ERR_INVALID, where + "idx[1] = " + std::to_string(c.idx[1]) + " is neither -1 nor inside its argument "
+                                      "vector (dimension " + std::to_string(arg_dim) + ")");
+  if (c.idx[1] == c.idx[0]) return fail(ILQG_ERR_INVALID, where + "idx[0] and idx[1] name the same entry");
+  if (desc.dense_params == nullptr || c.polyline < 0 || c.polyline >= desc.num_dense_params)
+    return fail(ILQG_ERR_INVALID, where + "its program block is out of range of ilqg_problem_desc::dense_params");
+  const ExprCheck chk = expr_validate(desc.dense_params + c.polyline, (long long)desc.num_dense_params - c.polyline, c.idx[1] >= 0);
+  const std::string at = where + "op " + std::to_string(chk.op) + ": ";
+  switch (chk.fault) {
+    case EXPR_OK: return ILQG_OK;
+    case EXPR_BAD_LENGTH:
+      return fail(ILQG_ERR_INVALID, where + "program length L must be a whole number in 1 .. " + std::to_string(ILQG_EXPR_MAX_OPS));
+    case EXPR_OUT_OF_RANGE:
+      return fail(ILQG_ERR_INVALID, where + "its program block is out of range of ilqg_problem_desc::dense_params");
+    case EXPR_BAD_OPCODE: return fail(ILQG_ERR_UNSUPPORTED, at + "unknown opcode");
+    case EXPR_UNDERFLOW: return fail(ILQG_ERR_INVALID, at + "stack underflow");
+    case EXPR_OVERFLOW:
+      return fail(ILQG_ERR_UNSUPPORTED, at + "stack overflow (more than " + std::to_string(ILQG_EXPR_MAX_DEPTH) + " entries)");
+    case EXPR_NO_SECOND_INPUT: return fail(ILQG_ERR_INVALID, at + "PUSH_Y in a program without a second input (idx[1] = -1)");
+  }
+  return fail(ILQG_ERR_INVALID, where + "the program ends with " + std::to_string(chk.depth) + " entries on the stack: exactly "
+                                    "one, the term's value, must be left");
+}
+
+// Programs of the expression costs, behind the affine blocks in the same table (DevProblem::dense_f / dense_d): the
+// block's floats as they are, and as doubles; DevTerm::polyline of such a term becomes its block's offset
+ilqg_status build_expression_blocks(const ilqg_problem_desc& desc, ProblemTables* t) {
+  for (int ti = 0; ti < desc.num_terms; ti++) {
+    DevTerm& o = t->terms[ti];
+    if (o.kind != ILQG_COST_EXPRESSION) continue;
+    if (const ilqg_status s = check_expression_term(desc, ti, o.arg_dim)) return s;
+    t->has_expression = true;
+    const float* src = desc.dense_params + desc.terms[ti].polyline;
+    const int count = 1 + 2 * int(src[0]);
+    o.polyline = int(t->dense.f.size());
+    t->dense.f.insert(t->dense.f.end(), src, src + count);
+    t->dense.d.insert(t->dense.d.end(), src, src + count);
+  }
+  return ILQG_OK;
+}
+
 // The polylines, and the LineSegment2 objects of each (line_segment2.h:55-62) with its two shortcuts
 // (DevProblem::segs_f / segs_d), each precision from the points' floats in its own arithmetic
 ilqg_status build_segments(const ilqg_problem_desc& desc, ProblemTables* t) {
@@ -466,7 +527,7 @@ ilqg_status build_problem_tables(const ilqg_problem_desc& desc, ProblemTables* t
   *t = ProblemTables();
   using Step = ilqg_status (*)(const ilqg_problem_desc&, ProblemTables*);
   for (Step step : {check_problem_sizes, flatten_subsystems, build_pair_table, build_term_table, build_affine_blocks,
-                    build_segments, build_time_nominals, build_cost_order, build_row_program_and_match})
+                    build_expression_blocks, build_segments, build_time_nominals, build_cost_order, build_row_program_and_match})
     if (ilqg_status s = step(desc, t)) return s;
   return ILQG_OK;
 }
@@ -520,6 +581,7 @@ ilqg_status upload_problem(const ilqg_problem_desc& desc, const ProblemTables& t
   p->b_constant = t.b_constant;
   p->mu_uniform = t.mu_uniform;
   p->has_route_progress = t.has_route_progress;
+  p->has_expression = t.has_expression;
   p->generic = t.generic;
   p->tnom_tables = t.tnom_tables;
   // the row program's device image: the program, then per op the per-instance column of its weight / value (none: -1)

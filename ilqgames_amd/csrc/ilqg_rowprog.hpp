@@ -67,7 +67,7 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
         for (int i = 0; i < dim; i++) e->push_back({true, i, j});
       return;
     }
-    const int pat = term_pattern_of(c.kind, c.idx[0]);
+    const int pat = term_pattern_of(c.kind, c.idx[0], c.idx[1]);
     if (pat == PAT_SINGLE) {
       e->push_back({false, c.idx[0], 0});
       e->push_back({true, c.idx[0], c.idx[0]});
@@ -239,6 +239,7 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
     const int op_begin = int(ops.size()) / ROP_WORDS, li_begin = int(linit.size()) / RINIT_WORDS;
     const size_t sids_begin = sids.size();
     std::vector<int> scratch_slots;  // an affine vector constraint's temporaries
+    int expr_scratch = 0;  // an expression cost's stack (ilqg_expr.hpp): unnamed slots behind the pass's live ones
     int nl = 0;
     // sigma_u on the diagonal of every control block of this player (player_cost.cpp:70-74)
     for (int q = 0; q < pt.npairs; q++) {
@@ -345,8 +346,11 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
         } else {
           want_closest(c, c);
           const int b0 = leaf_sids(c, c);
-          emit_op(ROP_TERM, b0, int(sids.size()) - b0, 0, c, c, term_is_time_dependent(c.kind) ? c.polyline : 0,
-                  term_pattern_of(c.kind, c.idx[0]), ti);
+          // (an expression cost is a leaf like any other: its op carries the offset of its program in the dense table)
+          const bool expr = c.kind == ILQG_COST_EXPRESSION;
+          if (expr) expr_scratch = kExprStackScalars;
+          emit_op(ROP_TERM, b0, int(sids.size()) - b0, 0, c, c, (term_is_time_dependent(c.kind) || expr) ? c.polyline : 0,
+                  term_pattern_of(c.kind, c.idx[0], c.idx[1]), ti);
         }
       }
     if (!ok) { *err = "row program: a term's indices are out of range or not distinct"; return false; }
@@ -379,7 +383,10 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
       for (int o = 0; o < nl; o++)
         for (int q = 0; q < RINIT_WORDS; q++) linit[(size_t(li_begin) + perm[o]) * RINIT_WORDS + q] = li[size_t(o) * RINIT_WORDS + q];
     }
-    if (ng > max_gslots) max_gslots = ng;
+    // The stack of the pass's expression costs lies behind the slots an evaluation keeps live — all of them, or the
+    // gradient slots of a merit-only one — and has no ids: nothing initialises it, no output word reads it (so it keeps no
+    // problem off the compact rows), it only has to fit the scratch the chunk width is chosen for.
+    if (ng + expr_scratch > max_gslots) max_gslots = ng + expr_scratch;
     // what this pass writes: Q_i, l_i and the R / r blocks of this player's control pairs
     const int reg_begin = int(regions.size()) / RREG_WORDS;
     {
@@ -414,7 +421,7 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
     }
     passes.insert(passes.end(), {op_begin, int(ops.size()) / ROP_WORDS, reg_begin, int(regions.size()) / RREG_WORDS,
                                  li_begin, nl, RPASS_PLAYER, i, ng});
-    if (nl > max_lslots) max_lslots = nl;
+    if (nl + expr_scratch > max_lslots) max_lslots = nl + expr_scratch;
     collect_compact(reg_begin, nl);
   }
   if (NPS + max_lslots > 32000) { *err = "row program: too many slots"; return false; }

@@ -400,8 +400,10 @@ __device__ __forceinline__ void rows_affine(int kind, bool is_equality, const T*
 }
 
 // The scatter pattern a cost kind produces when it is active (term_compute_leaf), known without evaluating it.
-__host__ __device__ inline int term_pattern_of(int kind, int idx0) {
+// (idx1: an expression cost's second input, -1 for a one-input program; no other kind reads it)
+__host__ __device__ inline int term_pattern_of(int kind, int idx0, int idx1 = -1) {
   switch (kind) {
+    case ILQG_COST_EXPRESSION: return idx1 >= 0 ? PAT_PAIR2 : PAT_SINGLE;
     case ILQG_COST_QUADRATIC: return idx0 >= 0 ? PAT_SINGLE : PAT_ALL;
     case ILQG_COST_SEMIQUADRATIC:
     case ILQG_COST_ORIENTATION:
@@ -507,11 +509,16 @@ constexpr int kStaticRowStride = 65;
 // descriptor it has fetched; the straight-line code exists in a second form, ProgStatic<ID, true>, whose ops read the
 // column table — kernels of their own, launched for a problem with a table bound, so that the unbound kernels are the
 // code they always were.
-struct ProgDynamic { static constexpr bool STATIC = false; static constexpr bool kBound = true; };
+// ProgDynamicExpr: the interpreter with the evaluator of the expression costs (ilqg_expr.hpp) in it — kernels of their own,
+// launched for a problem that holds such a term, so that every other problem's kernels are the code they always were
+// (the evaluator's jets and the exp / log / sincos bodies inlined behind them cost the fp64 row kernels ~45 registers).
+struct ProgDynamic { static constexpr bool STATIC = false; static constexpr bool kBound = true; static constexpr bool kExpr = false; };
+struct ProgDynamicExpr { static constexpr bool STATIC = false; static constexpr bool kBound = true; static constexpr bool kExpr = true; };
 template <int ID> struct StaticRowProg;  // { static constexpr int kWords, w[kWords]; } per registered structure
 template <int ID, bool BOUND = false> struct ProgStatic {
   static constexpr bool STATIC = true;
   static constexpr bool kBound = BOUND;
+  static constexpr bool kExpr = false;  // no registered structure holds an expression cost
   typedef StaticRowProg<ID> S;
 };
 
@@ -884,7 +891,22 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
           tnom[0] = tn[0];
           tnom[1] = tn[1];
         }
-        term_compute_leaf<T, Arg, true>(QuadTables<T>{}, c, v, lambda, a.mu, &o, &cc, tnom);
+        bool is_expr = false;
+        if constexpr (PROG::kExpr) is_expr = c.kind == ILQG_COST_EXPRESSION;  // (ProgDynamicExpr: the launchers pick it)
+        if (is_expr) {
+          // ilqg_expr.hpp: the program in scalar memory (its block of the dense table), the stack's lower entries in this
+          // lane's column behind the slots this pass keeps live (build_row_program counts them in)
+          const typename ConstPtr<T>::type prog = (typename ConstPtr<T>::type)problem_dense<T>(p) + od.template param<RO_POLY_FIRST>();
+          const bool two = c.idx[1] >= 0;
+          ExprJet<T> j;
+          expr_eval_jet<T>(prog, T(c.weight), T(c.value), v[c.idx[0]], two ? v[c.idx[1]] : T(0), quad_out,
+                           ExprStack<T>{col + (NPS + li_live) * cws, cws}, &j);
+          o.pattern = two ? PAT_PAIR2 : PAT_SINGLE;
+          o.i0 = c.idx[0]; o.i1 = c.idx[1]; o.i2 = c.idx[2]; o.i3 = c.idx[3];
+          o.value = j.f; o.gx = j.fx; o.gy = j.fy; o.hxx = j.fxx; o.hyy = j.fyy; o.hxy = j.fxy;
+        } else {
+          term_compute_leaf<T, Arg, true>(QuadTables<T>{}, c, v, lambda, a.mu, &o, &cc, tnom);
+        }
 #if ILQG_PROFILE2
         ILQG_QPH(3);
 #endif

@@ -471,8 +471,13 @@ __device__ __forceinline__ QuadArgs<T> trial_quad_args(const DevProblem& p, cons
 // PROGID of the row kernels: 0 = the interpreter, k = the straight-line code of registered structure k, kBoundProg + k =
 // the same for a problem with per-instance parameters bound (ilqg_rows.hpp: ProgStatic<k, true>)
 constexpr int kBoundProg = 1000;
+// ... and kExprProg = the interpreter that also evaluates expression costs (ProgDynamicExpr, ilqg_rows.hpp): what the
+// launchers pick for a problem that holds one (ilqg_problem::has_expression)
+constexpr int kExprProg = -1;
+constexpr bool prog_is_static(int id) { return id > 0; }
 template <int ID> struct RowProgSel { typedef ProgStatic<(ID >= kBoundProg ? ID - kBoundProg : ID), (ID >= kBoundProg)> type; };
 template <> struct RowProgSel<0> { typedef ProgDynamic type; };
+template <> struct RowProgSel<kExprProg> { typedef ProgDynamicExpr type; };
 
 // Row kernel of the split pass: one chunk of rows of instance b, one wave with its own scratch.
 // PROGID: 0 = interpret the problem's row program; k = straight-line code for registered structure k (ilqg_rows.hpp)
@@ -872,7 +877,7 @@ __device__ __forceinline__ void roll_pair_instances(const DevProblem& p, const S
 // kernels' (`ilq_trial_kernel<double, NX, NP, MU, 2, progid>`) scratch figure did not grow and the VGPR count stays at
 // 256 or below; a shape with no spill in either form belongs in the list.
 __host__ __device__ constexpr bool fused_rollout_room(int elem_bytes, int nx, int np, int mu, int progid) {
-  return elem_bytes == 4 || (progid != 0 && nx == 14 && np == 3 && mu == 2);
+  return elem_bytes == 4 || (progid > 0 && nx == 14 && np == 3 && mu == 2);
 }
 
 // Which of the fused kernels with a register-held static row stage keep running reductions over partials in LDS
@@ -920,7 +925,7 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
 
   const size_t re = PHASE == TRIAL_DECIDE ? 0 : (rollout_lds_elems(n, m) + 3) & ~size_t(3);  // (trial_phase_lds_bytes)
-  const size_t qe = trial_phase_quad_elems<T>(p, PHASE, sa.rows_cw, PROGID != 0 && PHASE == TRIAL_FUSED);
+  const size_t qe = trial_phase_quad_elems<T>(p, PHASE, sa.rows_cw, prog_is_static(PROGID) && PHASE == TRIAL_FUSED);
   constexpr int RW = W > 1 ? W - 1 : 1;     // row waves: all but the integrating wave 0
   const int rwave = W > 1 ? wave - 1 : 0;   // this wave's row scratch (-1: wave 0 of a multi-wave workgroup has none)
   T* const sm_roll = sm;
@@ -985,7 +990,7 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
     // merit and cost partials in LDS as well; the row wave carries the sums over each chunk it has finished while the
     // rollout still integrates, and only the last chunk's rows are added behind it.  The other passes (Q_COSTS,
     // Q_INIT, Q_LIN: a few per solve) and every other kernel reduce from global memory as before.
-    constexpr bool LDS_RED = PHASE == TRIAL_FUSED && PROGID != 0 && W == 2 && fused_partials_room(int(sizeof(T)), NX, NP, MU) &&
+    constexpr bool LDS_RED = PHASE == TRIAL_FUSED && prog_is_static(PROGID) && W == 2 && fused_partials_room(int(sizeof(T)), NX, NP, MU) &&
                              ProgInRegisters<typename RowProgSel<PROGID>::type>::value && rows_state_in_registers(NX, NP * MU);
     const bool lds_red = LDS_RED && sa.lds_part != 0 && qmode == Q_TRIAL;
     if constexpr (PHASE == TRIAL_FUSED) {
@@ -1024,7 +1029,7 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
     // chunk that can only start when the rollout has ended: the integrating wave, idle from then on, takes one half of
     // its passes, the row wave the other — that chunk's time is what the launch ends with.
     typedef typename RowProgSel<PROGID>::type RowProg;
-    constexpr bool SHARE_LAST = PROGID != 0 && W == 2 && ProgInRegisters<RowProg>::value && rows_state_in_registers(NX, NP * MU);
+    constexpr bool SHARE_LAST = prog_is_static(PROGID) && W == 2 && ProgInRegisters<RowProg>::value && rows_state_in_registers(NX, NP * MU);
     if constexpr (SHARE_LAST) {
       const int cw = sa.rows_cw;
       const int nchunks = (Tn + cw - 1) / cw;
@@ -1068,7 +1073,7 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
         tl_stamp(sa.prof, b, 4 + 2 * (c < 3 ? c : 3), lane == 0);
         // (the register-held rows of the split kernels gain nothing for the interpreter here — measured, B = 1024: 1.45 ->
         // 1.435 M it/s; the static form reads its entries straight out of them)
-        rows_chunk<T, NX, NP * MU, NP, (PROGID != 0 && rows_state_in_registers(NX, NP * MU)), false, typename RowProgSel<PROGID>::type>(
+        rows_chunk<T, NX, NP * MU, NP, (prog_is_static(PROGID) && rows_state_in_registers(NX, NP * MU)), false, typename RowProgSel<PROGID>::type>(
             p, maps, qa, k0, nrows, cw, sm_quad, lane);
         tl_stamp(sa.prof, b, 5 + 2 * (c < 3 ? c : 3), lane == 0);
         if (kProfile && sa.prof) { tq0 = clock64(); qph[7] += 1; }

@@ -852,6 +852,82 @@ def three_unicycle_scene(T=40, dt=0.1, open_loop=False):
     return s
 
 
+EXPRESSION_BUMP_CENTRE = (0.5, -27.0)  # of expression_scene's bump (its C++ twin: tests/host/expression_scene.h)
+
+
+def expression_scene(T=100, dt=0.1):
+    """A test scene, NOT a reference example: the two crossing Car5D of the skeleton example (n = 10, the specialised
+    (10, 2, 2) kernels) with three user-defined costs (abi.COST_EXPRESSION) beside built-in ones — a Gaussian bump
+    w exp(-0.5 |p - c|^2 / v^2) on car 1's own position about a fixed centre (two inputs; weight and width are the
+    term's), a log barrier -w log(v - speed) on car 2's speed (one input) and a one-sided penalty w hinge(a - v)^2 on
+    car 2's acceleration (a control cost)."""
+    from .abi import Expr
+    prm = SolverParams.default()
+    prm.max_backtracking_steps = 100
+    prm.initial_alpha_scaling = 0.1
+    prm.convergence_tolerance = 0.01
+    prm.expected_decrease_fraction = 0.001
+    s = ProblemSpec(T, dt, prm)
+    for _ in range(2):
+        s.add_player(DYN_CAR_5D, 4.0)
+    X, Y, H, PHI, V = [0, 5], [1, 6], [2, 7], [3, 8], [4, 9]
+    for i in range(2):
+        s.quadratic(i, 25.0, 0, 0.0, control_of=i)  # omega
+        s.quadratic(i, 15.0, 1, 0.0, control_of=i)  # acceleration
+    s.quadratic(0, 10.0, V[0], 8.0)
+    s.quadratic(1, 10.0, V[1], 8.0)
+    lane1 = s.add_polyline([(0.0, -1000.0), (0.0, 1000.0)])
+    lane2 = s.add_polyline([(-5.0, 1000.0), (-5.0, 5.0), (0.0, 0.0), (995.0, 0.0)])
+    s.quadratic_polyline2(0, 25.0, lane1, (X[0], Y[0]))
+    s.quadratic_polyline2(1, 25.0, lane2, (X[1], Y[1]))
+    cx, cy = EXPRESSION_BUMP_CENTRE
+    bump = (((Expr.x() - cx).square() + (Expr.y() - cy).square()) * -0.5 / Expr.value().square()).exp() * Expr.weight()
+    s.name_term("p1_bump", s.expression(0, bump, (X[0], Y[0]), weight=30.0, value=2.0))
+    s.proximity(0, 50.0, (X[0], Y[0]), (X[1], Y[1]), 6.0)
+    s.name_term("p2_speed_barrier", s.expression(1, -(Expr.weight() * (Expr.value() - Expr.x()).log()), (V[1],),
+                                                  weight=2.0, value=15.0))
+    s.proximity(1, 50.0, (X[1], Y[1]), (X[0], Y[0]), 6.0)
+    s.name_term("p2_acceleration_cap", s.expression(1, Expr.weight() * (Expr.x() - Expr.value()).hinge().square(), (1,),
+                                                     weight=20.0, value=0.5, control_of=1))
+    f = np.float32
+    x0 = np.zeros(10)
+    x0[[X[0], Y[0], H[0], V[0]]] = [0.0, -30.0, float(f(np.pi / 2)), 4.0]
+    x0[[X[1], Y[1], H[1], V[1]]] = [-5.0, 30.0, float(f(-np.pi / 2)), 3.0]
+    s.x0 = x0
+    s.position_dims, s.heading_dims, s.speed_dims = list(zip(X, Y)), H, V
+    return s
+
+
+def expression_twin(spec):
+    """`spec` with every single-dimension QuadraticCost, every CurvatureCost and every SemiquadraticNormCost on a state
+    pair replaced by the abi.COST_EXPRESSION term that restates it — 0.5 w (x - v)^2, 0.5 w (x / y)^2,
+    0.5 w hinge(+-(sqrt(x^2 + y^2) - v))^2 — with the same weight, value, role, player and gate; every other term as it
+    is.  -> (the twin, the number of terms replaced)."""
+    import copy
+    from . import abi
+    from .abi import Expr
+    twin = copy.deepcopy(spec)
+    replaced = 0
+    for t in twin.terms:
+        x, y, w, v = Expr.x(), Expr.y(), Expr.weight(), Expr.value()
+        if t["role"] not in (abi.ROLE_STATE_COST, abi.ROLE_CONTROL_COST):
+            continue
+        if t["kind"] == abi.COST_QUADRATIC and t["idx"][0] >= 0:
+            tree, dims = 0.5 * w * (x - v).square(), (t["idx"][0], -1)
+        elif t["kind"] == abi.COST_CURVATURE:
+            tree, dims = 0.5 * w * (x / y).square(), (t["idx"][0], t["idx"][1])
+        elif t["kind"] == abi.COST_SEMIQUADRATIC_NORM and t["role"] == abi.ROLE_STATE_COST:
+            gap = (x.square() + y.square()).sqrt() - v
+            tree = 0.5 * w * (gap if t["flags"] & abi.FLAG_ORIENTED else -gap).hinge().square()
+            dims = (t["idx"][0], t["idx"][1])
+        else:
+            continue
+        t.update(kind=abi.COST_EXPRESSION, idx=(dims[0], dims[1], -1, -1), flags=0, polyline=len(twin.dense_params))
+        twin.dense_params += abi.expr_block(tree.program())
+        replaced += 1
+    return twin, replaced
+
+
 def jittered_x0(spec, batch, seed=0):
     """Per-instance initial states of SURVEY.md §8(d): U(-1,1) m on px,py, U(-0.1,0.1) rad
     heading, U(-0.5,0.5) m/s speed; instance b uses numpy default_rng(seed + b)."""

@@ -23,7 +23,7 @@ EXPORTS = [
     "ilqg_solution_splice_batch", "ilqg_solve_again_batch", "ilqg_strategy_costs_batch",
     "ilqg_check_local_nash_batch", "ilqg_check_sufficient_nash_batch",
     "ilqg_receding_horizon_shift_batch", "ilqg_default_solve_options", "ilqg_solve_batch_ex", "ilqg_solve_state_batch",
-    "ilqg_set_scratch", "ilqg_problem_last_schedule", "ilqg_copy_bandwidth", "ilqg_problem_row_program", "ilqg_row_program_build",
+    "ilqg_set_scratch", "ilqg_problem_last_schedule", "ilqg_copy_bandwidth", "ilqg_problem_row_program", "ilqg_row_program_build", "ilqg_expression_check",
     "ilqg_problem_declare_instance_params", "ilqg_problem_bind_instance_values", "ilqg_instance_params_check",
     "ilqg_problem_declare_instance_subsystem_params", "ilqg_instance_subsystem_params_check",
     "ilqg_problem_declare_instance_solver_params", "ilqg_instance_solver_params_check",
@@ -176,6 +176,14 @@ def row_program_build(spec, dtype=abi.F64):
     _check(lib().ilqg_row_program_build(C.byref(desc), w.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(sid)))
     del keep
     return w, int(sid.value)
+
+
+def expression_check(spec, term, dtype=abi.F64):
+    """ilqg_expression_check: raises IlqgError where Problem creation would refuse the expression cost with index
+    `term` — host only, no device needed."""
+    desc, keep = spec.build(dtype)
+    _check(lib().ilqg_expression_check(C.byref(desc), int(term)))
+    del keep
 
 
 def sweep_b_structure(spec, dtype=abi.F64):

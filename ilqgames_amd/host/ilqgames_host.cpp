@@ -282,6 +282,11 @@ bool WeightedConvexProximityCost::Describe(host::TermDescription* out) const {
   out->term.idx_extra[1] = vidx2_;
   return true;
 }
+bool ExpressionCost::Describe(host::TermDescription* out) const {
+  FillTerm(out, ILQG_COST_EXPRESSION, weight_, value_, 0, {x_idx_, y_idx_ < 0 ? -1 : y_idx_, -1, -1});
+  out->dense = block_;  // its program: `polyline` becomes the block's offset in the dense table
+  return true;
+}
 bool CurvatureCost::Describe(host::TermDescription* out) const {
   FillTerm(out, ILQG_COST_CURVATURE, weight_, 0.0f, 0, {omega_idx_, v_idx_});
   return true;

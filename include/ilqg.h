@@ -209,10 +209,31 @@ typedef enum {
    * `polyline` field is the offset of its block there. */
   ILQG_CONSTRAINT_AFFINE_SCALAR = 22, /* include/ilqgames/constraint/affine_scalar_constraint.h:54-100: g = a^T v - b;
                                         block [a (d) | b] */
-  ILQG_CONSTRAINT_AFFINE_VECTOR = 23  /* include/ilqgames/constraint/affine_vector_constraint.h:52-112: g = |A v - b| with
+  ILQG_CONSTRAINT_AFFINE_VECTOR = 23, /* include/ilqgames/constraint/affine_vector_constraint.h:52-112: g = |A v - b| with
                                         a square A; block [A (d x d, column-major) | b (d)]; derivatives as written
                                         there (its Hessian mixes A A^T and A^T A) */
+  /* A user-defined cost (the reference's way is a Cost subclass): a small postfix program over one or two entries of
+   * its argument vector, evaluated and differentiated to second order on the device (forward mode, ilqg_expr_op below).
+   * idx[0] = input x, idx[1] = input y or -1; `polyline` = offset of the program's block in
+   * ilqg_problem_desc::dense_params: [L, (opcode_0, imm_0), ..., (opcode_{L-1}, imm_{L-1})] as floats.  The program's
+   * result is the term's value: `weight` and `value` enter only where it pushes them.  Top-level state / control cost. */
+  ILQG_COST_EXPRESSION = 24
 } ilqg_cost_kind;
+
+/* The program of an ILQG_COST_EXPRESSION term: 1 <= L <= ILQG_EXPR_MAX_OPS ops on a stack that never holds more than
+ * ILQG_EXPR_MAX_DEPTH entries and exactly one at the end.  An entry is the jet (f, fx, fy, fxx, fyy, fxy) in the solve's
+ * scalar type.  Pushes: X (x,1,0,0,0,0), Y (y,0,1,0,0,0), CONST (imm), WEIGHT, VALUE (the term's, or the instance's).
+ * Binary ops take a (below) and b (top): ADD, SUB, MUL, DIV.  Unary ops replace the top: NEG, SQUARE, SQRT, EXP, LOG, SIN,
+ * COS, and HINGE — the entry itself where its f > 0 strictly, else all zeros (src/semiquadratic_cost.cpp's one-sided
+ * rule).  Every product and sum rounds on its own (no contraction); a NaN or Inf is the program's own. */
+typedef enum {
+  ILQG_EXPR_PUSH_X = 1, ILQG_EXPR_PUSH_Y = 2, ILQG_EXPR_PUSH_CONST = 3, ILQG_EXPR_PUSH_WEIGHT = 4, ILQG_EXPR_PUSH_VALUE = 5,
+  ILQG_EXPR_ADD = 6, ILQG_EXPR_SUB = 7, ILQG_EXPR_MUL = 8, ILQG_EXPR_DIV = 9,
+  ILQG_EXPR_NEG = 10, ILQG_EXPR_SQUARE = 11, ILQG_EXPR_SQRT = 12, ILQG_EXPR_EXP = 13, ILQG_EXPR_LOG = 14,
+  ILQG_EXPR_SIN = 15, ILQG_EXPR_COS = 16, ILQG_EXPR_HINGE = 17
+} ilqg_expr_op;
+#define ILQG_EXPR_MAX_OPS 64
+#define ILQG_EXPR_MAX_DEPTH 4
 
 /* Where a term sits inside PlayerCost::Quadraticize (src/player_cost.cpp:194-215):
  * state costs, control costs, state constraints, control constraints — in that
@@ -336,6 +357,7 @@ void ilqg_problem_destroy(ilqg_problem* p);
  *   WEIGHTED_CONVEX_PROXIMITY              yes      yes (threshold)
  *   ORIENTATION, QUADRATIC_NORM,
  *   SEMIQUADRATIC_NORM                     yes      yes
+ *   EXPRESSION                             yes      yes (what its program's PUSH_WEIGHT / PUSH_VALUE push)
  *   QUADRATIC_DIFFERENCE, CURVATURE,
  *   RELATIVE_DISTANCE                      yes      no  (has none)
  *   NOMINAL_PATH_LENGTH, ROUTE_PROGRESS    yes      no  (tabulated per step by ilqg_problem_create; per instance:
@@ -738,6 +760,10 @@ ilqg_status ilqg_problem_row_program(const ilqg_problem* p, int32_t* words_out, 
  * it uploads tables, without a device (the one entry point that works without one). */
 ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words_out, int32_t capacity, int32_t* num_words,
                                    int32_t* static_id);
+/* Host only, no device needed: everything ilqg_problem_create checks about the ILQG_COST_EXPRESSION term `term` of a
+ * description — its role and placement, its inputs, its block inside dense_params and the program in it (length, opcodes,
+ * stack depth).  A refusal names the term, and the op where one is at fault, in ilqg_last_error(). */
+ilqg_status ilqg_expression_check(const ilqg_problem_desc* desc, int32_t term);
 /* Host only, no device needed: what the feedback sweep may assume about B (sweep_forms).  *constant_out is 1 when the
  * problem's solves run on compact rows, every non-zero of B is a constant of the row program (no computed entry) and
  * every row and every column of B holds at most one of them.  entries_out (capacity int32 words; may be NULL to query
@@ -918,7 +944,9 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
                                  ilqg_time_nominal_table_build: four new calls); still 9:
                                  ILQG_SCHEDULE_CONSTANT_B and the host-only ilqg_sweep_b_structure_build (one new call); still 9:
                                  per-instance solver parameters (ilqg_solver_field, ilqg_problem_declare_instance_solver_params,
-                                 ilqg_instance_solver_params_check: two new calls, the table gains columns);
+                                 ilqg_instance_solver_params_check: two new calls, the table gains columns); still 9:
+                                 ILQG_COST_EXPRESSION (cost kind 24, ilqg_expr_op) and the host-only ilqg_expression_check
+                                 (one new call, no layout change);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;

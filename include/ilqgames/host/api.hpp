@@ -379,6 +379,88 @@ class CurvatureCost : public TimeInvariantCost {
   const Dimension omega_idx_, v_idx_;
 };
 
+// A user's own cost function (the reference's way is a Cost subclass, whose C++ cannot run on the device): a formula
+// over one or two entries of the cost's argument vector, written with host::Expr and evaluated — value, gradient and
+// Hessian, by second-order forward differentiation — on the device (ILQG_COST_EXPRESSION, include/ilqg.h).
+//   using namespace ilqgames::host;
+//   const Expr bump = Expr::Weight() * Exp(-0.5 * (Square(Expr::X() - 3.0) + Square(Expr::Y())) / Square(Expr::Value()));
+//   cost.AddStateCost(std::make_shared<ExpressionCost>(bump, kP1XIdx, kP1YIdx, /* weight */ 10.0, /* value */ 2.0));
+// Nothing is multiplied in implicitly: the weight and the value enter where the formula names them.
+namespace host {
+class Expr {
+ public:
+  Expr(double constant) : node_(std::make_shared<Node>(Node{ILQG_EXPR_PUSH_CONST, static_cast<float>(constant), nullptr, nullptr})) {}
+  static Expr X() { return Expr(ILQG_EXPR_PUSH_X, nullptr, nullptr); }
+  static Expr Y() { return Expr(ILQG_EXPR_PUSH_Y, nullptr, nullptr); }
+  static Expr Weight() { return Expr(ILQG_EXPR_PUSH_WEIGHT, nullptr, nullptr); }
+  static Expr Value() { return Expr(ILQG_EXPR_PUSH_VALUE, nullptr, nullptr); }
+  friend Expr operator+(const Expr& a, const Expr& b) { return Expr(ILQG_EXPR_ADD, a.node_, b.node_); }
+  friend Expr operator-(const Expr& a, const Expr& b) { return Expr(ILQG_EXPR_SUB, a.node_, b.node_); }
+  friend Expr operator*(const Expr& a, const Expr& b) { return Expr(ILQG_EXPR_MUL, a.node_, b.node_); }
+  friend Expr operator/(const Expr& a, const Expr& b) { return Expr(ILQG_EXPR_DIV, a.node_, b.node_); }
+  Expr operator-() const { return Unary(ILQG_EXPR_NEG, *this); }
+  static Expr Unary(int op, const Expr& a) { return Expr(op, a.node_, nullptr); }
+  bool UsesY() const { return Uses(*node_, ILQG_EXPR_PUSH_Y); }
+
+  // The postfix block [L, (opcode, imm) x L] of ilqg_problem_desc::dense_params, operands left to right.  CHECK-fails
+  // past ILQG_EXPR_MAX_OPS ops or ILQG_EXPR_MAX_DEPTH stack entries (re-associate the formula: a + (b + (c + (d + e)))
+  // needs five entries, (((a + b) + c) + d) + e two).
+  std::vector<float> Compile() const {
+    std::vector<float> block(1, 0.0f);
+    int depth = 0, max_depth = 0;
+    Emit(*node_, &block, &depth, &max_depth);
+    const int length = static_cast<int>(block.size() - 1) / 2;
+    CHECK_LE(length, ILQG_EXPR_MAX_OPS) << "ExpressionCost: the formula compiles to more than ILQG_EXPR_MAX_OPS operations";
+    CHECK_LE(max_depth, ILQG_EXPR_MAX_DEPTH) << "ExpressionCost: the formula needs more than ILQG_EXPR_MAX_DEPTH stack entries";
+    block[0] = static_cast<float>(length);
+    return block;
+  }
+
+ private:
+  struct Node {
+    int op;
+    float imm;
+    std::shared_ptr<const Node> a, b;
+  };
+  Expr(int op, std::shared_ptr<const Node> a, std::shared_ptr<const Node> b)
+      : node_(std::make_shared<Node>(Node{op, 0.0f, std::move(a), std::move(b)})) {}
+  static bool Uses(const Node& n, int op) { return n.op == op || (n.a && Uses(*n.a, op)) || (n.b && Uses(*n.b, op)); }
+  static void Emit(const Node& n, std::vector<float>* block, int* depth, int* max_depth) {
+    if (n.a) Emit(*n.a, block, depth, max_depth);
+    if (n.b) Emit(*n.b, block, depth, max_depth);
+    block->push_back(static_cast<float>(n.op));
+    block->push_back(n.imm);
+    *depth += n.a ? (n.b ? -1 : 0) : 1;
+    if (*depth > *max_depth) *max_depth = *depth;
+  }
+  std::shared_ptr<const Node> node_;
+};
+inline Expr Square(const Expr& a) { return Expr::Unary(ILQG_EXPR_SQUARE, a); }
+inline Expr Sqrt(const Expr& a) { return Expr::Unary(ILQG_EXPR_SQRT, a); }
+inline Expr Exp(const Expr& a) { return Expr::Unary(ILQG_EXPR_EXP, a); }
+inline Expr Log(const Expr& a) { return Expr::Unary(ILQG_EXPR_LOG, a); }
+inline Expr Sin(const Expr& a) { return Expr::Unary(ILQG_EXPR_SIN, a); }
+inline Expr Cos(const Expr& a) { return Expr::Unary(ILQG_EXPR_COS, a); }
+inline Expr Hinge(const Expr& a) { return Expr::Unary(ILQG_EXPR_HINGE, a); }  // a where a > 0, else 0
+}  // namespace host
+
+// `expr` over entry `x_idx` (Expr::X()) and, when the formula names it, entry `y_idx` (Expr::Y()) of the state — or of
+// the control vector the cost is added for; `weight` is Expr::Weight(), `value` Expr::Value().
+class ExpressionCost : public TimeInvariantCost {
+ public:
+  ExpressionCost(const host::Expr& expr, Dimension x_idx, Dimension y_idx = -1, float weight = 1.0, float value = 0.0,
+                 const std::string& name = "")
+      : TimeInvariantCost(weight, name), block_(expr.Compile()), x_idx_(x_idx), y_idx_(y_idx), value_(value) {
+    CHECK(y_idx >= 0 || !expr.UsesY()) << "ExpressionCost: the formula names Expr::Y() and the cost has no second dimension";
+  }
+  bool Describe(host::TermDescription* out) const override;
+
+ private:
+  const std::vector<float> block_;
+  const Dimension x_idx_, y_idx_;
+  const float value_;
+};
+
 // include/ilqgames/cost/nominal_path_length_cost.h:54-77 — 0.5 w (x[dim] - t nominal_speed)^2, t the time the solver
 // hands to the cost (relative to the start of the window, src/ilq_solver.cpp:186,236).
 class NominalPathLengthCost : public Cost {
