@@ -41,6 +41,8 @@ COST_WEIGHTED_CONVEX_PROXIMITY = 21  # idx = (x1, y1, x2, y2), idx_extra = (v1, 
 CONSTRAINT_AFFINE_SCALAR = 22  # g = a^T v - b over the whole argument vector; `polyline` = offset of [a | b] in dense_params
 CONSTRAINT_AFFINE_VECTOR = 23  # g = |A v - b|; `polyline` = offset of [A (column-major) | b]
 COST_EXPRESSION = 24  # a postfix program over idx[0] (x) and idx[1] (y, or -1); `polyline` = offset of [L, (op, imm) x L]
+#                       idx[2] / idx[3] >= 0: the inputs are the differences v[idx0] - v[idx2], v[idx1] - v[idx3]
+CONSTRAINT_EXPRESSION = 25  # the same program as a constraint g <= 0 (g = 0 with FLAG_EQUALITY)
 # ilqg_expr_op
 (EXPR_PUSH_X, EXPR_PUSH_Y, EXPR_PUSH_CONST, EXPR_PUSH_WEIGHT, EXPR_PUSH_VALUE, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_DIV,
  EXPR_NEG, EXPR_SQUARE, EXPR_SQRT, EXPR_EXP, EXPR_LOG, EXPR_SIN, EXPR_COS, EXPR_HINGE) = range(1, 18)
@@ -418,17 +420,34 @@ class ProblemSpec:
         return self._term(CONSTRAINT_AFFINE_VECTOR, role, player, arg, (0,), 1.0, 0.0,
                           FLAG_EQUALITY if is_equality else 0, off, constraint=True)
 
-    def expression(self, player, program_or_tree, dims, weight=1.0, value=0.0, control_of=None, role=None):
+    @staticmethod
+    def _expression_idx(dims, relative_to):
+        dims = tuple(dims)
+        rel = () if relative_to is None else tuple(relative_to)
+        return (dims[0], dims[1] if len(dims) > 1 else -1, rel[0] if len(rel) > 0 else -1, rel[1] if len(rel) > 1 else -1)
+
+    def expression(self, player, program_or_tree, dims, weight=1.0, value=0.0, control_of=None, role=None, relative_to=None):
         """An ILQG_COST_EXPRESSION term (include/ilqg.h): `program_or_tree` is an Expr or a postfix list [(opcode, imm), ...],
-        `dims` the one or two entries (x, y) of the state — or of the control vector of player `control_of` — it reads.
+        `dims` the one or two entries (x, y) of the state — or of the control vector of player `control_of` — it reads;
+        `relative_to`: as many entries again, the program's inputs are then the differences dims - relative_to.
         Nothing is checked here: the library refuses a malformed term (`role` overrides the role, for those tests)."""
         r, arg = (ROLE_STATE_COST, -1) if control_of is None else (ROLE_CONTROL_COST, control_of)
-        dims = tuple(dims)
         program = program_or_tree.program() if isinstance(program_or_tree, Expr) else list(program_or_tree)
         off = len(self.dense_params)
         self.dense_params += expr_block(program)
         return self._term(COST_EXPRESSION, r if role is None else role, player, arg,
-                          (dims[0], dims[1] if len(dims) > 1 else -1, -1, -1), weight, value, 0, off)
+                          self._expression_idx(dims, relative_to), weight, value, 0, off)
+
+    def expression_constraint(self, player, program_or_tree, dims, relative_to=None, weight=1.0, value=0.0, is_equality=False,
+                              control_of=None):
+        """An ILQG_CONSTRAINT_EXPRESSION term (include/ilqg.h): the program is g of the constraint g <= 0 (g = 0 with
+        `is_equality`) over `dims` (minus `relative_to`) of the state, or of the control vector of player `control_of`."""
+        role, arg = (ROLE_STATE_CONSTRAINT, -1) if control_of is None else (ROLE_CONTROL_CONSTRAINT, control_of)
+        program = program_or_tree.program() if isinstance(program_or_tree, Expr) else list(program_or_tree)
+        off = len(self.dense_params)
+        self.dense_params += expr_block(program)
+        return self._term(CONSTRAINT_EXPRESSION, role, player, arg, self._expression_idx(dims, relative_to), weight, value,
+                          FLAG_EQUALITY if is_equality else 0, off, constraint=True)
 
     @property
     def num_constraints(self):
@@ -490,7 +509,7 @@ class ProblemSpec:
                 dim = self.n if t["arg"] < 0 else self.udims[t["arg"]]
                 cnt = dim + 1 if t["kind"] == CONSTRAINT_AFFINE_SCALAR else dim * dim + dim
                 poly = tuple(f32(v) for v in self.dense_params[t["polyline"]:t["polyline"] + cnt])
-            elif t["kind"] == COST_EXPRESSION:  # its program, by content
+            elif t["kind"] in (COST_EXPRESSION, CONSTRAINT_EXPRESSION):  # its program, by content
                 cnt = 1 + 2 * int(self.dense_params[t["polyline"]])
                 poly = tuple(f32(v) for v in self.dense_params[t["polyline"]:t["polyline"] + cnt])
             else:

@@ -2173,12 +2173,13 @@ ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words
   return s != ILQG_OK ? s : copy_row_program(tables.row_prog, tables.static_prog, words_out, capacity, num_words, static_id);
 }
 
-// The host half of creation up to the term table, then the checks of one expression cost (check_expression_term)
+// The host half of creation up to the term table, then the checks of one expression cost or constraint
+// (check_expression_term)
 ilqg_status ilqg_expression_check(const ilqg_problem_desc* desc, int32_t term) {
   if (!desc) return fail(ILQG_ERR_INVALID, "null argument");
   if (term < 0 || term >= desc->num_terms || !desc->terms)
     return fail(ILQG_ERR_INVALID, "ilqg_expression_check: term index out of range (the problem has " + std::to_string(desc->num_terms) + " terms)");
-  if (desc->terms[term].kind != ILQG_COST_EXPRESSION)
+  if (!term_is_expression(desc->terms[term].kind))  // (either kind; the message is the one the first kind came with)
     return fail(ILQG_ERR_INVALID, "ilqg_expression_check: term " + std::to_string(term) + " is not an ILQG_COST_EXPRESSION term");
   ProblemTables tables;
   using Step = ilqg_status (*)(const ilqg_problem_desc&, ProblemTables*);

@@ -17,9 +17,10 @@ const char* cost_kind_name(int kind) {  // ilqg_cost_kind without its prefix
       "EXTREME_VALUE", "CONSTRAINT_PROXIMITY", "CONSTRAINT_SINGLE_DIMENSION", "POLYLINE2_SIGNED_DISTANCE",
       "QUADRATIC_DIFFERENCE", "ORIENTATION", "QUADRATIC_NORM", "SEMIQUADRATIC_NORM", "RELATIVE_DISTANCE",
       "LOCALLY_CONVEX_PROXIMITY", "CURVATURE", "CONSTRAINT_POLYLINE2_SIGNED_DISTANCE", "NOMINAL_PATH_LENGTH",
-      "ROUTE_PROGRESS", "WEIGHTED_CONVEX_PROXIMITY", "CONSTRAINT_AFFINE_SCALAR", "CONSTRAINT_AFFINE_VECTOR", "EXPRESSION"};
-  static_assert(ILQG_COST_QUADRATIC == 1 && ILQG_COST_EXPRESSION == sizeof(names) / sizeof(names[0]), "one name per kind");
-  return kind >= 1 && kind <= ILQG_COST_EXPRESSION ? names[kind - 1] : "unknown kind";
+      "ROUTE_PROGRESS", "WEIGHTED_CONVEX_PROXIMITY", "CONSTRAINT_AFFINE_SCALAR", "CONSTRAINT_AFFINE_VECTOR", "EXPRESSION",
+      "CONSTRAINT_EXPRESSION"};
+  static_assert(ILQG_COST_QUADRATIC == 1 && ILQG_CONSTRAINT_EXPRESSION == sizeof(names) / sizeof(names[0]), "one name per kind");
+  return kind >= 1 && kind <= ILQG_CONSTRAINT_EXPRESSION ? names[kind - 1] : "unknown kind";
 }
 // Does a term of this kind read the field (the table of ilqg.h; ilqg_models.hpp: term_evaluate_leaf_of and the row ops)?
 // Null: yes; else why not.
@@ -50,7 +51,8 @@ const char* instance_param_refusal(int kind, int field) {
     case ILQG_COST_SEMIQUADRATIC_NORM:
     case ILQG_COST_LOCALLY_CONVEX_PROXIMITY:
     case ILQG_COST_WEIGHTED_CONVEX_PROXIMITY:
-    case ILQG_COST_EXPRESSION: return nullptr;  // (what its program pushes: PUSH_WEIGHT, PUSH_VALUE)
+    case ILQG_COST_EXPRESSION:
+    case ILQG_CONSTRAINT_EXPRESSION: return nullptr;  // (what its program pushes: PUSH_WEIGHT, PUSH_VALUE)
   }
   return "unknown cost kind";
 }

@@ -516,6 +516,10 @@ struct QuadTables {
 __host__ __device__ inline bool term_is_affine(int kind) {
   return kind == ILQG_CONSTRAINT_AFFINE_SCALAR || kind == ILQG_CONSTRAINT_AFFINE_VECTOR;
 }
+// the two kinds whose function is a program in the dense table (ilqg_expr.hpp)
+__host__ __device__ inline bool term_is_expression(int kind) {
+  return kind == ILQG_COST_EXPRESSION || kind == ILQG_CONSTRAINT_EXPRESSION;
+}
 // Constraint::Mu(lambda, g) (constraint.h:112-117): the inactive-inequality gate; an equality constraint has none
 template <typename T>
 __device__ __forceinline__ T constraint_mu(T lambda, T g, T mu, bool is_equality) {
@@ -781,7 +785,15 @@ __device__ __forceinline__ T term_evaluate_leaf_of(const QuadTables<T>& tb, cons
     case ILQG_CONSTRAINT_AFFINE_VECTOR:
       return tb.dense ? affine_evaluate<T, V>(c.kind, tb.dense + c.polyline, v, dim) : T(0);
     case ILQG_COST_EXPRESSION:  // ilqg_expr.hpp: the program's value alone
-      return tb.dense ? expr_eval_value<T>(tb.dense + c.polyline, w, val, v[c.idx[0]], c.idx[1] >= 0 ? v[c.idx[1]] : T(0)) : T(0);
+    case ILQG_CONSTRAINT_EXPRESSION: {
+      if (!tb.dense) return T(0);
+      T x = v[c.idx[0]], y = c.idx[1] >= 0 ? v[c.idx[1]] : T(0);
+      if (c.idx[2] >= 0) {  // relative inputs: one rounded difference each, as ProximityCost forms its own
+        x = x - v[c.idx[2]];
+        if (c.idx[3] >= 0) y = y - v[c.idx[3]];
+      }
+      return expr_eval_value<T>(tb.dense + c.polyline, w, val, x, y);
+    }
   }
   return T(0);
 }

@@ -300,7 +300,9 @@ ilqg_status build_term_table(const ilqg_problem_desc& desc, ProblemTables* t) {
     }
     // Constraint::is_equality_ is only carried for the affine constraints (ilqg.h): on any other kind the multiplier
     // update would drop its clip at zero while the mu gate stayed an inequality's
-    if ((c.flags & ILQG_FLAG_EQUALITY) && c.kind != ILQG_CONSTRAINT_AFFINE_SCALAR && c.kind != ILQG_CONSTRAINT_AFFINE_VECTOR)
+    // (... and for the expression constraint, whose row op takes the same equality-aware gate)
+    if ((c.flags & ILQG_FLAG_EQUALITY) && c.kind != ILQG_CONSTRAINT_AFFINE_SCALAR && c.kind != ILQG_CONSTRAINT_AFFINE_VECTOR &&
+        c.kind != ILQG_CONSTRAINT_EXPRESSION)
       return fail(ILQG_ERR_INVALID, "ILQG_FLAG_EQUALITY is only defined for the affine constraints");
     if (c.constraint_slot >= 0 && c.constraint_slot + 1 > nc) nc = c.constraint_slot + 1;
     const bool on_state = o.role == ILQG_ROLE_STATE_COST || o.role == ILQG_ROLE_STATE_CONSTRAINT || o.role == ILQG_ROLE_CHILD;
@@ -346,21 +348,40 @@ ilqg_status build_affine_blocks(const ilqg_problem_desc& desc, ProblemTables* t)
   return ILQG_OK;
 }
 
-// What creation checks about one ILQG_COST_EXPRESSION term (ilqg.h; the program's own rules: expr_validate,
-// ilqg_expr.hpp).  arg_dim: the length of the term's argument vector.
+// What creation checks about one ILQG_COST_EXPRESSION / ILQG_CONSTRAINT_EXPRESSION term (ilqg.h; the program's own
+// rules: expr_validate, ilqg_expr.hpp).  arg_dim: the length of the term's argument vector.
 ilqg_status check_expression_term(const ilqg_problem_desc& desc, int ti, int arg_dim) {
   const ilqg_cost_term& c = desc.terms[ti];
   const std::string where = "expression term " + std::to_string(ti) + ": ";
-  if (c.role == ILQG_ROLE_STATE_CONSTRAINT || c.role == ILQG_ROLE_CONTROL_CONSTRAINT)
-    return fail(ILQG_ERR_UNSUPPORTED, where + "an expression is a cost: a constraint role is not supported");
-  bool child = c.role == ILQG_ROLE_CHILD;
-  for (int q = 0; q < desc.num_terms; q++)
-    if (desc.terms[q].kind == ILQG_COST_EXTREME_VALUE && ti >= desc.terms[q].child_begin &&
-        ti < desc.terms[q].child_begin + desc.terms[q].child_count)
-      child = true;
-  if (child) return fail(ILQG_ERR_UNSUPPORTED, where + "an expression cannot be an EXTREME_VALUE child");
-  if (c.role != ILQG_ROLE_STATE_COST && c.role != ILQG_ROLE_CONTROL_COST)
-    return fail(ILQG_ERR_INVALID, where + "its role must be a top-level state or control cost");
+  const bool constraint_role = c.role == ILQG_ROLE_STATE_CONSTRAINT || c.role == ILQG_ROLE_CONTROL_CONSTRAINT;
+  if (c.kind == ILQG_CONSTRAINT_EXPRESSION) {
+    bool child = c.role == ILQG_ROLE_CHILD;
+    for (int q = 0; q < desc.num_terms; q++)
+      if (desc.terms[q].kind == ILQG_COST_EXTREME_VALUE && ti >= desc.terms[q].child_begin &&
+          ti < desc.terms[q].child_begin + desc.terms[q].child_count)
+        child = true;
+    if (child) return fail(ILQG_ERR_INVALID, where + "an expression constraint cannot be an EXTREME_VALUE child");
+    if (!constraint_role)
+      return fail(ILQG_ERR_INVALID, where + "an expression constraint's role must be a state or control constraint");
+    if (c.constraint_slot < 0)
+      return fail(ILQG_ERR_INVALID, where + "constraint_slot = " + std::to_string(c.constraint_slot) + ": an expression "
+                                        "constraint needs a multiplier slot of its own");
+    for (int q = 0; q < desc.num_terms; q++)
+      if (q != ti && desc.terms[q].constraint_slot == c.constraint_slot)
+        return fail(ILQG_ERR_INVALID, where + "constraint_slot = " + std::to_string(c.constraint_slot) + " is also term " +
+                                          std::to_string(q) + "'s");
+  } else {
+    if (constraint_role)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "an expression is a cost: a constraint role is not supported");
+    bool child = c.role == ILQG_ROLE_CHILD;
+    for (int q = 0; q < desc.num_terms; q++)
+      if (desc.terms[q].kind == ILQG_COST_EXTREME_VALUE && ti >= desc.terms[q].child_begin &&
+          ti < desc.terms[q].child_begin + desc.terms[q].child_count)
+        child = true;
+    if (child) return fail(ILQG_ERR_UNSUPPORTED, where + "an expression cannot be an EXTREME_VALUE child");
+    if (c.role != ILQG_ROLE_STATE_COST && c.role != ILQG_ROLE_CONTROL_COST)
+      return fail(ILQG_ERR_INVALID, where + "its role must be a top-level state or control cost");
+  }
   if (c.idx[0] < 0 || c.idx[0] >= arg_dim)
     return fail(ILQG_ERR_INVALID, where + "idx[0] = " + std::to_string(c.idx[0]) + " is outside its argument vector (dimension " +
                                       std::to_string(arg_dim) + ")");
@@ -368,6 +389,23 @@ ilqg_status check_expression_term(const ilqg_problem_desc& desc, int ti, int arg
     return fail(ILQG_ERR_INVALID, where + "idx[1] = " + std::to_string(c.idx[1]) + " is neither -1 nor inside its argument "
                                       "vector (dimension " + std::to_string(arg_dim) + ")");
   if (c.idx[1] == c.idx[0]) return fail(ILQG_ERR_INVALID, where + "idx[0] and idx[1] name the same entry");
+  // relative inputs: X = v[idx[0]] - v[idx[2]], Y = v[idx[1]] - v[idx[3]]
+  for (int k = 2; k < 4; k++)
+    if (c.idx[k] != -1 && (c.idx[k] < 0 || c.idx[k] >= arg_dim))
+      return fail(ILQG_ERR_INVALID, where + "idx[" + std::to_string(k) + "] = " + std::to_string(c.idx[k]) + " is neither -1 nor "
+                                        "inside its argument vector (dimension " + std::to_string(arg_dim) + ")");
+  if (c.idx[3] >= 0 && c.idx[2] < 0)
+    return fail(ILQG_ERR_INVALID, where + "idx[3] = " + std::to_string(c.idx[3]) + " without idx[2]: a relative term names the "
+                                      "partner of its first input");
+  if (c.idx[3] >= 0 && c.idx[1] < 0)
+    return fail(ILQG_ERR_INVALID, where + "idx[3] = " + std::to_string(c.idx[3]) + " on a one-input term (idx[1] = -1)");
+  if (c.idx[2] >= 0 && c.idx[1] >= 0 && c.idx[3] < 0)
+    return fail(ILQG_ERR_INVALID, where + "idx[3] = -1 on a two-input term whose idx[2] names a partner: both inputs are "
+                                      "relative or neither");
+  for (int k = 2; k < 4; k++)
+    for (int q = 0; q < k; q++)
+      if (c.idx[k] >= 0 && c.idx[k] == c.idx[q])
+        return fail(ILQG_ERR_INVALID, where + "idx[" + std::to_string(q) + "] and idx[" + std::to_string(k) + "] name the same entry");
   if (desc.dense_params == nullptr || c.polyline < 0 || c.polyline >= desc.num_dense_params)
     return fail(ILQG_ERR_INVALID, where + "its program block is out of range of ilqg_problem_desc::dense_params");
   const ExprCheck chk = expr_validate(desc.dense_params + c.polyline, (long long)desc.num_dense_params - c.polyline, c.idx[1] >= 0);
@@ -388,12 +426,12 @@ ilqg_status check_expression_term(const ilqg_problem_desc& desc, int ti, int arg
                                     "one, the term's value, must be left");
 }
 
-// Programs of the expression costs, behind the affine blocks in the same table (DevProblem::dense_f / dense_d): the
+// Programs of the expression costs and constraints, behind the affine blocks in the same table (DevProblem::dense_f / dense_d): the
 // block's floats as they are, and as doubles; DevTerm::polyline of such a term becomes its block's offset
 ilqg_status build_expression_blocks(const ilqg_problem_desc& desc, ProblemTables* t) {
   for (int ti = 0; ti < desc.num_terms; ti++) {
     DevTerm& o = t->terms[ti];
-    if (o.kind != ILQG_COST_EXPRESSION) continue;
+    if (!term_is_expression(o.kind)) continue;
     if (const ilqg_status s = check_expression_term(desc, ti, o.arg_dim)) return s;
     t->has_expression = true;
     const float* src = desc.dense_params + desc.terms[ti].polyline;

@@ -67,12 +67,13 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
         for (int i = 0; i < dim; i++) e->push_back({true, i, j});
       return;
     }
-    const int pat = term_pattern_of(c.kind, c.idx[0], c.idx[1]);
+    const int pat = term_pattern_of(c.kind, c.idx[0], c.idx[1], c.idx[2]);
     if (pat == PAT_SINGLE) {
       e->push_back({false, c.idx[0], 0});
       e->push_back({true, c.idx[0], c.idx[0]});
     } else if (pat == PAT_PAIR2) {
-      const int x = c.idx[0], y = c.idx[1];
+      // (an expression term over one relative input: the entry and its partner, ilqg.h's table)
+      const int x = c.idx[0], y = (term_is_expression(c.kind) && c.idx[1] < 0) ? c.idx[2] : c.idx[1];
       e->push_back({false, x, 0}); e->push_back({false, y, 0});
       e->push_back({true, x, x}); e->push_back({true, y, y}); e->push_back({true, x, y}); e->push_back({true, y, x});
     } else if (pat == PAT_PAIR4) {
@@ -347,10 +348,10 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
           want_closest(c, c);
           const int b0 = leaf_sids(c, c);
           // (an expression cost is a leaf like any other: its op carries the offset of its program in the dense table)
-          const bool expr = c.kind == ILQG_COST_EXPRESSION;
+          const bool expr = term_is_expression(c.kind);
           if (expr) expr_scratch = kExprStackScalars;
           emit_op(ROP_TERM, b0, int(sids.size()) - b0, 0, c, c, (term_is_time_dependent(c.kind) || expr) ? c.polyline : 0,
-                  term_pattern_of(c.kind, c.idx[0], c.idx[1]), ti);
+                  term_pattern_of(c.kind, c.idx[0], c.idx[1], c.idx[2]), ti);
         }
       }
     if (!ok) { *err = "row program: a term's indices are out of range or not distinct"; return false; }

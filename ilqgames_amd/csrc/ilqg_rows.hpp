@@ -400,10 +400,14 @@ __device__ __forceinline__ void rows_affine(int kind, bool is_equality, const T*
 }
 
 // The scatter pattern a cost kind produces when it is active (term_compute_leaf), known without evaluating it.
-// (idx1: an expression cost's second input, -1 for a one-input program; no other kind reads it)
-__host__ __device__ inline int term_pattern_of(int kind, int idx0, int idx1 = -1) {
+// (idx1: an expression term's second input, -1 for a one-input program; idx2: the partner of its first input, -1 where
+// the inputs are not relative — ilqg.h's table; no other kind reads them)
+__host__ __device__ inline int term_pattern_of(int kind, int idx0, int idx1 = -1, int idx2 = -1) {
   switch (kind) {
-    case ILQG_COST_EXPRESSION: return idx1 >= 0 ? PAT_PAIR2 : PAT_SINGLE;
+    case ILQG_COST_EXPRESSION:
+    case ILQG_CONSTRAINT_EXPRESSION:
+      if (idx2 >= 0) return idx1 >= 0 ? PAT_PAIR4 : PAT_PAIR2;
+      return idx1 >= 0 ? PAT_PAIR2 : PAT_SINGLE;
     case ILQG_COST_QUADRATIC: return idx0 >= 0 ? PAT_SINGLE : PAT_ALL;
     case ILQG_COST_SEMIQUADRATIC:
     case ILQG_COST_ORIENTATION:
@@ -892,18 +896,39 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
           tnom[1] = tn[1];
         }
         bool is_expr = false;
-        if constexpr (PROG::kExpr) is_expr = c.kind == ILQG_COST_EXPRESSION;  // (ProgDynamicExpr: the launchers pick it)
+        if constexpr (PROG::kExpr) is_expr = term_is_expression(c.kind);  // (ProgDynamicExpr: the launchers pick it)
         if (is_expr) {
           // ilqg_expr.hpp: the program in scalar memory (its block of the dense table), the stack's lower entries in this
           // lane's column behind the slots this pass keeps live (build_row_program counts them in)
           const typename ConstPtr<T>::type prog = (typename ConstPtr<T>::type)problem_dense<T>(p) + od.template param<RO_POLY_FIRST>();
-          const bool two = c.idx[1] >= 0;
+          const bool two = c.idx[1] >= 0, rel = c.idx[2] >= 0;
+          // relative inputs (ilqg.h): one rounded difference each, as ProximityCost forms its own
+          T ex = v[c.idx[0]], ey = two ? v[c.idx[1]] : T(0);
+          if (rel) {
+            ex = ex - v[c.idx[2]];
+            if (two) ey = ey - v[c.idx[3]];
+          }
           ExprJet<T> j;
-          expr_eval_jet<T>(prog, T(c.weight), T(c.value), v[c.idx[0]], two ? v[c.idx[1]] : T(0), quad_out,
-                           ExprStack<T>{col + (NPS + li_live) * cws, cws}, &j);
-          o.pattern = two ? PAT_PAIR2 : PAT_SINGLE;
+          expr_eval_jet<T>(prog, T(c.weight), T(c.value), ex, ey, quad_out, ExprStack<T>{col + (NPS + li_live) * cws, cws}, &j);
+          if (c.kind == ILQG_CONSTRAINT_EXPRESSION) {
+            // Constraint::ModifyDerivatives (modify_derivatives, ilqg_models.hpp) with the equality-aware Mu of the affine
+            // constraints; a gradient-only evaluation holds zeros in the jet's second derivatives and scatters none
+            const T mu_eff = constraint_mu<T>(lambda, j.f, a.mu, (c.flags & ILQG_FLAG_EQUALITY) != 0);
+            const T gx = lambda * j.fx + mu_eff * j.f * j.fx, gy = lambda * j.fy + mu_eff * j.f * j.fy;
+            if (quad_out) {
+              const T hxx = lambda * j.fxx + mu_eff * (j.fx * j.fx + j.f * j.fxx);
+              const T hyy = lambda * j.fyy + mu_eff * (j.fy * j.fy + j.f * j.fyy);
+              const T hxy = lambda * j.fxy + mu_eff * (j.fy * j.fx + j.f * j.fxy);
+              j.fxx = hxx; j.fyy = hyy; j.fxy = hxy;
+            }
+            j.fx = gx; j.fy = gy;
+          }
+          // the scatter of ilqg.h's table: PAIR4 carries the signs of a relative pair itself; one relative input is a
+          // PAIR2 over (idx0, idx2) with the partner's entries negated here
+          o.pattern = rel ? (two ? PAT_PAIR4 : PAT_PAIR2) : (two ? PAT_PAIR2 : PAT_SINGLE);
           o.i0 = c.idx[0]; o.i1 = c.idx[1]; o.i2 = c.idx[2]; o.i3 = c.idx[3];
           o.value = j.f; o.gx = j.fx; o.gy = j.fy; o.hxx = j.fxx; o.hyy = j.fyy; o.hxy = j.fxy;
+          if (rel && !two) { o.gy = -j.fx; o.hyy = j.fxx; o.hxy = -j.fxx; }
         } else {
           term_compute_leaf<T, Arg, true>(QuadTables<T>{}, c, v, lambda, a.mu, &o, &cc, tnom);
         }

@@ -928,6 +928,96 @@ def expression_twin(spec):
     return twin, replaced
 
 
+def expression_game_twin(spec):
+    """expression_twin's restatements and, beside them, those of the kinds that couple players or bound them, written over
+    relative inputs (X = v[idx0] - v[idx2], Y = v[idx1] - v[idx3]) and as abi.CONSTRAINT_EXPRESSION terms:
+    ProximityCost 0.5 w hinge(v - sqrt(X^2 + Y^2))^2, RelativeDistanceCost w sqrt(X^2 + Y^2), QuadraticDifferenceCost
+    0.5 w (X^2 + Y^2), a top-level SignedDistanceCost +-(v - sqrt(X^2 + Y^2)), ProximityConstraint
+    +-(sqrt(X^2 + Y^2) - v) and SingleDimensionConstraint x - v / v - x on a state or a control — each with the same
+    weight, value, role, player, multiplier slot and gate; every other term as it is.
+    -> (the twin, the number of terms replaced)."""
+    from . import abi
+    from .abi import Expr
+    twin, replaced = expression_twin(spec)
+    for t in twin.terms:
+        x, y, w, v = Expr.x(), Expr.y(), Expr.weight(), Expr.value()
+        dist = (x.square() + y.square()).sqrt()
+        oriented = bool(t["flags"] & abi.FLAG_ORIENTED)
+        cost = t["role"] in (abi.ROLE_STATE_COST, abi.ROLE_CONTROL_COST)
+        constraint = t["role"] in (abi.ROLE_STATE_CONSTRAINT, abi.ROLE_CONTROL_CONSTRAINT)
+        kind, idx = abi.COST_EXPRESSION, tuple(t["idx"])
+        if cost and t["kind"] == abi.COST_PROXIMITY:
+            tree = 0.5 * w * (v - dist).hinge().square()
+        elif cost and t["kind"] == abi.COST_RELATIVE_DISTANCE:
+            tree = w * dist
+        elif cost and t["kind"] == abi.COST_QUADRATIC_DIFFERENCE:
+            tree = 0.5 * w * (x.square() + y.square())
+        elif cost and t["kind"] == abi.COST_SIGNED_DISTANCE:
+            tree = (v - dist) if oriented else -(v - dist)
+        elif constraint and t["kind"] == abi.CONSTRAINT_PROXIMITY:
+            kind, tree = abi.CONSTRAINT_EXPRESSION, (dist - v) if oriented else -(dist - v)
+        elif constraint and t["kind"] == abi.CONSTRAINT_SINGLE_DIMENSION:
+            kind, tree, idx = abi.CONSTRAINT_EXPRESSION, (x - v) if oriented else (v - x), (t["idx"][0], -1, -1, -1)
+        else:
+            continue
+        t.update(kind=kind, idx=idx, flags=0, polyline=len(twin.dense_params))
+        twin.dense_params += abi.expr_block(tree.program())
+        replaced += 1
+    return twin, replaced
+
+
+EXPRESSION_DISC_CENTRE = (2.5, -2.0)  # of expression_game_scene's keep-out disc (its C++ twin: tests/host/expression_game_scene.h)
+
+
+def expression_game_scene(T=100, dt=0.1):
+    """A test scene, NOT a reference example: two Car5D (n = 10, the specialised (10, 2, 2) kernels) on the crossing
+    lanes of the skeleton example whose coupling and whose bounds are all user-defined (include/ilqg.h: relative inputs,
+    abi.CONSTRAINT_EXPRESSION) — for both players a Gaussian repulsion w exp(-0.5 (X^2 + Y^2) / v^2) over the relative
+    position; for car 2 a penalty 0.5 w (X - v)^2 on the speed difference (one relative input); as constraints a keep-out
+    disc about a fixed point for car 1, v^2 - (x - cx)^2 - (y - cy)^2 <= 0 (two plain inputs; only from 0.25 s on, as a
+    FinalTimeConstraint would gate it), a minimum clearance v - sqrt(X^2 + Y^2) <= 0 between the cars for car 2 (two
+    relative inputs) and an upper bound x - v <= 0 on car 1's acceleration (a control constraint)."""
+    from .abi import Expr
+    prm = SolverParams.default()
+    prm.max_backtracking_steps = 100
+    prm.initial_alpha_scaling = 0.1
+    prm.convergence_tolerance = 0.1
+    prm.expected_decrease_fraction = 0.001
+    prm.max_solver_iters = 40
+    s = ProblemSpec(T, dt, prm)
+    for _ in range(2):
+        s.add_player(DYN_CAR_5D, 4.0, state_reg=10.0, control_reg=10.0)
+    X, Y, H, PHI, V = [0, 5], [1, 6], [2, 7], [3, 8], [4, 9]
+    for i in range(2):
+        s.quadratic(i, 25.0, 0, 0.0, control_of=i)  # omega
+        s.quadratic(i, 15.0, 1, 0.0, control_of=i)  # acceleration
+        s.quadratic(i, 10.0, V[i], 6.0)
+    lane1 = s.add_polyline([(0.0, -1000.0), (0.0, 1000.0)])
+    lane2 = s.add_polyline([(-5.0, 1000.0), (-5.0, 5.0), (0.0, 0.0), (995.0, 0.0)])
+    s.quadratic_polyline2(0, 25.0, lane1, (X[0], Y[0]))
+    s.quadratic_polyline2(1, 25.0, lane2, (X[1], Y[1]))
+    x, y, w, v = Expr.x(), Expr.y(), Expr.weight(), Expr.value()
+    repulsion = ((x.square() + y.square()) * -0.5 / v.square()).exp() * w
+    cx, cy = EXPRESSION_DISC_CENTRE
+    disc = v.square() - (x - cx).square() - (y - cy).square()
+    # (player by player, as the C++ twin flattens: the programs follow one another in that order in the dense table)
+    s.name_term("p1_repulsion", s.expression(0, repulsion, (X[0], Y[0]), weight=40.0, value=5.0, relative_to=(X[1], Y[1])))
+    s.name_term("p1_keep_out", s.final_time(0.25, s.expression_constraint(0, disc, (X[0], Y[0]), value=2.0)))
+    s.name_term("p1_acceleration_max", s.expression_constraint(0, x - v, (1,), value=1.5, control_of=0))
+    s.name_term("p2_repulsion", s.expression(1, repulsion, (X[1], Y[1]), weight=40.0, value=5.0, relative_to=(X[0], Y[0])))
+    s.name_term("p2_speed_match", s.expression(1, 0.5 * w * (x - v).square(), (V[1],), weight=2.0, value=-1.0,
+                                                relative_to=(V[0],)))
+    s.name_term("p2_clearance", s.expression_constraint(1, v - (x.square() + y.square()).sqrt(), (X[1], Y[1]),
+                                                        relative_to=(X[0], Y[0]), value=3.0))
+    f = np.float32
+    x0 = np.zeros(10)
+    x0[[X[0], Y[0], H[0], V[0]]] = [0.0, -12.0, float(f(np.pi / 2)), 5.0]
+    x0[[X[1], Y[1], H[1], V[1]]] = [-5.0, 10.0, float(f(-np.pi / 2)), 4.0]
+    s.x0 = x0
+    s.position_dims, s.heading_dims, s.speed_dims = list(zip(X, Y)), H, V
+    return s
+
+
 def jittered_x0(spec, batch, seed=0):
     """Per-instance initial states of SURVEY.md §8(d): U(-1,1) m on px,py, U(-0.1,0.1) rad
     heading, U(-0.5,0.5) m/s speed; instance b uses numpy default_rng(seed + b)."""

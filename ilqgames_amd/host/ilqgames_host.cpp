@@ -283,8 +283,15 @@ bool WeightedConvexProximityCost::Describe(host::TermDescription* out) const {
   return true;
 }
 bool ExpressionCost::Describe(host::TermDescription* out) const {
-  FillTerm(out, ILQG_COST_EXPRESSION, weight_, value_, 0, {x_idx_, y_idx_ < 0 ? -1 : y_idx_, -1, -1});
+  FillTerm(out, ILQG_COST_EXPRESSION, weight_, value_, 0,
+           {x_idx_, y_idx_ < 0 ? -1 : y_idx_, rel_x_idx_ < 0 ? -1 : rel_x_idx_, rel_y_idx_ < 0 ? -1 : rel_y_idx_});
   out->dense = block_;  // its program: `polyline` becomes the block's offset in the dense table
+  return true;
+}
+bool ExpressionConstraint::Describe(host::TermDescription* out) const {
+  FillTerm(out, ILQG_CONSTRAINT_EXPRESSION, expr_weight_, value_, IsEquality() ? ILQG_FLAG_EQUALITY : 0,
+           {x_idx_, y_idx_ < 0 ? -1 : y_idx_, rel_x_idx_ < 0 ? -1 : rel_x_idx_, rel_y_idx_ < 0 ? -1 : rel_y_idx_});
+  out->dense = block_;
   return true;
 }
 bool CurvatureCost::Describe(host::TermDescription* out) const {

@@ -216,8 +216,26 @@ typedef enum {
    * its argument vector, evaluated and differentiated to second order on the device (forward mode, ilqg_expr_op below).
    * idx[0] = input x, idx[1] = input y or -1; `polyline` = offset of the program's block in
    * ilqg_problem_desc::dense_params: [L, (opcode_0, imm_0), ..., (opcode_{L-1}, imm_{L-1})] as floats.  The program's
-   * result is the term's value: `weight` and `value` enter only where it pushes them.  Top-level state / control cost. */
-  ILQG_COST_EXPRESSION = 24
+   * result is the term's value: `weight` and `value` enter only where it pushes them.  Top-level state / control cost.
+   *
+   * Relative inputs (both expression kinds).  idx[2] = idx[3] = -1: the inputs are the entries themselves, as above.
+   * idx[2] >= 0: the inputs are differences, rounded once in the solve's scalar type as the built-in kinds round theirs,
+   *   X = v[idx[0]] - v[idx[2]],  Y = v[idx[1]] - v[idx[3]] (a two-input term);
+   * idx[3] >= 0 exactly when idx[1] >= 0 and idx[2] >= 0; every named index lies inside the argument vector and all of
+   * them are distinct.  What the jet (f, fx, fy, fxx, fyy, fxy) adds to the tile:
+   *   inputs                 pattern                        gx   gy    hxx  hyy  hxy
+   *   x                      SINGLE (idx0)                  fx         fxx
+   *   x, y                   PAIR2  (idx0, idx1)            fx   fy    fxx  fyy  fxy
+   *   x - x'                 PAIR2  (idx0, idx2)            fx   -fx   fxx  fxx  -fxx
+   *   x - x', y - y'         PAIR4  (idx0, idx1, idx2, idx3) fx  fy    fxx  fyy  fxy   (the pattern carries the signs,
+   *                                                                                    as for ProximityCost) */
+  ILQG_COST_EXPRESSION = 24,
+  /* A user-defined constraint g(X, Y) <= 0 (g = 0 with ILQG_FLAG_EQUALITY): the same program block, validator, idx rules
+   * and relative inputs as ILQG_COST_EXPRESSION; `weight` and `value` enter only where the program pushes them.  Roles
+   * ILQG_ROLE_STATE_CONSTRAINT / ILQG_ROLE_CONTROL_CONSTRAINT only, with a multiplier slot of its own; `first_step` gates
+   * it as FinalTimeConstraint does (g = 0 before it).  The row stage applies Constraint::ModifyDerivatives to the jet
+   * (with the equality-aware Mu) before the scatter of the table above; the term adds nothing to a player's cost. */
+  ILQG_CONSTRAINT_EXPRESSION = 25
 } ilqg_cost_kind;
 
 /* The program of an ILQG_COST_EXPRESSION term: 1 <= L <= ILQG_EXPR_MAX_OPS ops on a stack that never holds more than
@@ -357,7 +375,7 @@ void ilqg_problem_destroy(ilqg_problem* p);
  *   WEIGHTED_CONVEX_PROXIMITY              yes      yes (threshold)
  *   ORIENTATION, QUADRATIC_NORM,
  *   SEMIQUADRATIC_NORM                     yes      yes
- *   EXPRESSION                             yes      yes (what its program's PUSH_WEIGHT / PUSH_VALUE push)
+ *   EXPRESSION, CONSTRAINT_EXPRESSION      yes      yes (what its program's PUSH_WEIGHT / PUSH_VALUE push)
  *   QUADRATIC_DIFFERENCE, CURVATURE,
  *   RELATIVE_DISTANCE                      yes      no  (has none)
  *   NOMINAL_PATH_LENGTH, ROUTE_PROGRESS    yes      no  (tabulated per step by ilqg_problem_create; per instance:
@@ -760,8 +778,8 @@ ilqg_status ilqg_problem_row_program(const ilqg_problem* p, int32_t* words_out, 
  * it uploads tables, without a device (the one entry point that works without one). */
 ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words_out, int32_t capacity, int32_t* num_words,
                                    int32_t* static_id);
-/* Host only, no device needed: everything ilqg_problem_create checks about the ILQG_COST_EXPRESSION term `term` of a
- * description — its role and placement, its inputs, its block inside dense_params and the program in it (length, opcodes,
+/* Host only, no device needed: everything ilqg_problem_create checks about the ILQG_COST_EXPRESSION or
+ * ILQG_CONSTRAINT_EXPRESSION term `term` of a description — its role and placement, its inputs, its block inside dense_params and the program in it (length, opcodes,
  * stack depth).  A refusal names the term, and the op where one is at fault, in ilqg_last_error(). */
 ilqg_status ilqg_expression_check(const ilqg_problem_desc* desc, int32_t term);
 /* Host only, no device needed: what the feedback sweep may assume about B (sweep_forms).  *constant_out is 1 when the
@@ -946,7 +964,8 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
                                  per-instance solver parameters (ilqg_solver_field, ilqg_problem_declare_instance_solver_params,
                                  ilqg_instance_solver_params_check: two new calls, the table gains columns); still 9:
                                  ILQG_COST_EXPRESSION (cost kind 24, ilqg_expr_op) and the host-only ilqg_expression_check
-                                 (one new call, no layout change);
+                                 (one new call, no layout change); still 9: relative inputs of the expression kinds
+                                 (idx[2], idx[3]) and ILQG_CONSTRAINT_EXPRESSION (kind 25; no new call, no layout change);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;

@@ -446,18 +446,35 @@ inline Expr Hinge(const Expr& a) { return Expr::Unary(ILQG_EXPR_HINGE, a); }  //
 
 // `expr` over entry `x_idx` (Expr::X()) and, when the formula names it, entry `y_idx` (Expr::Y()) of the state — or of
 // the control vector the cost is added for; `weight` is Expr::Weight(), `value` Expr::Value().
+// The relative forms couple two players: the formula's inputs are then differences, X = v[dims.first] -
+// v[relative_to.first], Y = v[dims.second] - v[relative_to.second] (or X = v[dim] - v[relative_to] alone), as
+// ProximityCost reads the relative position.
 class ExpressionCost : public TimeInvariantCost {
  public:
   ExpressionCost(const host::Expr& expr, Dimension x_idx, Dimension y_idx = -1, float weight = 1.0, float value = 0.0,
                  const std::string& name = "")
-      : TimeInvariantCost(weight, name), block_(expr.Compile()), x_idx_(x_idx), y_idx_(y_idx), value_(value) {
+      : TimeInvariantCost(weight, name), block_(expr.Compile()), x_idx_(x_idx), y_idx_(y_idx), rel_x_idx_(-1), rel_y_idx_(-1),
+        value_(value) {
     CHECK(y_idx >= 0 || !expr.UsesY()) << "ExpressionCost: the formula names Expr::Y() and the cost has no second dimension";
+  }
+  ExpressionCost(const host::Expr& expr, const std::pair<Dimension, Dimension>& dims,
+                 const std::pair<Dimension, Dimension>& relative_to, float weight = 1.0, float value = 0.0,
+                 const std::string& name = "")
+      : TimeInvariantCost(weight, name), block_(expr.Compile()), x_idx_(dims.first), y_idx_(dims.second),
+        rel_x_idx_(relative_to.first), rel_y_idx_(relative_to.second), value_(value) {}
+  // (a tag keeps this apart from (x_idx, y_idx): both are two Dimensions)
+  struct RelativeTo { Dimension dim; };
+  ExpressionCost(const host::Expr& expr, Dimension dim, RelativeTo relative_to, float weight = 1.0, float value = 0.0,
+                 const std::string& name = "")
+      : TimeInvariantCost(weight, name), block_(expr.Compile()), x_idx_(dim), y_idx_(-1), rel_x_idx_(relative_to.dim),
+        rel_y_idx_(-1), value_(value) {
+    CHECK(!expr.UsesY()) << "ExpressionCost: the formula names Expr::Y() and the cost has no second dimension";
   }
   bool Describe(host::TermDescription* out) const override;
 
  private:
   const std::vector<float> block_;
-  const Dimension x_idx_, y_idx_;
+  const Dimension x_idx_, y_idx_, rel_x_idx_, rel_y_idx_;
   const float value_;
 };
 
@@ -568,6 +585,28 @@ class SingleDimensionConstraint : public TimeInvariantConstraint {
   Dimension dim_;
   float threshold_;
   bool keep_below_;
+};
+
+// A user's own constraint g <= 0 (g = 0 when is_equality): the formula of an ExpressionCost in a constraint's place
+// (ILQG_CONSTRAINT_EXPRESSION, include/ilqg.h).  `dims`: the one or two entries the formula reads (second: -1 for
+// none); `relative_to`: their partners, the inputs are then the differences (-1, -1: the entries themselves).
+//   cost.AddStateConstraint(std::make_shared<ExpressionConstraint>(Expr::Value() - Sqrt(Square(Expr::X()) + Square(Expr::Y())),
+//       std::make_pair(kP1XIdx, kP1YIdx), std::make_pair(kP2XIdx, kP2YIdx), /* weight */ 1.0, /* value */ 3.0));
+class ExpressionConstraint : public TimeInvariantConstraint {
+ public:
+  ExpressionConstraint(const host::Expr& expr, const std::pair<Dimension, Dimension>& dims,
+                       const std::pair<Dimension, Dimension>& relative_to = {-1, -1}, float weight = 1.0, float value = 0.0,
+                       bool is_equality = false, const std::string& name = "")
+      : TimeInvariantConstraint(is_equality, name), block_(expr.Compile()), x_idx_(dims.first), y_idx_(dims.second),
+        rel_x_idx_(relative_to.first), rel_y_idx_(relative_to.second), expr_weight_(weight), value_(value) {
+    CHECK(y_idx_ >= 0 || !expr.UsesY()) << "ExpressionConstraint: the formula names Expr::Y() and the constraint has no second dimension";
+  }
+  bool Describe(host::TermDescription* out) const override;
+
+ private:
+  const std::vector<float> block_;
+  const Dimension x_idx_, y_idx_, rel_x_idx_, rel_y_idx_;
+  const float expr_weight_, value_;
 };
 
 // include/ilqgames/constraint/affine_scalar_constraint.h:54-100 — g(x) = a^T x - b on the whole input vector.
