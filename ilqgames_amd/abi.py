@@ -22,6 +22,7 @@ DYN_POINT_MASS_2D = 9  # (px, py, vx, vy), u = (ax, ay)
 DYN_UNICYCLE_5D = 10  # (px, py, theta, v, s), u = (omega, a)
 DYN_CAR_7D = 11  # (px, py, theta, phi, v, kappa, s), u = (omega, a), param0 = inter-axle distance
 DYN_DELAYED_DUBINS_CAR = 12  # (px, py, theta, omega), u = (alpha), param0 = speed
+DYN_EXPRESSION = 13  # a user-defined model: 1 .. 8 states, 1 or 2 controls, one DYN_ROW_EXPRESSION term per state row
 # ilqg_cost_kind
 (COST_QUADRATIC, COST_QUADRATIC_POLYLINE2, COST_SEMIQUADRATIC, COST_SEMIQUADRATIC_POLYLINE2,
  COST_PROXIMITY, COST_SIGNED_DISTANCE, COST_EXTREME_VALUE, CONSTRAINT_PROXIMITY,
@@ -43,12 +44,15 @@ CONSTRAINT_AFFINE_VECTOR = 23  # g = |A v - b|; `polyline` = offset of [A (colum
 COST_EXPRESSION = 24  # a postfix program over idx[0] (x) and idx[1] (y, or -1); `polyline` = offset of [L, (op, imm) x L]
 #                       idx[2] / idx[3] >= 0: the inputs are the differences v[idx0] - v[idx2], v[idx1] - v[idx3]
 CONSTRAINT_EXPRESSION = 25  # the same program as a constraint g <= 0 (g = 0 with FLAG_EQUALITY)
+DYN_ROW_EXPRESSION = 26  # a state row of a DYN_EXPRESSION subsystem (role ROLE_DYNAMICS_ROW): idx = (row, X, Y or -1, -1)
+#                          over the subsystem's own [x | u]; PUSH_VALUE = the subsystem's param0, PUSH_WEIGHT = `weight`
 # ilqg_expr_op
 (EXPR_PUSH_X, EXPR_PUSH_Y, EXPR_PUSH_CONST, EXPR_PUSH_WEIGHT, EXPR_PUSH_VALUE, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_DIV,
  EXPR_NEG, EXPR_SQUARE, EXPR_SQRT, EXPR_EXP, EXPR_LOG, EXPR_SIN, EXPR_COS, EXPR_HINGE) = range(1, 18)
 EXPR_MAX_OPS, EXPR_MAX_DEPTH = 64, 4
 # ilqg_cost_role
 ROLE_STATE_COST, ROLE_CONTROL_COST, ROLE_STATE_CONSTRAINT, ROLE_CONTROL_CONSTRAINT, ROLE_CHILD = range(5)
+ROLE_DYNAMICS_ROW = 5  # a DYN_ROW_EXPRESSION term: not a cost
 FLAG_ORIENTED, FLAG_IS_MIN, FLAG_EQUALITY = 1, 2, 4
 # ILQG_SCHEDULE_* (ilqg_problem_last_schedule)
 SCHEDULE_SINGLE_WAVE_SWEEP, SCHEDULE_ADJOINT_DECREASE, SCHEDULE_SPLIT_TRIAL, SCHEDULE_COMPACT_ROWS = 1, 2, 4, 8
@@ -239,6 +243,26 @@ class ProblemSpec:
         self.subsystems.append((kind, xdim, 1 if one_control else 2, param0))
         self.player_costs.append((state_reg, control_reg, structure))
         return len(self.subsystems) - 1
+
+    def add_expression_player(self, xdim, udim, rows, param0=0.0, state_reg=0.0, control_reg=0.0, structure=SUM, weights=None):
+        """An ILQG_DYN_EXPRESSION subsystem (include/ilqg.h): `rows` holds one (Expr tree or postfix program, x_input,
+        y_input or None) per state row, in row order — xdot_r is the program's value at the named entries of the
+        subsystem's own [x (xdim) | u (udim)]; Expr.value() is `param0`, Expr.weight() the row's entry of `weights`
+        (default 1).  Nothing is checked here: the library refuses a malformed model."""
+        self.subsystems.append((DYN_EXPRESSION, xdim, udim, param0))
+        self.player_costs.append((state_reg, control_reg, structure))
+        player = len(self.subsystems) - 1
+        for r, (program_or_tree, xin, yin) in enumerate(rows):
+            self.dynamics_row(player, r, program_or_tree, xin, yin, 1.0 if weights is None else weights[r])
+        return player
+
+    def dynamics_row(self, player, row, program_or_tree, x_input, y_input=None, weight=1.0):
+        """One ILQG_DYN_ROW_EXPRESSION term: state row `row` of expression subsystem `player`."""
+        program = program_or_tree.program() if isinstance(program_or_tree, Expr) else list(program_or_tree)
+        off = len(self.dense_params)
+        self.dense_params += expr_block(program)
+        return self._term(DYN_ROW_EXPRESSION, ROLE_DYNAMICS_ROW, player, -1,
+                          (row, x_input, -1 if y_input is None else y_input, -1), weight, 0.0, 0, off)
 
     @property
     def n(self):
@@ -509,7 +533,7 @@ class ProblemSpec:
                 dim = self.n if t["arg"] < 0 else self.udims[t["arg"]]
                 cnt = dim + 1 if t["kind"] == CONSTRAINT_AFFINE_SCALAR else dim * dim + dim
                 poly = tuple(f32(v) for v in self.dense_params[t["polyline"]:t["polyline"] + cnt])
-            elif t["kind"] in (COST_EXPRESSION, CONSTRAINT_EXPRESSION):  # its program, by content
+            elif t["kind"] in (COST_EXPRESSION, CONSTRAINT_EXPRESSION, DYN_ROW_EXPRESSION):  # its program, by content
                 cnt = 1 + 2 * int(self.dense_params[t["polyline"]])
                 poly = tuple(f32(v) for v in self.dense_params[t["polyline"]:t["polyline"] + cnt])
             else:
@@ -525,7 +549,7 @@ class ProblemSpec:
                 continue
             groups.setdefault((t["player"], t["role"]), []).append(term_key(t))
         subs = [(k, xd, ud, f32(p0) if k in (DYN_CAR_5D, DYN_CAR_6D, DYN_DUBINS_CAR, DYN_AIR_3D_EVADER, DYN_AIR_3D_PURSUER, DYN_CAR_7D,
-                                         DYN_DELAYED_DUBINS_CAR) else 0.0)
+                                         DYN_DELAYED_DUBINS_CAR, DYN_EXPRESSION) else 0.0)
                 for k, xd, ud, p0 in self.subsystems]
         pcs = [(f32(a), f32(b), c) for a, b, c in self.player_costs]
         return dict(T=self.T, dt=self.dt, subsystems=subs, player_costs=pcs, groups=groups, pairs=self.pairs())

@@ -216,8 +216,11 @@ struct RolloutBatchArgs {
   const int* active;
 };
 
-template <typename T>
-__global__ void rollout_kernel(DevProblem p, RolloutBatchArgs<T> g) {
+// XDYN: the problem holds an expression subsystem (rollout_instance's XDYN, ilqg_stages.hpp): a kernel of its own
+// (launched with one wavefront; the expression integrator wants the whole register file: 1024 is the bound a kernel
+// without the attribute gets)
+template <typename T, bool XDYN = false>
+__global__ void __launch_bounds__(XDYN ? 64 : 1024) rollout_kernel(DevProblem p, RolloutBatchArgs<T> g) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* sm = reinterpret_cast<T*>(smem_raw);
   const size_t b = blockIdx.x;
@@ -226,7 +229,7 @@ __global__ void rollout_kernel(DevProblem p, RolloutBatchArgs<T> g) {
   RolloutArgs<T> a{g.x0 + b * n,          g.xs_ref + b * Tn * n, g.us_ref + b * Tn * m, g.P + b * Tn * m * n,
                    g.alpha + b * Tn * m,  g.alpha_scale ? g.alpha_scale[b] : T(1),
                    g.xs + b * Tn * n,     g.us + b * Tn * m,     instance_values(p, int(b))};
-  rollout_instance_rt<T>(p, a, sm, threadIdx.x);
+  rollout_instance_rt<T, XDYN>(p, a, sm, threadIdx.x);
 }
 
 template <typename T>
@@ -264,7 +267,8 @@ __device__ __forceinline__ QuadArgs<T> quad_args_of(const DevProblem& p, const Q
 // Linearise / quadraticise / cost stage on its own (ilqg_rows.hpp): grid = (ceil(T / cw), B), one wavefront takes cw
 // consecutive rows of one instance.
 // EXPR: the interpreter that also evaluates expression costs (ProgDynamicExpr, ilqg_rows.hpp), for the problems that hold one
-template <typename T, int NX, int NP, int MU, bool EXPR = false>
+// XDYN: ... and linearises expression subsystems (ProgDynamicExprDyn)
+template <typename T, int NX, int NP, int MU, bool EXPR = false, bool XDYN = false>
 __global__ void __launch_bounds__(64) rows_kernel(DevProblem p, QuadBatchArgs<T> g, int cw) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const size_t b = blockIdx.y;
@@ -274,8 +278,8 @@ __global__ void __launch_bounds__(64) rows_kernel(DevProblem p, QuadBatchArgs<T>
   const QuadArgs<T> a = quad_args_of<T>(p, g, b);
   const int k0 = int(blockIdx.x) * cw;
   const int nrows = p.T - k0 < cw ? p.T - k0 : cw;
-  rows_chunk<T, NX, NP * MU, NP, false, false, typename std::conditional<EXPR, ProgDynamicExpr, ProgDynamic>::type>(
-      p, maps, a, k0, nrows, cw, sm, int(threadIdx.x));
+  typedef typename std::conditional<XDYN, ProgDynamicExprDyn, typename std::conditional<EXPR, ProgDynamicExpr, ProgDynamic>::type>::type Prog;
+  rows_chunk<T, NX, NP * MU, NP, false, false, Prog>(p, maps, a, k0, nrows, cw, sm, int(threadIdx.x));
 }
 
 // ilqg_solve_state_batch: the loop state of every instance out of the workspace
@@ -364,8 +368,9 @@ __global__ void __launch_bounds__(64 * W, (sizeof(T) == 4 && W == 2) ? ILQG_TRIA
 #ifndef ILQG_ROLL_WAVES
 #define ILQG_ROLL_WAVES 4
 #endif
-template <typename T, int NX, int NP, int MU>
-__global__ void __launch_bounds__(64, sizeof(T) == 8 ? ILQG_ROLL_WAVES : 1) ilq_roll_kernel(DevProblem p, SolveArgs<T> sa) {
+// XDYN: the problem holds an expression subsystem (kExprDynProg: the rollout with the expression integrator in it)
+template <typename T, int NX, int NP, int MU, bool XDYN = false>
+__global__ void __launch_bounds__(64, sizeof(T) == 8 ? (XDYN ? 2 : ILQG_ROLL_WAVES) : 1) ilq_roll_kernel(DevProblem p, SolveArgs<T> sa) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   if constexpr (rollout_pairs(NX, NP, MU)) {  // two instances per wavefront: entries 2 x and 2 x + 1 of the round
     const int i0 = 2 * int(blockIdx.x), i1 = i0 + 1;
@@ -381,7 +386,7 @@ __global__ void __launch_bounds__(64, sizeof(T) == 8 ? ILQG_ROLL_WAVES : 1) ilq_
     instance_mark_done<T>(p, sa, b);
     return;
   }
-  trial_part_instance<T, NX, NP, MU, 1, TRIAL_ROLL>(p, nullptr, sa, b, reinterpret_cast<T*>(smem_raw));
+  trial_part_instance<T, NX, NP, MU, 1, TRIAL_ROLL, (XDYN ? kExprDynProg : 0)>(p, nullptr, sa, b, reinterpret_cast<T*>(smem_raw));
 }
 
 template <typename T, int NX, int NP, int MU, int PROGID = 0>
@@ -416,13 +421,13 @@ __global__ void __launch_bounds__(64) ilq_decide_kernel(DevProblem p, SolveArgs<
 // SINGLE: one candidate per wavefront (rollout_instance) also where the shape has the paired form — for a round whose
 // candidates all find a SIMD of their own, where a launch costs one rollout's chain and the paired chain is the longer
 // one (n = 15, a few instances x 128 candidates: 176 us paired).
-template <typename T, int NX, int NP, int MU, bool FAT = false, bool SINGLE = false>
-__global__ void __launch_bounds__(64, sizeof(T) == 8 ? (FAT ? 2 : ILQG_ROLL_WAVES) : 1) ilq_probe_roll_kernel(DevProblem p, SolveArgs<T> sa) {
+template <typename T, int NX, int NP, int MU, bool FAT = false, bool SINGLE = false, bool XDYN = false>
+__global__ void __launch_bounds__(64, sizeof(T) == 8 ? ((FAT || XDYN) ? 2 : ILQG_ROLL_WAVES) : 1) ilq_probe_roll_kernel(DevProblem p, SolveArgs<T> sa) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   if constexpr (rollout_pairs(NX, NP, MU) && !SINGLE)  // candidates 2 y and 2 y + 1 in the two halves of the wave
     probe_roll_pair<T, NX, NP, MU>(p, sa, sa.ids[blockIdx.x], blockIdx.x, 2 * int(blockIdx.y), reinterpret_cast<T*>(smem_raw));
   else
-    probe_roll_instance<T, NX, NP, MU>(p, sa, sa.ids[blockIdx.x], blockIdx.x, blockIdx.y, reinterpret_cast<T*>(smem_raw));
+    probe_roll_instance<T, NX, NP, MU, XDYN>(p, sa, sa.ids[blockIdx.x], blockIdx.x, blockIdx.y, reinterpret_cast<T*>(smem_raw));
 }
 
 // The probing rollouts of a round that fills the chip: 64 / NP candidates of one instance per wavefront, a lane per
@@ -858,6 +863,13 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::rows(const DevProblem& d, int32_t batch, 
   const int cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), size_t(48) * 1024);
   const size_t lds = rows_maps_bytes(d) + rows_lds_elems(d.n, d.m, d.rp_pslots, d.rp_lslots, cw) * sizeof(T);
   auto kern = expr ? rows_kernel<T, NX, NP, MU, true> : rows_kernel<T, NX, NP, MU>;
+  // (a problem that holds an expression subsystem: the interpreter that linearises it; such a problem sits in a
+  // plain-RK4 shape or on the run-time-dimensioned path)
+  if constexpr (NX == 0 || dims_use_plain_rk4(NX, NP, MU)) {
+    bool xdyn = false;
+    for (int i = 0; i < d.N; i++) xdyn = xdyn || d.sub_kind[i] == ILQG_DYN_EXPRESSION;
+    if (xdyn) kern = rows_kernel<T, NX, NP, MU, true, true>;
+  }
   raise_lds_limit((const void*)kern, lds);
   hipLaunchKernelGGL(kern, dim3((d.T + cw - 1) / cw, batch), dim3(64), lds, stream, d, g, cw);
   HIP_TRY(hipGetLastError());
@@ -1545,6 +1557,12 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   const bool expr = p->has_expression;
   auto k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
   if (expr) k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, kExprProg, true> : ilq_trial_kernel<T, NX, NP, MU, W, kExprProg, false>;
+  // (... and a problem that holds an expression subsystem, in the two plain-RK4 shapes: kExprDynProg, the rollout with
+  // the expression integrator and the interpreter that linearises it — the fused kernel, the split and probing passes)
+  constexpr bool kMayXdyn = dims_use_plain_rk4(NX, NP, MU);
+  const bool xdyn = kMayXdyn && p->has_expression_dynamics;
+  if constexpr (kMayXdyn)
+    if (xdyn) k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, kExprDynProg, true> : ilq_trial_kernel<T, NX, NP, MU, W, kExprDynProg, false>;
   const bool pw = C::USE_MFMA && !open_loop;  // one wave per player (MFMA feedback sweep)
   // Compact rows (ilqg_common.hpp) between the row stage and the sweep: the one-tile player-parallel sweep and the
   // open-loop sweep read them; the other sweeps take the dense arrays.  What the row stage writes and the sweep reads
@@ -1562,6 +1580,11 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   int static_prog = 0;  // ... and the fused kernel
   auto k_rows = expr ? ilq_rows_kernel<T, NX, NP, MU, kExprProg> : ilq_rows_kernel<T, NX, NP, MU>;
   auto k_prows = expr ? ilq_probe_rows_kernel<T, NX, NP, MU, kExprProg> : ilq_probe_rows_kernel<T, NX, NP, MU>;
+  if constexpr (kMayXdyn)
+    if (xdyn) {
+      k_rows = ilq_rows_kernel<T, NX, NP, MU, kExprDynProg>;
+      k_prows = ilq_probe_rows_kernel<T, NX, NP, MU, kExprDynProg>;
+    }
   // (the static kernels exist for solves on compact rows: they write nothing dense)
   const bool will_compact = (pw && C::MFMA_ONE_TILE && compact_on) || ol_compact;
   bool static_in_regs = false;  // ... with the slots of a chunk in registers (ilqg_rows.hpp: no row scratch in LDS)
@@ -1741,6 +1764,12 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
       plan.proll_single = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, true>, 64, lds_roll};
       plan.proll_lanes = {ilq_probe_roll_lanes_kernel<T, NX, NP, MU>, 64, size_t(rollout_lanes_lds_elems(d.n, d.m, d.N)) * sizeof(T) + 16};
     }
+    if constexpr (kMayXdyn)  // (a plain-RK4 shape: one rollout per wavefront, no paired or lane-per-candidate form)
+      if (xdyn) {
+        plan.roll = {ilq_roll_kernel<T, NX, NP, MU, true>, 64, lds_proll};
+        plan.proll = {ilq_probe_roll_kernel<T, NX, NP, MU, false, false, true>, 64, lds_proll};
+        plan.proll_fat = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, false, true>, 64, lds_proll};
+      }
   }
   plan.cap = al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
                      : (long long)sa.prm.max_solver_iters + 2;
@@ -1881,6 +1910,12 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
   plan.decide = {ilq_decide_kernel<T, 0, 0, 0>, 64, trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw)};
   plan.proll = plan.proll_fat = {ilq_probe_roll_kernel<T, 0, 0, 0>, 64, lds_roll};
   plan.prows = {p->has_expression ? ilq_probe_rows_kernel<T, 0, 0, 0, kExprProg> : ilq_probe_rows_kernel<T, 0, 0, 0>, 64, rows_maps_bytes(d) + probe_rows_elems(d, 0, sa.rows_cw) * sizeof(T)};
+  if (p->has_expression_dynamics) {  // (kExprDynProg: kernels of their own, ilqg_solve.hpp)
+    plan.roll = {ilq_roll_kernel<T, 0, 0, 0, true>, 64, lds_roll};
+    plan.rows = {ilq_rows_kernel<T, 0, 0, 0, kExprDynProg>, 64, lds_rows};
+    plan.proll = plan.proll_fat = {ilq_probe_roll_kernel<T, 0, 0, 0, false, false, true>, 64, lds_roll};
+    plan.prows = {ilq_probe_rows_kernel<T, 0, 0, 0, kExprDynProg>, 64, plan.prows.lds};
+  }
   plan.sweep = {gen_lq_kernel<T>, kGenSweepThreads, lds_lq};
   plan.exit = {ilq_exit_kernel<T, 0, 0, 0>, 64, quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T)};
   plan.exit_fill_first = true; plan.read_restarts = sa.al_mode != 0;
@@ -2179,6 +2214,13 @@ ilqg_status ilqg_expression_check(const ilqg_problem_desc* desc, int32_t term) {
   if (!desc) return fail(ILQG_ERR_INVALID, "null argument");
   if (term < 0 || term >= desc->num_terms || !desc->terms)
     return fail(ILQG_ERR_INVALID, "ilqg_expression_check: term index out of range (the problem has " + std::to_string(desc->num_terms) + " terms)");
+  if (desc->terms[term].kind == ILQG_DYN_ROW_EXPRESSION) {  // a state row of an expression subsystem (check_dynamics_row_term)
+    ProblemTables tables;
+    using Step = ilqg_status (*)(const ilqg_problem_desc&, ProblemTables*);
+    for (Step step : {check_problem_sizes, flatten_subsystems})
+      if (ilqg_status s = step(*desc, &tables)) return s;
+    return check_dynamics_row_term(*desc, tables.dev, term);
+  }
   if (!term_is_expression(desc->terms[term].kind))  // (either kind; the message is the one the first kind came with)
     return fail(ILQG_ERR_INVALID, "ilqg_expression_check: term " + std::to_string(term) + " is not an ILQG_COST_EXPRESSION term");
   ProblemTables tables;
@@ -2472,7 +2514,8 @@ ilqg_status ilqg_rollout_batch(const ilqg_problem* p, int32_t batch, const void*
   [&]() -> ilqg_status {                                                                                     \
     RolloutBatchArgs<TY_> g{(const TY_*)x0, (const TY_*)xs_ref, (const TY_*)us_ref, (const TY_*)P, (const TY_*)alpha,    \
                           (const TY_*)alpha_scale, (TY_*)xs, (TY_*)us, active};                                    \
-    hipLaunchKernelGGL(rollout_kernel<TY_>, dim3(batch), dim3(64), rollout_lds_elems(d.n, d.m) * sizeof(TY_),    \
+    auto kern = p->has_expression_dynamics ? rollout_kernel<TY_, true> : rollout_kernel<TY_, false>;             \
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(64), rollout_lds_elems(d.n, d.m) * sizeof(TY_),                  \
                        (hipStream_t)stream, d, g);                                                           \
     HIP_TRY(hipGetLastError());                                                                              \
     return ILQG_OK;                                                                                          \
@@ -2655,7 +2698,8 @@ ilqg_status ilqg_receding_horizon_shift_batch(const ilqg_problem* p, int32_t bat
     g.x = (const TY_*)x0; g.t = t0; g.planner_runtime = planner_runtime;                                           \
     g.xs = (TY_*)xs; g.us = (TY_*)us; g.P = (TY_*)P; g.alpha = (TY_*)alpha; g.x0_next = (TY_*)x0_next;             \
     g.first_step = first_step;                                                                                     \
-    hipLaunchKernelGGL(receding_sync_kernel<TY_>, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(TY_),                \
+    auto kern = p->has_expression_dynamics ? receding_sync_kernel<TY_, true> : receding_sync_kernel<TY_, false>;     \
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(TY_),                                 \
                        (hipStream_t)stream, d, g);                                                                 \
     HIP_TRY(hipGetLastError());                                                                                  \
     return ILQG_OK;                                                                                              \
@@ -2673,7 +2717,8 @@ static ilqg_status launch_strategy_costs(const ilqg_problem* p, int32_t batch, c
     StrategyCostArgs<TY_> g{(const TY_*)x0, (const TY_*)xs, (const TY_*)us, (const TY_*)P, (const TY_*)alpha,      \
                             (TY_*)costs, TY_(eps), open_loop, euler, batch};                                       \
     const size_t lds = quad_tables_bytes(d, sizeof(TY_)) + strategy_cost_lds_elems(d.n, d.m, d.num_terms) * sizeof(TY_); \
-    hipLaunchKernelGGL(strategy_costs_kernel<TY_>, dim3(batch, moves), dim3(64), lds, (hipStream_t)stream, d, g);  \
+    auto kern = p->has_expression_dynamics ? strategy_costs_kernel<TY_, true> : strategy_costs_kernel<TY_, false>; \
+    hipLaunchKernelGGL(kern, dim3(batch, moves), dim3(64), lds, (hipStream_t)stream, d, g);                       \
     HIP_TRY(hipGetLastError());                                                                                  \
     return ILQG_OK;                                                                                              \
   }()
@@ -2786,7 +2831,8 @@ ilqg_status ilqg_plan_integrate_batch(const ilqg_problem* p, int32_t batch, int3
     g.plan = PlanBuffers<TY_>{(TY_*)plan_xs, (TY_*)plan_us, (TY_*)plan_P, (TY_*)plan_alpha, (int*)plan_len,       \
                               (double*)plan_t0, 0.0, plan_rows};                                                   \
     g.t_from = t_from; g.t_to = t_to; g.must_contain = must_contain; g.x = (TY_*)x; g.active = active;             \
-    hipLaunchKernelGGL(plan_integrate_kernel<TY_>, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(TY_),               \
+    auto kern = p->has_expression_dynamics ? plan_integrate_kernel<TY_, true> : plan_integrate_kernel<TY_, false>;   \
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(TY_),                                 \
                        (hipStream_t)stream, d, g);                                                                 \
     HIP_TRY(hipGetLastError());                                                                                  \
     return ILQG_OK;                                                                                              \
@@ -2819,7 +2865,8 @@ ilqg_status ilqg_receding_horizon_sync_batch(const ilqg_problem* p, int32_t batc
     g.x = (const TY_*)x; g.t = t; g.planner_runtime = planner_runtime;                                             \
     g.xs = (TY_*)xs; g.us = (TY_*)us; g.P = (TY_*)P; g.alpha = (TY_*)alpha; g.x0_next = (TY_*)x0_next;             \
     g.solve_t0 = solve_t0; g.first_step = first_step; g.active = active;                                           \
-    hipLaunchKernelGGL(receding_sync_kernel<TY_>, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(TY_),                \
+    auto kern = p->has_expression_dynamics ? receding_sync_kernel<TY_, true> : receding_sync_kernel<TY_, false>;     \
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(TY_),                                 \
                        (hipStream_t)stream, d, g);                                                                 \
     HIP_TRY(hipGetLastError());                                                                                  \
     return ILQG_OK;                                                                                              \

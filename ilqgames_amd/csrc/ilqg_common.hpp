@@ -120,6 +120,11 @@ struct DevProblem {
   // handle's [batch][total_segs][kSegStride] table and this is total_segs * kSegStride, the elements between two
   // instances' tables; 0: every instance reads the one baked table.
   int seg_inst_stride;
+  // ILQG_DYN_EXPRESSION subsystems (ilqg.h): where subsystem s's row directory starts in the dense table (dense_f /
+  // dense_d), four words per state row r — [offset of the row's program block in the same table, input X, input Y or -1,
+  // the row term's weight] — built by ilqg_problem_create (build_dynamics_rows).  Read by the expression integrator
+  // (sub_eval_expr, ilqg_models.hpp) alone; 0 for every other kind.  (Last: no other field moves.)
+  int dyn_rows[kMaxPlayers];
 };
 
 // Row b of the bound value table (null: nothing bound).  b is the instance a whole wavefront works on; the pointer is

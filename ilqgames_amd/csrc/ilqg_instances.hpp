@@ -18,9 +18,9 @@ const char* cost_kind_name(int kind) {  // ilqg_cost_kind without its prefix
       "QUADRATIC_DIFFERENCE", "ORIENTATION", "QUADRATIC_NORM", "SEMIQUADRATIC_NORM", "RELATIVE_DISTANCE",
       "LOCALLY_CONVEX_PROXIMITY", "CURVATURE", "CONSTRAINT_POLYLINE2_SIGNED_DISTANCE", "NOMINAL_PATH_LENGTH",
       "ROUTE_PROGRESS", "WEIGHTED_CONVEX_PROXIMITY", "CONSTRAINT_AFFINE_SCALAR", "CONSTRAINT_AFFINE_VECTOR", "EXPRESSION",
-      "CONSTRAINT_EXPRESSION"};
-  static_assert(ILQG_COST_QUADRATIC == 1 && ILQG_CONSTRAINT_EXPRESSION == sizeof(names) / sizeof(names[0]), "one name per kind");
-  return kind >= 1 && kind <= ILQG_CONSTRAINT_EXPRESSION ? names[kind - 1] : "unknown kind";
+      "CONSTRAINT_EXPRESSION", "DYN_ROW_EXPRESSION"};
+  static_assert(ILQG_COST_QUADRATIC == 1 && ILQG_DYN_ROW_EXPRESSION == sizeof(names) / sizeof(names[0]), "one name per kind");
+  return kind >= 1 && kind <= ILQG_DYN_ROW_EXPRESSION ? names[kind - 1] : "unknown kind";
 }
 // Does a term of this kind read the field (the table of ilqg.h; ilqg_models.hpp: term_evaluate_leaf_of and the row ops)?
 // Null: yes; else why not.
@@ -53,6 +53,8 @@ const char* instance_param_refusal(int kind, int field) {
     case ILQG_COST_WEIGHTED_CONVEX_PROXIMITY:
     case ILQG_COST_EXPRESSION:
     case ILQG_CONSTRAINT_EXPRESSION: return nullptr;  // (what its program pushes: PUSH_WEIGHT, PUSH_VALUE)
+    case ILQG_DYN_ROW_EXPRESSION:
+      return "a dynamics row is no cost term: its VALUE is the subsystem's param0 (declare the subsystem), its weight is baked";
   }
   return "unknown cost kind";
 }
@@ -81,9 +83,9 @@ ilqg_status instance_params_check_terms(int num_terms, const ilqg_cost_term* ter
 const char* dyn_kind_name(int kind) {  // ilqg_dyn_kind without its prefix
   static const char* const names[] = {"UNICYCLE_4D", "CAR_5D", "CAR_6D", "UNICYCLE_4D_DISTURBED", "PLANAR_DISTURBANCE",
                                       "DUBINS_CAR", "AIR_3D_EVADER", "AIR_3D_PURSUER", "POINT_MASS_2D", "UNICYCLE_5D",
-                                      "CAR_7D", "DELAYED_DUBINS_CAR"};
-  static_assert(ILQG_DYN_UNICYCLE_4D == 1 && ILQG_DYN_DELAYED_DUBINS_CAR == sizeof(names) / sizeof(names[0]), "one name per kind");
-  return kind >= 1 && kind <= ILQG_DYN_DELAYED_DUBINS_CAR ? names[kind - 1] : "unknown kind";
+                                      "CAR_7D", "DELAYED_DUBINS_CAR", "EXPRESSION"};
+  static_assert(ILQG_DYN_UNICYCLE_4D == 1 && ILQG_DYN_EXPRESSION == sizeof(names) / sizeof(names[0]), "one name per kind");
+  return kind >= 1 && kind <= ILQG_DYN_EXPRESSION ? names[kind - 1] : "unknown kind";
 }
 bool subsystem_reads_param0(int kind) {
   switch (kind) {
@@ -94,6 +96,7 @@ bool subsystem_reads_param0(int kind) {
     case ILQG_DYN_DELAYED_DUBINS_CAR:  // speed
     case ILQG_DYN_AIR_3D_EVADER:
     case ILQG_DYN_AIR_3D_PURSUER: return true;  // their speeds
+    case ILQG_DYN_EXPRESSION: return true;      // what its rows' programs push as VALUE
   }
   return false;
 }

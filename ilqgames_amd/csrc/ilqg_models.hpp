@@ -115,7 +115,8 @@ __device__ __forceinline__ void sub_integrate(int kind, T L, double interval, T*
 // kind through sub_eval: blocks of up to 8 states, the plain RK4 of MultiPlayerDynamicalSystem::Integrate.
 constexpr int kSubStatesMax = 8;
 __host__ __device__ inline bool is_plain_rk4_kind(int kind) {
-  return kind == ILQG_DYN_UNICYCLE_5D || kind == ILQG_DYN_CAR_7D || kind == ILQG_DYN_DELAYED_DUBINS_CAR;
+  return kind == ILQG_DYN_UNICYCLE_5D || kind == ILQG_DYN_CAR_7D || kind == ILQG_DYN_DELAYED_DUBINS_CAR ||
+         kind == ILQG_DYN_EXPRESSION;
 }
 // What a description's subsystem of this kind must look like (host only: creation validates against it).  xdim < 0: no
 // such kind; `paired`: a row of a two-player model with one shared state, which only occurs beside its partner.
@@ -134,6 +135,7 @@ inline SubsystemShape subsystem_shape(int kind) {
     case ILQG_DYN_UNICYCLE_5D: return {5, 2, false};
     case ILQG_DYN_CAR_7D: return {7, 2, false};
     case ILQG_DYN_DELAYED_DUBINS_CAR: return {4, 1, false};
+    case ILQG_DYN_EXPRESSION: return {0, 0, false};  // any 1 <= xdim <= kSubStatesMax, 1 <= udim <= 2 (flatten_subsystems)
   }
   return {-1, 2, false};
 }
@@ -192,6 +194,91 @@ __device__ __forceinline__ void sub_integrate8(int kind, T L, double interval, T
     }
   }
 }
+
+// ---- ILQG_DYN_EXPRESSION: a subsystem whose state rates are expression programs (ilqg.h) ----
+// The programs and the subsystem's row directory (DevProblem::dyn_rows: per row [program offset, input X, input Y or -1,
+// weight]) are read from the dense table through a constant-address-space view: `dir`, `xd` and every word read are
+// wave-uniform where the caller's subsystem is (scalar loads, scalar branches over the opcode stream), so a caller whose
+// lanes hold different subsystems walks them one after the other with the subsystem's lanes active.  No contraction:
+// every product and sum below rounds on its own, so a trajectory's bits depend neither on which lane evaluates a row nor
+// on the kernel the code is inlined into.
+template <typename T> struct DenseConst { typedef const __attribute__((address_space(4))) T* type; };
+template <typename T>
+__device__ __forceinline__ typename DenseConst<T>::type dense_const(const DevProblem& p);
+template <> __device__ __forceinline__ DenseConst<float>::type dense_const<float>(const DevProblem& p) { return (DenseConst<float>::type)p.dense_f; }
+template <> __device__ __forceinline__ DenseConst<double>::type dense_const<double>(const DevProblem& p) { return (DenseConst<double>::type)p.dense_d; }
+
+// entry i of the subsystem's [x (xd) | u]: selects over the register copy (no dynamically indexed array)
+template <typename T>
+__device__ __forceinline__ T sub_expr_input(int i, int xd, const T* x, T u0, T u1) {
+  T v = x[0];
+#pragma unroll
+  for (int e = 1; e < kSubStatesMax; e++) v = (i == e) ? x[e] : v;
+  const T u = (i == xd) ? u0 : u1;
+  return i < xd ? v : u;
+}
+// xdot of an expression subsystem: row r is the value of its program (expr_eval_value) at its one or two inputs, with
+// VALUE = the subsystem's param0 and WEIGHT = the row term's weight; rows past xd are zero
+template <typename T>
+__device__ __forceinline__ void sub_eval_expr(typename DenseConst<T>::type dense, int dir, int xd, T param, const T* x, T u0,
+                                              T u1, T* f) {
+#pragma unroll
+  for (int e = 0; e < kSubStatesMax; e++) f[e] = T(0);
+#pragma unroll 1
+  for (int r = 0; r < xd; r++) {
+    typename DenseConst<T>::type row = dense + dir + 4 * r;
+    const int po = int(row[0]), xi = int(row[1]), yi = int(row[2]);
+    const T xv = sub_expr_input<T>(xi, xd, x, u0, u1);
+    const T yv = yi >= 0 ? sub_expr_input<T>(yi, xd, x, u0, u1) : T(0);
+    const T v = expr_eval_value<T>(dense + po, T(row[3]), param, xv, yv);
+#pragma unroll
+    for (int e = 0; e < kSubStatesMax; e++) f[e] = (e == r) ? v : f[e];
+  }
+}
+// MultiPlayerDynamicalSystem::Integrate's RK4 with two half-steps, in sub_integrate8's operation order — k_j = h f,
+// the stage points x + k1 / 2, x + k2 / 2, x + k3, the update (k1 + 2 (k2 + k3) + k4) / 6 — with the four stages as one
+// loop around the one copy of the evaluator
+#pragma clang fp contract(off)
+template <typename T>
+__device__ __forceinline__ void sub_integrate_expr(typename DenseConst<T>::type dense, int dir, int xd, T param,
+                                                   double interval, T* x, T u0, T u1) {
+  constexpr int XS = kSubStatesMax;
+  const T h = T(interval / 2.0);
+#pragma unroll 1
+  for (int s = 0; s < 2; s++) {
+    T k1[XS], k23[XS], xt[XS];
+#pragma unroll
+    for (int i = 0; i < XS; i++) { xt[i] = x[i]; k1[i] = T(0); k23[i] = T(0); }
+#pragma unroll 1
+    for (int j = 0; j < 4; j++) {
+      T f[XS];
+      sub_eval_expr<T>(dense, dir, xd, param, xt, u0, u1, f);
+      if (j == 0) {
+#pragma unroll
+        for (int i = 0; i < XS; i++) { k1[i] = h * f[i]; xt[i] = x[i] + T(0.5) * k1[i]; }
+      } else if (j == 1) {
+#pragma unroll
+        for (int i = 0; i < XS; i++) { k23[i] = h * f[i]; xt[i] = x[i] + T(0.5) * k23[i]; }
+      } else if (j == 2) {
+#pragma unroll
+        for (int i = 0; i < XS; i++) { const T k3 = h * f[i]; k23[i] = k23[i] + k3; xt[i] = x[i] + k3; }
+      } else {
+#pragma unroll
+        for (int i = 0; i < XS; i++) { const T k4 = h * f[i]; x[i] += (k1[i] + T(2.0) * k23[i] + k4) / T(6.0); }
+      }
+    }
+  }
+}
+// one explicit Euler step (MultiPlayerDynamicalSystem::Integrate's other form, the equilibrium checks' option)
+template <typename T>
+__device__ __forceinline__ void sub_euler_expr(typename DenseConst<T>::type dense, int dir, int xd, T param, double interval,
+                                               T* x, T u0, T u1) {
+  T f[kSubStatesMax];
+  sub_eval_expr<T>(dense, dir, xd, param, x, u0, u1, f);
+#pragma unroll
+  for (int i = 0; i < kSubStatesMax; i++) x[i] += T(interval) * f[i];
+}
+#pragma clang fp contract(fast)
 
 template <typename T> __device__ __forceinline__ void t_sincos(T x, T* s, T* c);
 template <> __device__ __forceinline__ void t_sincos<float>(float x, float* s, float* c) { sincosf(x, s, c); }

@@ -23,7 +23,8 @@ __host__ __device__ inline size_t strategy_cost_lds_elems(int n, int m, int num_
   return size_t(2 * (n + m) + (num_terms > 0 ? num_terms : 1) + 4 + 2);  // +2: a one-control model's unused second input
 }
 
-template <typename T>
+// XDYN: the problem holds an expression subsystem (sub_integrate_expr / sub_euler_expr, ilqg_models.hpp): a kernel of its own
+template <typename T, bool XDYN = false>
 __global__ void __launch_bounds__(64) strategy_costs_kernel(DevProblem p, StrategyCostArgs<T> a) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const QuadTables<T> tb = quad_tables_load<T>(p, smem_raw, int(blockIdx.x));
@@ -66,7 +67,20 @@ __global__ void __launch_bounds__(64) strategy_costs_kernel(DevProblem p, Strate
       snx[n + t] = u;
     }
     __syncthreads();
-    if (t < N) {  // dynamics.Integrate(t, dt, x, us) (:85)
+    if constexpr (XDYN) {  // the expression subsystems one after the other, each on its own lane: uniform program reads
+      for (int s = 0; s < N; s++) {
+        if (p.sub_kind[s] != ILQG_DYN_EXPRESSION) continue;
+        const int xo = p.xoff[s], uo = p.uoff[s], xd = p.xoff[s + 1] - xo;
+        if (t == s) {
+          T xj[kSubStatesMax];
+          for (int e = 0; e < kSubStatesMax; e++) xj[e] = e < xd ? sx[xo + e] : T(0);
+          if (a.euler) sub_euler_expr<T>(dense_const<T>(p), p.dyn_rows[s], xd, Lp, p.dt, xj, sx[n + uo], sx[n + uo + 1]);
+          else sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], xd, Lp, p.dt, xj, sx[n + uo], sx[n + uo + 1]);
+          for (int e = 0; e < xd; e++) snx[xo + e] = xj[e];
+        }
+      }
+    }
+    if (t < N && !(XDYN && p.sub_kind[t] == ILQG_DYN_EXPRESSION)) {  // dynamics.Integrate(t, dt, x, us) (:85)
       const int xo = p.xoff[t], uo = p.uoff[t], xd = p.xoff[t + 1] - xo;
       T xj[kSubStatesMax], f[kSubStatesMax];
       for (int e = 0; e < kSubStatesMax; e++) xj[e] = e < xd ? sx[xo + e] : T(0);

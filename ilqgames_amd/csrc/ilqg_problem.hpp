@@ -25,7 +25,7 @@ namespace ilqg {
 // strides by its own constant (ilqg_time_nominal.hpp includes no device header): one layout
 static_assert(kTimeNominalSegStride == kSegStride, "ilqg_time_nominal.hpp and ilqg_common.hpp disagree on a segment's scalars");
 // the kernels take the DevProblem by value: its layout is part of every launch
-static_assert(sizeof(DevProblem) == 840, "DevProblem's size changed");
+static_assert(sizeof(DevProblem) == 872, "DevProblem's size changed");  // (840 + dyn_rows)
 
 // LoopTimer (include/ilqgames/utils/loop_timer.h:60-98, src/loop_timer.cpp:55-92): the last ten iteration times
 struct LoopTimer {
@@ -127,6 +127,8 @@ struct ilqg_problem {
   int mu_uniform = 0;
   bool has_route_progress = false;  // a RouteProgressCost term: its tables are a first solve's (initial time 0)
   bool has_expression = false;  // an expression cost: the row kernels with its evaluator in them run (kExprProg, ilqg_solve.hpp)
+  bool has_expression_dynamics = false;  // an ILQG_DYN_EXPRESSION subsystem: the kernels with its integrator and its
+                                         // linearisation in them run (kExprDynProg, ilqg_solve.hpp)
   int last_schedule = 0;  // ILQG_SCHEDULE_* of the last solve (ilqg_problem_last_schedule)
   bool generic = false;  // no specialised instantiation holds this problem: every entry point runs the run-time-dimensioned kernels
   // The solver object's LoopTimer over its iterations, kept across solves as the reference's member is (only solves with a
@@ -196,6 +198,7 @@ struct ProblemTables {
                             // (RowProgramHost::b_constant on a specialised instantiation): ilqg_sweep_b_structure_build
   bool has_route_progress = false;
   bool has_expression = false;  // an expression cost (build_expression_blocks)
+  bool has_expression_dynamics = false;  // an expression subsystem (flatten_subsystems)
   bool generic = false;  // no specialised instantiation holds the problem
 };
 
@@ -216,14 +219,28 @@ ilqg_status flatten_subsystems(const ilqg_problem_desc& desc, ProblemTables* t) 
   // TwoPlayerUnicycle4D is exactly the pair (disturbed unicycle, disturbance) and nothing else; Air3D likewise
   const bool is_pair = desc.num_players == 2 && ((kind0 == ILQG_DYN_UNICYCLE_4D_DISTURBED && kind1 == ILQG_DYN_PLANAR_DISTURBANCE) ||
                                                  (kind0 == ILQG_DYN_AIR_3D_EVADER && kind1 == ILQG_DYN_AIR_3D_PURSUER));
+  for (int i = 0; i < d.N; i++)  // an expression subsystem stands beside single-player models only
+    if (desc.subsystems[i].kind == ILQG_DYN_EXPRESSION)
+      for (int q = 0; q < d.N; q++)
+        if (subsystem_shape(desc.subsystems[q].kind).paired || desc.subsystems[q].kind == ILQG_DYN_POINT_MASS_2D)
+          return fail(ILQG_ERR_UNSUPPORTED, "subsystem " + std::to_string(i) + ": an expression subsystem (kind 13) does not occur "
+                                            "beside the shared-state kinds (4, 5, 7, 8) or in a point-mass game (subsystem " +
+                                                std::to_string(q) + ")");
   for (int i = 0; i < d.N; i++) {
     const ilqg_subsystem& sub = desc.subsystems[i];
     const SubsystemShape want = subsystem_shape(sub.kind);
-    if (want.paired && !is_pair)
+    if (sub.kind == ILQG_DYN_EXPRESSION) {
+      if (sub.xdim < 1 || sub.xdim > kSubStatesMax || sub.udim < 1 || sub.udim > 2)
+        return fail(ILQG_ERR_UNSUPPORTED, "subsystem " + std::to_string(i) + ": an expression subsystem has 1 .. " +
+                                              std::to_string(kSubStatesMax) + " states and 1 or 2 controls (xdim = " +
+                                              std::to_string(sub.xdim) + ", udim = " + std::to_string(sub.udim) + ")");
+      t->has_expression_dynamics = true;
+    } else if (want.paired && !is_pair) {
       return fail(ILQG_ERR_UNSUPPORTED, "the shared-state kinds only occur as the pairs (4, 5) and (7, 8)");
+    }
     if ((sub.kind == ILQG_DYN_POINT_MASS_2D) != (kind0 == ILQG_DYN_POINT_MASS_2D))
       return fail(ILQG_ERR_UNSUPPORTED, "point masses (kind 9) only occur in games made of point masses");
-    if (want.xdim < 0 || sub.xdim != want.xdim || sub.udim != want.udim)
+    if (sub.kind != ILQG_DYN_EXPRESSION && (want.xdim < 0 || sub.xdim != want.xdim || sub.udim != want.udim))
       return fail(ILQG_ERR_UNSUPPORTED, "unknown subsystem kind / dimension");
     d.sub_kind[i] = sub.kind;
     d.sub_param[i] = sub.param0;
@@ -241,6 +258,7 @@ ilqg_status flatten_subsystems(const ilqg_problem_desc& desc, ProblemTables* t) 
   // DistanceBetween of the first subsystem: (px, py) where the model overrides it (two_player_unicycle_4d.h:141-147
   // too), the whole block where it does not (the two Dubins cars: single_player_dynamical_system.h:69-71)
   d.sync_dist_dims = d.sub_kind[0] == ILQG_DYN_DUBINS_CAR ? 3 : (d.sub_kind[0] == ILQG_DYN_DELAYED_DUBINS_CAR ? 4 : 2);
+  if (d.sub_kind[0] == ILQG_DYN_EXPRESSION) d.sync_dist_dims = d.xoff[1];  // the default DistanceBetween: the whole block
   if (!uniform_udim(d.udim, d.N, &t->mu_uniform)) t->mu_uniform = 0;
   bool plain = false;
   for (int i = 0; i < d.N; i++) plain = plain || is_plain_rk4_kind(d.sub_kind[i]);
@@ -305,6 +323,11 @@ ilqg_status build_term_table(const ilqg_problem_desc& desc, ProblemTables* t) {
         c.kind != ILQG_CONSTRAINT_EXPRESSION)
       return fail(ILQG_ERR_INVALID, "ILQG_FLAG_EQUALITY is only defined for the affine constraints");
     if (c.constraint_slot >= 0 && c.constraint_slot + 1 > nc) nc = c.constraint_slot + 1;
+    if (c.role == ILQG_ROLE_DYNAMICS_ROW || c.kind == ILQG_DYN_ROW_EXPRESSION) {  // not a cost: build_dynamics_rows checks it
+      o.arg_off = 0;
+      o.arg_dim = 0;
+      continue;
+    }
     const bool on_state = o.role == ILQG_ROLE_STATE_COST || o.role == ILQG_ROLE_STATE_CONSTRAINT || o.role == ILQG_ROLE_CHILD;
     o.arg_off = on_state ? 0 : d.n + d.uoff[o.arg];
     o.arg_dim = on_state ? d.n : d.udim[o.arg];
@@ -443,6 +466,99 @@ ilqg_status build_expression_blocks(const ilqg_problem_desc& desc, ProblemTables
   return ILQG_OK;
 }
 
+// What creation checks about one ILQG_DYN_ROW_EXPRESSION term (ilqg.h): its subsystem, its row, its inputs and its
+// program.  `d`: the flattened subsystems.
+ilqg_status check_dynamics_row_term(const ilqg_problem_desc& desc, const DevProblem& d, int ti) {
+  const ilqg_cost_term& c = desc.terms[ti];
+  const std::string term = "dynamics-row term " + std::to_string(ti);
+  if (c.kind != ILQG_DYN_ROW_EXPRESSION || c.role != ILQG_ROLE_DYNAMICS_ROW)
+    return fail(ILQG_ERR_INVALID, term + ": kind ILQG_DYN_ROW_EXPRESSION (26) and role ILQG_ROLE_DYNAMICS_ROW (5) only occur together");
+  if (c.player < 0 || c.player >= d.N)
+    return fail(ILQG_ERR_INVALID, term + ": player = " + std::to_string(c.player) + " names no subsystem");
+  const std::string where = term + " (subsystem " + std::to_string(c.player) + ", row " + std::to_string(c.idx[0]) + "): ";
+  if (d.sub_kind[c.player] != ILQG_DYN_EXPRESSION)
+    return fail(ILQG_ERR_INVALID, where + "the subsystem is not an expression subsystem (kind 13)");
+  const int xdim = d.xoff[c.player + 1] - d.xoff[c.player], udim = d.udim[c.player];
+  if (c.idx[0] < 0 || c.idx[0] >= xdim)
+    return fail(ILQG_ERR_INVALID, where + "the row lies outside the subsystem's " + std::to_string(xdim) + " states");
+  for (int q = 0; q < ti; q++)
+    if (desc.terms[q].kind == ILQG_DYN_ROW_EXPRESSION && desc.terms[q].player == c.player && desc.terms[q].idx[0] == c.idx[0])
+      return fail(ILQG_ERR_INVALID, where + "the row is defined twice (also by term " + std::to_string(q) + ")");
+  if (c.idx[1] < 0 || c.idx[1] >= xdim + udim)
+    return fail(ILQG_ERR_INVALID, where + "input X = " + std::to_string(c.idx[1]) + " is outside the subsystem's [x | u] (dimension " +
+                                      std::to_string(xdim + udim) + ")");
+  if (c.idx[2] != -1 && (c.idx[2] < 0 || c.idx[2] >= xdim + udim))
+    return fail(ILQG_ERR_INVALID, where + "input Y = " + std::to_string(c.idx[2]) + " is neither -1 nor inside the subsystem's [x | u] "
+                                      "(dimension " + std::to_string(xdim + udim) + ")");
+  if (c.idx[2] == c.idx[1]) return fail(ILQG_ERR_INVALID, where + "inputs X and Y name the same entry");
+  if (c.idx[3] != -1) return fail(ILQG_ERR_INVALID, where + "idx[3] must be -1");
+  if (c.arg != -1 || c.constraint_slot != -1)
+    return fail(ILQG_ERR_INVALID, where + "arg and constraint_slot must be -1: a dynamics row is no cost and no constraint");
+  if (c.first_step != 0)
+    return fail(ILQG_ERR_UNSUPPORTED, where + "first_step = " + std::to_string(c.first_step) + ": a dynamics row cannot be gated");
+  for (int q = 0; q < desc.num_terms; q++)
+    if (desc.terms[q].kind == ILQG_COST_EXTREME_VALUE && ti >= desc.terms[q].child_begin &&
+        ti < desc.terms[q].child_begin + desc.terms[q].child_count)
+      return fail(ILQG_ERR_INVALID, where + "a dynamics row cannot be an EXTREME_VALUE child");
+  if (desc.dense_params == nullptr || c.polyline < 0 || c.polyline >= desc.num_dense_params)
+    return fail(ILQG_ERR_INVALID, where + "its program block is out of range of ilqg_problem_desc::dense_params");
+  const ExprCheck chk = expr_validate(desc.dense_params + c.polyline, (long long)desc.num_dense_params - c.polyline, c.idx[2] >= 0);
+  const std::string at = where + "op " + std::to_string(chk.op) + ": ";
+  switch (chk.fault) {
+    case EXPR_OK: return ILQG_OK;
+    case EXPR_BAD_LENGTH:
+      return fail(ILQG_ERR_INVALID, where + "program length L must be a whole number in 1 .. " + std::to_string(ILQG_EXPR_MAX_OPS));
+    case EXPR_OUT_OF_RANGE:
+      return fail(ILQG_ERR_INVALID, where + "its program block is out of range of ilqg_problem_desc::dense_params");
+    case EXPR_BAD_OPCODE: return fail(ILQG_ERR_UNSUPPORTED, at + "unknown opcode");
+    case EXPR_UNDERFLOW: return fail(ILQG_ERR_INVALID, at + "stack underflow");
+    case EXPR_OVERFLOW:
+      return fail(ILQG_ERR_UNSUPPORTED, at + "stack overflow (more than " + std::to_string(ILQG_EXPR_MAX_DEPTH) + " entries)");
+    case EXPR_NO_SECOND_INPUT: return fail(ILQG_ERR_INVALID, at + "PUSH_Y in a program without a second input (Y = -1)");
+  }
+  return fail(ILQG_ERR_INVALID, where + "the program ends with " + std::to_string(chk.depth) + " entries on the stack: exactly "
+                                    "one, the row's rate, must be left");
+}
+
+// The rows of the expression subsystems: every dynamics-row term checked, every row of every expression subsystem
+// defined once; the programs go behind the other blocks of the dense table (DevTerm::polyline becomes the block's offset,
+// DevTerm::child_count 1 where the whole program is one PUSH_X: build_row_program makes that entry the constant dt), and
+// behind them each subsystem's row directory (DevProblem::dyn_rows)
+ilqg_status build_dynamics_rows(const ilqg_problem_desc& desc, ProblemTables* t) {
+  DevProblem& d = t->dev;
+  for (int ti = 0; ti < desc.num_terms; ti++) {
+    const ilqg_cost_term& c = desc.terms[ti];
+    if (c.kind != ILQG_DYN_ROW_EXPRESSION && c.role != ILQG_ROLE_DYNAMICS_ROW) continue;
+    if (const ilqg_status s = check_dynamics_row_term(desc, d, ti)) return s;
+    DevTerm& o = t->terms[ti];
+    const float* src = desc.dense_params + c.polyline;
+    const int count = 1 + 2 * int(src[0]);
+    o.polyline = int(t->dense.f.size());
+    o.child_begin = 0;
+    o.child_count = (int(src[0]) == 1 && int(src[1]) == ILQG_EXPR_PUSH_X) ? 1 : 0;
+    t->dense.f.insert(t->dense.f.end(), src, src + count);
+    t->dense.d.insert(t->dense.d.end(), src, src + count);
+  }
+  for (int s = 0; s < d.N; s++) {
+    if (d.sub_kind[s] != ILQG_DYN_EXPRESSION) continue;
+    const int xdim = d.xoff[s + 1] - d.xoff[s];
+    d.dyn_rows[s] = int(t->dense.f.size());
+    for (int r = 0; r < xdim; r++) {
+      const DevTerm* row = nullptr;
+      for (int ti = 0; ti < desc.num_terms; ti++)
+        if (t->terms[ti].kind == ILQG_DYN_ROW_EXPRESSION && t->terms[ti].player == s && t->terms[ti].idx[0] == r) row = &t->terms[ti];
+      if (!row)
+        return fail(ILQG_ERR_INVALID, "subsystem " + std::to_string(s) + ", row " + std::to_string(r) + ": an expression subsystem's "
+                                      "row has no ILQG_DYN_ROW_EXPRESSION term");
+      for (float v : {float(row->polyline), float(row->idx[1]), float(row->idx[2]), row->weight}) {
+        t->dense.f.push_back(v);
+        t->dense.d.push_back(double(v));
+      }
+    }
+  }
+  return ILQG_OK;
+}
+
 // The polylines, and the LineSegment2 objects of each (line_segment2.h:55-62) with its two shortcuts
 // (DevProblem::segs_f / segs_d), each precision from the points' floats in its own arithmetic
 ilqg_status build_segments(const ilqg_problem_desc& desc, ProblemTables* t) {
@@ -565,7 +681,7 @@ ilqg_status build_problem_tables(const ilqg_problem_desc& desc, ProblemTables* t
   *t = ProblemTables();
   using Step = ilqg_status (*)(const ilqg_problem_desc&, ProblemTables*);
   for (Step step : {check_problem_sizes, flatten_subsystems, build_pair_table, build_term_table, build_affine_blocks,
-                    build_expression_blocks, build_segments, build_time_nominals, build_cost_order, build_row_program_and_match})
+                    build_expression_blocks, build_dynamics_rows, build_segments, build_time_nominals, build_cost_order, build_row_program_and_match})
     if (ilqg_status s = step(desc, t)) return s;
   return ILQG_OK;
 }
@@ -620,6 +736,7 @@ ilqg_status upload_problem(const ilqg_problem_desc& desc, const ProblemTables& t
   p->mu_uniform = t.mu_uniform;
   p->has_route_progress = t.has_route_progress;
   p->has_expression = t.has_expression;
+  p->has_expression_dynamics = t.has_expression_dynamics;
   p->generic = t.generic;
   p->tnom_tables = t.tnom_tables;
   // the row program's device image: the program, then per op the per-instance column of its weight / value (none: -1)

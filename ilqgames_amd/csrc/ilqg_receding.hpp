@@ -27,7 +27,8 @@ struct PlanRef {  // one instance's stored plan
 
 // State stepping under a stored plan: Strategy::operator() (strategy.h:73-76) + Integrate (RK4, two sub-steps).
 // sx [n] holds the state, su [m] the controls; every thread of the wavefront calls.
-template <typename T>
+// XDYN: the problem holds an expression subsystem (sub_integrate_expr, ilqg_models.hpp): kernels of their own
+template <typename T, bool XDYN = false>
 struct PlanStepper {
   const DevProblem& p;
   PlanRef<T> pl;
@@ -54,7 +55,19 @@ struct PlanStepper {
     __syncthreads();
   }
   __device__ __forceinline__ void integrate(double interval) {
-    if (t < p.N) {
+    if constexpr (XDYN) {  // the expression subsystems one after the other, each on its own lane: uniform program reads
+      for (int s = 0; s < p.N; s++) {
+        if (p.sub_kind[s] != ILQG_DYN_EXPRESSION) continue;
+        const int xo = p.xoff[s], uo = p.uoff[s], xd = p.xoff[s + 1] - xo;
+        if (t == s) {
+          T xj[kSubStatesMax];
+          for (int e = 0; e < kSubStatesMax; e++) xj[e] = e < xd ? sx[xo + e] : T(0);
+          sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], xd, Lp, interval, xj, su[uo], su[uo + 1]);
+          for (int e = 0; e < xd; e++) sx[xo + e] = xj[e];
+        }
+      }
+    }
+    if (t < p.N && !(XDYN && p.sub_kind[t] == ILQG_DYN_EXPRESSION)) {
       const int xo = p.xoff[t], uo = p.uoff[t], xd = p.xoff[t + 1] - xo;
       T xj[kSubStatesMax];
       for (int e = 0; e < kSubStatesMax; e++) xj[e] = e < xd ? sx[xo + e] : T(0);
@@ -92,8 +105,8 @@ struct PlanStepper {
 
 // The stepper of instance b: the subsystems' parameters are read here, once — the baked ones, or with per-instance
 // values bound (DevProblem::inst_values) and the subsystem declared, row b's
-template <typename T>
-__device__ __forceinline__ PlanStepper<T> plan_stepper(const DevProblem& p, const PlanRef<T>& pl, T* sx, T* su, int t, int b) {
+template <typename T, bool XDYN = false>
+__device__ __forceinline__ PlanStepper<T, XDYN> plan_stepper(const DevProblem& p, const PlanRef<T>& pl, T* sx, T* su, int t, int b) {
   const float* const iv = instance_values(p, b);
   T Lp = T(0), Lp_next = T(0);
   if (t < p.N) {
@@ -101,7 +114,7 @@ __device__ __forceinline__ PlanStepper<T> plan_stepper(const DevProblem& p, cons
     // t + 1 < N: flatten_subsystems (ilqg_problem.hpp) admits the evader only as row 0 of the pair (evader, pursuer)
     if (p.sub_kind[t] == ILQG_DYN_AIR_3D_EVADER) Lp_next = T(subsystem_param(p, iv, t + 1));
   }
-  return PlanStepper<T>{p, pl, sx, su, t, Lp, Lp_next};
+  return PlanStepper<T, XDYN>{p, pl, sx, su, t, Lp, Lp_next};
 }
 
 template <typename T>
@@ -126,7 +139,7 @@ struct PlanIntegrateArgs {
   int* active;  // [B] in/out
 };
 
-template <typename T>
+template <typename T, bool XDYN = false>
 __global__ void __launch_bounds__(64) plan_integrate_kernel(DevProblem p, PlanIntegrateArgs<T> a) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* sx = reinterpret_cast<T*>(smem_raw);
@@ -149,7 +162,7 @@ __global__ void __launch_bounds__(64) plan_integrate_kernel(DevProblem p, PlanIn
   }
   if (t < p.n) sx[t] = a.x[b * p.n + t];
   __syncthreads();
-  PlanStepper<T> st = plan_stepper<T>(p, pl, sx, su, t, int(b));
+  PlanStepper<T, XDYN> st = plan_stepper<T, XDYN>(p, pl, sx, su, t, int(b));
   if (a.t_from > pl.t0) st.to_next_step(a.t_from);
   st.whole_steps(int(current) + 1, int(final_step));
   st.from_prior_step(a.t_to);
@@ -169,7 +182,7 @@ struct RecedingArgs {
   int* active;                   // [B] in/out (nullable): cleared where the reference would CHECK-abort
 };
 
-template <typename T>
+template <typename T, bool XDYN = false>
 __global__ void __launch_bounds__(64) receding_sync_kernel(DevProblem p, RecedingArgs<T> a) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* sx = reinterpret_cast<T*>(smem_raw);
@@ -209,7 +222,7 @@ __global__ void __launch_bounds__(64) receding_sync_kernel(DevProblem p, Recedin
   }
   if (t < n) sx[t] = a.x[b * n + t];
   __syncthreads();
-  PlanStepper<T> st = plan_stepper<T>(p, pl, sx, su, t, int(b));
+  PlanStepper<T, XDYN> st = plan_stepper<T, XDYN>(p, pl, sx, su, t, int(b));
   st.to_next_step(a.t);
   st.whole_steps(int_begin, int_end);
   // nearest plan state in the first subsystem's metric (concatenated_dynamical_system.cpp:109-113: its position for

@@ -165,6 +165,7 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
     for (int i = 0; i < n; i++) mapA[i + n * i] = short(S_ONE);
     const int op_begin = int(ops.size()) / ROP_WORDS, li_begin = int(linit.size()) / RINIT_WORDS;
     int nl = 0;
+    int jac_scratch = 0;  // the stack of an expression subsystem's jets: unnamed slots behind the pass's, as an expression cost's
     for (int s = 0; s < N; s++) {
       const int kind = d.sub_kind[s], xo = d.xoff[s], uo = d.uoff[s];
       std::vector<std::pair<int, int>> av, bv;  // computed entries, in the order rows_chunk's Jacobian op writes them
@@ -197,6 +198,43 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
         B(-1, 0) = short(S_DT);
       } else if (kind == ILQG_DYN_PLANAR_DISTURBANCE) {
         B(-4, 0) = short(S_DT); B(-3, 1) = short(S_DT);
+      } else if (kind == ILQG_DYN_EXPRESSION) {
+        // One op per state row, from the row's term (ilqg.h: idx = (row, X, Y); DevTerm::polyline = its program's offset in
+        // the dense table, child_count = 1 where the whole program is one PUSH_X — build_dynamics_rows): its d/dX and
+        // d/dY entries are computed slots.  A row that is just one of the other entries is the constant dt, like the
+        // built-in models' rows of that form, and has no op.
+        const int xdim = d.xoff[s + 1] - xo;
+        for (int r = 0; r < xdim; r++) {
+          const DevTerm* row = nullptr;
+          for (int ti = 0; ti < d.num_terms; ti++)
+            if (dt[ti].role == ILQG_ROLE_DYNAMICS_ROW && dt[ti].player == s && dt[ti].idx[0] == r) row = &dt[ti];
+          if (!row) { *err = "row program: an expression subsystem's row has no term"; return false; }
+          const int X = row->idx[1], Y = row->idx[2];
+          auto place = [&](int in) -> short& { return in < xdim ? A(r, in) : B(r, in - xdim); };
+          auto entry = [&](int in) { return in < xdim ? xo + in : n + uo + (in - xdim); };  // of a row's [x | u]
+          if (row->child_count == 1 && X != r) {
+            place(X) = short(S_DT);
+            continue;
+          }
+          DevTerm j{};
+          j.kind = kind;
+          j.idx[0] = entry(X); j.idx[1] = Y >= 0 ? entry(Y) : -1; j.idx[2] = j.idx[3] = -1;
+          j.weight = d.sub_param[s];  // VALUE of the program: the subsystem's param0, where every Jacobian op carries it
+          j.value = row->weight;      // WEIGHT of the program: the row term's second constant
+          j.flags = (X == r ? 1 : 0) | (Y == r ? 2 : 0);  // which of the two entries sits on A's diagonal
+          j.polyline = row->polyline;
+          const int sid_begin = int(sids.size());
+          for (int in : {X, Y}) {
+            if (in < 0) continue;
+            place(in) = short(NPS + nl);
+            sids.push_back(NPS + nl);
+            add_linit(RI_VALUE, 0.0f);
+            nl++;
+          }
+          emit_op(ROP_JACOBIAN, sid_begin, int(sids.size()) - sid_begin, s, j, j, j.polyline, 0);
+          jac_scratch = kExprStackScalars;
+        }
+        continue;
       } else {
         *err = "row program: unknown subsystem kind";
         return false;
@@ -226,7 +264,7 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
     add_region(RA_B, n * m, 0, mapB);
     passes.insert(passes.end(), {op_begin, int(ops.size()) / ROP_WORDS, reg_begin, int(regions.size()) / RREG_WORDS,
                                  li_begin, nl, RPASS_JACOBIANS, 0, 0});
-    if (nl > max_lslots) max_lslots = nl;
+    if (nl + jac_scratch > max_lslots) max_lslots = nl + jac_scratch;
     collect_compact(reg_begin, nl);
   }
 

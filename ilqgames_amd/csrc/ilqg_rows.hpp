@@ -516,13 +516,17 @@ constexpr int kStaticRowStride = 65;
 // ProgDynamicExpr: the interpreter with the evaluator of the expression costs (ilqg_expr.hpp) in it — kernels of their own,
 // launched for a problem that holds such a term, so that every other problem's kernels are the code they always were
 // (the evaluator's jets and the exp / log / sincos bodies inlined behind them cost the fp64 row kernels ~45 registers).
-struct ProgDynamic { static constexpr bool STATIC = false; static constexpr bool kBound = true; static constexpr bool kExpr = false; };
-struct ProgDynamicExpr { static constexpr bool STATIC = false; static constexpr bool kBound = true; static constexpr bool kExpr = true; };
+// ProgDynamicExprDyn: ... and with the linearisation of the ILQG_DYN_EXPRESSION subsystems in its Jacobian op, for the
+// problems that hold one: kernels of their own once more.
+struct ProgDynamic { static constexpr bool STATIC = false; static constexpr bool kBound = true; static constexpr bool kExpr = false; static constexpr bool kExprDyn = false; };
+struct ProgDynamicExpr { static constexpr bool STATIC = false; static constexpr bool kBound = true; static constexpr bool kExpr = true; static constexpr bool kExprDyn = false; };
+struct ProgDynamicExprDyn { static constexpr bool STATIC = false; static constexpr bool kBound = true; static constexpr bool kExpr = true; static constexpr bool kExprDyn = true; };
 template <int ID> struct StaticRowProg;  // { static constexpr int kWords, w[kWords]; } per registered structure
 template <int ID, bool BOUND = false> struct ProgStatic {
   static constexpr bool STATIC = true;
   static constexpr bool kBound = BOUND;
   static constexpr bool kExpr = false;  // no registered structure holds an expression cost
+  static constexpr bool kExprDyn = false;  // ... or an expression subsystem
   typedef StaticRowProg<ID> S;
 };
 
@@ -816,6 +820,29 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
           // the constant entries (dt, -dt, the identity) are in the word maps.
           const int kind = c.kind, xo = c.idx[0], uo = c.idx[1];
           const T L = T(c.weight);
+          if constexpr (PROG::kExprDyn) {
+            if (kind == ILQG_DYN_EXPRESSION) {
+              // One state row of an expression subsystem (ilqg.h), an op of its own: idx[0] / idx[1] are the row's inputs
+              // X and Y (-1: none) as entries of the row's [x | u], the program's offset rides in RO_POLY_FIRST, VALUE is
+              // the subsystem's param0 (the op's weight word, as every Jacobian op carries it) and WEIGHT the row term's
+              // weight (its value word).  The jet is evaluated without second derivatives, its stack behind the pass's
+              // slots like an expression cost's; d/dX goes to the op's first slot, d/dY to the second, each as
+              // T(double(d) * dt), with T(1) in front where RO_FLAGS marks the entry as a diagonal one.
+              const typename ConstPtr<T>::type prog = (typename ConstPtr<T>::type)problem_dense<T>(p) + od.template param<RO_POLY_FIRST>();
+              auto entry = [&](int gi) -> T {
+                if constexpr (XREG) return gi < CN ? T(xrow[gi & (XW - 1)]) : T(urow[(gi - CN) & (UW - 1)]);
+                else return arg[gi * ast + rl];
+              };
+              const bool two = c.idx[1] >= 0;
+              const T ex = entry(c.idx[0]), ey = two ? entry(c.idx[1]) : T(0);
+              ExprJet<T> j;
+              expr_eval_jet<T>(prog, T(c.value), T(c.weight), ex, ey, false, ExprStack<T>{col + (NPS + li_count) * cws, cws}, &j);
+              const T dx = T(double(j.fx) * p.dt), dy = T(double(j.fy) * p.dt);
+              if (nsid > 0) col[sid[0] * cws] = (c.flags & 1) ? T(1) + dx : dx;
+              if (nsid > 1) col[sid[1] * cws] = (c.flags & 2) ? T(1) + dy : dy;
+              return;
+            }
+          }
           const Arg x = rows_make_arg<T, XREG, XW, UW>(xrow, urow, xg, ug, arg, ast, CN, xo, rl, 2, kind == ILQG_DYN_AIR_3D_EVADER ? 0 : 3,
                                                    kind == ILQG_DYN_AIR_3D_EVADER ? 1 : 4, -1);
           auto put = [&](int e, T val) { if (e < nsid) col[sid[e] * cws] = val; };

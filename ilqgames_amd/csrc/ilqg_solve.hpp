@@ -474,10 +474,15 @@ constexpr int kBoundProg = 1000;
 // ... and kExprProg = the interpreter that also evaluates expression costs (ProgDynamicExpr, ilqg_rows.hpp): what the
 // launchers pick for a problem that holds one (ilqg_problem::has_expression)
 constexpr int kExprProg = -1;
+// ... and kExprDynProg = the kernels of a problem that holds an ILQG_DYN_EXPRESSION subsystem (ilqg_problem::
+// has_expression_dynamics): the interpreter that also linearises such a subsystem and evaluates expression costs
+// (ProgDynamicExprDyn, ilqg_rows.hpp), and the rollout with the expression integrator in it (rollout_instance's XDYN)
+constexpr int kExprDynProg = -2;
 constexpr bool prog_is_static(int id) { return id > 0; }
 template <int ID> struct RowProgSel { typedef ProgStatic<(ID >= kBoundProg ? ID - kBoundProg : ID), (ID >= kBoundProg)> type; };
 template <> struct RowProgSel<0> { typedef ProgDynamic type; };
 template <> struct RowProgSel<kExprProg> { typedef ProgDynamicExpr type; };
+template <> struct RowProgSel<kExprDynProg> { typedef ProgDynamicExprDyn type; };
 
 // Row kernel of the split pass: one chunk of rows of instance b, one wave with its own scratch.
 // PROGID: 0 = interpret the problem's row program; k = straight-line code for registered structure k (ilqg_rows.hpp)
@@ -539,7 +544,8 @@ __device__ __forceinline__ T probe_step(const ilqg_solver_params& prm, const Sol
   return step;
 }
 
-template <typename T, int NX, int NP, int MU>
+// XDYN: the problem holds an expression subsystem (rollout_instance's XDYN)
+template <typename T, int NX, int NP, int MU, bool XDYN = false>
 __device__ __forceinline__ void probe_roll_instance(const DevProblem& p, const SolveArgs<T>& sa, int b, int slot, int j,
                                                     T* sm) {
   const InstanceBuffers<T> ib(p, sa, b);
@@ -561,10 +567,10 @@ __device__ __forceinline__ void probe_roll_instance(const DevProblem& p, const S
   ra.iv = instance_values(p, b);
   if constexpr (NX > 0)
     rollout_instance<T, NX, NP * MU, (NX == 4 && NP == 2), (MU == 1), (NX == 3 && NP == 2 && MU == 1),
-                     (NX == 4 * NP && MU == 2 && NP <= 2), dims_use_plain_rk4(NX, NP, MU)>(p, ra, sm, int(threadIdx.x),
-                                                                                           nullptr, nullptr);
+                     (NX == 4 * NP && MU == 2 && NP <= 2), dims_use_plain_rk4(NX, NP, MU), true,
+                     XDYN && dims_use_plain_rk4(NX, NP, MU)>(p, ra, sm, int(threadIdx.x), nullptr, nullptr);
   else
-    rollout_instance_rt<T>(p, ra, sm, int(threadIdx.x));  // the run-time-dimensioned path picks its integrator from the models
+    rollout_instance_rt<T, XDYN>(p, ra, sm, int(threadIdx.x));  // the run-time-dimensioned path picks its integrator from the models
 }
 
 // Two candidates of one instance per wavefront (rollout_pair): j0 and j0 + 1 share the staged gains and references.
@@ -966,11 +972,12 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
       if constexpr (NX > 0)
         rollout_instance<T, NX, NP * MU, (NX == 4 && NP == 2), (MU == 1), (NX == 3 && NP == 2 && MU == 1),
                          (NX == 4 * NP && MU == 2 && NP <= 2), dims_use_plain_rk4(NX, NP, MU),
-                         fused_rollout_room(int(sizeof(T)), NX, NP, MU, PROGID)>(
+                         fused_rollout_room(int(sizeof(T)), NX, NP, MU, PROGID),
+                         (PROGID == kExprDynProg) && dims_use_plain_rk4(NX, NP, MU)>(
                                          p, ra, sm_roll, lane, W > 1 ? &flags[0] : nullptr,
                                          (kProfile && sa.prof) ? rph : nullptr, kTimeline ? sa.prof : nullptr, b);
       else
-        rollout_instance_rt<T>(p, ra, sm_roll, lane);
+        rollout_instance_rt<T, (PROGID == kExprDynProg)>(p, ra, sm_roll, lane);
 #if ILQG_ROLL_PRIO
       __builtin_amdgcn_s_setprio(0);
 #endif

@@ -90,8 +90,10 @@ __device__ __forceinline__ void dma_g2l_wave(const void* g_, void* l, int nbytes
 // ROOM = false: the caller is at its register limit (fused_rollout_room, ilqg_solve.hpp) and its step loop keeps the form
 // the compiler gives it — no loop-carried copies of the lane roles (lane_roles_opaque below), the trigonometry's
 // polynomial steps as the compiler forms them: the two registers the leaner stream costs are a spilled pair there.
+// XDYN (with GEN): the game may hold ILQG_DYN_EXPRESSION subsystems (sub_integrate_expr, ilqg_models.hpp) — instantiations
+// of their own, picked for the problems that hold one, so that every other problem's kernels are the code they were.
 template <typename T, int CN = 0, int CM = 0, bool DIST = false, bool DUB = false, bool AIR = false, bool PM = false,
-          bool GEN = false, bool ROOM = true>
+          bool GEN = false, bool ROOM = true, bool XDYN = false>
 __device__ __forceinline__ void rollout_instance(const DevProblem& p, const RolloutArgs<T>& a, T* sm, int t,
                                                  int* ready = nullptr, long long* phacc = nullptr,
                                                  long long* tl = nullptr, int tl_b = 0) {
@@ -211,7 +213,16 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
       // behind su: inside the LDS block, read and never used (u1 of a one-control subsystem), as it was for the
       // integrating lanes before.
       const T u0 = su[uo], u1 = su[uo + 1];
-      if constexpr (GEN) {
+      if constexpr (GEN && XDYN) {
+        // the expression subsystems one after the other, each with its group's lanes active: the subsystem, its row
+        // directory and its programs are then wave-uniform (scalar loads, scalar branches over the opcode stream); every
+        // lane of the group evaluates every row, as the plain RK4 below keeps one copy of the block per lane
+        for (int s = 0; s < N; s++) {
+          if (p.sub_kind[s] != ILQG_DYN_EXPRESSION) continue;
+          if (grp == s) sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], p.xoff[s + 1] - p.xoff[s], Lp, p.dt, xj, u0, u1);
+        }
+        if (integ && kind != ILQG_DYN_EXPRESSION) sub_integrate8<T>(kind, Lp, p.dt, xj, u0, u1);
+      } else if constexpr (GEN) {
         if (integ) sub_integrate8<T>(kind, Lp, p.dt, xj, u0, u1);
       } else if constexpr (AIR) {
         if (grp == 0) sub_integrate<T>(kind, Lp, p.dt, xj, u0, u1, air_vp);  // every lane of the group keeps the state
@@ -472,25 +483,30 @@ __device__ __forceinline__ void rollout_lanes(const DevProblem& p, const Rollout
 // The rollout with run-time dimensions, the integrator picked from the problem's models at run time (what the
 // instantiated solves pick at compile time from their dimensions): the stand-alone rollout entry point and the
 // run-time-dimensioned solve path.
-template <typename T>
+// XDYN: the twin for problems that hold an expression subsystem (rollout_instance's XDYN) — those are plain-RK4 games.
+template <typename T, bool XDYN = false>
 __device__ __forceinline__ void rollout_instance_rt(const DevProblem& p, const RolloutArgs<T>& a, T* sm, int t) {
-  bool dubins = false, plain = false;
-  for (int i = 0; i < p.N; i++) {
-    dubins = dubins || p.sub_kind[i] == ILQG_DYN_DUBINS_CAR;
-    plain = plain || is_plain_rk4_kind(p.sub_kind[i]);
+  if constexpr (XDYN) {
+    rollout_instance<T, 0, 0, false, false, false, false, true, true, true>(p, a, sm, t);
+  } else {
+    bool dubins = false, plain = false;
+    for (int i = 0; i < p.N; i++) {
+      dubins = dubins || p.sub_kind[i] == ILQG_DYN_DUBINS_CAR;
+      plain = plain || is_plain_rk4_kind(p.sub_kind[i]);
+    }
+    if (plain)
+      rollout_instance<T, 0, 0, false, false, false, false, true>(p, a, sm, t);
+    else if (p.sub_kind[0] == ILQG_DYN_AIR_3D_EVADER)
+      rollout_instance<T, 0, 0, false, false, true>(p, a, sm, t);
+    else if (p.sub_kind[0] == ILQG_DYN_UNICYCLE_4D_DISTURBED)
+      rollout_instance<T, 0, 0, true>(p, a, sm, t);
+    else if (dubins)
+      rollout_instance<T, 0, 0, false, true>(p, a, sm, t);
+    else if (p.sub_kind[0] == ILQG_DYN_POINT_MASS_2D)
+      rollout_instance<T, 0, 0, false, false, false, true>(p, a, sm, t);
+    else
+      rollout_instance<T>(p, a, sm, t);
   }
-  if (plain)
-    rollout_instance<T, 0, 0, false, false, false, false, true>(p, a, sm, t);
-  else if (p.sub_kind[0] == ILQG_DYN_AIR_3D_EVADER)
-    rollout_instance<T, 0, 0, false, false, true>(p, a, sm, t);
-  else if (p.sub_kind[0] == ILQG_DYN_UNICYCLE_4D_DISTURBED)
-    rollout_instance<T, 0, 0, true>(p, a, sm, t);
-  else if (dubins)
-    rollout_instance<T, 0, 0, false, true>(p, a, sm, t);
-  else if (p.sub_kind[0] == ILQG_DYN_POINT_MASS_2D)
-    rollout_instance<T, 0, 0, false, false, false, true>(p, a, sm, t);
-  else
-    rollout_instance<T>(p, a, sm, t);
 }
 
 // ---------------------------------------------------------------------------

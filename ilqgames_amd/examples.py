@@ -1018,6 +1018,82 @@ def expression_game_scene(T=100, dt=0.1):
     return s
 
 
+def expression_model_rows(kind):
+    """The state rows of a built-in single-player model restated as expression programs (abi.DYN_ROW_EXPRESSION): per row
+    (Expr tree, x_input, y_input or None) over the model's own [x | u], `value` = the model's param0.  Every row of these
+    models has at most two inputs; tan is sin / cos.  None: the kind has no restatement here."""
+    from .abi import Expr
+    x, y, p = Expr.x(), Expr.y(), Expr.value()
+    tan = lambda a: a.sin() / a.cos()
+    if kind == abi.DYN_UNICYCLE_4D:  # (px, py, theta, v), u = (omega, a)
+        return 4, 2, [(y * x.cos(), 2, 3), (y * x.sin(), 2, 3), (x, 4, None), (x, 5, None)]
+    if kind == abi.DYN_DUBINS_CAR:  # (px, py, theta), u = (omega), param0 = speed
+        return 3, 1, [(p * x.cos(), 2, None), (p * x.sin(), 2, None), (x, 3, None)]
+    if kind == abi.DYN_DELAYED_DUBINS_CAR:  # (px, py, theta, omega), u = (alpha), param0 = speed
+        return 4, 1, [(p * x.cos(), 2, None), (p * x.sin(), 2, None), (x, 3, None), (x, 4, None)]
+    if kind == abi.DYN_UNICYCLE_5D:  # (px, py, theta, v, s), u = (omega, a)
+        return 5, 2, [(y * x.cos(), 2, 3), (y * x.sin(), 2, 3), (x, 5, None), (x, 6, None), (x, 3, None)]
+    if kind == abi.DYN_CAR_5D:  # (px, py, theta, phi, v), u = (omega, a), param0 = inter-axle distance
+        return 5, 2, [(y * x.cos(), 2, 4), (y * x.sin(), 2, 4), ((y / p) * tan(x), 3, 4), (x, 5, None), (x, 6, None)]
+    if kind == abi.DYN_CAR_7D:  # (px, py, theta, phi, v, kappa, s), u = (omega, a), param0 = inter-axle distance
+        return 7, 2, [(y * x.cos(), 2, 4), (y * x.sin(), 2, 4), ((y / p) * tan(x), 3, 4), (x, 7, None), (x, 8, None),
+                      (x / (y.cos().square() * p), 7, 3), (x, 4, None)]
+    return None
+
+
+def expression_dynamics_twin(spec):
+    """`spec` with every Unicycle4D, DubinsCar, DelayedDubinsCar, Unicycle5D, Car5D and Car7D subsystem restated as an
+    abi.DYN_EXPRESSION subsystem (expression_model_rows) with the same param0; every other subsystem and every cost
+    term as it is.  The row terms follow the description's terms, so term indices stay what they were.
+    -> (the twin, the number of subsystems restated)."""
+    import copy
+    twin = copy.deepcopy(spec)
+    restated = 0
+    for i, (kind, xdim, udim, p0) in enumerate(spec.subsystems):
+        model = expression_model_rows(kind)
+        if model is None:
+            continue
+        assert model[:2] == (xdim, udim)
+        twin.subsystems[i] = (abi.DYN_EXPRESSION, xdim, udim, p0)
+        for r, (tree, xin, yin) in enumerate(model[2]):
+            twin.dynamics_row(i, r, tree, xin, yin)
+        restated += 1
+    return twin, restated
+
+
+COASTING_CAR_DRAG = 0.05  # coasting_car_scene's drag coefficient c (its C++ twin: tests/host/coasting_car_scene.h)
+
+
+def coasting_car_scene(T=100, dt=0.1):
+    """A test scene, NOT a reference example: two cars of a model the tables do not hold (abi.DYN_EXPRESSION), n = 8 with
+    one control each — the specialised (8, 2, 1) kernels.  x = (px, py, theta, v), u = (kappa): the car steers by its
+    path curvature and only loses speed, xdot = (v cos theta, v sin theta, v kappa, -c v^2) with c = param0.  The game is
+    delayed_dubins_scene's: player 1 is drawn to the origin, player 2 to player 1, and both keep clear of each other.
+    The heading row has an A and a B entry computed from one program, the speed row a computed diagonal entry."""
+    from .abi import Expr
+    prm = SolverParams.default()
+    prm.max_backtracking_steps = 100
+    prm.initial_alpha_scaling = 0.1
+    prm.convergence_tolerance = 0.01
+    prm.expected_decrease_fraction = 0.001
+    s = ProblemSpec(T, dt, prm)
+    x, y, c = Expr.x(), Expr.y(), Expr.value()
+    rows = [(y * x.cos(), 2, 3), (y * x.sin(), 2, 3), (x * y, 3, 4), (-(c * x.square()), 3, None)]
+    for _ in range(2):
+        s.add_expression_player(4, 1, rows, param0=COASTING_CAR_DRAG)
+    X, Y, H, V = [0, 4], [1, 5], [2, 6], [3, 7]
+    for i in range(2):
+        s.name_term("p%d_curvature" % (i + 1), s.quadratic(i, 1.0, 0, 0.0, control_of=i))
+    s.name_term("p1_goal_x", s.quadratic(0, 1.0, X[0], 0.0))
+    s.name_term("p1_goal_y", s.quadratic(0, 1.0, Y[0], 0.0))
+    s.name_term("p1_proximity", s.proximity(0, 5.0, (X[0], Y[0]), (X[1], Y[1]), 1.0))
+    s.name_term("p2_follow", s.quadratic_difference(1, 1.0, (X[1], Y[1]), (X[0], Y[0])))
+    s.name_term("p2_proximity", s.proximity(1, 5.0, (X[1], Y[1]), (X[0], Y[0]), 1.0))
+    s.x0 = [2.0, 1.0, float(np.float32(np.pi / 2)), 1.5, -1.0, -2.0, 0.3, 2.0]
+    s.position_dims, s.heading_dims, s.speed_dims = list(zip(X, Y)), H, V
+    return s
+
+
 def jittered_x0(spec, batch, seed=0):
     """Per-instance initial states of SURVEY.md §8(d): U(-1,1) m on px,py, U(-0.1,0.1) rad
     heading, U(-0.5,0.5) m/s speed; instance b uses numpy default_rng(seed + b)."""

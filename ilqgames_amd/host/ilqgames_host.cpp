@@ -668,6 +668,29 @@ bool DescribeProblem(const Problem& problem, const SolverParams& params, ilqg_dt
   // constraints in that order (src/player_cost.cpp:194-215); the (i, j) block list follows the
   // first touch of each j among player i's control costs then control constraints (:59-86).
   Packer packer(out);
+  // the state rows of the expression subsystems (ILQG_DYN_ROW_EXPRESSION), subsystem by subsystem, in front of the costs
+  for (int i = 0; i < N; i++)
+    if (const auto* model = dynamic_cast<const SinglePlayerExpressionSystem*>(out->subsystem_objects[i])) {
+      for (size_t r = 0; r < model->Rows().size(); r++) {
+        const SinglePlayerExpressionSystem::Row& row = model->Rows()[r];
+        const std::vector<float> block = row.expr.Compile();
+        ilqg_cost_term term{};
+        term.kind = ILQG_DYN_ROW_EXPRESSION;
+        term.role = ILQG_ROLE_DYNAMICS_ROW;
+        term.player = i;
+        term.arg = -1;
+        term.idx[0] = static_cast<int>(r);
+        term.idx[1] = row.x_input;
+        term.idx[2] = row.y_input;
+        term.idx[3] = -1;
+        term.weight = row.weight;
+        term.polyline = static_cast<int>(out->dense_params.size());
+        term.constraint_slot = -1;
+        out->dense_params.insert(out->dense_params.end(), block.begin(), block.end());
+        out->terms.push_back(term);
+        out->term_objects.push_back(nullptr);
+      }
+    }
   for (int i = 0; i < N; i++) {
     const PlayerCost& pc = problem.PlayerCosts()[i];
     for (const auto& c : pc.StateCosts())

@@ -152,8 +152,22 @@ typedef enum {
                                 u = (omega, a); s = path length; xdim 5, udim 2 */
   ILQG_DYN_CAR_7D = 11,      /* include/ilqgames/dynamics/single_player_car_7d.h:61-170: x = (px, py, theta, phi, v,
                                 kappa, s), u = (omega, a), param0 = inter-axle distance; xdim 7, udim 2 */
-  ILQG_DYN_DELAYED_DUBINS_CAR = 12 /* include/ilqgames/dynamics/single_player_delayed_dubins_car.h:57-129: x = (px, py,
+  ILQG_DYN_DELAYED_DUBINS_CAR = 12, /* include/ilqgames/dynamics/single_player_delayed_dubins_car.h:57-129: x = (px, py,
                                 theta, omega), u = (alpha), constant speed param0; xdim 4, udim 1 */
+  /* A user-defined single-player model (the reference's way is a SinglePlayerDynamicalSystem subclass): 1 <= xdim <= 8,
+   * 1 <= udim <= 2, param0 = the model's one free parameter.  Every state row r has exactly one term of kind
+   * ILQG_DYN_ROW_EXPRESSION (role ILQG_ROLE_DYNAMICS_ROW) in the description's term table, whose program is the rate
+   * xdot_r (see that kind).  A plain-RK4 kind like 10-12; never beside the paired kinds (4/5, 7/8) or in a point-mass game.
+   *   Rate.  xdot_r is the program's value (the value-only evaluator: every product and sum rounded on its own).
+   *   Integration.  MultiPlayerDynamicalSystem::Integrate's RK4 with two half-steps of dt / 2: per half-step
+   *     k1 = h f(x), k2 = h f(x + 0.5 k1), k3 = h f(x + 0.5 k2), k4 = h f(x + k3), x += (k1 + 2 (k2 + k3) + k4) / 6,
+   *     each operation rounded on its own, on every path alike.
+   *   Linearisation.  A = I + dt J_x, B = dt J_u: the program's jet is evaluated without second derivatives, each
+   *     derivative d becomes the entry T(double(d) * dt), a diagonal entry T(1) + that.  A row whose whole program is one
+   *     PUSH_X is the constant entry dt.
+   *   Distance.  DistanceBetween of an expression first subsystem is over its whole block (the reference's default, as
+   *     for the two Dubins cars). */
+  ILQG_DYN_EXPRESSION = 13
 } ilqg_dyn_kind;
 
 /* One block of a ConcatenatedDynamicalSystem
@@ -235,7 +249,16 @@ typedef enum {
    * ILQG_ROLE_STATE_CONSTRAINT / ILQG_ROLE_CONTROL_CONSTRAINT only, with a multiplier slot of its own; `first_step` gates
    * it as FinalTimeConstraint does (g = 0 before it).  The row stage applies Constraint::ModifyDerivatives to the jet
    * (with the equality-aware Mu) before the scatter of the table above; the term adds nothing to a player's cost. */
-  ILQG_CONSTRAINT_EXPRESSION = 25
+  ILQG_CONSTRAINT_EXPRESSION = 25,
+  /* One state row of an ILQG_DYN_EXPRESSION subsystem: the same program block, ilqg_expr_op set and limits.  `player` =
+   * the subsystem; idx[0] = the row r it defines (0 <= r < xdim); idx[1] = input X, idx[2] = input Y or -1, both indices
+   * into the subsystem's own [x (xdim) | u (udim)] and distinct; idx[3] = -1; `polyline` = offset of the program's block
+   * in dense_params; arg = -1, constraint_slot = -1, first_step = 0.  PUSH_VALUE pushes the subsystem's param0 (the
+   * instance's, where the subsystem is declared per instance), PUSH_WEIGHT the term's `weight`, a second constant.
+   * Role ILQG_ROLE_DYNAMICS_ROW only: the term takes no part in any cost walk (it is in no cost order, is no child and no
+   * constraint, has no multiplier slot), and cannot carry a per-instance cost parameter.  Every row of an expression
+   * subsystem has exactly one such term; a subsystem of any other kind has none. */
+  ILQG_DYN_ROW_EXPRESSION = 26
 } ilqg_cost_kind;
 
 /* The program of an ILQG_COST_EXPRESSION term: 1 <= L <= ILQG_EXPR_MAX_OPS ops on a stack that never holds more than
@@ -261,7 +284,8 @@ typedef enum {
   ILQG_ROLE_CONTROL_COST = 1,
   ILQG_ROLE_STATE_CONSTRAINT = 2,
   ILQG_ROLE_CONTROL_CONSTRAINT = 3,
-  ILQG_ROLE_CHILD = 4
+  ILQG_ROLE_CHILD = 4,
+  ILQG_ROLE_DYNAMICS_ROW = 5 /* an ILQG_DYN_ROW_EXPRESSION term: a state row of an expression subsystem, not a cost */
 } ilqg_cost_role;
 
 #define ILQG_FLAG_ORIENTED 1 /* oriented_right / keep_within / keep_below / less_is_positive */
@@ -780,7 +804,9 @@ ilqg_status ilqg_row_program_build(const ilqg_problem_desc* desc, int32_t* words
                                    int32_t* static_id);
 /* Host only, no device needed: everything ilqg_problem_create checks about the ILQG_COST_EXPRESSION or
  * ILQG_CONSTRAINT_EXPRESSION term `term` of a description — its role and placement, its inputs, its block inside dense_params and the program in it (length, opcodes,
- * stack depth).  A refusal names the term, and the op where one is at fault, in ilqg_last_error(). */
+ * stack depth).  A refusal names the term, and the op where one is at fault, in ilqg_last_error().  An
+ * ILQG_DYN_ROW_EXPRESSION term is checked too — its subsystem, its row, its inputs and its program — and a refusal names
+ * the subsystem and the row. */
 ilqg_status ilqg_expression_check(const ilqg_problem_desc* desc, int32_t term);
 /* Host only, no device needed: what the feedback sweep may assume about B (sweep_forms).  *constant_out is 1 when the
  * problem's solves run on compact rows, every non-zero of B is a constant of the row program (no computed entry) and
@@ -965,7 +991,9 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
                                  ilqg_instance_solver_params_check: two new calls, the table gains columns); still 9:
                                  ILQG_COST_EXPRESSION (cost kind 24, ilqg_expr_op) and the host-only ilqg_expression_check
                                  (one new call, no layout change); still 9: relative inputs of the expression kinds
-                                 (idx[2], idx[3]) and ILQG_CONSTRAINT_EXPRESSION (kind 25; no new call, no layout change);
+                                 (idx[2], idx[3]) and ILQG_CONSTRAINT_EXPRESSION (kind 25; no new call, no layout change); still 9:
+                                 ILQG_DYN_EXPRESSION (subsystem kind 13), ILQG_ROLE_DYNAMICS_ROW (role 5) and
+                                 ILQG_DYN_ROW_EXPRESSION (term kind 26): three enumerators, no new call, no layout change;
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;

@@ -9,6 +9,8 @@
 // libilqg_hip.so; there is no CPU evaluation path behind `Cost`, `Constraint` or
 // `SinglePlayerDynamicalSystem`, so user-defined subclasses with their own Evaluate() have no device
 // kernel and make Solve() report ILQG_ERR_UNSUPPORTED through a CHECK, the reference's error style.
+// A user's own cost, constraint or single-player model is written as a formula instead (host::Expr: ExpressionCost,
+// ExpressionConstraint, SinglePlayerExpressionSystem), which the device evaluates and differentiates itself.
 #ifndef ILQGAMES_HOST_API_HPP_
 #define ILQGAMES_HOST_API_HPP_
 
@@ -835,6 +837,41 @@ class SinglePlayerDelayedDubinsCar : public SinglePlayerDynamicalSystem {
 
  private:
   const float v_;
+};
+
+// A user's own single-player model (the reference's way is a SinglePlayerDynamicalSystem subclass with its own
+// Evaluate / Linearize): every state rate is a formula over one or two entries of the model's own [x (xdim) | u (udim)],
+// integrated (RK4) and linearised on the device (ILQG_DYN_EXPRESSION, include/ilqg.h).  Expr::Value() is `param`, the
+// model's one free parameter, Expr::Weight() the row's own `weight`.  1 <= xdim <= 8, 1 <= udim <= 2.
+//   using host::Expr;
+//   // x = (px, py, theta, v), u = (kappa): a car that steers by curvature and loses speed to drag c = param
+//   auto car = std::make_shared<SinglePlayerExpressionSystem>(4, 1, std::vector<SinglePlayerExpressionSystem::Row>{
+//       {Expr::Y() * host::Cos(Expr::X()), 2, 3}, {Expr::Y() * host::Sin(Expr::X()), 2, 3},
+//       {Expr::X() * Expr::Y(), 3, 4}, {-(Expr::Value() * host::Square(Expr::X())), 3}}, 0.05f, std::vector<Dimension>{0, 1});
+class SinglePlayerExpressionSystem : public SinglePlayerDynamicalSystem {
+ public:
+  struct Row {
+    host::Expr expr;        // xdot of this row
+    Dimension x_input;      // Expr::X(): an entry of [x | u]
+    Dimension y_input = -1; // Expr::Y(), or -1
+    float weight = 1.0f;    // Expr::Weight()
+    Row(const host::Expr& e, Dimension x, Dimension y = -1, float w = 1.0f) : expr(e), x_input(x), y_input(y), weight(w) {}
+  };
+  SinglePlayerExpressionSystem(Dimension xdim, Dimension udim, const std::vector<Row>& rows, float param,
+                               const std::vector<Dimension>& position_dims)
+      : SinglePlayerDynamicalSystem(xdim, udim), rows_(rows), param_(param), position_dims_(position_dims) {
+    CHECK_EQ(static_cast<Dimension>(rows_.size()), xdim) << "SinglePlayerExpressionSystem: one row per state";
+    for (const Row& row : rows_)
+      CHECK(row.y_input >= 0 || !row.expr.UsesY()) << "SinglePlayerExpressionSystem: a row names Expr::Y() and has no second input";
+  }
+  std::vector<Dimension> PositionDimensions() const override { return position_dims_; }
+  ilqg_subsystem Describe() const override { return ilqg_subsystem{ILQG_DYN_EXPRESSION, xdim_, udim_, param_}; }
+  const std::vector<Row>& Rows() const { return rows_; }
+
+ private:
+  const std::vector<Row> rows_;
+  const float param_;
+  const std::vector<Dimension> position_dims_;
 };
 
 // include/ilqgames/dynamics/multi_player_integrable_system.h:57-140 (shape queries only; the
