@@ -22,7 +22,7 @@ const char* cost_kind_name(int kind) {  // ilqg_cost_kind without its prefix
   static_assert(ILQG_COST_QUADRATIC == 1 && ILQG_DYN_ROW_EXPRESSION == sizeof(names) / sizeof(names[0]), "one name per kind");
   return kind >= 1 && kind <= ILQG_DYN_ROW_EXPRESSION ? names[kind - 1] : "unknown kind";
 }
-// Does a term of this kind read the field (the table of ilqg.h; ilqg_models.hpp: term_evaluate_leaf_of and the row ops)?
+// Does a term of this kind read the field (the table of ilqg.h; ilqg_models.hpp: term_compute_leaf, and the affine and expression evaluators beside it)?
 // Null: yes; else why not.
 const char* instance_param_refusal(int kind, int field) {
   const bool weight = field == ILQG_PARAM_WEIGHT;

@@ -576,8 +576,9 @@ struct Closest {
   Seg<T> seg;
 };
 
-template <typename T>
-__device__ __forceinline__ Seg<T> load_seg(const T* s) {
+// P: a pointer to T in global or in scalar memory (ConstPtr<T>::type, ilqg_rows.hpp)
+template <typename T, typename P>
+__device__ __forceinline__ Seg<T> load_seg(P s) {
   Seg<T> o;
   o.p1x = s[0]; o.p1y = s[1]; o.p2x = s[2]; o.p2y = s[3]; o.len = s[4]; o.ux = s[5]; o.uy = s[6];
   return o;
@@ -677,6 +678,10 @@ __host__ inline DevTerm wcp_sub_term(const DevTerm& c, const WcpIdx& ix, int whi
 __host__ __device__ inline bool term_is_time_dependent(int kind) {
   return kind == ILQG_COST_NOMINAL_PATH_LENGTH || kind == ILQG_COST_ROUTE_PROGRESS;
 }
+__host__ __device__ inline bool term_is_polyline(int kind) {
+  return kind == ILQG_COST_QUADRATIC_POLYLINE2 || kind == ILQG_COST_SEMIQUADRATIC_POLYLINE2 ||
+         kind == ILQG_COST_POLYLINE2_SIGNED_DISTANCE || kind == ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE;
+}
 enum {
   LC_KIND = 0, LC_XOFF = LC_KIND + kMaxPlayers, LC_UOFF = LC_XOFF + kMaxPlayers + 1,
   LC_UDIM = LC_UOFF + kMaxPlayers + 1, LC_PARAM = LC_UDIM + kMaxPlayers, LC_SREG = LC_PARAM + kMaxPlayers,
@@ -688,23 +693,19 @@ enum {
 // Polyline2::ClosestPoint, src/polyline2.cpp:105-174 — linear scan over the 1..15 segments of a
 // lane; the "shortcut" sign rule at interior vertices and the 1e-4 endpoint rule are reproduced.
 // Segments (and the shortcut segments of interior vertices) are precomputed LineSegment2 objects.
-// UNIFORM: `poly` is the same on every lane (the lane-per-time-step stage): the scan's bounds are pinned to scalar
-// registers so that its loop is a scalar branch.
-template <typename T, bool UNIFORM = false>
-__device__ __forceinline__ Closest<T> polyline_closest(const QuadTables<T>& tb, int poly, T qx, T qy) {
-  int first = tb.poly_off[poly] - poly;  // segments before this polyline
-  int nseg = tb.poly_off[poly + 1] - tb.poly_off[poly] - 1;
-  if constexpr (UNIFORM) {
-    first = __builtin_amdgcn_readfirstlane(first);
-    nseg = __builtin_amdgcn_readfirstlane(nseg);
-  }
-  const T* base = tb.segs + size_t(first) * kSegStride;
+// `segs` (P: as load_seg) is the segment table, the polyline's segments are [first, first + nseg) of it; every lane
+// its own query point.  The one scan of the device: the CLOSEST op of the row programs (table in scalar memory) and
+// polyline_closest below (table in global memory) both run it.
+template <typename T, typename P>
+__device__ __forceinline__ Closest<T> polyline_closest_scan(P segs, int first, int nseg, T qx, T qy) {
+  P base = segs + first * kSegStride;
   Closest<T> out;
   T best = dinf<T>();
   out.cx = T(0);
   out.cy = T(0);
   out.is_vertex = false;
-  int best_idx = 0;
+  out.seg = load_seg<T>(base);
+#pragma unroll 1
   for (int c = 0; c < nseg; c++) {
     const Seg<T> s = load_seg<T>(base + c * kSegStride);
     T px, py, cur;
@@ -714,17 +715,20 @@ __device__ __forceinline__ Closest<T> polyline_closest(const QuadTables<T>& tb, 
       const bool at2 = (px == s.p2x && py == s.p2y);
       const bool at1 = (px == s.p1x && py == s.p1y);
       if (se && (c > 0 || at2) && (c < nseg - 1 || at1)) {
-        const Seg<T> sc = load_seg<T>(base + c * kSegStride + (at1 ? 7 : 14));
+        // the "shortcut" segment of the vertex (both candidates are loaded, uniform data in the row kernels; the lane picks)
+        const Seg<T> s1 = load_seg<T>(base + c * kSegStride + 7), s2 = load_seg<T>(base + c * kSegStride + 14);
+        Seg<T> sc;
+        sc.p1x = at1 ? s1.p1x : s2.p1x; sc.p1y = at1 ? s1.p1y : s2.p1y;
+        sc.ux = at1 ? s1.ux : s2.ux; sc.uy = at1 ? s1.uy : s2.uy;
         cur *= seg_side(sc, qx, qy) ? sgn(cur) : -sgn(cur);
       }
       best = cur;
       out.cx = px;
       out.cy = py;
       out.is_vertex = se;
-      best_idx = c;
+      out.seg = s;
     }
   }
-  out.seg = load_seg<T>(base + best_idx * kSegStride);
   out.ssd = best;
   const Seg<T> s0 = load_seg<T>(base), sl = load_seg<T>(base + (nseg - 1) * kSegStride);
   const T ax = out.cx - s0.p1x, ay = out.cy - s0.p1y;
@@ -732,12 +736,20 @@ __device__ __forceinline__ Closest<T> polyline_closest(const QuadTables<T>& tb, 
   out.is_endpoint = (ax * ax + ay * ay < T(1e-4f)) || (bx * bx + by * by < T(1e-4f));
   return out;
 }
+// the closest point of polyline `poly` of the tables (poly_off counts points: one more than segments per polyline)
+template <typename T>
+__device__ __forceinline__ Closest<T> polyline_closest(const QuadTables<T>& tb, int poly, T qx, T qy) {
+  const int first = tb.poly_off[poly] - poly;  // segments before this polyline
+  const int nseg = tb.poly_off[poly + 1] - tb.poly_off[poly] - 1;
+  return polyline_closest_scan<T>(tb.segs, first, nseg, qx, qy);
+}
 
 // ---------------------------------------------------------------------------
 // Costs.  `v` is the argument vector (state x or one player's u) in LDS/global,
 // `dim` its length.  H is a column-major tile with leading dimension ld.
 // ---------------------------------------------------------------------------
-// Constraint::Mu(lambda, g), include/ilqgames/constraint/constraint.h:112-117
+// Constraint::Mu(lambda, g), include/ilqgames/constraint/constraint.h:112-117: the gate of the equality-aware form
+// above with is_equality false.  Why the two are not one function yet: DESIGN.md 3.4, "Which code evaluates a cost kind".
 template <typename T>
 __device__ __forceinline__ T constraint_mu(T lambda, T g, T mu) {
   return (g <= T(1e-4f) && t_abs(lambda) <= T(1e-4f)) ? T(0) : mu;
@@ -749,162 +761,6 @@ template <typename T>
 __device__ __forceinline__ T orientation_difference(T angle, T nominal) {
   const double kPi = 3.14159265358979323846;
   return T(fmod(double(angle - nominal) + kPi, kPi * 2.0) - kPi);
-}
-
-// `v` is anything indexable that yields the argument vector's entries: a pointer (LDS / global row) or the
-// transposed-row accessor of the lane-per-time-step stage (ilqg_rows.hpp).
-// `step`: the time step the term is evaluated at (the time-dependent kinds read their nominal of that step).
-template <typename T, typename V>
-__device__ __forceinline__ T term_evaluate_leaf_of(const QuadTables<T>& tb, const DevTerm& c, const V& v, int dim,
-                                                   int step = 0) {
-  const T w = T(c.weight), val = T(c.value);
-  const bool oriented = c.flags & ILQG_FLAG_ORIENTED;
-  switch (c.kind) {
-    case ILQG_COST_NOMINAL_PATH_LENGTH: {  // src/nominal_path_length_cost.cpp:50-56
-      const double nom = tb.tnom[(size_t(c.polyline) * tb.tnom_T + step) * 2];
-      const T delta = T(double(v[c.idx[0]]) - nom);
-      return T(0.5) * w * delta * delta;
-    }
-    case ILQG_COST_ROUTE_PROGRESS: {  // src/route_progress_cost.cpp:52-64
-      const double* nom = tb.tnom + (size_t(c.polyline) * tb.tnom_T + step) * 2;
-      const T dx = v[c.idx[0]] - T(nom[0]), dy = v[c.idx[1]] - T(nom[1]);
-      return T(0.5) * w * (dx * dx + dy * dy);
-    }
-    case ILQG_COST_QUADRATIC: {  // src/quadratic_cost.cpp:51-63
-      if (c.idx[0] >= 0) {
-        const T d = v[c.idx[0]] - val;
-        return T(0.5) * w * d * d;
-      }
-      T sq = 0;
-      for (int i = 0; i < dim; i++) sq += (v[i] - val) * (v[i] - val);
-      return T(0.5) * w * sq;
-    }
-    case ILQG_COST_SEMIQUADRATIC: {  // src/semiquadratic_cost.cpp:51-59
-      const T d = v[c.idx[0]] - val;
-      if ((d > T(0) && oriented) || (d < T(0) && !oriented)) return T(0.5) * w * d * d;
-      return T(0);
-    }
-    case ILQG_COST_QUADRATIC_POLYLINE2: {  // src/quadratic_polyline2_cost.cpp:52-69
-      const Closest<T> cl = polyline_closest<T>(tb, c.polyline, v[c.idx[0]], v[c.idx[1]]);
-      const T ssd = cl.is_endpoint ? T(0) : cl.ssd;
-      return T(0.5) * w * t_abs(ssd);
-    }
-    case ILQG_COST_SEMIQUADRATIC_POLYLINE2: {  // src/semiquadratic_polyline2_cost.cpp:52-74
-      const Closest<T> cl = polyline_closest<T>(tb, c.polyline, v[c.idx[0]], v[c.idx[1]]);
-      if (cl.is_endpoint) return T(0);
-      const T sst = sgn(val) * val * val;
-      const bool active = (cl.ssd > sst && oriented) || (cl.ssd < sst && !oriented);
-      if (!active) return T(0);
-      const T sd = sgn(cl.ssd) * t_sqrt(t_abs(cl.ssd));
-      const T d = sd - val;
-      return T(0.5) * w * d * d;
-    }
-    case ILQG_COST_PROXIMITY: {  // src/proximity_cost.cpp:52-61
-      const T dx = v[c.idx[0]] - v[c.idx[2]], dy = v[c.idx[1]] - v[c.idx[3]];
-      const T dsq = dx * dx + dy * dy;
-      if (dsq >= val * val) return T(0);
-      const T gap = val - t_sqrt(dsq);
-      return T(0.5) * w * gap * gap;
-    }
-    case ILQG_COST_SIGNED_DISTANCE: {  // src/signed_distance_cost.cpp:51-63
-      const T dx = v[c.idx[0]] - v[c.idx[2]], dy = v[c.idx[1]] - v[c.idx[3]];
-      const T cost = val - t_hypot(dx, dy);
-      return oriented ? cost : -cost;
-    }
-    case ILQG_COST_QUADRATIC_DIFFERENCE: {  // src/quadratic_difference_cost.cpp:51-59
-      const T ex = v[c.idx[0]] - v[c.idx[2]], ey = v[c.idx[1]] - v[c.idx[3]];
-      return T(0.5) * w * (ex * ex + ey * ey);
-    }
-    case ILQG_COST_POLYLINE2_SIGNED_DISTANCE: {  // src/polyline2_signed_distance_cost.cpp:52-65
-      const Closest<T> cl = polyline_closest<T>(tb, c.polyline, v[c.idx[0]], v[c.idx[1]]);
-      const T ssd = oriented ? cl.ssd : -cl.ssd;
-      return sgn(ssd) * t_sqrt(t_abs(ssd)) - val;
-    }
-    case ILQG_CONSTRAINT_PROXIMITY: {  // src/proximity_constraint.cpp:56-62
-      const T dx = v[c.idx[0]] - v[c.idx[2]], dy = v[c.idx[1]] - v[c.idx[3]];
-      const T value = t_hypot(dx, dy) - val;
-      return oriented ? value : -value;
-    }
-    case ILQG_CONSTRAINT_SINGLE_DIMENSION:  // single_dimension_constraint.h:68-70
-      return oriented ? v[c.idx[0]] - val : val - v[c.idx[0]];
-    case ILQG_COST_ORIENTATION: {  // src/orientation_cost.cpp:50-58
-      const T diff = orientation_difference<T>(v[c.idx[0]], val);
-      return T(0.5) * w * diff * diff;
-    }
-    case ILQG_COST_QUADRATIC_NORM: {  // src/quadratic_norm_cost.cpp:52-57
-      const T diff = t_hypot(v[c.idx[0]], v[c.idx[1]]) - val;
-      return T(0.5) * w * diff * diff;
-    }
-    case ILQG_COST_SEMIQUADRATIC_NORM: {  // src/semiquadratic_norm_cost.cpp:52-59
-      const T diff = t_hypot(v[c.idx[0]], v[c.idx[1]]) - val;
-      if ((diff > T(0) && oriented) || (diff < T(0) && !oriented)) return T(0.5) * w * diff * diff;
-      return T(0);
-    }
-    case ILQG_COST_RELATIVE_DISTANCE:  // src/relative_distance_cost.cpp:48-54
-      return w * t_hypot(v[c.idx[0]] - v[c.idx[2]], v[c.idx[1]] - v[c.idx[3]]);
-    case ILQG_COST_LOCALLY_CONVEX_PROXIMITY: {  // src/locally_convex_proximity_cost.cpp:50-60
-      const T dx = v[c.idx[0]] - v[c.idx[2]], dy = v[c.idx[1]] - v[c.idx[3]];
-      if (dx * dx >= val * val || dy * dy >= val * val) return T(0);
-      const T ax = val - t_abs(dx), ay = val - t_abs(dy);
-      const T sx = ax * ax, sy = ay * ay;
-      return T(0.5) * w * (sy < sx ? sy : sx);
-    }
-    case ILQG_COST_CURVATURE: {  // src/curvature_cost.cpp:50-53
-      const T curvature = v[c.idx[0]] / v[c.idx[1]];
-      return T(0.5) * w * curvature * curvature;
-    }
-    case ILQG_COST_WEIGHTED_CONVEX_PROXIMITY: {  // src/weighted_convex_proximity_cost.cpp:50-61
-      const WcpIdx ix = wcp_indices(c);
-      const T dx = v[ix.x1] - v[ix.x2], dy = v[ix.y1] - v[ix.y2];
-      const T v1 = v[ix.v1], v2 = v[ix.v2];
-      const T vv = v1 * v1 + v2 * v2;
-      if (dx * dx >= val * val || dy * dy >= val * val) return T(0);
-      const T ax = val - t_abs(dx), ay = val - t_abs(dy);
-      const T sx = ax * ax, sy = ay * ay;
-      return T(0.5) * w * vv * (sy < sx ? sy : sx);
-    }
-    case ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE: {  // src/polyline2_signed_distance_constraint.cpp:57-69
-      const Closest<T> cl = polyline_closest<T>(tb, c.polyline, v[c.idx[0]], v[c.idx[1]]);
-      const T value = sgn(cl.ssd) * t_sqrt(t_abs(cl.ssd)) - val;
-      return oriented ? value : -value;
-    }
-    case ILQG_CONSTRAINT_AFFINE_SCALAR:
-    case ILQG_CONSTRAINT_AFFINE_VECTOR:
-      return tb.dense ? affine_evaluate<T, V>(c.kind, tb.dense + c.polyline, v, dim) : T(0);
-    case ILQG_COST_EXPRESSION:  // ilqg_expr.hpp: the program's value alone
-    case ILQG_CONSTRAINT_EXPRESSION: {
-      if (!tb.dense) return T(0);
-      T x = v[c.idx[0]], y = c.idx[1] >= 0 ? v[c.idx[1]] : T(0);
-      if (c.idx[2] >= 0) {  // relative inputs: one rounded difference each, as ProximityCost forms its own
-        x = x - v[c.idx[2]];
-        if (c.idx[3] >= 0) y = y - v[c.idx[3]];
-      }
-      return expr_eval_value<T>(tb.dense + c.polyline, w, val, x, y);
-    }
-  }
-  return T(0);
-}
-template <typename T, typename V>
-__device__ __forceinline__ T term_evaluate_leaf(const QuadTables<T>& tb, int ti, const V& v, int dim, int step = 0) {
-  const DevTerm c = tb.terms[ti];
-  return term_evaluate_leaf_of<T, V>(tb, c, v, dim, step);
-}
-
-// ExtremeValueCost::ExtremeCost, src/extreme_value_cost.cpp:66-85: index of the active child.
-template <typename T, typename V>
-__device__ __forceinline__ int extreme_child(const QuadTables<T>& tb, const DevTerm& c, const V& v, int dim, T* value_out) {
-  const bool is_min = c.flags & ILQG_FLAG_IS_MIN;
-  T ext = is_min ? dinf<T>() : -dinf<T>();
-  int best = c.child_begin;
-  for (int q = 0; q < c.child_count; q++) {
-    const T value = term_evaluate_leaf<T, V>(tb, c.child_begin + q, v, dim);
-    if ((is_min && value < ext) || (!is_min && value > ext)) {
-      ext = value;
-      best = c.child_begin + q;
-    }
-  }
-  *value_out = ext;
-  return best;
 }
 
 // Constraint::ModifyDerivatives, src/constraint.cpp:63-89
@@ -947,15 +803,17 @@ struct TermOut {
   T value;  // Cost::Evaluate (only meaningful for cost terms)
 };
 
-// Cost::Evaluate + Cost::Quadraticize of one LEAF term in one pass (the polyline closest-point
-// search is shared).  `lambda`, `mu`: augmented-Lagrangian state of a constraint term.
-// `pre`: the closest point of this term's polyline to its position, when the caller already has it.  HAVE_PRE: the
-// caller always has it (the polyline searches are compiled out of this function).
-// `tnom`: this step's nominal pair of a time-dependent term (term_is_time_dependent).
-template <typename T, typename V, bool HAVE_PRE = false>
-__device__ __forceinline__ void term_compute_leaf(const QuadTables<T>& tb, const DevTerm& c, const V& v, T lambda,
-                                                  T mu, TermOut<T>* o, const Closest<T>* pre = nullptr,
-                                                  const double* tnom = nullptr) {
+// Cost::Evaluate + Cost::Quadraticize of one LEAF term in one pass: the only place a built-in kind's formula is written
+// (the affine and expression kinds are evaluated by their own functions, around this one).
+// `v` is anything indexable that yields the argument vector's entries: a pointer (LDS / global row) or the
+// transposed-row accessor of the lane-per-time-step stage (ilqg_rows.hpp).
+// `lambda`, `mu`: augmented-Lagrangian state of a constraint term.
+// `pre`: the closest point of this term's polyline to its position.  Only the kinds of term_is_polyline read it, each
+// through a copy of its own, so a caller may pass an unset one for any other kind.
+// `tnom`: this step's nominal pair of a time-dependent term (term_is_time_dependent; no other kind reads it).
+template <typename T, typename V>
+__device__ __forceinline__ void term_compute_leaf(const DevTerm& c, const V& v, T lambda, T mu, TermOut<T>* o,
+                                                  const Closest<T>& pre, const double* tnom) {
   const T w = T(c.weight), val = T(c.value);
   const bool oriented = c.flags & ILQG_FLAG_ORIENTED;
   o->pattern = PAT_NONE;
@@ -1009,11 +867,7 @@ __device__ __forceinline__ void term_compute_leaf(const QuadTables<T>& tb, const
       const bool semi = c.kind == ILQG_COST_SEMIQUADRATIC_POLYLINE2;
       const T px = v[c.idx[0]], py = v[c.idx[1]];
       Closest<T> cl;
-      if constexpr (HAVE_PRE) {
-        cl = *pre;
-      } else {
-        cl = pre != nullptr ? *pre : polyline_closest<T>(tb, c.polyline, px, py);
-      }
+      cl = pre;
       T dx, dy;
       if (semi) {
         const T sst = sgn(val) * val * val;
@@ -1060,7 +914,7 @@ __device__ __forceinline__ void term_compute_leaf(const QuadTables<T>& tb, const
     case ILQG_COST_POLYLINE2_SIGNED_DISTANCE: {  // src/polyline2_signed_distance_cost.cpp:52-126
       const T px = v[c.idx[0]], py = v[c.idx[1]];
       Closest<T> cl;
-      if constexpr (HAVE_PRE) cl = *pre; else cl = polyline_closest<T>(tb, c.polyline, px, py);
+      cl = pre;
       const T ssd = oriented ? cl.ssd : -cl.ssd;
       const T sign = sgn(ssd);
       const T distance = t_sqrt(t_abs(ssd));
@@ -1239,7 +1093,7 @@ __device__ __forceinline__ void term_compute_leaf(const QuadTables<T>& tb, const
     case ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE: {  // src/polyline2_signed_distance_constraint.cpp:57-144
       const T x = v[c.idx[0]], y = v[c.idx[1]];
       Closest<T> cl;
-      if constexpr (HAVE_PRE) cl = *pre; else cl = polyline_closest<T>(tb, c.polyline, x, y);
+      cl = pre;
       const T s = sgn(cl.ssd);
       const T sign = oriented ? T(1) : T(-1);
       const T sd = s * t_sqrt(t_abs(cl.ssd));
@@ -1263,6 +1117,55 @@ __device__ __forceinline__ void term_compute_leaf(const QuadTables<T>& tb, const
       return;
     }
   }
+}
+
+// Cost::Evaluate alone (strategy costs, Nash checks, the multiplier update): term_compute_leaf's value, with what the
+// row interpreter does around its TERM op — the polyline search, this step's nominal pair, and the affine and
+// expression kinds through their own evaluators.  The gradient and Hessian of the body are unused here and compile
+// away; with no contraction in this region the value is the same sequence of rounded operations as in the row programs.
+// `step`: the time step the term is evaluated at (the time-dependent kinds read their nominal of that step).
+template <typename T, typename V>
+__device__ __forceinline__ T term_evaluate_leaf_of(const QuadTables<T>& tb, const DevTerm& c, const V& v, int dim,
+                                                   int step = 0) {
+  if (term_is_affine(c.kind)) return tb.dense ? affine_evaluate<T, V>(c.kind, tb.dense + c.polyline, v, dim) : T(0);
+  if (term_is_expression(c.kind)) {  // ilqg_expr.hpp: the program's value alone
+    if (!tb.dense) return T(0);
+    T x = v[c.idx[0]], y = c.idx[1] >= 0 ? v[c.idx[1]] : T(0);
+    if (c.idx[2] >= 0) {  // relative inputs: one rounded difference each, as ProximityCost forms its own
+      x = x - v[c.idx[2]];
+      if (c.idx[3] >= 0) y = y - v[c.idx[3]];
+    }
+    return expr_eval_value<T>(tb.dense + c.polyline, T(c.weight), T(c.value), x, y);
+  }
+  Closest<T> cl;
+  if (term_is_polyline(c.kind)) cl = polyline_closest<T>(tb, c.polyline, v[c.idx[0]], v[c.idx[1]]);
+  const double* tnom = nullptr;
+  if (term_is_time_dependent(c.kind)) tnom = tb.tnom + (size_t(c.polyline) * tb.tnom_T + step) * 2;
+  TermOut<T> o;
+  term_compute_leaf<T, V>(c, v, T(0), T(0), &o, cl, tnom);
+  return o.value;
+}
+template <typename T, typename V>
+__device__ __forceinline__ T term_evaluate_leaf(const QuadTables<T>& tb, int ti, const V& v, int dim, int step = 0) {
+  const DevTerm c = tb.terms[ti];
+  return term_evaluate_leaf_of<T, V>(tb, c, v, dim, step);
+}
+
+// ExtremeValueCost::ExtremeCost, src/extreme_value_cost.cpp:66-85: index of the active child.
+template <typename T, typename V>
+__device__ __forceinline__ int extreme_child(const QuadTables<T>& tb, const DevTerm& c, const V& v, int dim, T* value_out) {
+  const bool is_min = c.flags & ILQG_FLAG_IS_MIN;
+  T ext = is_min ? dinf<T>() : -dinf<T>();
+  int best = c.child_begin;
+  for (int q = 0; q < c.child_count; q++) {
+    const T value = term_evaluate_leaf<T, V>(tb, c.child_begin + q, v, dim);
+    if ((is_min && value < ext) || (!is_min && value > ext)) {
+      ext = value;
+      best = c.child_begin + q;
+    }
+  }
+  *value_out = ext;
+  return best;
 }
 
 #pragma clang fp contract(fast)  // back to the translation unit's default

@@ -434,60 +434,6 @@ __host__ __device__ inline int term_pattern_of(int kind, int idx0, int idx1 = -1
   }
   return PAT_NONE;
 }
-__host__ __device__ inline bool term_is_polyline(int kind) {
-  return kind == ILQG_COST_QUADRATIC_POLYLINE2 || kind == ILQG_COST_SEMIQUADRATIC_POLYLINE2 ||
-         kind == ILQG_COST_POLYLINE2_SIGNED_DISTANCE || kind == ILQG_CONSTRAINT_POLYLINE2_SIGNED_DISTANCE;
-}
-
-// Polyline2::ClosestPoint (src/polyline2.cpp:105-174) with the segment table in scalar memory: the same scan as
-// polyline_closest (ilqg_models.hpp), every lane its own query point against the same segments.
-template <typename T>
-__device__ __forceinline__ Seg<T> load_seg_const(typename ConstPtr<T>::type s) {
-  Seg<T> o;
-  o.p1x = s[0]; o.p1y = s[1]; o.p2x = s[2]; o.p2y = s[3]; o.len = s[4]; o.ux = s[5]; o.uy = s[6];
-  return o;
-}
-template <typename T>
-__device__ __forceinline__ Closest<T> polyline_closest_rows(typename ConstPtr<T>::type segs, int first, int nseg, T qx,
-                                                            T qy) {
-  typename ConstPtr<T>::type base = segs + first * kSegStride;
-  Closest<T> out;
-  T best = dinf<T>();
-  out.cx = T(0);
-  out.cy = T(0);
-  out.is_vertex = false;
-  out.seg = load_seg_const<T>(base);
-#pragma unroll 1
-  for (int c = 0; c < nseg; c++) {
-    const Seg<T> s = load_seg_const<T>(base + c * kSegStride);
-    T px, py, cur;
-    bool se;
-    seg_closest(s, qx, qy, &px, &py, &se, &cur);
-    if (t_abs(cur) < t_abs(best)) {
-      const bool at2 = (px == s.p2x && py == s.p2y);
-      const bool at1 = (px == s.p1x && py == s.p1y);
-      if (se && (c > 0 || at2) && (c < nseg - 1 || at1)) {
-        // the "shortcut" segment of the vertex (both candidates are scalar data; the lane picks)
-        const Seg<T> s1 = load_seg_const<T>(base + c * kSegStride + 7), s2 = load_seg_const<T>(base + c * kSegStride + 14);
-        Seg<T> sc;
-        sc.p1x = at1 ? s1.p1x : s2.p1x; sc.p1y = at1 ? s1.p1y : s2.p1y;
-        sc.ux = at1 ? s1.ux : s2.ux; sc.uy = at1 ? s1.uy : s2.uy;
-        cur *= seg_side(sc, qx, qy) ? sgn(cur) : -sgn(cur);
-      }
-      best = cur;
-      out.cx = px;
-      out.cy = py;
-      out.is_vertex = se;
-      out.seg = s;
-    }
-  }
-  out.ssd = best;
-  const Seg<T> s0 = load_seg_const<T>(base), sl = load_seg_const<T>(base + (nseg - 1) * kSegStride);
-  const T ax = out.cx - s0.p1x, ay = out.cy - s0.p1y;
-  const T bx = out.cx - sl.p2x, by = out.cy - sl.p2y;
-  out.is_endpoint = (ax * ax + ay * ay < T(1e-4f)) || (bx * bx + by * by < T(1e-4f));
-  return out;
-}
 
 // ---- where a chunk reads its program from ----
 // ProgDynamic: the row program built by ilqg_problem_create, in scalar memory — the interpreter: one loop over the ops,
@@ -899,7 +845,7 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
           return;
         }
         if (mode == ROP_CLOSEST) {
-          cc = polyline_closest_rows<T>(segs, od.template param<RO_POLY_FIRST>(), od.template param<RO_PATTERN_NSEG>(), v[c.idx[0]], v[c.idx[1]]);
+          cc = polyline_closest_scan<T>(segs, od.template param<RO_POLY_FIRST>(), od.template param<RO_PATTERN_NSEG>(), v[c.idx[0]], v[c.idx[1]]);
           return;
         }
 #if ILQG_PROFILE2
@@ -957,7 +903,7 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
           o.value = j.f; o.gx = j.fx; o.gy = j.fy; o.hxx = j.fxx; o.hyy = j.fyy; o.hxy = j.fxy;
           if (rel && !two) { o.gy = -j.fx; o.hyy = j.fxx; o.hxy = -j.fxx; }
         } else {
-          term_compute_leaf<T, Arg, true>(QuadTables<T>{}, c, v, lambda, a.mu, &o, &cc, tnom);
+          term_compute_leaf<T, Arg>(c, v, lambda, a.mu, &o, cc, tnom);
         }
 #if ILQG_PROFILE2
         ILQG_QPH(3);

@@ -3,8 +3,8 @@
 The cases, their points and the branch census are tests/term_cases.py's (one term per problem, 6 x 67 points, two
 shapes); tests/test_term_branches.py establishes on the CPU that every branch of every kind is among them.  Four
 tests, in this order below:
-  1. ilqg_quadraticize_batch and ilqg_total_costs_batch (the row programs: term_compute_leaf and the row form of the
-     polyline search) against the oracle on those points;
+  1. ilqg_quadraticize_batch and ilqg_total_costs_batch (the row programs: term_compute_leaf behind the TERM op, the
+     polyline search behind the CLOSEST op) against the oracle on those points;
   2. the same cases inside one iteration of a solve, so that the fused, split, probing, compact and run-time-dimensioned
      row paths see the same branches: split / probing / compact against the fused form bit for bit; the
      run-time-dimensioned kernels against the shape's own, and the shape's own against the oracle, per instance at the
@@ -12,9 +12,12 @@ tests, in this order below:
      the fp64 oracle;
   3. ilqg_total_costs_batch of a two-step problem standing still at each point: the value the row path returns for
      the cost kinds, per point (the 67-step totals of test 1 hold it only as a sum);
-  4. ilqg_strategy_costs_batch on the same points: the value-only restatement of the COST kinds (term_evaluate_leaf_of
-     and its own polyline search), which no row path runs.  Its constraint kinds run only in the multiplier update of
-     an augmented-Lagrangian solve and are not compared here.
+  4. ilqg_strategy_costs_batch on the same points: the value path of the COST kinds (term_evaluate_leaf_of), which no
+     row path runs.  It returns the value of the same term_compute_leaf and runs the same polyline scan as the rows,
+     so tests 3 and 4 reach one body through two wrappers and two kernels; what is this path's own is the wrapper
+     (the search over the table in global memory, the step's nominal pair, the affine / expression dispatch).  Its
+     constraint kinds run only in the multiplier update of an augmented-Lagrangian solve and are not compared here:
+     their g is the function whose derivatives test 1 pins.
 
 Every point is judged on its own scale s, the largest absolute entry of the fp64 oracle's (Q, l, R, r) rows of that
 point, and its bound comes from the oracle alone:
@@ -255,10 +258,11 @@ def test_solve_row_paths_agree_on_every_branch(hip, oracle, name, shape, dtype):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the value-only restatement (term_evaluate_leaf_of, polyline_closest): reached through ilqg_strategy_costs_batch
+# the value path (term_evaluate_leaf_of, polyline_closest): reached through ilqg_strategy_costs_batch
 # ---------------------------------------------------------------------------------------------------------------------
-# The rows and ilqg_total_costs_batch take a term's value from the row programs (term_compute_leaf and the row form of
-# the polyline search).  The second restatement of every kind — value only, with its own polyline search — runs in the
+# The rows and ilqg_total_costs_batch take a term's value from the row programs (term_compute_leaf behind the TERM op,
+# the polyline scan behind the CLOSEST op).  The value path — a wrapper that runs the same scan over the table in global
+# memory, fetches the step's nominal pair and returns the value of the same term_compute_leaf — runs in the
 # strategy-cost / Nash-check kernel and in the multiplier update.  It is pinned here per point: every point is an
 # instance of its own of a two-step problem (the shortest the library takes) rolled out with the Euler step, so its
 # cost is the term at the point plus the term one Euler step on; judged on the sum of the two steps' absolute costs,
