@@ -160,6 +160,23 @@ class SolveOptions(C.Structure):
                 ("iterate_log", C.POINTER(IterateLog)), ("max_runtime", C.c_double)]
 
 
+class ScheduleQuery(C.Structure):
+    """ilqg_schedule_query (include/ilqg.h): what ilqg_schedule_build needs beside the description and the options."""
+    _fields_ = [(f, C.c_int32) for f in ("batch", "active", "num_cus", "tables_bound", "solver_bound")]
+
+
+class ScheduleInfo(C.Structure):
+    """ilqg_schedule_info (include/ilqg.h): the schedule of a solve, every decision as a named integer."""
+    _fields_ = [(f, C.c_int32) for f in (
+        "word", "sched_batch", "num_cus", "split", "counted", "handoff", "lists", "bursts", "probe", "timed",
+        "pairs", "lanes_auto", "deep_tails", "read_restarts", "proll_single", "proll_lanes", "probe_max", "probe_budget",
+        "compact", "defer_forward", "single_wave", "adjoint", "b_const", "packed", "sweep_kind", "sweep_forms",
+        "sweep_threads", "prog_kind", "bound", "static_id", "static_prog", "static_in_regs", "decide_solver",
+        "rows_cw", "row_chunks", "lane_width", "prio_div", "nt_exit", "lds_part",
+        "lds_trial", "lds_roll", "lds_rows", "lds_decide", "lds_proll", "lds_proll_single", "lds_proll_lanes", "lds_prows",
+        "lds_sweep", "lds_exit")] + [("cap", C.c_int64)]
+
+
 class Subsystem(C.Structure):
     _fields_ = [("kind", C.c_int32), ("xdim", C.c_int32), ("udim", C.c_int32), ("param0", C.c_float)]
 

@@ -825,6 +825,7 @@ const ShapeEntry* find_shape(int n, int N, int mu);
 
 #include "ilqg_problem.hpp"  // the problem object: its host tables, its device buffers, the handle
 #include "ilqg_instances.hpp"  // per-instance declarations and bindings on it
+#include "ilqg_schedule.hpp"  // how a solve runs: decide_schedule and the per-round choices
 
 // Launchers of the kernels that are instantiated per (n, N, m_i).  Members are defined out of class (not inline),
 // so `extern template struct DimsLaunch<...>` in the main unit of a split build leaves their code — and the
@@ -1129,42 +1130,6 @@ ilqg_status iteration_bound(long long round, long long cap) {
   return round > cap ? fail(ILQG_ERR_HIP, "solve did not terminate within its iteration bound") : ILQG_OK;
 }
 
-// Step sizes probed per listed instance in a round of a line-search tail: as many as the pool holds for a list this long,
-// ramping up from `probe_first` in a tail's first round (ilqg_solve_options::probe_first) and doubling per round (most
-// line searches that back-track at all end within a step or two; the ones that do not are mostly on their way through
-// all max_backtracking_steps of a failing search, and a round for the few instances left costs the latency of its
-// launches whatever it probes: 2, 4, 8, 16, 32, ...).
-// The library's `probe_first`: as many candidates per instance as keep the round's rollouts within one filling of the
-// chip (kProbeRoundBudget of them), between 2 and kProbeCandidates.  A short list is a few deep searches — the instances
-// that back-track at all mostly go on for tens of steps (the n = 16 intersection: ~10 % of the batch, mean depth ~30) —
-// and 32 at once ends them in a round or two (measured, B = 1024: 280 k -> 335 k it/s); a long list (config 4: ~40 % of
-// 4096 instances, most done within a step or two) pays for every candidate it does not need (226 k it/s at 2, 193 k at
-// 32).  Round 4, with two rollouts per wavefront and the gradient-only row pass: a budget of 8192 rollouts (config 5 /
-// n = 16 constrained / config 4: 249 k / 483 k / 248 k it/s; 4096: 240 / 469 / 252; 16384: 261 / 483 / 236; 4096
-// growing fourfold per round: 245 / 457 / 251).
-int probe_candidates(int pool_entries, int round_instances, int probe_first, int tail_rounds) {
-  int probe_k = pool_entries / round_instances;
-  if (probe_k > kProbeCandidates) probe_k = kProbeCandidates;
-  int first = probe_first;
-  if (first <= 0) {
-    first = kProbeRoundBudget / round_instances;
-    first = first < 2 ? 2 : (first > kProbeCandidates ? kProbeCandidates : first);
-  }
-  long long ramp = (long long)first << (tail_rounds < 8 ? tail_rounds : 8);
-  if (ramp < 2) ramp = 2;
-  return probe_k > ramp ? int(ramp) : probe_k;
-}
-
-// The specialised driver's choices on top of probe_candidates, measured on the MI355X and kept as
-// constants rather than scaled by the device's CU count:
-// - deep tails probe whole lane wavefronts up to this many per round, where they fill the chip;
-constexpr int kDeepTailWaves = 2400;
-// - the cost of a probing round per time step, max(one wave's chain, waves / SIMDs x a wave's issue time), in cycles as
-//   measured on the n = 15 scene: the paired form (two candidates per wave) and the lane form (64 / N candidates per
-//   wave, thirteen trigonometric evaluations in sequence, ~1180 instructions).
-constexpr double kPairChainCycles = 1500.0, kPairIssueCycles = 550.0;
-constexpr double kLaneChainCycles = 3500.0, kLaneIssueCycles = 1530.0;
-
 // What follows the per-instance blocks of a solve's workspace (ws_tail), as pointers.
 template <typename T>
 struct SolveTail {
@@ -1298,15 +1263,8 @@ struct RoundPlan {
   KernelLaunch<T> sweep, exit;          // (the sweep: unless `padded` runs it)
   PaddedSweep padded = nullptr;
   const PairTable* pad_pairs = nullptr; void* pad = nullptr;  // the padded sweep's control blocks and scratch
-  long long cap = 0;                    // the iteration bound in rounds
-  int row_chunks = 1;                   // workgroups per instance of the row kernels
-  int lane_width = 1;                   // candidates per wavefront of the lane form
-  int num_cus = 256;
-  bool split = false, counted = false, handoff = false, lists = false, bursts = false, probe = false, timed = false;
-  bool pairs = false;       // two rollouts per wavefront (roll, proll, proll_fat)
-  bool lanes_auto = false, deep_tails = false;  // AUTO may take the lane form; the deep-tail rule holds
+  SolveSchedule s{};                    // the rounds' flags, cap, row_chunks, lane_width, num_cus (ilqg_schedule.hpp)
   bool exit_fill_first = false;  // clear the round counters in front of the exit launch where they are not clean
-  bool read_restarts = false;    // read the augmented Lagrangian's restarts back behind it
 };
 
 // LDS limits of every launch of a plan (raise_lds_limit; the padded sweep raises its own)
@@ -1327,15 +1285,16 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
                        const ilqg_solve_options& opt, hipStream_t stream) {
   const DevProblem& d = p->dev;
   const int batch = sa.batch;
+  const SolveSchedule& sc = plan.s;
   raise_lds_limits(plan);
   IterLog<T> lg;
   ilqg_status s = iterate_log_open(opt, batch, stream, &lg);
   if (s != ILQG_OK) return s;
   const bool al_constrained = sa.al_mode && d.num_constraints > 0;
-  InnerClock clock(p, plan.timed, opt.max_runtime, al_constrained);
-  AlOuterClock outer(p, plan.timed && al_constrained, opt.max_runtime, clock.budget);
+  InnerClock clock(p, sc.timed, opt.max_runtime, al_constrained);
+  AlOuterClock outer(p, sc.timed && al_constrained, opt.max_runtime, clock.budget);
   p->counters_clean = false;  // whatever an earlier solve left in the round counters
-  RoundLists<T> rl(sa, tail.pass_ids, plan.cap);
+  RoundLists<T> rl(sa, tail.pass_ids, sc.cap);
   auto launch = [&](const KernelLaunch<T>& k, dim3 grid) -> ilqg_status {
     hipLaunchKernelGGL(k.kernel, grid, dim3(k.threads), k.lds, stream, d, sa);
     HIP_TRY(hipGetLastError());
@@ -1347,43 +1306,24 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
     if (s == ILQG_OK && sa.clear_counters) p->counters_clean = true;  // (SolveArgs::clear_counters)
     return s;
   };
-  const int probe_lanes_min = opt.probe_lanes == ILQG_CHOICE_OFF ? (1 << 30) : (opt.probe_lanes == ILQG_CHOICE_ON ? 2 : 8);
-  const int C = plan.lane_width;
-  bool deep_tails = false;  // a tail of this solve kept half of its list through three rounds (see the ramp below)
+  bool deep_tails = false;  // a tail of this solve kept half of its list through three rounds (round_probe_candidates)
   // the listed instances' next step sizes side by side; their states move to the first acceptable one
   auto probe_round = [&](int instances, int probe_k) -> ilqg_status {
     sa.probe_pool = tail.probe_pool;
     sa.probe_k = probe_k;
-    const int proll_y = plan.pairs ? (probe_k + 1) / 2 : probe_k;
-    // the register-rich build while every rollout of the round is resident at once at two waves per SIMD
-    const bool fat = (long long)instances * proll_y <= 8ll * plan.num_cus;
-    // A lane per (candidate, subsystem) where that is the shorter round.  A round of W waves takes about
-    // max(one wave's chain, W / SIMDs x a wave's issue time) per time step (the kProbe*Cycles model).  So the lane
-    // form wins once its own waves fill the chip (config 5's scene from 16 candidates per instance on), and loses a
-    // round of a few deep searches (n = 16: ~100 instances x 128 candidates are 700 lane waves, one chain long).
-    // (n > 16: the lane form's step carries a 2 n-term control product per lane and, for the six-state cars, spills
-    // inside the time loop — n = 24 on the feedback sweep: 2.2 ms per launch against 0.4-0.6 for the paired form,
-    // 99 k -> 83 k it/s; the model's constants are the n = 15 scene's, so AUTO leaves those shapes on pairs.)
-    const double simds = 4.0 * plan.num_cus;
-    const double w_pair = double(instances) * proll_y, w_lane = double(instances) * ((probe_k + C - 1) / C);
-    const double t_pair = std::max(kPairChainCycles, w_pair / simds * kPairIssueCycles),
-                 t_lane = std::max(kLaneChainCycles, w_lane / simds * kLaneIssueCycles);
-    const bool lanes = plan.proll_lanes.kernel && probe_k >= probe_lanes_min &&
-                       (opt.probe_lanes == ILQG_CHOICE_ON || (plan.lanes_auto && t_lane < 0.9 * t_pair));
-    // a candidate per wavefront while every one of them finds a SIMD of its own
-    const bool single = plan.proll_single.kernel && !lanes && (long long)instances * probe_k <= 4ll * plan.num_cus &&
-                        opt.probe_lanes != ILQG_CHOICE_ON;
-    const ilqg_status s = lanes    ? launch(plan.proll_lanes, dim3(instances, (probe_k + C - 1) / C))
-                          : single ? launch(plan.proll_single, dim3(instances, probe_k))
-                                   : launch(fat ? plan.proll_fat : plan.proll, dim3(instances, proll_y));
-    if (s != ILQG_OK || launch(plan.prows, dim3(plan.row_chunks, instances * probe_k)) != ILQG_OK) return ILQG_ERR_HIP;
+    const int C = sc.lane_width, proll_y = probe_pair_rows(sc, probe_k);
+    const ProbeForm form = probe_form(sc, opt, instances, probe_k);
+    const ilqg_status s = form == PROBE_LANES    ? launch(plan.proll_lanes, dim3(instances, (probe_k + C - 1) / C))
+                          : form == PROBE_SINGLE ? launch(plan.proll_single, dim3(instances, probe_k))
+                                                 : launch(form == PROBE_FAT ? plan.proll_fat : plan.proll, dim3(instances, proll_y));
+    if (s != ILQG_OK || launch(plan.prows, dim3(sc.row_chunks, instances * probe_k)) != ILQG_OK) return ILQG_ERR_HIP;
     return launch(KernelLaunch<T>{ilq_probe_pick_kernel<T>, kProbeCandidates, 0}, dim3(instances));
   };
   auto pass = [&]() -> ilqg_status {
-    if (plan.counted && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished.get(), 0, 4 * sizeof(int), stream));
+    if (sc.counted && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished.get(), 0, 4 * sizeof(int), stream));
     p->counters_clean = false;  // (the round's kernels count into them)
-    if (!plan.split && !sa.ids) {
-      sa.ids_next = plan.handoff ? rl.free_list() : nullptr;
+    if (!sc.split && !sa.ids) {
+      sa.ids_next = sc.handoff ? rl.free_list() : nullptr;
       const ilqg_status s = launch(plan.trial, dim3(batch));
       sa.first = 0;
       return s;
@@ -1391,33 +1331,15 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
     sa.ids_next = rl.free_list();
     const int instances = rl.round_instances;
     if (sa.ids) {
-      int probe_k = probe_candidates(tail.pool_entries, instances, opt.probe_first, rl.tail_rounds);
-      // Deep searches: once a tail of this solve has kept half of its list through three rounds (2 + 4 + 8 or more
-      // rejected candidates each: they are mostly on their way through all max_backtracking_steps), later tails skip the
-      // ramp.  A probing round costs one wave's chain per time step until its waves fill the chip, so every candidate up
-      // to that point is free: with the lane form (rollout_lanes: 64 / N candidates per wavefront) that is
-      // C floor(kDeepTailWaves / instances) candidates per instance — whole wavefronts —, as far as the pool holds them.
-      // (config 5's scene: rounds of 4, 10, 20, 21, 42 ... candidates -> 16 - 63 from a tail's first round on;
-      // config 4's ~1600 back-tracking instances are mostly done after a step or two: they keep the ramp.)
-      if (plan.deep_tails && rl.tail_rounds == 3 && 2 * instances >= rl.tail_first_instances) deep_tails = true;
-      if (deep_tails && opt.probe_first <= 0) {
-        int k_deep = std::min(tail.pool_entries / instances, kProbeCandidates);  // what the pool holds
-        if (plan.pairs && opt.probe_lanes != ILQG_CHOICE_OFF) {
-          const int free_waves = kDeepTailWaves / instances;
-          const int k_lane = C * (free_waves > 1 ? free_waves : 1);
-          if (k_deep > k_lane) k_deep = k_lane;
-          if (k_deep >= C) k_deep = k_deep / C * C;
-        }
-        if (probe_k < k_deep) probe_k = k_deep;
-      }
-      ilqg_status s = rl.tail_round(plan.probe, probe_k);
-      if (s == ILQG_OK && plan.probe && probe_k >= 2) s = probe_round(instances, probe_k);
+      const int probe_k = round_probe_candidates(sc, opt, tail.pool_entries, instances, rl.tail_rounds, rl.tail_first_instances, &deep_tails);
+      ilqg_status s = rl.tail_round(sc.probe, probe_k);
+      if (s == ILQG_OK && sc.probe && probe_k >= 2) s = probe_round(instances, probe_k);
       if (s != ILQG_OK) return s;
     }
     sa.round_count = instances;
-    if (launch(plan.roll, dim3(plan.pairs ? (instances + 1) / 2 : instances)) != ILQG_OK) return ILQG_ERR_HIP;
+    if (launch(plan.roll, dim3(sc.pairs ? (instances + 1) / 2 : instances)) != ILQG_OK) return ILQG_ERR_HIP;
     sa.first = 0;
-    if (launch(plan.rows, dim3(plan.row_chunks, instances)) != ILQG_OK) return ILQG_ERR_HIP;
+    if (launch(plan.rows, dim3(sc.row_chunks, instances)) != ILQG_OK) return ILQG_ERR_HIP;
     return launch(plan.decide, dim3(instances));
   };
   // Free-running solves: the kernels select their instances by the stage each one is in, so a round launched for
@@ -1429,7 +1351,7 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
   int burst = 1;
   bool exit_pending = false;  // a burst round went without its exit launch (see the burst loop)
   for (long long round = 0;; round++) {
-    if (plan.bursts && !sa.ids) {
+    if (sc.bursts && !sa.ids) {
       // a fixed-iteration solve knows its last round: no burst runs past it
       const long long left = fixed ? (long long)opt.fixed_iters - round : (long long)burst;
       for (int q = 1; q < burst && q <= left; q++) {  // rounds without a read-back
@@ -1452,11 +1374,11 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
     s = pass();
     if (s != ILQG_OK) return s;
     int want_lq = 1, want_exit = 0;
-    if (plan.counted) {
+    if (sc.counted) {
       if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
       want_lq = p->h_unfinished[0];
       want_exit = p->h_unfinished[1];
-      if (plan.lists) {
+      if (sc.lists) {
         bool again = false;
         s = rl.after_round(p->h_unfinished.get(), round, &again, &want_lq, &want_exit);
         if (s != ILQG_OK) return s;
@@ -1465,7 +1387,7 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
           continue;
         }
       }
-      if (plan.bursts) burst = p->h_unfinished[3] ? 1 : (burst < 8 ? burst * 2 : 8);
+      if (sc.bursts) burst = p->h_unfinished[3] ? 1 : (burst < 8 ? burst * 2 : 8);
     } else if (round == opt.fixed_iters) {
       want_lq = 0;
       want_exit = 1;
@@ -1490,7 +1412,7 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
       if (outer.before_exit()) sa.outer_closed = 1;  // out of time: inner solves that end now are the last ones
       if (launch(plan.exit, dim3(batch)) != ILQG_OK) return ILQG_ERR_HIP;
       p->counters_clean = false;
-      if (plan.read_restarts) {
+      if (sc.read_restarts) {
         if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
         restarted = p->h_unfinished[2];
         if (restarted) clock.restart();
@@ -1503,7 +1425,7 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
       if (s != ILQG_OK) return s;
     }
     if (!want_lq && !restarted) return ILQG_OK;  // the solve has ended
-    if (iteration_bound(round, plan.cap) != ILQG_OK) return ILQG_ERR_HIP;
+    if (iteration_bound(round, sc.cap) != ILQG_OK) return ILQG_ERR_HIP;
   }
 }
 
@@ -1511,113 +1433,159 @@ ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& ta
 
 #define DT_DISPATCH(p, CALL) ((p)->desc.dtype == ILQG_F32 ? CALL(float) : CALL(double))
 
-// The LDS of a CU (gfx950: 160 KB): the most one workgroup can be given, and what the workgroups resident on a CU share
-static constexpr size_t kLdsPerCu = size_t(160) * 1024;
-// ... among the four instances per CU of the headline batch, which the fused trial kernel's LDS is sized for
-static constexpr size_t kTrialInstancesPerCu = 4;
+// The compile-time facts of an instantiation the schedule's policy reads (ShapeTraits, ilqg_schedule.hpp)
+template <typename T, int NX, int NP, int MU>
+constexpr ShapeTraits shape_traits() {
+  using C = LQCfg<T, NX, NP, MU>;
+  using O = OLCfg<T, NX, NP, MU>;
+  using W1 = W1Cfg<T, NX, NP, MU>;
+  static_assert(O::ROW == ol_row_elems(NX, NP * MU, NP) && O::ROW_FAT == ol_row_elems(NX, NP * MU, NP, true), "ol_row_elems");
+  ShapeTraits t{};
+  t.nx = NX; t.np = NP; t.mu = MU; t.elem = int(sizeof(T));
+  t.trial_waves = TrialWaves<T>::W;
+  t.use_mfma = C::USE_MFMA;
+  t.one_tile = C::MFMA_ONE_TILE;
+  t.has_1w = W1::SUPPORTED && C::USE_MFMA && C::MFMA_ONE_TILE;
+  t.has_packed = sizeof(T) == 4 && C::USE_MFMA && C::MFMA_ONE_TILE && NP == 3;
+  if constexpr (C::USE_MFMA) {
+    t.has_forms = C::MFMA_ONE_TILE && SolveRows<NP * MU, NX + 1>::FITS;
+    t.has_bconst = t.has_forms && NX < 16 && MU == 2;
+    t.pw_lds_elems = MfmaSweepLds<T, NX, NP, MU>::ELEMS + (C::MFMA_ONE_TILE ? 0 : 4);
+  }
+  if constexpr (W1::SUPPORTED && C::USE_MFMA && C::MFMA_ONE_TILE) t.w1_lds_elems = W1::ELEMS;
+  t.w1_words = W1::kWords;
+  t.ol_threads = O::NT; t.ol_lds_elems = O::LDS_ELEMS;
+  t.valu_threads = C::NT; t.valu_lds_elems = C::LDS_ELEMS;
+  t.fwd_elems = 4 * 2 * ((NX * NX + C::SCR + 3) & ~3) + 2 * NX + 8;
+  t.pairs = rollout_pairs(NX, NP, MU);
+  t.may_xdyn = dims_use_plain_rk4(NX, NP, MU);
+  t.rows_in_regs = rows_state_in_registers(NX, NP * MU);
+  t.partials_room = fused_partials_room(int(sizeof(T)), NX, NP, MU);
+  t.lane_width = rollout_lanes_per_wave(NP > 0 ? NP : 1);
+#define X(ID_, NX_, NP_, MU_)                                                             \
+  if constexpr (NX_ == NX && NP_ == NP && MU_ == MU) {                                   \
+    t.static_ids[t.num_static] = ID_;                                                     \
+    t.static_in_regs[t.num_static++] = static_prog_in_registers<StaticRowProg<ID_>>();    \
+  }
+  ILQG_STATIC_PROGS(X)
+#undef X
+  return t;
+}
 
+inline ProblemFacts problem_facts(const ilqg_problem* p) {
+  return {p->desc.params, p->static_prog, p->b_constant, p->has_expression, p->has_expression_dynamics, p->bindings.any(),
+          p->dev.inst_solver != 0};
+}
+
+// The one place a row program's (kind, bound, static id) picks an instantiation: f(PROGID, BOUND) as integral constants,
+// for the fused trial kernel, the split row kernel and the probing row kernel of a shape (NX = 0: the run-time-dimensioned
+// kernels).  A registered structure goes before the expression kinds (it holds none); a problem with per-instance tables
+// bound runs twins of its own where the kernel has one (ilqg_solve.hpp).
+template <typename R, int NX, int NP, int MU, typename F>
+R for_row_program(int prog_kind, int static_id, bool bound, F f) {
+  using Bound = std::true_type;
+  using Unbound = std::false_type;
+#define X(ID_, NX_, NP_, MU_)                                  \
+  if constexpr (NX_ == NX && NP_ == NP && MU_ == MU)           \
+    if (static_id == ID_)                                      \
+      return bound ? f(std::integral_constant<int, kBoundProg + ID_>{}, Bound{}) : f(std::integral_constant<int, ID_>{}, Unbound{});
+  ILQG_STATIC_PROGS(X)
+#undef X
+  if constexpr (NX == 0 || dims_use_plain_rk4(NX, NP, MU))
+    if (prog_kind == PROG_EXPR_DYN)
+      return bound ? f(std::integral_constant<int, kExprDynProg>{}, Bound{}) : f(std::integral_constant<int, kExprDynProg>{}, Unbound{});
+  if (prog_kind == PROG_EXPR)
+    return bound ? f(std::integral_constant<int, kExprProg>{}, Bound{}) : f(std::integral_constant<int, kExprProg>{}, Unbound{});
+  return bound ? f(std::integral_constant<int, 0>{}, Bound{}) : f(std::integral_constant<int, 0>{}, Unbound{});
+}
+template <typename T>
+using SolveKernel = void (*)(DevProblem, SolveArgs<T>);
+template <typename T, int NX, int NP, int MU>
+SolveKernel<T> rows_kernel_of(int prog_kind, int static_id, bool bound) {
+  return for_row_program<SolveKernel<T>, NX, NP, MU>(prog_kind, static_id, bound, [](auto id, auto) {
+    return SolveKernel<T>(ilq_rows_kernel<T, NX, NP, MU, decltype(id)::value>);
+  });
+}
+template <typename T, int NX, int NP, int MU>
+SolveKernel<T> probe_rows_kernel_of(int prog_kind, int static_id, bool bound) {
+  return for_row_program<SolveKernel<T>, NX, NP, MU>(prog_kind, static_id, bound, [](auto id, auto) {
+    return SolveKernel<T>(ilq_probe_rows_kernel<T, NX, NP, MU, decltype(id)::value>);
+  });
+}
+
+// The sweep instantiation of (sweep_kind, sweep_forms)
+template <typename T, int NX, int NP, int MU>
+SolveKernel<T> sweep_kernel_of(const SolveSchedule& s) {
+  static constexpr ShapeTraits st = shape_traits<T, NX, NP, MU>();
+  if (s.sweep_kind == LQ_OPEN_LOOP_COMPACT) return ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP_COMPACT>;
+  if (s.sweep_kind == LQ_OPEN_LOOP) return ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP>;
+  if constexpr (!st.use_mfma) {
+    return ilq_lq_kernel<T, NX, NP, MU, LQ_VALU_FEEDBACK>;
+  } else {
+    auto forms_of = [&](auto kind) -> SolveKernel<T> {
+      constexpr int KIND = decltype(kind)::value;
+      if constexpr (st.has_bconst && KIND != LQ_SINGLE_WAVE)
+        if (s.sweep_forms == 2) return ilq_lq_kernel<T, NX, NP, MU, KIND, 2>;
+      if constexpr (st.has_forms)
+        if (s.sweep_forms == 0) return ilq_lq_kernel<T, NX, NP, MU, KIND, 0>;
+      return ilq_lq_kernel<T, NX, NP, MU, KIND>;
+    };
+    if constexpr (st.has_1w)
+      if (s.sweep_kind == LQ_SINGLE_WAVE) return forms_of(std::integral_constant<int, LQ_SINGLE_WAVE>{});
+    if constexpr (st.has_packed)
+      if (s.sweep_kind == LQ_PLAYER_WAVES_PACKED) return forms_of(std::integral_constant<int, LQ_PLAYER_WAVES_PACKED>{});
+    return forms_of(std::integral_constant<int, LQ_PLAYER_WAVES>{});
+  }
+}
+
+// A schedule's decisions as kernel addresses: nothing is decided here.
+template <typename T, int NX, int NP, int MU>
+RoundPlan<T> bind_plan(const SolveSchedule& s) {
+  constexpr int W = TrialWaves<T>::W;
+  constexpr bool kMayXdyn = dims_use_plain_rk4(NX, NP, MU);
+  RoundPlan<T> plan;
+  plan.s = s;
+  plan.trial = {for_row_program<SolveKernel<T>, NX, NP, MU>(s.prog_kind, s.static_prog, s.bound != 0, [](auto id, auto bound) {
+                  return SolveKernel<T>(ilq_trial_kernel<T, NX, NP, MU, W, decltype(id)::value, decltype(bound)::value>);
+                }), 64 * W, size_t(s.lds_trial)};
+  plan.sweep = {sweep_kernel_of<T, NX, NP, MU>(s), s.sweep_threads, size_t(s.lds_sweep)};
+  plan.exit = {ilq_exit_kernel<T, NX, NP, MU>, s.nt_exit, size_t(s.lds_exit)};
+  if (!s.lists) return plan;
+  plan.roll = {ilq_roll_kernel<T, NX, NP, MU>, 64, size_t(s.lds_roll)};
+  plan.rows = {rows_kernel_of<T, NX, NP, MU>(s.prog_kind, s.static_id, s.bound != 0), 64, size_t(s.lds_rows)};
+  plan.decide = {s.decide_solver ? ilq_decide_kernel<T, NX, NP, MU, true> : ilq_decide_kernel<T, NX, NP, MU, false>, 64, size_t(s.lds_decide)};
+  plan.prows = {probe_rows_kernel_of<T, NX, NP, MU>(s.prog_kind, s.static_id, s.bound != 0), 64, size_t(s.lds_prows)};
+  plan.proll = {ilq_probe_roll_kernel<T, NX, NP, MU>, 64, size_t(s.lds_proll)};
+  plan.proll_fat = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8>, 64, size_t(s.lds_proll)};  // (fp32: the same kernel)
+  if (s.proll_single) plan.proll_single = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, true>, 64, size_t(s.lds_proll_single)};
+  if (s.proll_lanes) plan.proll_lanes = {ilq_probe_roll_lanes_kernel<T, NX, NP, MU>, 64, size_t(s.lds_proll_lanes)};
+  if constexpr (kMayXdyn)  // (a plain-RK4 shape: one rollout per wavefront, no paired or lane-per-candidate form)
+    if (s.prog_kind == PROG_EXPR_DYN) {
+      plan.roll.kernel = ilq_roll_kernel<T, NX, NP, MU, true>;
+      plan.proll.kernel = ilq_probe_roll_kernel<T, NX, NP, MU, false, false, true>;
+      plan.proll_fat.kernel = ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, false, true>;
+    }
+  return plan;
+}
+
+// The specialised solve: its arguments, the mask's count where the schedule wants it (the only device interaction before
+// the rounds), the schedule (decide_schedule, ilqg_schedule.hpp), its kernels (bind_plan), the rounds.
 template <typename T, int NX, int NP, int MU>
 ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, const void* x0, void* xs, void* us,
                                              void* P, void* alpha, void* total_costs, int32_t* iters, int32_t* status,
                                              int32_t* converged, void* workspace, const ilqg_solve_options& opt,
                                              hipStream_t stream) {
-  using C = LQCfg<T, NX, NP, MU>;
-  using O = OLCfg<T, NX, NP, MU>;
   const DevProblem& d = p->dev;
-  const int32_t fixed_iters = opt.fixed_iters;
-  const bool open_loop = p->desc.params.open_loop;
-  auto choice = [](int32_t c, bool automatic) { return c == ILQG_CHOICE_ON ? true : (c == ILQG_CHOICE_OFF ? false : automatic); };
-  static_assert(O::ROW == ol_row_elems(NX, NP * MU, NP) && O::ROW_FAT == ol_row_elems(NX, NP * MU, NP, true), "ol_row_elems");
   SolveTail<T> tail;
   SolveArgs<T> sa = solve_args_of<T>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, opt, &tail);
-  const int al_mode = sa.al_mode;
-  const WsLayout L = ws_layout_of(d, sa.ol_row, al_mode);
 #if ILQG_DIAGNOSTIC_BUILD
   sa.prof = g_prof;
 #endif
   // ws_tail places the lists behind the augmented-Lagrangian layout (the larger one): whatever al_mode this solve runs in
-  if (ws_layout_of(d, sa.ol_row, 1).total < L.total)
+  if (ws_layout_of(d, sa.ol_row, 1).total < ws_layout_of(d, sa.ol_row, sa.al_mode).total)
     return fail(ILQG_ERR_INVALID, "workspace layout: the tail offset does not cover this solve's per-instance blocks");
-
-  // The schedule: every AUTO decision, into `plan` and `sa`.  Nothing is launched here but the mask count.
-  RoundPlan<T> plan;
-  constexpr int W = TrialWaves<T>::W;
-  // Rows per chunk of the row stage: the widest whose scratch lets a CU hold four instances of the fused trial kernel
-  // (the headline batch is four instances per CU); the split row kernels get the same width.
-  {
-    const size_t fixed = rows_maps_bytes(d) + ((rollout_lds_elems(d.n, d.m) + 3) & ~size_t(3)) * sizeof(T) + 16;
-    const size_t per_instance = kLdsPerCu / kTrialInstancesPerCu;
-    const size_t budget = per_instance > fixed ? (per_instance - fixed) / trial_row_waves(W) : 0;
-    sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), budget);
-  }
-  // (a problem with per-instance tables bound runs fused kernels of its own, here and below: ilqg_solve.hpp)
-  const bool bound = p->bindings.any();
-  // (... and so does a problem that holds an expression cost: the interpreter with the evaluator in it, kExprProg — in
-  // the fused kernel, the split row kernel and the merit-only one; it matches no registered structure)
-  const bool expr = p->has_expression;
-  auto k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, 0, true> : ilq_trial_kernel<T, NX, NP, MU, W>;
-  if (expr) k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, kExprProg, true> : ilq_trial_kernel<T, NX, NP, MU, W, kExprProg, false>;
-  // (... and a problem that holds an expression subsystem, in the two plain-RK4 shapes: kExprDynProg, the rollout with
-  // the expression integrator and the interpreter that linearises it — the fused kernel, the split and probing passes)
-  constexpr bool kMayXdyn = dims_use_plain_rk4(NX, NP, MU);
-  const bool xdyn = kMayXdyn && p->has_expression_dynamics;
-  if constexpr (kMayXdyn)
-    if (xdyn) k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, kExprDynProg, true> : ilq_trial_kernel<T, NX, NP, MU, W, kExprDynProg, false>;
-  const bool pw = C::USE_MFMA && !open_loop;  // one wave per player (MFMA feedback sweep)
-  // Compact rows (ilqg_common.hpp) between the row stage and the sweep: the one-tile player-parallel sweep and the
-  // open-loop sweep read them; the other sweeps take the dense arrays.  What the row stage writes and the sweep reads
-  // per time step shrinks from N (n^2 + n) + ... words to the ones a cost term can touch.
-  // ... and only when the [T][rp_compact_w] rows fit the space they are kept in: the dense Q, l, R, r arrays up to the
-  // sweep's scratch rows (a small or densely coupled problem's row carries the A and B words too)
-  const bool compact_on = d.rp_compact_w > 0 && size_t(d.T) * size_t(d.rp_compact_w) <= L.lqscr - L.Q &&
-                          choice(opt.compact_rows, true);
-  const bool ol_compact = open_loop && compact_on;
-  // A registered row-program structure (ilqg_rowprog_static.hpp): the row stage as straight-line code for it — in the
-  // fused kernel (state rows in registers, i.e. without the chunk's (x, u) image in LDS, so it takes the 64-row chunk
-  // where the interpreter's scratch would not fit four instances on a CU: n = 16 in fp64), in the split row kernel and
-  // in the merit-only row kernel of the speculative line search.  Same results, bit for bit.
-  int static_id = 0;    // the structure the split / probing row kernels are compiled for (0: they interpret)
-  int static_prog = 0;  // ... and the fused kernel
-  auto k_rows = expr ? ilq_rows_kernel<T, NX, NP, MU, kExprProg> : ilq_rows_kernel<T, NX, NP, MU>;
-  auto k_prows = expr ? ilq_probe_rows_kernel<T, NX, NP, MU, kExprProg> : ilq_probe_rows_kernel<T, NX, NP, MU>;
-  if constexpr (kMayXdyn)
-    if (xdyn) {
-      k_rows = ilq_rows_kernel<T, NX, NP, MU, kExprDynProg>;
-      k_prows = ilq_probe_rows_kernel<T, NX, NP, MU, kExprDynProg>;
-    }
-  // (the static kernels exist for solves on compact rows: they write nothing dense)
-  const bool will_compact = (pw && C::MFMA_ONE_TILE && compact_on) || ol_compact;
-  bool static_in_regs = false;  // ... with the slots of a chunk in registers (ilqg_rows.hpp: no row scratch in LDS)
-  if (opt.static_rows != ILQG_CHOICE_OFF && will_compact) {
-#define X(ID_, NX_, NP_, MU_)                                                                                  \
-    if constexpr (NX_ == NX && NP_ == NP && MU_ == MU)                                                         \
-      if (p->static_prog == ID_) {                                                                             \
-        static_id = ID_;                                                                                       \
-        static_in_regs = static_prog_in_registers<StaticRowProg<ID_>>();                                       \
-        k_rows = bound ? ilq_rows_kernel<T, NX, NP, MU, kBoundProg + ID_> : ilq_rows_kernel<T, NX, NP, MU, ID_>; \
-        k_prows = bound ? ilq_probe_rows_kernel<T, NX, NP, MU, kBoundProg + ID_>                               \
-                        : ilq_probe_rows_kernel<T, NX, NP, MU, ID_>;                                           \
-        if (rows_state_in_registers(NX, NP * MU) && trial_lds_bytes<T>(d, W, 64, true) <= kLdsPerCu / kTrialInstancesPerCu) { \
-          k_trial = bound ? ilq_trial_kernel<T, NX, NP, MU, W, kBoundProg + ID_>                               \
-                          : ilq_trial_kernel<T, NX, NP, MU, W, ID_>;                                           \
-          static_prog = ID_;                                                                                   \
-        }                                                                                                      \
-      }
-    ILQG_STATIC_PROGS(X)
-#undef X
-  }
-  const int rows_cw_interpreted = sa.rows_cw;
-  if (static_prog) sa.rows_cw = 64;
-  const size_t lds_trial = trial_lds_bytes<T>(d, W, sa.rows_cw, static_prog != 0);
-  // The schedules below are chosen by how many instances the chip will hold at once.  Under a mask that is the number
-  // of instances taking part, not the length of the buffers: a receding-horizon loop replans the few dozen plans
-  // still running of a batch of 2048 (src/receding_horizon_simulator.cpp:77), and the throughput forms chosen for 2048
-  // — single-wave sweep, adjoint expected decrease, split trial pass — are latency forms three times slower for them
-  // (config 5 as written: 400 us per sweep launch instead of 190).  A free-running solve waits for the device every
-  // round anyway, so it counts its mask first (one more read-back per call); a fixed-iteration solve stays
-  // asynchronous and keeps the buffer length.
   int sched_batch = batch;
-  if (opt.active && !opt.forced_steps && !opt.deterministic && !(fixed_iters > 0 && !al_mode)) {
+  if (schedule_counts_mask(opt)) {
     HIP_TRY(hipMemsetAsync(p->d_unfinished.get(), 0, 4 * sizeof(int), stream));  // (whatever an earlier solve left there)
     hipLaunchKernelGGL(ilq_count_active_kernel, dim3(1), dim3(256), 0, stream, opt.active, int(batch), p->d_unfinished.get());
     HIP_TRY(hipGetLastError());
@@ -1627,168 +1595,16 @@ ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, con
   int num_cus = 256, dev = 0;
   hipDeviceProp_t prop;
   if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) num_cus = prop.multiProcessorCount;
-  // (the exit kernel copies an instance's final iterate, T m n words of strategies among them: four waves where the
-  // instances are few and the kernel is a link of the round's chain, one where they share the chip's bandwidth anyway)
-  const int nt_exit = sched_batch <= 2 * num_cus ? 256 : 64;
-  const bool big_batch = size_t(sched_batch) >= size_t(8) * num_cus;
-  // the whole batch resident at once (four instances per CU): fair issue arbitration among the co-resident instances
-  sa.prio_div = (sched_batch > num_cus && sched_batch <= 4 * num_cus) ? num_cus : 0;
-  // ... and wherever the single-wave sweep (below) will run: it takes its expected decrease from its own adjoint pass, so
-  // nothing is left for the fused kernel's row wave to overlap with the rollout, and the three split kernels each keep
-  // more instances on a CU than the fused one (measured, n = 14, B = 8192, LQ single-wave + adjoint: fp64 1.58 M it/s
-  // fused vs 1.65 M split, fp32 2.61 M vs 2.77 M; B = 2048 fp64 1.40 M vs 1.50 M).  (want_1w foresees that sweep with
-  // its adjoint pass; single_wave below is the one that runs, which may take a fused kernel's forward pass instead.)
-  constexpr bool has_1w = W1Cfg<T, NX, NP, MU>::SUPPORTED && C::USE_MFMA && C::MFMA_ONE_TILE;
-  const bool want_1w = has_1w && pw && compact_on && !kProfile && d.rp_compact_w <= W1Cfg<T, NX, NP, MU>::kWords &&
-                       choice(opt.single_wave_sweep, !opt.deterministic && size_t(sched_batch) >= size_t(5) * num_cus) &&
-                       opt.adjoint_expected_decrease != ILQG_CHOICE_OFF;
-  // Split passes: where the fused kernel cannot keep four instances on a CU (n = 24), and for batches that are several
-  // times what it keeps resident when the split integration kernel (a quarter of the registers, 4 KB of LDS) gains from
-  // the co-residency — measured: n = 24, B = 4096: 65 k vs 39 k it/s.  For n <= 16 the fused kernel stays
-  // (round 3, with compact rows: n = 14 fp32, B = 8192: 1.97 M fused vs 1.79 M split; fp64: 1.34 M vs 1.27 M).  The
-  // host then counts every round: an instance may ask for another pass (back-tracking) before its sweep.
-  // ilqg_solve_options::split_trial overrides the choice.
-  bool split = choice(opt.split_trial, kTrialInstancesPerCu * lds_trial > kLdsPerCu || (big_batch && NX > 16) || want_1w);
-  if (kProfile || opt.forced_steps) split = false;  // the phase profile reads the fused kernel's counters
-  if (split) {  // the split row kernels interpret the program: their chunk width is the interpreter's
-    static_prog = 0;
-    sa.rows_cw = rows_cw_interpreted;
-  }
-  sa.compact = will_compact ? 1 : 0;
-  const size_t split_maps_bytes = sa.compact ? 0 : rows_maps_bytes(d);  // the split row kernels' copy of the word maps
-  if (split) {
-    // The split row kernel is one wave per chunk with the chunk's scratch to itself, and its instances per CU are what
-    // the scratch leaves room for: chunks of equal width (T = 100: 2 x 50 rows, 28 KB, five per CU — not 64 + 36 at 36 KB
-    // and four).
-    const int chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;
-    sa.rows_cw = (d.T + chunks - 1) / chunks;
-  }
-  const bool counted = !opt.forced_steps && (split || !(fixed_iters > 0 && !al_mode) || choice(opt.counted, false));
-  // Hand-off: whenever the host counts rounds anyway, the fused kernel keeps an instance only until its line
-  // search rejects a step; the back-tracking instances then go through split passes with the speculative line
-  // search (ilqg_solve_options::handoff = OFF keeps every pass in the fused kernel).
-  const bool handoff = counted && !split && !kProfile && sa.prm.linesearch && choice(opt.handoff, true);
-  const bool lists = split || handoff;
-  // The sweep's forward pass runs in the fused trial kernel that follows it, beside the rollout, whenever that is the
-  // kernel that follows (split passes and the open-loop sweep keep it in the sweep's kernel).
-  sa.defer_forward = (!split && !open_loop) ? 1 : 0;
-  {
-    constexpr size_t fwd_elems = 4 * 2 * ((NX * NX + C::SCR + 3) & ~3) + 2 * NX + 8;
-    if (trial_rows_elems(d, sa.rows_cw, static_prog != 0) < fwd_elems + 8) sa.defer_forward = 0;
-  }
-  // The throughput form of the one-tile feedback sweep — one wave per instance, twice the instances per CU
-  // (ilqg_lq_feedback1w.hpp) — for batches of five or more instances per CU (measured, n = 14 fp64: B = 1024 1.47 M it/s
-  // player-parallel vs 1.11 M single-wave; 1280: 1.09 vs 1.10; 1536: 1.17 vs 1.25; 2048: 1.20 vs 1.45; 8192: 1.45 vs
-  // 1.68); it reads compact rows and leaves the forward pass to the trial kernel.
-  // ilqg_solve_options::single_wave_sweep overrides the choice (same results to rounding).
-  // Where the expected decrease of a single-wave sweep comes from: its own adjoint recursion, or — only possible with the
-  // fused trial kernel, whose row wave runs it — the deferred forward pass over the sweep's scratch rows.
-  const bool adjoint = choice(opt.adjoint_expected_decrease, sa.defer_forward == 0);
-  const bool single_wave = has_1w && pw && sa.compact && !kProfile && (adjoint || sa.defer_forward) &&
-                           d.rp_compact_w <= W1Cfg<T, NX, NP, MU>::kWords &&
-                           choice(opt.single_wave_sweep, !opt.deterministic && size_t(sched_batch) >= size_t(5) * num_cus);
-  if (single_wave) {
-    sa.prio_div = 0;
-    if (adjoint) sa.defer_forward = 0;  // the sweep forms the expected decrease itself: no forward pass anywhere
-  }
-  // The sweep kernel.  The open-loop sweep's LDS is its own working set plus the slot the expected decrease is handed
-  // over in (n = 24: 54 KB, three instances per CU; the feedback layout would take 85 KB).  fp32, one-tile sweep of
-  // three player waves, many instances per CU: the 128-register build (see ilq_lq_kernel).
-  constexpr bool has_packed = sizeof(T) == 4 && C::USE_MFMA && C::MFMA_ONE_TILE && NP == 3;
-  bool b_const = false;  // the sweep with B's constant entries in registers (ILQG_SCHEDULE_CONSTANT_B)
-  if (open_loop) {
-    plan.sweep = {ol_compact ? ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP_COMPACT> : ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP>,
-                  O::NT, (O::LDS_ELEMS + 4) * sizeof(T)};
-  } else if constexpr (!C::USE_MFMA) {
-    plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_VALU_FEEDBACK>, C::NT, C::LDS_ELEMS * sizeof(T)};
-  } else {
-    plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES>, 64 * NP,
-                  (MfmaSweepLds<T, NX, NP, MU>::ELEMS + (C::MFMA_ONE_TILE ? 0 : 4)) * sizeof(T)};
-    // ilqg_solve_options::sweep_forms = OFF: the read-lane instantiation of the same kind (only where the two differ)
-    constexpr bool has_forms = C::MFMA_ONE_TILE && SolveRows<NP * MU, NX + 1>::FITS;
-    const bool forms = choice(opt.sweep_forms, true);
-    // ... and with the forms on, a problem whose B is constant entries, at most one per row and column (ilqg_problem::
-    // b_constant), takes them from registers instead of the B tile — the solver's instantiation of the one-tile sweep with
-    // a spare tile column and two controls per player, i.e. compact rows and the forward pass in the trial kernel
-    constexpr bool has_bconst = has_forms && NX < 16 && MU == 2;
-    b_const = has_bconst && forms && p->b_constant && sa.compact && sa.defer_forward && !single_wave;
-    if constexpr (has_forms)
-      if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES, 0>;
-    if constexpr (has_bconst)
-      if (b_const) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES, 2>;
-    if constexpr (has_packed) {
-      if (size_t(sched_batch) >= size_t(5) * 256) {
-        plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED>;
-        if constexpr (has_forms)
-          if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED, 0>;
-        if constexpr (has_bconst)
-          if (b_const) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_PLAYER_WAVES_PACKED, 2>;
-      }
-    }
-    if constexpr (has_1w) {
-      if (single_wave) {
-        plan.sweep = {ilq_lq_kernel<T, NX, NP, MU, LQ_SINGLE_WAVE>, 64, size_t(W1Cfg<T, NX, NP, MU>::ELEMS + 4) * sizeof(T)};
-        if constexpr (has_forms)
-          if (!forms) plan.sweep.kernel = ilq_lq_kernel<T, NX, NP, MU, LQ_SINGLE_WAVE, 0>;
-      }
-    }
-  }
+  static constexpr ShapeTraits traits = shape_traits<T, NX, NP, MU>();
+  const SolveSchedule s = decide_schedule(traits, d, problem_facts(p), opt, batch, sched_batch, num_cus, kProfile);
+  sa.rows_cw = s.rows_cw;
+  sa.compact = s.compact;
+  sa.defer_forward = s.defer_forward;
+  sa.prio_div = s.prio_div;
+  sa.lds_part = s.lds_part;
   sa.clear_counters = 1;
-  // The fused kernel with a register-held static row stage keeps the per-row partials of a trial's reductions in LDS as
-  // well (trial_part_instance's running reductions) — where four instances still fit a CU with that block behind theirs.
-  size_t lds_part_bytes = 0;
-  if (static_prog && static_in_regs && W == 2 && fused_partials_room(int(sizeof(T)), NX, NP, MU)) {
-    const size_t extra = partials_lds_elems(d.T, d.N) * sizeof(T);
-    if (kTrialInstancesPerCu * (lds_trial + extra) <= kLdsPerCu) lds_part_bytes = extra;
-  }
-  sa.lds_part = lds_part_bytes ? 1 : 0;
-  plan.trial = {k_trial, 64 * W, lds_trial + lds_part_bytes};
-  plan.exit = {ilq_exit_kernel<T, NX, NP, MU>, nt_exit, quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T)};
-  plan.read_restarts = counted && al_mode;
-  constexpr bool pairs = rollout_pairs(NX, NP, MU);  // two rollouts per wavefront (ilqg_stages.hpp)
-  if (lists) {
-    const size_t lds_roll = trial_phase_lds_bytes<T>(d, TRIAL_ROLL, sa.rows_cw);
-    const size_t lds_proll = pairs ? size_t(rollout_pair_lds_elems(d.n, d.m)) * sizeof(T) + 16 : lds_roll;
-    // (a static row kernel whose slots are registers needs no scratch beyond the (x, u) image of shapes past 16 states)
-    const size_t static_regs_lds = (rows_state_in_registers(NX, NP * MU) ? 0 : size_t(d.n + d.m) * 64) * sizeof(T) + 16;
-    const int rows_cw = static_id ? 64 : sa.rows_cw;
-    const bool regs = static_id && static_in_regs;
-    plan.roll = {ilq_roll_kernel<T, NX, NP, MU>, 64, lds_proll};
-    plan.rows = {k_rows, 64, regs ? static_regs_lds : split_maps_bytes + split_rows_elems(d, NX, rows_cw) * sizeof(T)};
-    plan.decide = {d.inst_solver ? ilq_decide_kernel<T, NX, NP, MU, true> : ilq_decide_kernel<T, NX, NP, MU, false>, 64,
-                   trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw)};
-    plan.prows = {k_prows, 64, regs ? static_regs_lds : split_maps_bytes + probe_rows_elems(d, NX, rows_cw) * sizeof(T)};
-    plan.proll = {ilq_probe_roll_kernel<T, NX, NP, MU>, 64, lds_proll};
-    plan.proll_fat = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8>, 64, lds_proll};  // (fp32: the same kernel)
-    if (pairs) {  // (not `if constexpr`: every shape keeps these kernels)
-      plan.proll_single = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, true>, 64, lds_roll};
-      plan.proll_lanes = {ilq_probe_roll_lanes_kernel<T, NX, NP, MU>, 64, size_t(rollout_lanes_lds_elems(d.n, d.m, d.N)) * sizeof(T) + 16};
-    }
-    if constexpr (kMayXdyn)  // (a plain-RK4 shape: one rollout per wavefront, no paired or lane-per-candidate form)
-      if (xdyn) {
-        plan.roll = {ilq_roll_kernel<T, NX, NP, MU, true>, 64, lds_proll};
-        plan.proll = {ilq_probe_roll_kernel<T, NX, NP, MU, false, false, true>, 64, lds_proll};
-        plan.proll_fat = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, false, true>, 64, lds_proll};
-      }
-  }
-  plan.cap = al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
-                     : (long long)sa.prm.max_solver_iters + 2;
-  if (split || counted) plan.cap = (plan.cap + 2) * ((long long)sa.prm.max_backtracking_steps + 3);
-  plan.row_chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;
-  plan.lane_width = rollout_lanes_per_wave(NP > 0 ? NP : 1);
-  plan.num_cus = num_cus;
-  plan.split = split; plan.counted = counted; plan.handoff = handoff; plan.lists = lists; plan.pairs = pairs;
-  plan.timed = opt.max_runtime > 0.0 && counted;  // (InnerClock reads the clock in front of every iteration: no bursts)
-  plan.bursts = counted && !kProfile && !plan.timed && choice(opt.round_bursts, true);
-  plan.probe = lists && sa.prm.linesearch && choice(opt.probe, true);
-  plan.lanes_auto = NX <= 16;
-  plan.deep_tails = true;
-  p->last_schedule = (single_wave ? ILQG_SCHEDULE_SINGLE_WAVE_SWEEP : 0) | ((single_wave && adjoint) ? ILQG_SCHEDULE_ADJOINT_DECREASE : 0) |
-                     (split ? ILQG_SCHEDULE_SPLIT_TRIAL : 0) | (sa.compact ? ILQG_SCHEDULE_COMPACT_ROWS : 0) |
-                     (counted ? ILQG_SCHEDULE_COUNTED : 0) | (open_loop ? ILQG_SCHEDULE_OPEN_LOOP : 0) |
-                     ((static_prog || (static_id && split)) ? ILQG_SCHEDULE_STATIC_ROWS : 0) |
-                     (b_const ? ILQG_SCHEDULE_CONSTANT_B : 0);
-  return run_rounds(p, sa, tail, plan, opt, stream);
+  p->last_schedule = s.word;
+  return run_rounds(p, sa, tail, bind_plan<T, NX, NP, MU>(s), opt, stream);
 }
 
 #if defined(ILQG_PART_NX)
@@ -1820,13 +1636,15 @@ struct ShapeEntry {
   decltype(&DimsLaunch<float, 0, 0, 0>::rows) rows[2];
   PaddedSweep lq_padded[2];
   decltype(&DimsLaunch<float, 0, 0, 0>::lq_padded_batch) lq_padded_batch[2];
+  ShapeTraits traits[2];  // what decide_schedule reads of the shape (needs no kernel: ilqg_schedule_build)
 };
 template <int NX, int NP, int MU>
 constexpr ShapeEntry shape_entry() {
   using F = DimsLaunch<float, NX, NP, MU>;
   using D = DimsLaunch<double, NX, NP, MU>;
   return {NX, NP, MU, {F::lq, D::lq}, {F::lq_openloop, D::lq_openloop}, {F::solve, D::solve}, {F::rows, D::rows},
-          {F::lq_padded, D::lq_padded}, {F::lq_padded_batch, D::lq_padded_batch}};
+          {F::lq_padded, D::lq_padded}, {F::lq_padded_batch, D::lq_padded_batch},
+          {shape_traits<float, NX, NP, MU>(), shape_traits<double, NX, NP, MU>()}};
 }
 #define X(NX_, NP_, MU_) shape_entry<NX_, NP_, MU_>(),
 const ShapeEntry kShapes[] = {ILQG_FOR_DIMS(X)};
@@ -1892,12 +1710,12 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
   const DevProblem& d = p->dev;
   SolveTail<T> tail;
   SolveArgs<T> sa = solve_args_of<T>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, opt, &tail);
-  p->last_schedule = ILQG_SCHEDULE_GENERIC | ILQG_SCHEDULE_SPLIT_TRIAL | ILQG_SCHEDULE_COUNTED |
-                     (p->desc.params.open_loop ? ILQG_SCHEDULE_OPEN_LOOP : 0);
+  const bool open_loop = p->desc.params.open_loop != 0;
+  p->last_schedule = generic_schedule_word(open_loop, false);
   sa.rows_cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), size_t(48) * 1024);
   const size_t lds_roll = trial_phase_lds_bytes<T>(d, TRIAL_ROLL, sa.rows_cw);
   const size_t lds_rows = rows_maps_bytes(d) + trial_rows_elems(d, sa.rows_cw) * sizeof(T);
-  const size_t lds_lq = ((p->desc.params.open_loop ? gen_openloop_lds_elems(d.n, d.N, d.m) : gen_feedback_lds_elems(d.n, d.N, d.m)) + 4) * sizeof(T);
+  const size_t lds_lq = ((open_loop ? gen_openloop_lds_elems(d.n, d.N, d.m) : gen_feedback_lds_elems(d.n, d.N, d.m)) + 4) * sizeof(T);
   if (lds_lq > kLdsPerCu || lds_rows > kLdsPerCu)
     return fail(ILQG_ERR_UNSUPPORTED, "the game does not fit a CU's LDS");
   // Back-tracking instances are listed and their next step sizes probed side by side, as in the specialised solve
@@ -1905,27 +1723,29 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
   // (round 5: mixed_dubins_car_scene, B = 1024: 76 passes per iteration, 42 k it/s).  One rollout per wavefront and
   // candidate: the probing rollout has a single form, so "fat" is the same kernel.
   RoundPlan<T> plan;
-  plan.roll = {ilq_roll_kernel<T, 0, 0, 0>, 64, lds_roll};
-  plan.rows = {p->has_expression ? ilq_rows_kernel<T, 0, 0, 0, kExprProg> : ilq_rows_kernel<T, 0, 0, 0>, 64, lds_rows};
+  const bool xdyn = p->has_expression_dynamics;  // (kExprDynProg: kernels of their own, ilqg_solve.hpp)
+  const int prog_kind = xdyn ? PROG_EXPR_DYN : p->has_expression ? PROG_EXPR : PROG_PLAIN;
+  plan.roll = {xdyn ? ilq_roll_kernel<T, 0, 0, 0, true> : ilq_roll_kernel<T, 0, 0, 0>, 64, lds_roll};
+  plan.rows = {rows_kernel_of<T, 0, 0, 0>(prog_kind, 0, false), 64, lds_rows};
   plan.decide = {ilq_decide_kernel<T, 0, 0, 0>, 64, trial_phase_lds_bytes<T>(d, TRIAL_DECIDE, sa.rows_cw)};
-  plan.proll = plan.proll_fat = {ilq_probe_roll_kernel<T, 0, 0, 0>, 64, lds_roll};
-  plan.prows = {p->has_expression ? ilq_probe_rows_kernel<T, 0, 0, 0, kExprProg> : ilq_probe_rows_kernel<T, 0, 0, 0>, 64, rows_maps_bytes(d) + probe_rows_elems(d, 0, sa.rows_cw) * sizeof(T)};
-  if (p->has_expression_dynamics) {  // (kExprDynProg: kernels of their own, ilqg_solve.hpp)
-    plan.roll = {ilq_roll_kernel<T, 0, 0, 0, true>, 64, lds_roll};
-    plan.rows = {ilq_rows_kernel<T, 0, 0, 0, kExprDynProg>, 64, lds_rows};
-    plan.proll = plan.proll_fat = {ilq_probe_roll_kernel<T, 0, 0, 0, false, false, true>, 64, lds_roll};
-    plan.prows = {ilq_probe_rows_kernel<T, 0, 0, 0, kExprDynProg>, 64, plan.prows.lds};
-  }
+  plan.proll = plan.proll_fat = {xdyn ? ilq_probe_roll_kernel<T, 0, 0, 0, false, false, true> : ilq_probe_roll_kernel<T, 0, 0, 0>, 64, lds_roll};
+  plan.prows = {probe_rows_kernel_of<T, 0, 0, 0>(prog_kind, 0, false), 64, rows_maps_bytes(d) + probe_rows_elems(d, 0, sa.rows_cw) * sizeof(T)};
   plan.sweep = {gen_lq_kernel<T>, kGenSweepThreads, lds_lq};
   plan.exit = {ilq_exit_kernel<T, 0, 0, 0>, 64, quad_tables_bytes(d, sizeof(T)) + 64 * sizeof(T)};
-  plan.exit_fill_first = true; plan.read_restarts = sa.al_mode != 0;
-  plan.cap = sa.al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
-                        : (long long)(opt.fixed_iters > 0 ? opt.fixed_iters : sa.prm.max_solver_iters) + 2;
-  plan.cap = (plan.cap + 2) * ((long long)sa.prm.max_backtracking_steps + 3);
-  plan.row_chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;
-  plan.split = plan.counted = plan.lists = true;
-  plan.probe = !opt.forced_steps && sa.prm.linesearch && opt.probe != ILQG_CHOICE_OFF;
-  plan.timed = opt.max_runtime > 0.0;
+  plan.exit_fill_first = true;
+  SolveSchedule& sc = plan.s;  // the fixed schedule of this path
+  sc.read_restarts = sa.al_mode != 0;
+  sc.cap = sa.al_mode ? (long long)(sa.prm.max_solver_iters + 1) * (sa.prm.unconstrained_solver_max_iters + 2)
+                      : (long long)(opt.fixed_iters > 0 ? opt.fixed_iters : sa.prm.max_solver_iters) + 2;
+  sc.cap = (sc.cap + 2) * ((long long)sa.prm.max_backtracking_steps + 3);
+  sc.row_chunks = (d.T + sa.rows_cw - 1) / sa.rows_cw;
+  sc.split = sc.counted = sc.lists = 1;
+  sc.probe = !opt.forced_steps && sa.prm.linesearch && opt.probe != ILQG_CHOICE_OFF;
+  sc.timed = opt.max_runtime > 0.0;
+  sc.lane_width = 1;
+  sc.num_cus = 256;
+  sc.probe_max = kProbeCandidates;
+  sc.probe_budget = kProbeRoundBudget;
   // The sweep on a specialised kernel: the smallest instantiated shape the game embeds in (padded_lq_kernel).  AUTO: for
   // problems that have no instantiation of their own (ilqg_problem::generic); a problem sent here by
   // ilqg_solve_options::generic_kernels keeps the run-time-dimensioned sweeps unless padded_sweep = ON.
@@ -1940,13 +1760,13 @@ static ilqg_status generic_solve(ilqg_problem* p, int32_t batch, const void* x0,
       std::string err;
       if (!padded_pairs(d.pairs, d.N, shape->mu, &ptp, &err)) return fail(ILQG_ERR_INVALID, err);
       size_t elems = 0;
-      ilqg_status s = plan.padded(d, &sa, ptp, nullptr, &elems, p->desc.params.open_loop != 0, stream);
+      ilqg_status s = plan.padded(d, &sa, ptp, nullptr, &elems, open_loop, stream);
       if (s != ILQG_OK) return s;
       s = Scratch().reserve(size_t(batch) * elems * sizeof(T));
       if (s != ILQG_OK) return s;
       plan.pad_pairs = &ptp;
       plan.pad = ilqg_shared::scratch_state().ptr;
-      p->last_schedule |= ILQG_SCHEDULE_PADDED_SWEEP;
+      p->last_schedule = generic_schedule_word(open_loop, true);
     }
   }
   return run_rounds(p, sa, tail, plan, opt, stream);
@@ -2245,6 +2065,32 @@ ilqg_status ilqg_sweep_b_structure_build(const ilqg_problem_desc* desc, int32_t*
     if (size_t(capacity) < e.size()) return fail(ILQG_ERR_INVALID, "ilqg_sweep_b_structure_build: buffer too small");
     std::memcpy(entries_out, e.data(), sizeof(int32_t) * e.size());
   }
+  return ILQG_OK;
+}
+
+// The host half of creation alone, then the schedule a solve of it would run: decide_schedule as DimsLaunch::solve calls
+// it, on what the query says the call and the device are
+ilqg_status ilqg_schedule_build(const ilqg_problem_desc* desc, const ilqg_solve_options* options, const ilqg_schedule_query* query,
+                                ilqg_schedule_info* out) {
+  if (!desc || !options || !query || !out) return fail(ILQG_ERR_INVALID, "null argument");
+  if (query->batch < 1 || query->num_cus < 1) return fail(ILQG_ERR_INVALID, "ilqg_schedule_build: batch and num_cus are positive");
+  ProblemTables tables;
+  const ilqg_status s = build_problem_tables(*desc, &tables);
+  if (s != ILQG_OK) return s;
+  const DevProblem& d = tables.dev;
+  *out = ilqg_schedule_info{};
+  if (tables.generic || options->generic_kernels == ILQG_CHOICE_ON) {
+    const bool padded = (options->padded_sweep == ILQG_CHOICE_ON || (options->padded_sweep == ILQG_CHOICE_AUTO && tables.generic)) &&
+                        pick_padded_shape(d.n, d.N, d.udim) != nullptr;
+    out->word = generic_schedule_word(desc->params.open_loop != 0, padded);
+    return ILQG_OK;
+  }
+  const ShapeEntry* e = find_shape(d.n, d.N, tables.mu_uniform);
+  if (!e) return fail(ILQG_ERR_UNSUPPORTED, "no device kernel instantiated for this problem's dimensions");
+  const ProblemFacts f{desc->params, tables.static_prog, tables.b_constant, tables.has_expression, tables.has_expression_dynamics,
+                       query->tables_bound != 0 || query->solver_bound != 0, query->solver_bound != 0};
+  const int sched_batch = (schedule_counts_mask(*options) && query->active >= 0) ? std::max(query->active, 1) : query->batch;
+  *out = decide_schedule(e->traits[dtype_index(desc->dtype)], d, f, *options, query->batch, sched_batch, query->num_cus, kProfile);
   return ILQG_OK;
 }
 
@@ -2584,18 +2430,12 @@ ilqg_status ilqg_solve_batch_ex(ilqg_problem* p, int32_t batch, const void* x0, 
     return fail(ILQG_ERR_INVALID, "forced_steps needs fixed_iters > 0 and no augmented-Lagrangian loop");
   if (o.max_runtime > 0.0 && (o.fixed_iters > 0 || o.forced_steps))
     return fail(ILQG_ERR_INVALID, "max_runtime needs a free-running solve (fixed_iters = 0, no forced steps)");
-  if (o.single_wave_sweep < ILQG_CHOICE_AUTO || o.single_wave_sweep > ILQG_CHOICE_ON ||
-      o.adjoint_expected_decrease < ILQG_CHOICE_AUTO || o.adjoint_expected_decrease > ILQG_CHOICE_ON)
-    return fail(ILQG_ERR_INVALID, "scheduling choices are ilqg_choice values");
-  if (o.probe_first < 0 || o.probe_first > 1024) return fail(ILQG_ERR_INVALID, "probe_first: 0 (the library's choice) or a count");
-  for (int32_t c : {o.split_trial, o.handoff, o.probe, o.counted})
+  for (int32_t c : {o.single_wave_sweep, o.adjoint_expected_decrease, o.split_trial, o.handoff, o.probe, o.counted,
+                    o.generic_kernels, o.padded_sweep, o.probe_lanes, o.sweep_forms})
     if (c < ILQG_CHOICE_AUTO || c > ILQG_CHOICE_ON) return fail(ILQG_ERR_INVALID, "scheduling choices are ilqg_choice values");
+  if (o.probe_first < 0 || o.probe_first > 1024) return fail(ILQG_ERR_INVALID, "probe_first: 0 (the library's choice) or a count");
   const DevProblem& d = p->dev;
   hipStream_t st = (hipStream_t)stream;
-  if (o.generic_kernels < ILQG_CHOICE_AUTO || o.generic_kernels > ILQG_CHOICE_ON || o.padded_sweep < ILQG_CHOICE_AUTO ||
-      o.padded_sweep > ILQG_CHOICE_ON || o.probe_lanes < ILQG_CHOICE_AUTO || o.probe_lanes > ILQG_CHOICE_ON ||
-      o.sweep_forms < ILQG_CHOICE_AUTO || o.sweep_forms > ILQG_CHOICE_ON)
-    return fail(ILQG_ERR_INVALID, "scheduling choices are ilqg_choice values");
   if (p->generic || o.generic_kernels == ILQG_CHOICE_ON)
     return p->desc.dtype == ILQG_F32
                ? generic_solve<float>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, o, st)

@@ -30,7 +30,7 @@ EXPORTS = [
     "ilqg_problem_declare_instance_routes", "ilqg_problem_bind_instance_routes", "ilqg_instance_routes_check",
     "ilqg_segment_table_build",
     "ilqg_problem_bind_instance_time_nominals", "ilqg_instance_time_nominals_build", "ilqg_problem_time_nominal_terms",
-    "ilqg_time_nominal_table_build", "ilqg_sweep_b_structure_build",
+    "ilqg_time_nominal_table_build", "ilqg_sweep_b_structure_build", "ilqg_schedule_build",
 ]
 
 
@@ -198,6 +198,37 @@ def sweep_b_structure(spec, dtype=abi.F64):
     _check(lib().ilqg_sweep_b_structure_build(C.byref(desc), C.byref(ok), e.ctypes.data_as(C.c_void_p), e.size, C.byref(n)))
     del keep
     return bool(ok.value), e
+
+
+def _solve_options(fixed_iters=0, augmented_lagrangian=False, resume=False, deterministic=False, probe_first=0,
+                   max_runtime=0.0, **choices):
+    """abi.SolveOptions with the library's defaults, the scalar fields as given and every ilqg_choice field in `choices`
+    set from None (the library chooses) / True / False."""
+    o = abi.SolveOptions()
+    lib().ilqg_default_solve_options(C.byref(o))
+    o.fixed_iters, o.probe_first, o.max_runtime = int(fixed_iters), int(probe_first), float(max_runtime)
+    o.augmented_lagrangian, o.resume, o.deterministic = int(bool(augmented_lagrangian)), int(bool(resume)), int(bool(deterministic))
+    for name, v in choices.items():
+        setattr(o, name, abi.CHOICE_AUTO if v is None else (abi.CHOICE_ON if v else abi.CHOICE_OFF))
+    return o
+
+
+def schedule_build(spec, dtype, batch, num_cus, active=None, tables_bound=False, solver_bound=False,
+                   **options):
+    """ilqg_schedule_build: the schedule a solve of `spec` would run, as a dict of ilqg_schedule_info's members ("word":
+    what Problem.last_schedule() reports after that solve) — host only, no device needed.  num_cus: the device's
+    (device_info()[1]); active: how many instances the solve's mask lets take part (None: no mask); tables_bound /
+    solver_bound: per-instance tables / solver columns are bound; options: Problem.solve's keywords."""
+    desc, keep = spec.build(dtype)
+    o = _solve_options(**options)
+    if active is not None:
+        o.active = 1  # (only read as "the solve has a mask")
+    q = abi.ScheduleQuery(int(batch), -1 if active is None else int(active), int(num_cus), int(tables_bound or solver_bound),
+                          int(solver_bound))
+    info = abi.ScheduleInfo()
+    _check(lib().ilqg_schedule_build(C.byref(desc), C.byref(o), C.byref(q), C.byref(info)))
+    del keep
+    return {f: int(getattr(info, f)) for f, _ in abi.ScheduleInfo._fields_}
 
 
 def _instance_params(spec, params):
@@ -507,31 +538,18 @@ class Problem:
         B = x0.shape[0]
         if bufs is None:
             bufs = self.alloc_solve_buffers(B)
-        o = abi.SolveOptions()
-        lib().ilqg_default_solve_options(C.byref(o))
-        o.fixed_iters = int(fixed_iters)
-        o.augmented_lagrangian = 1 if augmented_lagrangian else 0
-        o.resume = 1 if resume else 0
-        o.deterministic = 1 if deterministic else 0
+        o = _solve_options(fixed_iters, augmented_lagrangian, resume, deterministic, probe_first, max_runtime,
+                           split_trial=split_trial, handoff=handoff, probe=probe, counted=counted, compact_rows=compact_rows,
+                           round_bursts=round_bursts, generic_kernels=generic_kernels,
+                           single_wave_sweep=self.single_wave_sweep if single_wave_sweep is None else single_wave_sweep,
+                           adjoint_expected_decrease=adjoint_expected_decrease, static_rows=static_rows,
+                           padded_sweep=padded_sweep, probe_lanes=probe_lanes, sweep_forms=sweep_forms)
         o.active = None if active is None else active.data_ptr()
         fs = None
         if forced_steps is not None:
             fs = _dev(forced_steps, self.dtype)
             assert tuple(fs.shape) == (B, fixed_iters)
             o.forced_steps = fs.data_ptr()
-        tri = lambda v: abi.CHOICE_AUTO if v is None else (abi.CHOICE_ON if v else abi.CHOICE_OFF)  # noqa: E731
-        o.split_trial, o.handoff, o.probe, o.counted = tri(split_trial), tri(handoff), tri(probe), tri(counted)
-        o.compact_rows = tri(compact_rows)
-        o.round_bursts = tri(round_bursts)
-        o.generic_kernels = tri(generic_kernels)
-        o.probe_first = int(probe_first)
-        o.single_wave_sweep = tri(self.single_wave_sweep if single_wave_sweep is None else single_wave_sweep)
-        o.adjoint_expected_decrease = tri(adjoint_expected_decrease)
-        o.static_rows = tri(static_rows)
-        o.padded_sweep = tri(padded_sweep)
-        o.probe_lanes = tri(probe_lanes)
-        o.sweep_forms = tri(sweep_forms)
-        o.max_runtime = float(max_runtime)
         il = None
         if log_capacity > 0:
             cap = int(log_capacity)

@@ -793,6 +793,38 @@ ilqg_status ilqg_solve_state_batch(const ilqg_problem* p, int32_t batch, const v
 #define ILQG_SCHEDULE_CONSTANT_B 512        /* player-parallel sweep with B's constant entries in registers (sweep_forms)   */
 ilqg_status ilqg_problem_last_schedule(const ilqg_problem* p, int32_t* schedule_out);
 
+/* Host only, no device needed: the schedule a solve of this description would run — every decision the library makes
+ * about how a solve runs, from the description, the options and what `query` says about the call and the device.  It runs
+ * the function the solve itself runs (csrc/ilqg_schedule.hpp), so `word` is what ilqg_problem_last_schedule reports after
+ * that solve; the other members name what the word has no bit for.  Flags are 0 / 1; a problem on the run-time-dimensioned
+ * kernels reports its word and zeros. */
+typedef struct {
+  int32_t batch;         /* instances in the call's buffers                                                       */
+  int32_t active;        /* instances its mask (ilqg_solve_options::active) lets take part; -1: no mask            */
+  int32_t num_cus;       /* compute units of the device (ilqg_device_info)                                        */
+  int32_t tables_bound;  /* per-instance tables are bound to the problem (values, routes or time nominals)        */
+  int32_t solver_bound;  /* ... among them per-instance solver columns                                            */
+} ilqg_schedule_query;
+typedef struct {
+  int32_t word;                     /* ILQG_SCHEDULE_* */
+  int32_t sched_batch, num_cus;     /* the instances the schedule was chosen for (the mask's count where the solve counts it) */
+  int32_t split, counted, handoff, lists, bursts, probe, timed;  /* the rounds: split trial pass, host-counted, hand-off
+                                       to split passes, instance lists, bursts of rounds, speculative line search, anytime exit */
+  int32_t pairs, lanes_auto, deep_tails, read_restarts, proll_single, proll_lanes;  /* probing rollout forms, AL read-back */
+  int32_t probe_max, probe_budget;  /* most candidates per instance and round; rollouts of a tail's first probing round */
+  int32_t compact, defer_forward, single_wave, adjoint, b_const, packed;
+  int32_t sweep_kind, sweep_forms, sweep_threads;  /* the sweep kernel: its kind (csrc/ilqg_solve.hpp LQ_*), FORMS, threads */
+  int32_t prog_kind, bound;         /* row program: 0 plain, 1 expression costs, 2 expression dynamics; the bound twins */
+  int32_t static_id, static_prog, static_in_regs;  /* registered structure of the split row kernels / of the fused kernel */
+  int32_t decide_solver;            /* the decision kernel's twin that reads per-instance solver columns */
+  int32_t rows_cw, row_chunks, lane_width, prio_div, nt_exit, lds_part;
+  int32_t lds_trial, lds_roll, lds_rows, lds_decide, lds_proll, lds_proll_single, lds_proll_lanes, lds_prows, lds_sweep,
+      lds_exit;                     /* dynamic LDS bytes of each launch (0: the solve has no such launch) */
+  int64_t cap;                      /* the iteration bound in rounds */
+} ilqg_schedule_info;
+ilqg_status ilqg_schedule_build(const ilqg_problem_desc* desc, const ilqg_solve_options* options,
+                                const ilqg_schedule_query* query, ilqg_schedule_info* out);
+
 /* The row program ilqg_problem_create compiled the problem's dynamics and cost list into (csrc/ilqg_rowprog.hpp: passes,
  * ops, slot ids, word maps; host memory, int32 words) and the id of the registered structure it matches (0: none — the
  * row stage interprets it).  words_out may be NULL to ask for the size only. */
@@ -993,7 +1025,8 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
                                  (one new call, no layout change); still 9: relative inputs of the expression kinds
                                  (idx[2], idx[3]) and ILQG_CONSTRAINT_EXPRESSION (kind 25; no new call, no layout change); still 9:
                                  ILQG_DYN_EXPRESSION (subsystem kind 13), ILQG_ROLE_DYNAMICS_ROW (role 5) and
-                                 ILQG_DYN_ROW_EXPRESSION (term kind 26): three enumerators, no new call, no layout change;
+                                 ILQG_DYN_ROW_EXPRESSION (term kind 26): three enumerators, no new call, no layout change; still 9:
+                                 the host-only ilqg_schedule_build (ilqg_schedule_query, ilqg_schedule_info: one new call);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;
