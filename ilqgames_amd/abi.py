@@ -49,6 +49,7 @@ DYN_ROW_EXPRESSION = 26  # a state row of a DYN_EXPRESSION subsystem (role ROLE_
 # ilqg_expr_op
 (EXPR_PUSH_X, EXPR_PUSH_Y, EXPR_PUSH_CONST, EXPR_PUSH_WEIGHT, EXPR_PUSH_VALUE, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_DIV,
  EXPR_NEG, EXPR_SQUARE, EXPR_SQRT, EXPR_EXP, EXPR_LOG, EXPR_SIN, EXPR_COS, EXPR_HINGE) = range(1, 18)
+EXPR_PUSH_TIME = 18  # a leaf: the window-relative time double(k) * dt of the step (in a model row: of the stage)
 EXPR_MAX_OPS, EXPR_MAX_DEPTH = 64, 4
 # ilqg_cost_role
 ROLE_STATE_COST, ROLE_CONTROL_COST, ROLE_STATE_CONSTRAINT, ROLE_CONTROL_CONSTRAINT, ROLE_CHILD = range(5)
@@ -64,6 +65,7 @@ SUM, MAX, MIN = 0, 1, 2
 
 class Expr:
     """An expression tree for ProblemSpec.expression: Expr.x(), Expr.y(), Expr.const(c), Expr.weight(), Expr.value(),
+    Expr.time() (the window-relative time of the step the term is evaluated at),
     + - * / and unary minus between them (numbers become constants), and the functions square / sqrt / exp / log / sin /
     cos / hinge.  program() is its postfix form [(opcode, imm), ...], operands left to right."""
 
@@ -75,6 +77,7 @@ class Expr:
     const = staticmethod(lambda c: Expr(EXPR_PUSH_CONST, c))
     weight = staticmethod(lambda: Expr(EXPR_PUSH_WEIGHT))
     value = staticmethod(lambda: Expr(EXPR_PUSH_VALUE))
+    time = staticmethod(lambda: Expr(EXPR_PUSH_TIME))
 
     @staticmethod
     def of(v):

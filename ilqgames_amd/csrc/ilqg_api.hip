@@ -1878,6 +1878,16 @@ static const char* const kRouteProgressReceding =
     "receding horizon: the problem holds a RouteProgressCost, whose per-step nominals are tabulated for a first solve "
     "(initial time 0) only";
 
+// An expression subsystem whose rows push the time (ILQG_EXPR_PUSH_TIME): the plan kernels integrate partial steps at
+// absolute plan times (IntegrateToNextTimeStep, IntegrateFromPriorTimeStep), where the reference hands a model no
+// consistent time.  The entry points that run them refuse such a problem; time-reading costs and constraints pass.
+static ilqg_status refuse_time_reading_dynamics(const ilqg_problem* p, const char* entry) {
+  if (p->time_reading_subsystem < 0) return ILQG_OK;
+  return fail(ILQG_ERR_UNSUPPORTED, std::string(entry) + ": subsystem " + std::to_string(p->time_reading_subsystem) +
+                                        " is an expression subsystem whose rows read the time (ILQG_EXPR_PUSH_TIME); the plan "
+                                        "kernels integrate partial steps at absolute plan times and give a model no time");
+}
+
 extern "C" {
 
 const char* ilqg_last_error(void) { return g_err.c_str(); }
@@ -2502,6 +2512,7 @@ ilqg_status ilqg_receding_horizon_shift_batch(const ilqg_problem* p, int32_t bat
                                               double* new_plan_t0_host, void* stream) {
   if (!p || !x0 || !xs || !us || !P || !alpha || !x0_next || !first_step) return fail(ILQG_ERR_INVALID, "null argument");
   if (p->has_route_progress) return fail(ILQG_ERR_UNSUPPORTED, kRouteProgressReceding);
+  if (ilqg_status st = refuse_time_reading_dynamics(p, "receding horizon")) return st;
   const DevProblem& d = p->dev;
   const double dt = d.dt, horizon = dt * d.T;
   // the reference's CHECKs (src/problem.cpp:68-70)
@@ -2662,6 +2673,7 @@ ilqg_status ilqg_plan_integrate_batch(const ilqg_problem* p, int32_t batch, int3
   ilqg_status s = check_plan(p, plan_rows, plan_xs, plan_us, plan_P, plan_alpha, plan_len, plan_t0);
   if (s != ILQG_OK) return s;
   if (!x || !active) return fail(ILQG_ERR_INVALID, "null argument");
+  if (ilqg_status st = refuse_time_reading_dynamics(p, "plan integration")) return st;
   if (batch <= 0) return ILQG_OK;
   if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
   const DevProblem& d = p->dev;
@@ -2694,6 +2706,7 @@ ilqg_status ilqg_receding_horizon_sync_batch(const ilqg_problem* p, int32_t batc
   if (xs == plan_xs || us == plan_us || P == plan_P || alpha == plan_alpha)
     return fail(ILQG_ERR_INVALID, "the next solve's buffers must not alias the stored plan");
   if (p->has_route_progress) return fail(ILQG_ERR_UNSUPPORTED, kRouteProgressReceding);
+  if (ilqg_status st = refuse_time_reading_dynamics(p, "receding horizon")) return st;
   if (batch <= 0) return ILQG_OK;
   if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
   const DevProblem& d = p->dev;

@@ -41,6 +41,14 @@ ILQG_EXPR_FN void expr_sincos(double v, double* s, double* c) { *s = ::sin(v); *
 #define ILQG_EXPR_SINCOS(x, s, c) ::ilqg::expr_sincos(x, s, c)
 #endif
 
+// PUSH_TIME (18) joined the pushes after the operators were numbered: a push is 1 .. PUSH_VALUE, or it — every valid
+// opcode outside the operators' range ADD .. HINGE.  One unsigned compare, as the range test `op <= PUSH_VALUE` was: the
+// interpreter's step is a chain of scalar compares and branches, and a second test per op showed in the rollout of an
+// expression model.
+ILQG_EXPR_FN bool expr_is_push(int op) {
+  return unsigned(op - ILQG_EXPR_ADD) > unsigned(ILQG_EXPR_HINGE - ILQG_EXPR_ADD);
+}
+
 constexpr int kExprJetScalars = 6;
 constexpr int kExprStackScalars = (ILQG_EXPR_MAX_DEPTH - 1) * kExprJetScalars;  // what an evaluation keeps in memory
 
@@ -65,8 +73,8 @@ inline ExprCheck expr_validate(const float* blk, long long avail, bool two_input
   for (int i = 0; i < L; i++) {
     const float of = blk[1 + 2 * i];
     const int op = (of >= 1.0f && of <= 64.0f && of == float(int(of))) ? int(of) : 0;
-    if (op < ILQG_EXPR_PUSH_X || op > ILQG_EXPR_HINGE) return {EXPR_BAD_OPCODE, i, depth};
-    if (op <= ILQG_EXPR_PUSH_VALUE) {
+    if (op < ILQG_EXPR_PUSH_X || op > ILQG_EXPR_PUSH_TIME) return {EXPR_BAD_OPCODE, i, depth};
+    if (expr_is_push(op)) {
       if (op == ILQG_EXPR_PUSH_Y && !two_inputs) return {EXPR_NO_SECOND_INPUT, i, depth};
       if (depth == ILQG_EXPR_MAX_DEPTH) return {EXPR_OVERFLOW, i, depth};
       depth++;
@@ -111,8 +119,10 @@ ILQG_EXPR_FN ExprJet<T> expr_chain(const ExprJet<T>& a, T g, T g1, T g2, bool wa
 }
 
 // P: anything indexable that yields the block's words (floats, or the solve's scalars made from them).
+// `time`: what PUSH_TIME pushes (include/ilqg.h); a program without that op never reads it.
 template <typename T, typename P>
-ILQG_EXPR_FN void expr_eval_jet(P program, T weight, T value, T x, T y, bool want_h, ExprStack<T> stack, ExprJet<T>* out) {
+ILQG_EXPR_FN void expr_eval_jet(P program, T weight, T value, T x, T y, bool want_h, ExprStack<T> stack, ExprJet<T>* out,
+                                T time = T(0)) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -121,7 +131,7 @@ ILQG_EXPR_FN void expr_eval_jet(P program, T weight, T value, T x, T y, bool wan
   int n = 0;  // entries on the stack, t the top one
   for (int i = 0; i < L; i++) {
     const int op = int(program[1 + 2 * i]);
-    if (op <= ILQG_EXPR_PUSH_VALUE) {
+    if (expr_is_push(op)) {
       if (n > 0) {
         T* const s = stack.base + (n - 1) * kExprJetScalars * stack.stride;
         s[0] = t.f; s[stack.stride] = t.fx; s[2 * stack.stride] = t.fy;
@@ -133,7 +143,8 @@ ILQG_EXPR_FN void expr_eval_jet(P program, T weight, T value, T x, T y, bool wan
       else if (op == ILQG_EXPR_PUSH_Y) { t.f = y; t.fy = T(1); }
       else if (op == ILQG_EXPR_PUSH_CONST) t.f = T(program[2 + 2 * i]);
       else if (op == ILQG_EXPR_PUSH_WEIGHT) t.f = weight;
-      else t.f = value;
+      else if (op == ILQG_EXPR_PUSH_VALUE) t.f = value;
+      else t.f = time;
     } else if (op <= ILQG_EXPR_DIV) {
       n--;
       const T* const s = stack.base + (n - 1) * kExprJetScalars * stack.stride;
@@ -191,7 +202,7 @@ ILQG_EXPR_FN void expr_eval_jet(P program, T weight, T value, T x, T y, bool wan
 
 // The value alone (Cost::Evaluate): the same f of every op, four scalars and no memory.
 template <typename T, typename P>
-ILQG_EXPR_FN T expr_eval_value(P program, T weight, T value, T x, T y) {
+ILQG_EXPR_FN T expr_eval_value(P program, T weight, T value, T x, T y, T time = T(0)) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -200,13 +211,14 @@ ILQG_EXPR_FN T expr_eval_value(P program, T weight, T value, T x, T y) {
   T t = T(0), s1 = T(0), s2 = T(0), s3 = T(0);  // the top and the entries below it, nearest first
   for (int i = 0; i < L; i++) {
     const int op = int(program[1 + 2 * i]);
-    if (op <= ILQG_EXPR_PUSH_VALUE) {
+    if (expr_is_push(op)) {
       s3 = s2; s2 = s1; s1 = t;
       if (op == ILQG_EXPR_PUSH_X) t = x;
       else if (op == ILQG_EXPR_PUSH_Y) t = y;
       else if (op == ILQG_EXPR_PUSH_CONST) t = T(program[2 + 2 * i]);
       else if (op == ILQG_EXPR_PUSH_WEIGHT) t = weight;
-      else t = value;
+      else if (op == ILQG_EXPR_PUSH_VALUE) t = value;
+      else t = time;
     } else if (op <= ILQG_EXPR_DIV) {
       const T a = s1, b = t;
       s1 = s2; s2 = s3;

@@ -218,10 +218,11 @@ __device__ __forceinline__ T sub_expr_input(int i, int xd, const T* x, T u0, T u
   return i < xd ? v : u;
 }
 // xdot of an expression subsystem: row r is the value of its program (expr_eval_value) at its one or two inputs, with
-// VALUE = the subsystem's param0 and WEIGHT = the row term's weight; rows past xd are zero
+// VALUE = the subsystem's param0, WEIGHT = the row term's weight and TIME = `time`, the time of the stage being evaluated
+// (SinglePlayerDynamicalSystem::Evaluate(t, x, u)); rows past xd are zero
 template <typename T>
 __device__ __forceinline__ void sub_eval_expr(typename DenseConst<T>::type dense, int dir, int xd, T param, const T* x, T u0,
-                                              T u1, T* f) {
+                                              T u1, T* f, T time) {
 #pragma unroll
   for (int e = 0; e < kSubStatesMax; e++) f[e] = T(0);
 #pragma unroll 1
@@ -230,29 +231,35 @@ __device__ __forceinline__ void sub_eval_expr(typename DenseConst<T>::type dense
     const int po = int(row[0]), xi = int(row[1]), yi = int(row[2]);
     const T xv = sub_expr_input<T>(xi, xd, x, u0, u1);
     const T yv = yi >= 0 ? sub_expr_input<T>(yi, xd, x, u0, u1) : T(0);
-    const T v = expr_eval_value<T>(dense + po, T(row[3]), param, xv, yv);
+    const T v = expr_eval_value<T>(dense + po, T(row[3]), param, xv, yv, time);
 #pragma unroll
     for (int e = 0; e < kSubStatesMax; e++) f[e] = (e == r) ? v : f[e];
   }
 }
 // MultiPlayerDynamicalSystem::Integrate's RK4 with two half-steps, in sub_integrate8's operation order — k_j = h f,
 // the stage points x + k1 / 2, x + k2 / 2, x + k3, the update (k1 + 2 (k2 + k3) + k4) / 6 — with the four stages as one
-// loop around the one copy of the evaluator
+// loop around the one copy of the evaluator.  `t_start`: the time the step begins at (k dt); the stages of half-step s
+// are at t0, t0 + h/2, t0 + h/2, t0 + h with t0 = t_start + s h (multi_player_dynamical_system.cpp:66-72), each formed in
+// double and rounded once.
 #pragma clang fp contract(off)
 template <typename T>
 __device__ __forceinline__ void sub_integrate_expr(typename DenseConst<T>::type dense, int dir, int xd, T param,
-                                                   double interval, T* x, T u0, T u1) {
+                                                   double interval, T* x, T u0, T u1, double t_start) {
   constexpr int XS = kSubStatesMax;
   const T h = T(interval / 2.0);
+  const double hd = interval / 2.0;
 #pragma unroll 1
   for (int s = 0; s < 2; s++) {
     T k1[XS], k23[XS], xt[XS];
 #pragma unroll
     for (int i = 0; i < XS; i++) { xt[i] = x[i]; k1[i] = T(0); k23[i] = T(0); }
+    // the half-step's three stage times, once a half-step (the double arithmetic stays out of the stage loop)
+    const double t0 = t_start + double(s) * hd;
+    const T t_first = T(t0), t_mid = T(t0 + 0.5 * hd), t_last = T(t0 + hd);
 #pragma unroll 1
     for (int j = 0; j < 4; j++) {
       T f[XS];
-      sub_eval_expr<T>(dense, dir, xd, param, xt, u0, u1, f);
+      sub_eval_expr<T>(dense, dir, xd, param, xt, u0, u1, f, j == 0 ? t_first : (j == 3 ? t_last : t_mid));
       if (j == 0) {
 #pragma unroll
         for (int i = 0; i < XS; i++) { k1[i] = h * f[i]; xt[i] = x[i] + T(0.5) * k1[i]; }
@@ -272,9 +279,9 @@ __device__ __forceinline__ void sub_integrate_expr(typename DenseConst<T>::type 
 // one explicit Euler step (MultiPlayerDynamicalSystem::Integrate's other form, the equilibrium checks' option)
 template <typename T>
 __device__ __forceinline__ void sub_euler_expr(typename DenseConst<T>::type dense, int dir, int xd, T param, double interval,
-                                               T* x, T u0, T u1) {
+                                               T* x, T u0, T u1, double t_start) {
   T f[kSubStatesMax];
-  sub_eval_expr<T>(dense, dir, xd, param, x, u0, u1, f);
+  sub_eval_expr<T>(dense, dir, xd, param, x, u0, u1, f, T(t_start));
 #pragma unroll
   for (int i = 0; i < kSubStatesMax; i++) x[i] += T(interval) * f[i];
 }
@@ -600,6 +607,7 @@ struct QuadTables {
   int tnom_T;
   const T* dense = nullptr;  // coefficient blocks of the affine constraints and programs of the expression costs
                              // (DevProblem::dense_f / dense_d)
+  double dt = 0.0;           // the time step: an expression program's PUSH_TIME is T(double(step) * dt)
 };
 __host__ __device__ inline bool term_is_affine(int kind) {
   return kind == ILQG_CONSTRAINT_AFFINE_SCALAR || kind == ILQG_CONSTRAINT_AFFINE_VECTOR;
@@ -1123,10 +1131,10 @@ __device__ __forceinline__ void term_compute_leaf(const DevTerm& c, const V& v, 
 // row interpreter does around its TERM op — the polyline search, this step's nominal pair, and the affine and
 // expression kinds through their own evaluators.  The gradient and Hessian of the body are unused here and compile
 // away; with no contraction in this region the value is the same sequence of rounded operations as in the row programs.
-// `step`: the time step the term is evaluated at (the time-dependent kinds read their nominal of that step).
+// `step`: the time step the term is evaluated at (the time-dependent kinds read their nominal of that step, an expression
+// program's PUSH_TIME pushes its time).  No default: every caller says which step it means.
 template <typename T, typename V>
-__device__ __forceinline__ T term_evaluate_leaf_of(const QuadTables<T>& tb, const DevTerm& c, const V& v, int dim,
-                                                   int step = 0) {
+__device__ __forceinline__ T term_evaluate_leaf_of(const QuadTables<T>& tb, const DevTerm& c, const V& v, int dim, int step) {
   if (term_is_affine(c.kind)) return tb.dense ? affine_evaluate<T, V>(c.kind, tb.dense + c.polyline, v, dim) : T(0);
   if (term_is_expression(c.kind)) {  // ilqg_expr.hpp: the program's value alone
     if (!tb.dense) return T(0);
@@ -1135,7 +1143,7 @@ __device__ __forceinline__ T term_evaluate_leaf_of(const QuadTables<T>& tb, cons
       x = x - v[c.idx[2]];
       if (c.idx[3] >= 0) y = y - v[c.idx[3]];
     }
-    return expr_eval_value<T>(tb.dense + c.polyline, T(c.weight), T(c.value), x, y);
+    return expr_eval_value<T>(tb.dense + c.polyline, T(c.weight), T(c.value), x, y, T(double(step) * tb.dt));
   }
   Closest<T> cl;
   if (term_is_polyline(c.kind)) cl = polyline_closest<T>(tb, c.polyline, v[c.idx[0]], v[c.idx[1]]);
@@ -1146,19 +1154,20 @@ __device__ __forceinline__ T term_evaluate_leaf_of(const QuadTables<T>& tb, cons
   return o.value;
 }
 template <typename T, typename V>
-__device__ __forceinline__ T term_evaluate_leaf(const QuadTables<T>& tb, int ti, const V& v, int dim, int step = 0) {
+__device__ __forceinline__ T term_evaluate_leaf(const QuadTables<T>& tb, int ti, const V& v, int dim, int step) {
   const DevTerm c = tb.terms[ti];
   return term_evaluate_leaf_of<T, V>(tb, c, v, dim, step);
 }
 
-// ExtremeValueCost::ExtremeCost, src/extreme_value_cost.cpp:66-85: index of the active child.
+// ExtremeValueCost::ExtremeCost, src/extreme_value_cost.cpp:66-85: index of the active child.  The children are
+// evaluated at step 0 whatever step the parent is at (an open point for time-dependent children).
 template <typename T, typename V>
 __device__ __forceinline__ int extreme_child(const QuadTables<T>& tb, const DevTerm& c, const V& v, int dim, T* value_out) {
   const bool is_min = c.flags & ILQG_FLAG_IS_MIN;
   T ext = is_min ? dinf<T>() : -dinf<T>();
   int best = c.child_begin;
   for (int q = 0; q < c.child_count; q++) {
-    const T value = term_evaluate_leaf<T, V>(tb, c.child_begin + q, v, dim);
+    const T value = term_evaluate_leaf<T, V>(tb, c.child_begin + q, v, dim, 0);
     if ((is_min && value < ext) || (!is_min && value > ext)) {
       ext = value;
       best = c.child_begin + q;

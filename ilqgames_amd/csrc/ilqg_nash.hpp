@@ -74,8 +74,8 @@ __global__ void __launch_bounds__(64) strategy_costs_kernel(DevProblem p, Strate
         if (t == s) {
           T xj[kSubStatesMax];
           for (int e = 0; e < kSubStatesMax; e++) xj[e] = e < xd ? sx[xo + e] : T(0);
-          if (a.euler) sub_euler_expr<T>(dense_const<T>(p), p.dyn_rows[s], xd, Lp, p.dt, xj, sx[n + uo], sx[n + uo + 1]);
-          else sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], xd, Lp, p.dt, xj, sx[n + uo], sx[n + uo + 1]);
+          if (a.euler) sub_euler_expr<T>(dense_const<T>(p), p.dyn_rows[s], xd, Lp, p.dt, xj, sx[n + uo], sx[n + uo + 1], double(kk) * p.dt);
+          else sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], xd, Lp, p.dt, xj, sx[n + uo], sx[n + uo + 1], double(kk) * p.dt);
           for (int e = 0; e < xd; e++) snx[xo + e] = xj[e];
         }
       }

@@ -129,6 +129,8 @@ struct ilqg_problem {
   bool has_expression = false;  // an expression cost: the row kernels with its evaluator in them run (kExprProg, ilqg_solve.hpp)
   bool has_expression_dynamics = false;  // an ILQG_DYN_EXPRESSION subsystem: the kernels with its integrator and its
                                          // linearisation in them run (kExprDynProg, ilqg_solve.hpp)
+  int time_reading_subsystem = -1;  // the first expression subsystem with a row that pushes the time (ILQG_EXPR_PUSH_TIME), -1:
+                                    // none.  The receding-horizon plan kernels refuse such a problem (ilqg.h).
   int last_schedule = 0;  // ILQG_SCHEDULE_* of the last solve (ilqg_problem_last_schedule)
   bool generic = false;  // no specialised instantiation holds this problem: every entry point runs the run-time-dimensioned kernels
   // The solver object's LoopTimer over its iterations, kept across solves as the reference's member is (only solves with a
@@ -199,6 +201,7 @@ struct ProblemTables {
   bool has_route_progress = false;
   bool has_expression = false;  // an expression cost (build_expression_blocks)
   bool has_expression_dynamics = false;  // an expression subsystem (flatten_subsystems)
+  int time_reading_subsystem = -1;  // the first expression subsystem with a row that pushes the time (build_dynamics_rows)
   bool generic = false;  // no specialised instantiation holds the problem
 };
 
@@ -536,6 +539,9 @@ ilqg_status build_dynamics_rows(const ilqg_problem_desc& desc, ProblemTables* t)
     o.polyline = int(t->dense.f.size());
     o.child_begin = 0;
     o.child_count = (int(src[0]) == 1 && int(src[1]) == ILQG_EXPR_PUSH_X) ? 1 : 0;
+    for (int i = 0; i < int(src[0]); i++)
+      if (int(src[1 + 2 * i]) == ILQG_EXPR_PUSH_TIME && (t->time_reading_subsystem < 0 || c.player < t->time_reading_subsystem))
+        t->time_reading_subsystem = c.player;
     t->dense.f.insert(t->dense.f.end(), src, src + count);
     t->dense.d.insert(t->dense.d.end(), src, src + count);
   }
@@ -735,6 +741,7 @@ ilqg_status upload_problem(const ilqg_problem_desc& desc, const ProblemTables& t
   p->b_constant = t.b_constant;
   p->mu_uniform = t.mu_uniform;
   p->has_route_progress = t.has_route_progress;
+  p->time_reading_subsystem = t.time_reading_subsystem;
   p->has_expression = t.has_expression;
   p->has_expression_dynamics = t.has_expression_dynamics;
   p->generic = t.generic;

@@ -782,7 +782,8 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
               const bool two = c.idx[1] >= 0;
               const T ex = entry(c.idx[0]), ey = two ? entry(c.idx[1]) : T(0);
               ExprJet<T> j;
-              expr_eval_jet<T>(prog, T(c.value), T(c.weight), ex, ey, false, ExprStack<T>{col + (NPS + li_count) * cws, cws}, &j);
+              expr_eval_jet<T>(prog, T(c.value), T(c.weight), ex, ey, false, ExprStack<T>{col + (NPS + li_count) * cws, cws}, &j,
+                               T(tt));  // Linearize(t_k, x, u)
               const T dx = T(double(j.fx) * p.dt), dy = T(double(j.fy) * p.dt);
               if (nsid > 0) col[sid[0] * cws] = (c.flags & 1) ? T(1) + dx : dx;
               if (nsid > 1) col[sid[1] * cws] = (c.flags & 2) ? T(1) + dy : dy;
@@ -882,7 +883,8 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
             if (two) ey = ey - v[c.idx[3]];
           }
           ExprJet<T> j;
-          expr_eval_jet<T>(prog, T(c.weight), T(c.value), ex, ey, quad_out, ExprStack<T>{col + (NPS + li_live) * cws, cws}, &j);
+          expr_eval_jet<T>(prog, T(c.weight), T(c.value), ex, ey, quad_out, ExprStack<T>{col + (NPS + li_live) * cws, cws}, &j,
+                           T(tt));  // RelativeTime(row), what PUSH_TIME pushes
           if (c.kind == ILQG_CONSTRAINT_EXPRESSION) {
             // Constraint::ModifyDerivatives (modify_derivatives, ilqg_models.hpp) with the equality-aware Mu of the affine
             // constraints; a gradient-only evaluation holds zeros in the jet's second derivatives and scatters none

@@ -329,7 +329,7 @@ __device__ __forceinline__ void solve_exit_path(const DevProblem& p, const QuadT
             auto error_at = [&](int kk) {
               const T* v = on_state ? xs0 + size_t(kk) * n : us0 + size_t(kk) * m + p.uoff[c.arg];
               // FinalTimeConstraint::Evaluate (constraint/final_time_constraint.h:66-70): 0 before its threshold
-              return kk < c.k_start ? T(0) : term_evaluate_leaf<T>(tb, ti, v, c.arg_dim);
+              return kk < c.k_start ? T(0) : term_evaluate_leaf<T>(tb, ti, v, c.arg_dim, kk);  // Constraint::Evaluate(t_kk, .)
             };
             const T err = error_at(k);
             my_err = err > my_err ? err : my_err;

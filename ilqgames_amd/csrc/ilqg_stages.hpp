@@ -219,7 +219,8 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
         // lane of the group evaluates every row, as the plain RK4 below keeps one copy of the block per lane
         for (int s = 0; s < N; s++) {
           if (p.sub_kind[s] != ILQG_DYN_EXPRESSION) continue;
-          if (grp == s) sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], p.xoff[s + 1] - p.xoff[s], Lp, p.dt, xj, u0, u1);
+          if (grp == s)
+            sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], p.xoff[s + 1] - p.xoff[s], Lp, p.dt, xj, u0, u1, double(k) * p.dt);
         }
         if (integ && kind != ILQG_DYN_EXPRESSION) sub_integrate8<T>(kind, Lp, p.dt, xj, u0, u1);
       } else if constexpr (GEN) {
@@ -582,6 +583,7 @@ __device__ __forceinline__ QuadTables<T> quad_tables_load(const DevProblem& p, v
   tb.tnom = problem_time_nominal<T>(p) + instance_tnom_offset(p, inst);  // a bound table of time nominals: this instance's
   tb.tnom_T = p.T;
   tb.dense = problem_dense<T>(p);
+  tb.dt = p.dt;
   return tb;
 }
 

@@ -1094,6 +1094,119 @@ def coasting_car_scene(T=100, dt=0.1):
     return s
 
 
+def time_expression_twin(spec):
+    """`spec` with every NominalPathLengthCost replaced by the abi.COST_EXPRESSION term that restates it through the time
+    leaf, 0.5 w (x - t v)^2 with t = Expr.time() (include/ilqg.h: ILQG_EXPR_PUSH_TIME) — the same weight, value, role,
+    player and gate; every other term as it is.  RouteProgressCost stays: its nominal goes through the polyline's float
+    arithmetic, which a formula does not reproduce.  -> (the twin, the number of terms replaced)."""
+    import copy
+    from .abi import Expr
+    twin = copy.deepcopy(spec)
+    replaced = 0
+    for t in twin.terms:
+        if t["kind"] != abi.COST_NOMINAL_PATH_LENGTH or t["role"] != abi.ROLE_STATE_COST:
+            continue
+        tree = 0.5 * Expr.weight() * (Expr.x() - Expr.time() * Expr.value()).square()
+        t.update(kind=abi.COST_EXPRESSION, idx=(t["idx"][0], -1, -1, -1), flags=0, polyline=len(twin.dense_params))
+        twin.dense_params += abi.expr_block(tree.program())
+        replaced += 1
+    return twin, replaced
+
+
+# moving_obstacle_scene's pedestrian: where it starts and its constant velocity
+MOVING_OBSTACLE_START, MOVING_OBSTACLE_VELOCITY = (3.0, -6.0), (-2.0, 1.0)
+
+
+def moving_obstacle_offset(input_expr, start, speed):
+    """(input - start) - speed * t as an Expr: one coordinate of the offset from a point moving at constant velocity,
+    associated so that it needs three stack entries (input - (start + speed t) needs four)."""
+    from .abi import Expr
+    return (input_expr - start) - speed * Expr.time()
+
+
+def moving_obstacle_scene(T=100, dt=0.1):
+    """A test scene, NOT a reference example: the two crossing Car5D of the skeleton example (n = 10, the specialised
+    (10, 2, 2) kernels) and a pedestrian no player controls, walking at constant velocity from MOVING_OBSTACLE_START:
+    p(t) = start + velocity t, read through the time leaf (Expr.time()).  Both cars carry a Gaussian bump
+    w exp(-0.5 |p_i - p(t)|^2 / v^2) about it (abi.COST_EXPRESSION), car 1 besides a keep-out disc of radius v,
+    v^2 - |p_1 - p(t)|^2 <= 0 (abi.CONSTRAINT_EXPRESSION).  Car 1 drives up x = 0 and meets the pedestrian about one
+    second in, so the constraint is active at steps well past the first."""
+    from .abi import Expr
+    prm = SolverParams.default()
+    prm.max_backtracking_steps = 100
+    prm.initial_alpha_scaling = 0.1
+    prm.convergence_tolerance = 0.1
+    prm.expected_decrease_fraction = 0.001
+    prm.max_solver_iters = 40
+    s = ProblemSpec(T, dt, prm)
+    for _ in range(2):
+        s.add_player(DYN_CAR_5D, 4.0, state_reg=10.0, control_reg=10.0)
+    X, Y, H, PHI, V = [0, 5], [1, 6], [2, 7], [3, 8], [4, 9]
+    for i in range(2):
+        s.quadratic(i, 25.0, 0, 0.0, control_of=i)  # omega
+        s.quadratic(i, 15.0, 1, 0.0, control_of=i)  # acceleration
+        s.quadratic(i, 10.0, V[i], 6.0)
+    lane1 = s.add_polyline([(0.0, -1000.0), (0.0, 1000.0)])
+    lane2 = s.add_polyline([(-5.0, 1000.0), (-5.0, 5.0), (0.0, 0.0), (995.0, 0.0)])
+    s.quadratic_polyline2(0, 25.0, lane1, (X[0], Y[0]))
+    s.quadratic_polyline2(1, 25.0, lane2, (X[1], Y[1]))
+    (cx, cy), (vx, vy) = MOVING_OBSTACLE_START, MOVING_OBSTACLE_VELOCITY
+    dx, dy = moving_obstacle_offset(Expr.x(), cx, vx), moving_obstacle_offset(Expr.y(), cy, vy)
+    bump = ((dx.square() + dy.square()) * -0.5 / Expr.value().square()).exp() * Expr.weight()
+    keep_out = Expr.value().square() - dx.square() - dy.square()
+    s.name_term("p1_pedestrian_bump", s.expression(0, bump, (X[0], Y[0]), weight=40.0, value=2.0))
+    s.name_term("p1_pedestrian_keep_out", s.expression_constraint(0, keep_out, (X[0], Y[0]), value=1.5))
+    s.name_term("p2_pedestrian_bump", s.expression(1, bump, (X[1], Y[1]), weight=40.0, value=2.0))
+    s.proximity(0, 50.0, (X[0], Y[0]), (X[1], Y[1]), 6.0)
+    s.proximity(1, 50.0, (X[1], Y[1]), (X[0], Y[0]), 6.0)
+    f = np.float32
+    x0 = np.zeros(10)
+    x0[[X[0], Y[0], H[0], V[0]]] = [0.0, -10.0, float(f(np.pi / 2)), 5.0]
+    x0[[X[1], Y[1], H[1], V[1]]] = [-5.0, 10.0, float(f(-np.pi / 2)), 4.0]
+    s.x0 = x0
+    s.position_dims, s.heading_dims, s.speed_dims = list(zip(X, Y)), H, V
+    return s
+
+
+# gusting_car_scene's gust on the heading rate, a sin(omega t) (its C++ twin: tests/host/gusting_car_scene.h)
+GUSTING_CAR_AMPLITUDE, GUSTING_CAR_OMEGA = 0.4, 3.0
+
+
+def gusting_car_rows():
+    """The state rows of gusting_car_scene's model, as add_expression_player takes them: the coasting car's, with the
+    gust a sin(omega t) added to the heading rate (a = Expr.weight(), the row's second constant)."""
+    from .abi import Expr
+    x, y, c, a, t = Expr.x(), Expr.y(), Expr.value(), Expr.weight(), Expr.time()
+    return [(y * x.cos(), 2, 3), (y * x.sin(), 2, 3), (x * y + a * (GUSTING_CAR_OMEGA * t).sin(), 3, 4),
+            (-(c * x.square()), 3, None)]
+
+
+def gusting_car_scene(T=100, dt=0.1):
+    """A test scene, NOT a reference example: coasting_car_scene (two cars of an abi.DYN_EXPRESSION model, n = 8 with one
+    control each: the specialised (8, 2, 1) kernels) in a periodic side wind — the heading rate reads the time,
+    theta' = v kappa + a sin(omega t), through Expr.time().  The costs are the coasting car's."""
+    prm = SolverParams.default()
+    prm.max_backtracking_steps = 100
+    prm.initial_alpha_scaling = 0.1
+    prm.convergence_tolerance = 0.01
+    prm.expected_decrease_fraction = 0.001
+    s = ProblemSpec(T, dt, prm)
+    rows = gusting_car_rows()
+    for _ in range(2):
+        s.add_expression_player(4, 1, rows, param0=COASTING_CAR_DRAG, weights=[1.0, 1.0, GUSTING_CAR_AMPLITUDE, 1.0])
+    X, Y, H, V = [0, 4], [1, 5], [2, 6], [3, 7]
+    for i in range(2):
+        s.name_term("p%d_curvature" % (i + 1), s.quadratic(i, 1.0, 0, 0.0, control_of=i))
+    s.name_term("p1_goal_x", s.quadratic(0, 1.0, X[0], 0.0))
+    s.name_term("p1_goal_y", s.quadratic(0, 1.0, Y[0], 0.0))
+    s.name_term("p1_proximity", s.proximity(0, 5.0, (X[0], Y[0]), (X[1], Y[1]), 1.0))
+    s.name_term("p2_follow", s.quadratic_difference(1, 1.0, (X[1], Y[1]), (X[0], Y[0])))
+    s.name_term("p2_proximity", s.proximity(1, 5.0, (X[1], Y[1]), (X[0], Y[0]), 1.0))
+    s.x0 = [2.0, 1.0, float(np.float32(np.pi / 2)), 1.5, -1.0, -2.0, 0.3, 2.0]
+    s.position_dims, s.heading_dims, s.speed_dims = list(zip(X, Y)), H, V
+    return s
+
+
 def jittered_x0(spec, batch, seed=0):
     """Per-instance initial states of SURVEY.md §8(d): U(-1,1) m on px,py, U(-0.1,0.1) rad
     heading, U(-0.5,0.5) m/s speed; instance b uses numpy default_rng(seed + b)."""

@@ -1513,6 +1513,14 @@ struct DynamicsHandle {
     ilqg_problem_desc d{};
     std::string why;
     CHECK(DescribeDynamics(dynamics, &d, &why)) << why;
+    // The plan kernels integrate partial steps at absolute plan times, where the reference hands a model no consistent
+    // time: a model whose rows read it is refused here as the C ABI's plan entry points refuse it (ILQG_EXPR_PUSH_TIME).
+    if (const auto* cat = dynamic_cast<const ConcatenatedDynamicalSystem*>(&dynamics))
+      for (size_t i = 0; i < cat->Subsystems().size(); i++)
+        if (const auto* model = dynamic_cast<const SinglePlayerExpressionSystem*>(cat->Subsystems()[i].get()))
+          for (const SinglePlayerExpressionSystem::Row& row : model->Rows())
+            CHECK(!row.expr.UsesTime()) << "plan integration / receding horizon: subsystem " << i
+                                        << " is an expression subsystem whose rows read the time (Expr::Time())";
     // the handle's tables want every player to own a control Hessian; the plan kernels never evaluate it
     ilqg_cost_term own_control[ILQG_MAX_PLAYERS] = {};
     for (int i = 0; i < d.num_players; i++) {

@@ -263,15 +263,40 @@ typedef enum {
 
 /* The program of an ILQG_COST_EXPRESSION term: 1 <= L <= ILQG_EXPR_MAX_OPS ops on a stack that never holds more than
  * ILQG_EXPR_MAX_DEPTH entries and exactly one at the end.  An entry is the jet (f, fx, fy, fxx, fyy, fxy) in the solve's
- * scalar type.  Pushes: X (x,1,0,0,0,0), Y (y,0,1,0,0,0), CONST (imm), WEIGHT, VALUE (the term's, or the instance's).
+ * scalar type.  Pushes: X (x,1,0,0,0,0), Y (y,0,1,0,0,0), CONST (imm), WEIGHT, VALUE (the term's, or the instance's),
+ * TIME (t,0,0,0,0,0) — see below.
  * Binary ops take a (below) and b (top): ADD, SUB, MUL, DIV.  Unary ops replace the top: NEG, SQUARE, SQRT, EXP, LOG, SIN,
  * COS, and HINGE — the entry itself where its f > 0 strictly, else all zeros (src/semiquadratic_cost.cpp's one-sided
- * rule).  Every product and sum rounds on its own (no contraction); a NaN or Inf is the program's own. */
+ * rule).  Every product and sum rounds on its own (no contraction); a NaN or Inf is the program's own.
+ *
+ *   opcode  name         kind    what it does
+ *   1       PUSH_X       push    the first input, (x, 1, 0, 0, 0, 0)
+ *   2       PUSH_Y       push    the second input, (y, 0, 1, 0, 0, 0); a two-input term only
+ *   3       PUSH_CONST   push    the op's immediate
+ *   4       PUSH_WEIGHT  push    the term's `weight` (the instance's where it is bound per instance)
+ *   5       PUSH_VALUE   push    the term's `value` (a dynamics row: the subsystem's param0)
+ *   6-9     ADD SUB MUL DIV      binary, a (below) op b (top)
+ *   10-17   NEG SQUARE SQRT EXP LOG SIN COS HINGE   unary, on the top entry
+ *   18      PUSH_TIME    push    the time, (t, 0, 0, 0, 0, 0): a leaf whose derivatives are all zero
+ *
+ * PUSH_TIME.  t is the time the reference's ILQSolver hands the object at that step, RelativeTimeTracker::RelativeTime(k):
+ * double(k) * dt, rounded once to the solve's scalar type.  It is relative to the start of the window: in a
+ * receding-horizon loop a time-reading cost or constraint sees what NominalPathLengthCost sees there.  In the value-only
+ * walks of the open-loop form the step is the one the term is evaluated at there (the "next step" index).  A child of an
+ * ExtremeValueCost cannot be an expression, so no program is evaluated at a step of a parent's.
+ *   In an ILQG_DYN_ROW_EXPRESSION program t is the time of the stage being evaluated: the linearisation is at t_k = k dt,
+ *   the Euler form integrates at t_k, and the two RK4 half-steps of h = dt / 2 evaluate their stages at t0, t0 + h/2,
+ *   t0 + h/2, t0 + h with t0 = k dt and then k dt + h (MultiPlayerDynamicalSystem::Integrate), each time formed in double
+ *   and rounded once.  The receding-horizon plan kernels integrate partial steps at absolute plan times, where the
+ *   reference gives no consistent time: a problem with a dynamics row that reads the time is refused there
+ *   (ILQG_ERR_UNSUPPORTED; ilqg_receding_horizon_shift_batch, _sync_batch, plan integration).  Time-reading costs and
+ *   constraints are not. */
 typedef enum {
   ILQG_EXPR_PUSH_X = 1, ILQG_EXPR_PUSH_Y = 2, ILQG_EXPR_PUSH_CONST = 3, ILQG_EXPR_PUSH_WEIGHT = 4, ILQG_EXPR_PUSH_VALUE = 5,
   ILQG_EXPR_ADD = 6, ILQG_EXPR_SUB = 7, ILQG_EXPR_MUL = 8, ILQG_EXPR_DIV = 9,
   ILQG_EXPR_NEG = 10, ILQG_EXPR_SQUARE = 11, ILQG_EXPR_SQRT = 12, ILQG_EXPR_EXP = 13, ILQG_EXPR_LOG = 14,
-  ILQG_EXPR_SIN = 15, ILQG_EXPR_COS = 16, ILQG_EXPR_HINGE = 17
+  ILQG_EXPR_SIN = 15, ILQG_EXPR_COS = 16, ILQG_EXPR_HINGE = 17,
+  ILQG_EXPR_PUSH_TIME = 18
 } ilqg_expr_op;
 #define ILQG_EXPR_MAX_OPS 64
 #define ILQG_EXPR_MAX_DEPTH 4
@@ -1026,7 +1051,8 @@ ilqg_status ilqg_set_scratch(void* device_buffer, size_t bytes);
                                  (idx[2], idx[3]) and ILQG_CONSTRAINT_EXPRESSION (kind 25; no new call, no layout change); still 9:
                                  ILQG_DYN_EXPRESSION (subsystem kind 13), ILQG_ROLE_DYNAMICS_ROW (role 5) and
                                  ILQG_DYN_ROW_EXPRESSION (term kind 26): three enumerators, no new call, no layout change; still 9:
-                                 the host-only ilqg_schedule_build (ilqg_schedule_query, ilqg_schedule_info: one new call);
+                                 the host-only ilqg_schedule_build (ilqg_schedule_query, ilqg_schedule_info: one new call); still 9:
+                                 ILQG_EXPR_PUSH_TIME (expression opcode 18: one enumerator, no new call, no layout change);
                               8: ilqg_solve_options::padded_sweep (was reserved1) / probe_lanes (new, with reserved2: the struct grew by
                                  eight bytes), ILQG_SCHEDULE_PADDED_SWEEP;
                               7: ilqg_solve_options::deterministic (was reserved0) / static_rows, ilqg_copy_bandwidth, ilqg_problem_row_program, ilqg_row_program_build;

@@ -396,6 +396,10 @@ class Expr {
   static Expr Y() { return Expr(ILQG_EXPR_PUSH_Y, nullptr, nullptr); }
   static Expr Weight() { return Expr(ILQG_EXPR_PUSH_WEIGHT, nullptr, nullptr); }
   static Expr Value() { return Expr(ILQG_EXPR_PUSH_VALUE, nullptr, nullptr); }
+  // The time the solver hands the object at the step it is evaluated at, relative to the start of the window
+  // (Cost::Evaluate(Time t, ...)'s t; in a model row the time of the stage): ILQG_EXPR_PUSH_TIME, a leaf with no derivative.
+  static Expr Time() { return Expr(ILQG_EXPR_PUSH_TIME, nullptr, nullptr); }
+  bool UsesTime() const { return Uses(*node_, ILQG_EXPR_PUSH_TIME); }
   friend Expr operator+(const Expr& a, const Expr& b) { return Expr(ILQG_EXPR_ADD, a.node_, b.node_); }
   friend Expr operator-(const Expr& a, const Expr& b) { return Expr(ILQG_EXPR_SUB, a.node_, b.node_); }
   friend Expr operator*(const Expr& a, const Expr& b) { return Expr(ILQG_EXPR_MUL, a.node_, b.node_); }
