@@ -1,779 +1,89 @@
-// ilqg_api.hip — kernels and the C ABI of libilqg_hip.so (gfx950 only).
+// ilqg_api.hip — the main unit of libilqg_hip.so (gfx950 only): the state the units share, the table of instantiated
+// shapes, the run-time-dimensioned solve and the C ABI.  The per-shape unit is ilqg_dims.hip; DESIGN.md 3.18 has the layout.
 // Entry points and the reference methods they replace: include/ilqg.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "ilqg_common.hpp"
-#include "ilqg_lq.hpp"
-#include "ilqg_lq_openloop.hpp"
-#include "ilqg_lq_feedback2.hpp"
-#include "ilqg_lq_generic.hpp"
 #include "ilqg_costates.hpp"
-#include "ilqg_models.hpp"
+#include "ilqg_decide_schedule.hpp"  // decide_schedule's definition
+#include "ilqg_instances.hpp"        // per-instance declarations and bindings on the problem object
+#include "ilqg_kernels.hpp"
+#include "ilqg_launch.hpp"
 #include "ilqg_nash.hpp"
+#include "ilqg_problem_build.hpp"  // the problem object's host tables and its upload
 #include "ilqg_receding.hpp"
-#include "ilqg_rowprog.hpp"
-#include "ilqg_rowprog_static.hpp"
-#include "ilqg_solve.hpp"
-#include "ilqg_stages.hpp"
+#include "ilqg_round_loop.hpp"  // run_rounds' definition
+#include "ilqg_shapes.hpp"
+#include "ilqg_shared.hpp"
 
 using namespace ilqg;
 
-// The library is built from several translation units of this one file (__graft_entry__.build): one "main" unit
-// with the C ABI and every kernel that does not depend on the (n, N, m_i) instantiation, and one unit per entry of
-// ILQG_FOR_DIMS (compiled with -DILQG_PART_NX/NP/MU) that holds DimsLaunch<T, n, N, m_i> and the kernels it
-// launches — they compile in parallel.  Without those macros the file is a single self-contained unit.
-// This is the state the units share.
+// ---- the state the units share (ilqg_shared.hpp), defined here ----
 namespace ilqg_shared __attribute__((visibility("hidden"))) {
-// g_prof: the diagnostic builds' buffer (-DILQG_PROFILE=1 / -DILQG_TIMELINE=1: ilqg_debug_set_profile_buffer exists only
-// there); the product library has neither the symbol nor the global.
-#define ILQG_DIAGNOSTIC_BUILD (ILQG_PROFILE || ILQG_TIMELINE)
-#if defined(ILQG_PART_NX)
-extern thread_local std::string g_err;
-#if ILQG_DIAGNOSTIC_BUILD
-extern long long* g_prof;
-#endif
-#else
+
 thread_local std::string g_err;
 #if ILQG_DIAGNOSTIC_BUILD
-long long* g_prof = nullptr;  // set through ilqg_debug_set_profile_buffer
+long long* g_prof = nullptr;
 #endif
-#endif
-}  // namespace ilqg_shared
-using ilqg_shared::g_err;
-#if ILQG_DIAGNOSTIC_BUILD
-using ilqg_shared::g_prof;
-#endif
-
-namespace {
 
 ilqg_status fail(ilqg_status s, const std::string& msg) {
   g_err = msg;
   return s;
 }
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return fail(ILQG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
-  } while (0)
 
-}  // namespace
-
-// Device scratch of the stand-alone entry points that take no workspace argument (ilqg_lq_*_batch with delta_x /
-// costates, ilqg_total_costs_batch, the equilibrium checks).  The caller may hand the library a buffer of its own
-// (ilqg_set_scratch): then nothing is allocated here and a call that needs more fails with the size it needs.  Without
-// one the library keeps a grow-only allocation per calling thread.  (The solves never use it: ilqg_workspace_bytes.)
-namespace ilqg_shared __attribute__((visibility("hidden"))) {
-struct ScratchState {
-  void* ptr = nullptr;
-  size_t bytes = 0;
-  bool caller_owned = false;
-};
-// One per calling thread, shared by the library's translation units — through an accessor: an `extern thread_local` of a
-// constant-initialised class type makes the other units call a TLS init function that the defining unit never emits.
-ScratchState& scratch_state();
-#if !defined(ILQG_PART_NX)
 ScratchState& scratch_state() {
   static thread_local ScratchState st;
   return st;
 }
-#endif
+
+ilqg_status Scratch::reserve(size_t need) {
+  ScratchState& st = scratch_state();
+  if (need <= st.bytes) return ILQG_OK;
+  if (st.caller_owned)
+    return fail(ILQG_ERR_INVALID, "the scratch buffer given to ilqg_set_scratch is too small: this call needs " +
+                                      std::to_string(need) + " bytes");
+  if (st.ptr) (void)hipFree(st.ptr);
+  st.ptr = nullptr;
+  st.bytes = 0;
+  HIP_TRY(hipMalloc(&st.ptr, need));
+  st.bytes = need;
+  return ILQG_OK;
+}
+
+void raise_lds_limit(const void* kern, size_t lds) {
+  if (lds <= 48 * 1024) return;
+  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
+}
+
+ilqg_status check_device() {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
+    return fail(ILQG_ERR_NO_DEVICE, "no HIP device visible: libilqg_hip.so has no CPU fallback");
+  return ILQG_OK;
+}
+
+template ilqg_status run_rounds<float>(ilqg_problem*, SolveArgs<float>&, const SolveTail<float>&, const RoundPlan<float>&,
+                                       const ilqg_solve_options&, hipStream_t);
+template ilqg_status run_rounds<double>(ilqg_problem*, SolveArgs<double>&, const SolveTail<double>&, const RoundPlan<double>&,
+                                        const ilqg_solve_options&, hipStream_t);
+
 }  // namespace ilqg_shared
 
-namespace {
-struct Scratch {  // this unit's view of the shared state
-  ilqg_status reserve(size_t need) {
-    ilqg_shared::ScratchState& st = ilqg_shared::scratch_state();
-    if (need <= st.bytes) return ILQG_OK;
-    if (st.caller_owned)
-      return fail(ILQG_ERR_INVALID, "the scratch buffer given to ilqg_set_scratch is too small: this call needs " +
-                                        std::to_string(need) + " bytes");
-    if (st.ptr) (void)hipFree(st.ptr);
-    st.ptr = nullptr;
-    st.bytes = 0;
-    HIP_TRY(hipMalloc(&st.ptr, need));
-    st.bytes = need;
-    return ILQG_OK;
-  }
-};
-}  // namespace
+// The list's one expansion besides the table: without these declarations the table's addresses would instantiate every
+// shape's launchers, and the kernels behind them, in this unit as well.
+#define X(NX_, NP_, MU_)                                   \
+  extern template struct DimsLaunch<float, NX_, NP_, MU_>; \
+  extern template struct DimsLaunch<double, NX_, NP_, MU_>;
+ILQG_FOR_DIMS(X)
+#undef X
 
 namespace {
-
-
-// ------------------------------------------------------------------------------------
-// Kernels — one workgroup per game instance
-// ------------------------------------------------------------------------------------
-template <typename T>
-struct LQBatchArgs {
-  const T *A, *Bm, *Q, *l, *R, *r, *x0;
-  T *P, *alpha, *dx, *scratch;
-  int T_steps, adaptive, batch, force_valu;
-  T* costates = nullptr;
-  // the arrays of an ilqg_lq_*_batch call; no scratch, no costates, the caller's regularisation
-  LQBatchArgs(const ilqg_dims* d, const void* A_, const void* Bm_, const void* Q_, const void* l_, const void* R_,
-              const void* r_, const void* x0_, void* P_, void* alpha_, void* dx_)
-      : A((const T*)A_), Bm((const T*)Bm_), Q((const T*)Q_), l((const T*)l_), R((const T*)R_), r((const T*)r_),
-        x0((const T*)x0_), P((T*)P_), alpha((T*)alpha_), dx((T*)dx_), scratch(nullptr), T_steps(d->T),
-        adaptive(d->adaptive_regularization), batch(d->batch), force_valu(0) {}
-};
-
-template <typename T, int NX, int NP, int MU, bool FORCE_VALU>
-__global__ void __launch_bounds__((LQFeedbackThreads<T, NX, NP, MU, FORCE_VALU>::NT),
-                                  (LQFeedbackThreads<T, NX, NP, MU, FORCE_VALU>::PLAYER_WAVES ? (NX <= 16 ? NP : 2) : 1))
-lq_feedback_kernel(LQBatchArgs<T> g, PairTable pt) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* sm = reinterpret_cast<T*>(smem_raw);
-  const int b = blockIdx.x;
-  constexpr int M = NP * MU;
-  const size_t Tn = g.T_steps;
-  LQArgs<T> a;
-  a.A = g.A + b * Tn * NX * NX;
-  a.Bm = g.Bm + b * Tn * NX * M;
-  a.Q = g.Q + b * Tn * NP * NX * NX;
-  a.l = g.l + b * Tn * NP * NX;
-  a.R = g.R + b * Tn * pt.Rsz;
-  a.r = g.r + b * Tn * pt.rsz;
-  a.x0 = g.x0 ? g.x0 + size_t(b) * NX : nullptr;
-  a.P = g.P + b * Tn * M * NX;
-  a.alpha = g.alpha + b * Tn * M;
-  a.dx = g.dx ? g.dx + b * Tn * NX : nullptr;
-  a.scratch = g.scratch ? g.scratch + b * Tn * (NP * (NX + 1) + NX) : nullptr;
-  a.ed_out = nullptr;
-  a.T_steps = g.T_steps;
-  a.adaptive = g.adaptive;
-  lq_feedback_dispatch<T, NX, NP, MU, FORCE_VALU>(a, pt, sm);
-}
-
-template <typename T, int NX, int NP, int MU>
-__global__ void __launch_bounds__((OLCfg<T, NX, NP, MU>::NT), 3)  // three instances per CU (see ilqg_lq_openloop.hpp)
-lq_openloop_kernel(LQBatchArgs<T> g, PairTable pt) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* sm = reinterpret_cast<T*>(smem_raw);
-  const int b = blockIdx.x;
-  constexpr int M = NP * MU;
-  const size_t Tn = g.T_steps;
-  LQArgs<T> a;
-  a.A = g.A + b * Tn * NX * NX;
-  a.Bm = g.Bm + b * Tn * NX * M;
-  a.Q = g.Q + b * Tn * NP * NX * NX;
-  a.l = g.l + b * Tn * NP * NX;
-  a.R = g.R + b * Tn * pt.Rsz;
-  a.r = g.r + b * Tn * pt.rsz;
-  a.x0 = g.x0 ? g.x0 + size_t(b) * NX : nullptr;
-  a.P = g.P + b * Tn * M * NX;
-  a.alpha = g.alpha + b * Tn * M;
-  a.dx = g.dx ? g.dx + b * Tn * NX : nullptr;
-  a.scratch = g.scratch + b * Tn * (g.costates ? OLCfg<T, NX, NP, MU>::ROW_FAT : OLCfg<T, NX, NP, MU>::ROW);
-  a.costates = g.costates ? g.costates + b * Tn * NP * NX : nullptr;
-  a.ed_out = nullptr;
-  a.T_steps = g.T_steps;
-  a.adaptive = 0;
-  lq_openloop_instance<T, NX, NP, MU>(a, pt, sm);
-}
-
-// The sweeps with run-time dimensions (ilqg_lq_generic.hpp): whatever has no specialised instantiation above.
-template <typename T>
-__global__ void __launch_bounds__(256) lq_generic_kernel(LQBatchArgs<T> g, GenDims d, PairTable pt, int open_loop,
-                                                         int scratch_row) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* sm = reinterpret_cast<T*>(smem_raw);
-  const size_t b = blockIdx.x, Tn = d.T, n = d.n, m = d.m, N = d.N;
-  GenLQArgs<T> a;
-  a.A = g.A + b * Tn * n * n;
-  a.Bm = g.Bm + b * Tn * n * m;
-  a.Q = g.Q + b * Tn * N * n * n;
-  a.l = g.l + b * Tn * N * n;
-  a.R = g.R + b * Tn * pt.Rsz;
-  a.r = g.r + b * Tn * pt.rsz;
-  a.x0 = g.x0 ? g.x0 + b * n : nullptr;
-  a.P = g.P + b * Tn * m * n;
-  a.alpha = g.alpha + b * Tn * m;
-  a.dx = g.dx ? g.dx + b * Tn * n : nullptr;
-  a.costates = (open_loop && g.costates) ? g.costates + b * Tn * N * n : nullptr;
-  a.scratch = g.scratch ? g.scratch + b * Tn * size_t(scratch_row) : nullptr;
-  a.ed_out = nullptr;
-  a.adaptive = g.adaptive;
-  const ParDevice par;
-  if (open_loop)
-    lq_openloop_generic<T>(d, a, pt, sm, par);
-  else
-    lq_feedback_generic<T>(d, a, pt, sm, par);
-}
-
-template <typename T>
-struct RolloutBatchArgs {
-  const T *x0, *xs_ref, *us_ref, *P, *alpha, *alpha_scale;
-  T *xs, *us;
-  const int* active;
-};
-
-// XDYN: the problem holds an expression subsystem (rollout_instance's XDYN, ilqg_stages.hpp): a kernel of its own
-// (launched with one wavefront; the expression integrator wants the whole register file: 1024 is the bound a kernel
-// without the attribute gets)
-template <typename T, bool XDYN = false>
-__global__ void __launch_bounds__(XDYN ? 64 : 1024) rollout_kernel(DevProblem p, RolloutBatchArgs<T> g) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* sm = reinterpret_cast<T*>(smem_raw);
-  const size_t b = blockIdx.x;
-  if (g.active && !g.active[b]) return;
-  const size_t Tn = p.T, n = p.n, m = p.m;
-  RolloutArgs<T> a{g.x0 + b * n,          g.xs_ref + b * Tn * n, g.us_ref + b * Tn * m, g.P + b * Tn * m * n,
-                   g.alpha + b * Tn * m,  g.alpha_scale ? g.alpha_scale[b] : T(1),
-                   g.xs + b * Tn * n,     g.us + b * Tn * m,     instance_values(p, int(b))};
-  rollout_instance_rt<T, XDYN>(p, a, sm, threadIdx.x);
-}
-
-template <typename T>
-struct QuadBatchArgs {
-  const T *xs, *us, *lambdas, *mu;
-  const int* t_extreme;
-  T *A, *Bm, *Q, *l, *R, *r, *merit_part, *cost_part;
-  const int* active;
-};
-
-template <typename T>
-__device__ __forceinline__ QuadArgs<T> quad_args_of(const DevProblem& p, const QuadBatchArgs<T>& g, size_t b) {
-  const size_t Tn = p.T, n = p.n, m = p.m, N = p.N;
-  QuadArgs<T> a;
-  a.xs = g.xs + b * Tn * n;
-  a.us = g.us + b * Tn * m;
-  a.lambdas = g.lambdas ? g.lambdas + b * p.num_constraints * Tn : nullptr;
-  a.mu = g.mu ? g.mu[b] : T(10);
-  a.t_extreme = g.t_extreme ? g.t_extreme + b * N : nullptr;
-  a.t_init = 0.0;
-  a.A = g.A ? g.A + b * Tn * n * n : nullptr;
-  a.Bm = g.Bm ? g.Bm + b * Tn * n * m : nullptr;
-  a.Q = g.Q ? g.Q + b * Tn * N * n * n : nullptr;
-  a.l = g.l ? g.l + b * Tn * N * n : nullptr;
-  a.R = g.R ? g.R + b * Tn * p.pairs.Rsz : nullptr;
-  a.r = g.r ? g.r + b * Tn * p.pairs.rsz : nullptr;
-  a.merit_part = g.merit_part ? g.merit_part + b * Tn * N * 2 : nullptr;
-  a.cost_part = g.cost_part ? g.cost_part + b * Tn * N : nullptr;
-  a.iv = instance_values(p, int(b));
-  a.seg_off = instance_segs_offset(p, int(b));
-  a.tnom_off = instance_tnom_offset(p, int(b));
-  return a;
-}
-
-// Linearise / quadraticise / cost stage on its own (ilqg_rows.hpp): grid = (ceil(T / cw), B), one wavefront takes cw
-// consecutive rows of one instance.
-// EXPR: the interpreter that also evaluates expression costs (ProgDynamicExpr, ilqg_rows.hpp), for the problems that hold one
-// XDYN: ... and linearises expression subsystems (ProgDynamicExprDyn)
-template <typename T, int NX, int NP, int MU, bool EXPR = false, bool XDYN = false>
-__global__ void __launch_bounds__(64) rows_kernel(DevProblem p, QuadBatchArgs<T> g, int cw) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const size_t b = blockIdx.y;
-  if (g.active && !g.active[b]) return;
-  const short* maps = rows_maps_load(p, smem_raw);
-  T* sm = reinterpret_cast<T*>(smem_raw + rows_maps_bytes(p));
-  const QuadArgs<T> a = quad_args_of<T>(p, g, b);
-  const int k0 = int(blockIdx.x) * cw;
-  const int nrows = p.T - k0 < cw ? p.T - k0 : cw;
-  typedef typename std::conditional<XDYN, ProgDynamicExprDyn, typename std::conditional<EXPR, ProgDynamicExpr, ProgDynamic>::type>::type Prog;
-  rows_chunk<T, NX, NP * MU, NP, false, false, Prog>(p, maps, a, k0, nrows, cw, sm, int(threadIdx.x));
-}
-
-// ilqg_solve_state_batch: the loop state of every instance out of the workspace
-template <typename T>
-__global__ void solve_state_kernel(const T* ws, size_t ws_stride, size_t state_off, int batch, T* last_merit,
-                                   T* expected_decrease, T* step, int* backtracks) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= batch) return;
-  const SolveState<T>* s = reinterpret_cast<const SolveState<T>*>(ws + size_t(b) * ws_stride + state_off);
-  if (last_merit) last_merit[b] = s->last_merit;
-  if (expected_decrease) expected_decrease[b] = s->expected_decrease;
-  if (step) step[b] = s->acc_scale;
-  if (backtracks) backtracks[b] = s->rejected;
-}
-
-// What follows the per-instance blocks in a solve's workspace: two lists of instance ids (this round's back-tracking
-// instances, the next round's) and the pool of the speculative line search.
-struct WsTail {
-  size_t ids_off, pool_off, total;
-  int pool_entries;
-};
-inline WsTail ws_tail(const DevProblem& d, int batch, size_t elem, int ol_row) {
-  auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-  const WsLayout L = ws_layout_of(d, ol_row, 1);  // the augmented-Lagrangian layout, the larger one: for either al_mode
-  WsTail t;
-  t.ids_off = up(size_t(L.total) * elem * size_t(batch));
-  t.pool_off = up(t.ids_off + size_t(2) * batch * sizeof(int));
-  // sixteen candidates per instance up to kProbeEntries; a small batch gets every candidate of every instance up to
-  // one round's budget (a few dozen instances in failing line searches walk through all their step sizes, 128 a round
-  // each: config 5's 47 surviving plans as a dense batch, 752 entries: 75 ms per replan; 6016: see DESIGN.md 3.13),
-  // and never fewer than two full rounds' worth for a single instance
-  const long long small = std::min<long long>((long long)batch * kProbeCandidates, kProbeRoundBudget);
-  const long long want = std::max<long long>((long long)batch * 16, small);
-  t.pool_entries = int(std::min<long long>(want, kProbeEntries));
-  if (t.pool_entries < 2 * kProbeCandidates) t.pool_entries = 2 * kProbeCandidates;
-  t.total = up(t.pool_off + size_t(t.pool_entries) * ProbeEntry(d.n, d.m, d.N, d.T).total * elem);
-  return t;
-}
-
-template <typename T>
-__global__ void costs_reduce_kernel(DevProblem p, const T* cost_part, T* costs, int* t_extreme, const int* active) {
-  const size_t b = blockIdx.x;
-  if (active && !active[b]) return;
-  costs_reduce<T>(p, cost_part + b * p.T * p.N, costs + b * p.N, t_extreme ? t_extreme + b * p.N : nullptr);
-}
-
-// Wavefronts per instance in the trial kernel: wave 0 integrates, the others take the chunks of rows it has
-// produced (ilqg_solve.hpp).  One row wave keeps up with the integration; each more costs a row scratch of LDS.
-#ifndef ILQG_TRIAL_WAVES_F32
-#define ILQG_TRIAL_WAVES_F32 2
-#endif
-#ifndef ILQG_TRIAL_WAVES_F64
-#define ILQG_TRIAL_WAVES_F64 2
-#endif
-template <typename T>
-struct TrialWaves {
-  static constexpr int W = sizeof(T) == 4 ? ILQG_TRIAL_WAVES_F32 : ILQG_TRIAL_WAVES_F64;
-};
-
-// Trial kernel: rollout + linearise/quadraticise + line-search decision (ilqg_solve.hpp).  The second
-// launch-bound argument is the number of waves per SIMD the register allocation must allow.  fp32 was compiled for
-// three (168 registers: six instances per CU) until round 5; since the large batches of the one-tile shapes run the
-// split pass, the fused kernel serves four instances per CU at most there, and the full register file is worth 1.6 %
-// at the headline batch in fp32 (2.105 -> 2.140 M it/s).  -DILQG_TRIAL_OCCUPANCY_F32=3 restores the old build.
-#ifndef ILQG_TRIAL_OCCUPANCY_F32
-#define ILQG_TRIAL_OCCUPANCY_F32 2
-#endif
-template <typename T, int NX, int NP, int MU, int W, int PROGID = 0, bool BOUND = (PROGID >= kBoundProg)>
-__global__ void __launch_bounds__(64 * W, (sizeof(T) == 4 && W == 2) ? ILQG_TRIAL_OCCUPANCY_F32 : W) ilq_trial_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int b = blockIdx.x;
-  if (!sa.first) {  // instances that are done (or waiting for the LQ kernel) leave without touching LDS
-    const int stage = instance_stage<T>(p, sa, b);
-    if (stage != ST_ROLLOUT && stage != ST_QUAD) return;
-  } else if (sa.active && !sa.active[b]) {  // skipped instance
-    instance_mark_done<T>(p, sa, b);
-    return;
-  }
-  const short* maps = rows_maps_load(p, smem_raw);
-  T* sm = reinterpret_cast<T*>(smem_raw + rows_maps_bytes(p));
-  trial_part_instance<T, NX, NP, MU, W, TRIAL_FUSED, PROGID, BOUND>(p, maps, sa, b, sm);
-}
-
-// The same pass cut into three launches (ilqg_solve.hpp, TRIAL_ROLL / rows_part_instance / TRIAL_DECIDE), for
-// problems whose fused trial kernel fits fewer than three instances on a CU.
-#ifndef ILQG_ROLL_WAVES
-#define ILQG_ROLL_WAVES 4
-#endif
-// XDYN: the problem holds an expression subsystem (kExprDynProg: the rollout with the expression integrator in it)
-template <typename T, int NX, int NP, int MU, bool XDYN = false>
-__global__ void __launch_bounds__(64, sizeof(T) == 8 ? (XDYN ? 2 : ILQG_ROLL_WAVES) : 1) ilq_roll_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  if constexpr (rollout_pairs(NX, NP, MU)) {  // two instances per wavefront: entries 2 x and 2 x + 1 of the round
-    const int i0 = 2 * int(blockIdx.x), i1 = i0 + 1;
-    const int b0 = sa.ids ? sa.ids[i0] : i0;
-    const int b1 = i1 < sa.round_count ? (sa.ids ? sa.ids[i1] : i1) : -1;
-    roll_pair_instances<T, NX, NP, MU>(p, sa, b0, b1, reinterpret_cast<T*>(smem_raw));
-    return;
-  }
-  const int b = sa.ids ? sa.ids[blockIdx.x] : int(blockIdx.x);
-  if (!sa.first) {
-    if (instance_stage<T>(p, sa, b) != ST_ROLLOUT) return;
-  } else if (sa.active && !sa.active[b]) {
-    instance_mark_done<T>(p, sa, b);
-    return;
-  }
-  trial_part_instance<T, NX, NP, MU, 1, TRIAL_ROLL, (XDYN ? kExprDynProg : 0)>(p, nullptr, sa, b, reinterpret_cast<T*>(smem_raw));
-}
-
-template <typename T, int NX, int NP, int MU, int PROGID = 0>
-__global__ void __launch_bounds__(64) ilq_rows_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int b = sa.ids ? sa.ids[blockIdx.y] : int(blockIdx.y);
-  if (const int stage = instance_stage<T>(p, sa, b); stage != ST_ROLLOUT && stage != ST_QUAD) return;
-  // compact rows: nothing dense is written, so the word maps of the dense images are not needed (nor their LDS)
-  const short* maps = sa.compact ? nullptr : rows_maps_load(p, smem_raw);
-  T* sm = reinterpret_cast<T*>(smem_raw + (sa.compact ? 0 : rows_maps_bytes(p)));
-  rows_part_instance<T, NX, NP, MU, PROGID>(p, maps, sa, b, int(blockIdx.x), sm);
-}
-
-// SOLVER: the kernel of a problem with per-instance solver columns bound (solver_params_of).  A twin, as the fused trial
-// kernel has one for bound problems: this kernel is a chain of dependent loads per instance, and the test of
-// DevProblem::inst_solver with its wait cost the unbound fp32 batch of 8192 0.4-0.55 % — the unbound
-// twin is the code it was.
-template <typename T, int NX, int NP, int MU, bool SOLVER = true>
-__global__ void __launch_bounds__(64) ilq_decide_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int b = sa.ids ? sa.ids[blockIdx.x] : int(blockIdx.x);
-  if (const int stage = instance_stage<T>(p, sa, b); stage != ST_ROLLOUT && stage != ST_QUAD) return;
-  trial_part_instance<T, NX, NP, MU, 1, TRIAL_DECIDE, 0, false, SOLVER>(p, nullptr, sa, b, reinterpret_cast<T*>(smem_raw));
-}
-
-// Speculative line search of the listed instances (ilqg_solve.hpp): candidate j of list entry `slot`.
-// FAT (fp64): compiled for two waves per SIMD instead of ILQG_ROLL_WAVES — 256 registers, none spilled.  At four waves per
-// SIMD the paired fp64 rollout keeps 42 registers in scratch memory, reloaded inside the time-step chain: a round of a few
-// candidates, which costs the latency of one rollout however empty the chip is, runs a third faster without them (n = 16,
-// 6 instances x 128 candidates: 248 -> 166 us; the n = 16 constrained workload at B = 1024: 517 -> 533 k it/s); a round
-// that fills the chip wants the occupancy back (config 5's scene: 255 k it/s lean, 244 k fat).  The launcher picks.
-// SINGLE: one candidate per wavefront (rollout_instance) also where the shape has the paired form — for a round whose
-// candidates all find a SIMD of their own, where a launch costs one rollout's chain and the paired chain is the longer
-// one (n = 15, a few instances x 128 candidates: 176 us paired).
-template <typename T, int NX, int NP, int MU, bool FAT = false, bool SINGLE = false, bool XDYN = false>
-__global__ void __launch_bounds__(64, sizeof(T) == 8 ? ((FAT || XDYN) ? 2 : ILQG_ROLL_WAVES) : 1) ilq_probe_roll_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  if constexpr (rollout_pairs(NX, NP, MU) && !SINGLE)  // candidates 2 y and 2 y + 1 in the two halves of the wave
-    probe_roll_pair<T, NX, NP, MU>(p, sa, sa.ids[blockIdx.x], blockIdx.x, 2 * int(blockIdx.y), reinterpret_cast<T*>(smem_raw));
-  else
-    probe_roll_instance<T, NX, NP, MU, XDYN>(p, sa, sa.ids[blockIdx.x], blockIdx.x, blockIdx.y, reinterpret_cast<T*>(smem_raw));
-}
-
-// The probing rollouts of a round that fills the chip: 64 / NP candidates of one instance per wavefront, a lane per
-// (candidate, subsystem), the RK4 stages in sequence (rollout_lanes, ilqg_stages.hpp) — an eighth of the instructions
-// per trajectory of the paired form above, a longer chain per step: the launcher takes it where the round has more
-// rollouts than the chip holds at once.
-template <typename T, int NX, int NP, int MU>
-__global__ void __launch_bounds__(64, 4) ilq_probe_roll_lanes_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  if constexpr (rollout_pairs(NX, NP, MU))
-    probe_roll_lanes<T, NX, NP, MU>(p, sa, sa.ids[blockIdx.x], blockIdx.x, rollout_lanes_per_wave(NP) * int(blockIdx.y),
-                                    reinterpret_cast<T*>(smem_raw));
-}
-
-template <typename T, int NX, int NP, int MU, int PROGID = 0>
-__global__ void __launch_bounds__(64, sizeof(T) == 8 ? 4 : 1) ilq_probe_rows_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int slot = blockIdx.y / sa.probe_k, j = blockIdx.y % sa.probe_k;
-  const int b = sa.ids[slot];
-  {  // leave before the table load if this candidate is not wanted
-    const SolveState<T> s = state_load<T>(sa.ws + size_t(b) * sa.ws_stride, ws_layout_of(p, sa));
-    if (!probe_wanted(sa, solver_params_of(p, sa.prm, b), s, j)) return;
-  }
-  const short* maps = sa.compact ? nullptr : rows_maps_load(p, smem_raw);  // merit only: no dense image either way
-  T* sm = reinterpret_cast<T*>(smem_raw + (sa.compact ? 0 : rows_maps_bytes(p)));
-  probe_rows_instance<T, NX, NP, MU, PROGID>(p, maps, sa, b, slot, j, int(blockIdx.x), sm);
-}
-
-template <typename T>
-__global__ void __launch_bounds__(kProbeCandidates) ilq_probe_pick_kernel(DevProblem p, SolveArgs<T> sa) {
-  __shared__ T merits[kProbeCandidates];  // the candidates' merit values, reduced here one lane per candidate
-  probe_pick_instance<T>(p, sa, sa.ids[blockIdx.x], blockIdx.x, merits);
-}
-
-// Iterate log and anytime exit (ilqg_solve.hpp): only launched by solves that ask for them.
-template <typename T>
-__global__ void __launch_bounds__(256) ilq_log_kernel(DevProblem p, SolveArgs<T> sa, IterLog<T> lg) {
-  log_part_instance<T>(p, sa, lg, int(blockIdx.x));
-}
-template <typename T>
-__global__ void __launch_bounds__(64) ilq_deadline_kernel(DevProblem p, SolveArgs<T> sa) {
-  deadline_part_instance<T>(p, sa, int(blockIdx.x));
-}
-
-// Exit kernel: return path of ILQSolver::Solve / AugmentedLagrangianSolver bookkeeping for the instances
-// whose inner solve has ended (converged, out of iterations, or line search exhausted).
-template <typename T, int NX, int NP, int MU>
-__global__ void __launch_bounds__(256) ilq_exit_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int b = blockIdx.x;
-  if (instance_stage<T>(p, sa, b) != ST_INNER_DONE) return;
-  const QuadTables<T> tb = quad_tables_load<T>(p, smem_raw, b);
-  T* sm = reinterpret_cast<T*>(smem_raw + quad_tables_bytes(p, sizeof(T)));
-  exit_part_instance<T, NX, NP, MU>(p, tb, sa, b, sm);
-}
-
-// LQ kernel: the Riccati sweep at the accepted operating point of every instance that asked for one.
-// KIND LQ_PLAYER_WAVES_PACKED is LQ_PLAYER_WAVES compiled for four waves per SIMD (128 registers): the fp32 one-tile
-// sweep is three registers over that by itself, and at batches of many instances per CU a fifth resident instance is
-// worth more than the two spilled registers cost (n = 14 fp32, B = 8192: 2.15 M vs 2.04 M it/s; B = 1024, where only
-// four instances per CU exist: 1.81 M vs 1.85 M — so the launcher picks it for large batches only).
-#ifndef ILQG_1W_WAVES_F64
-#define ILQG_1W_WAVES_F64 2
-#endif
-// KIND LQ_SINGLE_WAVE: one wave per instance (ilqg_lq_feedback1w.hpp), compiled for as many waves per SIMD as its LDS
-// lets a CU hold instances (fp64: 20 KB -> eight per CU, two per SIMD; fp32: 10 KB -> sixteen, four per SIMD).
-// FORMS = false: the same sweep with the m x m solve's broadcasts through read-lanes (ilqg_solve_options::sweep_forms =
-// OFF), a second instantiation of the kinds that have the row-broadcast form: each step loop carries one of the two.
-// FORMS = 2: the player-parallel sweep with B's constant entries in registers as well (lq_part_instance).
-template <typename T, int NX, int NP, int MU, int KIND, int FORMS = 1>
-__global__ void __launch_bounds__((KIND == LQ_SINGLE_WAVE ? 64 : KIND == LQ_VALU_FEEDBACK ? LQCfg<T, NX, NP, MU>::NT : ((KIND == LQ_OPEN_LOOP || KIND == LQ_OPEN_LOOP_COMPACT) ? OLCfg<T, NX, NP, MU>::NT : 64 * NP)),
-                                  (KIND == LQ_SINGLE_WAVE ? (sizeof(T) == 4 ? 4 : ILQG_1W_WAVES_F64) : KIND == LQ_PLAYER_WAVES_PACKED ? 4 : KIND == LQ_PLAYER_WAVES ? (NX <= 16 ? NP : 2) : ((KIND == LQ_OPEN_LOOP || KIND == LQ_OPEN_LOOP_COMPACT) ? 3 : 1)))
-ilq_lq_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int b = blockIdx.x;
-  if (sa.clear_counters && b == 0 && threadIdx.x < 4) sa.unfinished[threadIdx.x] = 0;  // (SolveArgs::clear_counters)
-  {  // instance_stage, written out: through the helper the compiler schedules this kernel's whole sweep differently
-    const WsLayout L = ws_layout_of(p, sa);
-    const int stage = reinterpret_cast<const SolveState<T>*>(sa.ws + size_t(b) * sa.ws_stride + L.state)->stage;
-    if (stage != ST_LQ) return;
-  }
-  lq_part_instance<T, NX, NP, MU, (KIND == LQ_PLAYER_WAVES_PACKED ? LQ_PLAYER_WAVES : KIND), FORMS>(p, sa, b, reinterpret_cast<T*>(smem_raw));
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The sweep of a run-time-dimensioned solve on a SPECIALISED sweep: a game whose (n, N, m_i) has no instantiation is
-// embedded in the smallest instantiated shape (NX >= n, NP == N, MU >= max m_i) —
-//   states n .. NX - 1:   A = 1 on the diagonal, no column of any B, no row of any Q_i or l_i;
-//   controls m_i .. MU - 1 of player i:  a zero column of B_i, a unit diagonal entry of R_ii, zeros in every other block —
-// which solves to exact zeros in the added rows of [P | alpha] and leaves every other entry the recursion of
-// src/lq_feedback_solver.cpp:110-213 (src/lq_open_loop_solver.cpp:73-195) produces for the game itself: the added
-// column of S = R + B^T Z B is the unit vector (the Gershgorin step of :163-176 reads a column at a time and leaves it
-// alone: radius 0, diagonal 1), the added rows and columns of every Z_i stay zero.  One workgroup per instance whose
-// stage is LQ: (1) the instance's dense rows, written by the run-time-dimensioned row stage, are copied into the padded
-// layout (a region of the library's scratch buffer), (2) the specialised sweep of the padded shape runs on them —
-// strategies, delta_x and ILQSolver::ExpectedDecrease as in lq_part_instance —, (3) the rows of [P | alpha] that belong
-// to the game are copied to where the solve keeps its strategies.  The copies are ~2 x the sweep's own traffic; the sweep
-// is the register-tiled one instead of the all-LDS form with a barrier per phase (ilqg_lq_generic.hpp): n = 8,
-// m_i = (1, 2), B = 1024: 1.7 ms -> see DESIGN.md 3.8.
-// ---------------------------------------------------------------------------------------------------------------
-template <typename T, int NX, int NP, int MU, bool OL>
-struct PadLayout {
-  static constexpr int M = NP * MU;
-  size_t A, B, Q, l, R, r, P, al, dx, scr, x0, total;
-  __host__ __device__ PadLayout(int T_steps, int Rsz, int rsz) {
-    size_t o = 0;
-    auto take = [&](size_t cnt) {
-      const size_t at = o;
-      o += (cnt + 3) & ~size_t(3);
-      return at;
-    };
-    const size_t Tn = size_t(T_steps);
-    A = take(Tn * NX * NX);
-    B = take(Tn * NX * M);
-    Q = take(Tn * NP * NX * NX);
-    l = take(Tn * NP * NX);
-    R = take(Tn * Rsz);
-    r = take(Tn * rsz);
-    P = take(Tn * M * NX);
-    al = take(Tn * M);
-    dx = take(Tn * NX);
-    scr = take(Tn * size_t(OL ? OLCfg<T, NX, NP, MU>::ROW : NP * (NX + 1) + NX));
-    x0 = take(NX);
-    total = o;
-  }
-};
-
-template <typename T>
-struct PadArgs {
-  T* pad;             // [batch][PadLayout::total]
-  size_t pad_stride;  // elements
-  PairTable ptp;      // the game's control blocks at MU x MU each
-};
-
-template <typename T, int NX, int NP, int MU, bool OL>
-struct PadSweep {
-  using C = LQCfg<T, NX, NP, MU>;
-  static constexpr bool PW = !OL && C::USE_MFMA;
-  static constexpr int NT = OL ? OLCfg<T, NX, NP, MU>::NT : LQFeedbackThreads<T, NX, NP, MU, false>::NT;
-  static constexpr int WG_PER_CU = OL ? 3 : (PW ? (NX <= 16 ? NP : 2) : 1);
-  // the slot the sweep leaves ILQSolver::ExpectedDecrease in (lq_part_instance), and the LDS the launch asks for
-  static constexpr int ED_SLOT = OL ? OLCfg<T, NX, NP, MU>::LDS_ELEMS
-                                 : (PW && !C::MFMA_ONE_TILE) ? FB2Cfg<T, NX, NP, MU>::LDS_ELEMS : C::oX;
-  static constexpr size_t LDS_ELEMS = OL ? OLCfg<T, NX, NP, MU>::LDS_ELEMS + 4
-                                      : PW ? MfmaSweepLds<T, NX, NP, MU>::ELEMS + (C::MFMA_ONE_TILE ? 0 : 4) : C::LDS_ELEMS;
-};
-
-// The game as the copies see it: its own dimensions and control blocks, and where its rows are.
-template <typename T>
-struct PadGame {
-  int n, m, N, T_steps;
-  const int *udim, *uoff;            // [N], [N + 1]
-  const PairTable* pt;               // the game's blocks at their own sizes
-  const T *A, *Bm, *Q, *l, *R, *r;   // instance bases, the game's dense rows
-  const T* x0;                       // [n] or nullptr
-  T *P, *alpha, *dx;                 // instance bases of the results; dx may be nullptr
-  int want_ed;                       // ILQSolver::ExpectedDecrease into sm[PadSweep::ED_SLOT]
-  int adaptive, symmetric;
-  const int* xoff;                   // open loop: [N + 1] state offsets of a block-diagonal A, or nullptr (dense)
-};
-
-// Steps (1) - (3) above for one instance, by the whole workgroup; `q`: the instance's region of the padded buffer.
-template <typename T, int NX, int NP, int MU, bool OL>
-__device__ __forceinline__ void padded_sweep_instance(const PadGame<T>& g, const PairTable& ptp, T* q, T* sm) {
-  using PS = PadSweep<T, NX, NP, MU, OL>;
-  constexpr int M = NP * MU, NT = PS::NT;
-  const int tid = threadIdx.x;
-  const int n = g.n, m = g.m, Tn = g.T_steps;
-  const PadLayout<T, NX, NP, MU, OL> PL(Tn, ptp.Rsz, ptp.rsz);
-  // (eight loads in flight per lane: the workgroup is two to four waves, and a load-store pair per trip leaves the
-  // copy bound by one memory latency per element)
-  auto copy = [&](T* dst, int count, auto src_of) {
-    constexpr int U = 8;
-    for (int e0 = tid; e0 < count; e0 += NT * U) {
-      T v[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const int e = e0 + u * NT;
-        v[u] = e < count ? src_of(e) : T(0);
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const int e = e0 + u * NT;
-        if (e < count) dst[e] = v[u];
-      }
-    }
-  };
-  // ---- (1) dense rows of the game -> rows of the padded shape ----
-  {
-    const T *A = g.A, *Bm = g.Bm, *Q = g.Q, *l = g.l, *R = g.R, *r = g.r;
-    const PairTable& pt = *g.pt;
-    copy(q + PL.A, Tn * NX * NX, [&](int e) {
-      const int k = e / (NX * NX), f = e - k * (NX * NX), c = f / NX, row = f - c * NX;
-      return (row < n && c < n) ? A[size_t(k) * n * n + row + n * c] : (row == c ? T(1) : T(0));
-    });
-    copy(q + PL.B, Tn * NX * M, [&](int e) {
-      const int k = e / (NX * M), f = e - k * (NX * M), c = f / NX, row = f - c * NX, i = c / MU, ce = c - i * MU;
-      return (row < n && ce < g.udim[i]) ? Bm[size_t(k) * n * m + row + n * (g.uoff[i] + ce)] : T(0);
-    });
-    copy(q + PL.Q, Tn * NP * NX * NX, [&](int e) {
-      const int ki = e / (NX * NX), f = e - ki * (NX * NX), c = f / NX, row = f - c * NX;  // ki = k * NP + i
-      return (row < n && c < n) ? Q[size_t(ki) * n * n + row + n * c] : T(0);
-    });
-    copy(q + PL.l, Tn * NP * NX, [&](int e) {
-      const int ki = e / NX, row = e - ki * NX;
-      return row < n ? l[size_t(ki) * n + row] : T(0);
-    });
-    const int Rsz_p = ptp.Rsz, rsz_p = ptp.rsz;  // npairs * MU * MU, npairs * MU
-    copy(q + PL.R, Tn * Rsz_p, [&](int e) {
-      const int k = e / Rsz_p, f = e - k * Rsz_p, pq = f / (MU * MU), h = f - pq * (MU * MU), cb = h / MU, ca = h - cb * MU;
-      const int mj = g.udim[pt.pj[pq]];
-      return (ca < mj && cb < mj) ? R[size_t(k) * pt.Rsz + pt.roff[pq] + ca + mj * cb]
-                                  : ((pt.pi[pq] == pt.pj[pq] && ca == cb) ? T(1) : T(0));
-    });
-    copy(q + PL.r, Tn * rsz_p, [&](int e) {
-      const int k = e / rsz_p, f = e - k * rsz_p, pq = f / MU, ca = f - pq * MU;
-      const int mj = g.udim[pt.pj[pq]];
-      return ca < mj ? r[size_t(k) * pt.rsz + pt.rgoff[pq] + ca] : T(0);
-    });
-    if (g.x0 && tid < NX) q[PL.x0 + tid] = tid < n ? g.x0[tid] : T(0);
-  }
-  __threadfence_block();
-  __syncthreads();
-  // ---- (2) the specialised sweep (dense rows, its own forward pass) ----
-  LQArgs<T> la;
-  la.A = q + PL.A; la.Bm = q + PL.B; la.Q = q + PL.Q; la.l = q + PL.l; la.R = q + PL.R; la.r = q + PL.r;
-  la.x0 = g.x0 ? q + PL.x0 : nullptr;
-  la.P = q + PL.P; la.alpha = q + PL.al;
-  const bool forward = g.dx != nullptr || g.want_ed;
-  la.dx = forward ? q + PL.dx : nullptr;
-  la.scratch = (forward || OL) ? q + PL.scr : nullptr;
-  la.ed_out = g.want_ed ? sm + PS::ED_SLOT : nullptr;
-  la.T_steps = Tn;
-  la.adaptive = g.adaptive;
-  la.symmetric = g.symmetric;
-  if constexpr (OL) {
-    if (g.xoff) {  // the added states extend the last player's block (their A entries are its diagonal's)
-      la.nsub = NP;
-#pragma unroll
-      for (int i = 0; i < NP; i++) la.xoff[i] = g.xoff[i];
-      la.xoff[NP] = NX;
-    }
-    lq_openloop_instance<T, NX, NP, MU>(la, ptp, sm);
-  } else {
-    lq_feedback_dispatch<T, NX, NP, MU, false>(la, ptp, sm);
-  }
-  __threadfence_block();
-  __syncthreads();
-  // ---- (3) the game's rows of [P | alpha] (and of delta_x) ----
-  copy(g.P, Tn * m * n, [&](int e) {
-    const int k = e / (m * n), f = e - k * (m * n), c = f / m, row = f - c * m;
-    int i = 0;
-    while (i + 1 < g.N && row >= g.uoff[i + 1]) i++;
-    return q[PL.P + size_t(k) * M * NX + (i * MU + row - g.uoff[i]) + M * c];
-  });
-  copy(g.alpha, Tn * m, [&](int e) {
-    const int k = e / m, row = e - k * m;
-    int i = 0;
-    while (i + 1 < g.N && row >= g.uoff[i + 1]) i++;
-    return q[PL.al + size_t(k) * M + i * MU + row - g.uoff[i]];
-  });
-  if (g.dx)
-    copy(g.dx, Tn * n, [&](int e) {
-      const int k = e / n, row = e - k * n;
-      return q[PL.dx + size_t(k) * NX + row];
-    });
-}
-
-template <typename T, int NX, int NP, int MU, bool OL>
-__global__ void __launch_bounds__((PadSweep<T, NX, NP, MU, OL>::NT), (PadSweep<T, NX, NP, MU, OL>::WG_PER_CU))
-padded_lq_kernel(DevProblem p, SolveArgs<T> sa, PadArgs<T> pa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* sm = reinterpret_cast<T*>(smem_raw);
-  using PS = PadSweep<T, NX, NP, MU, OL>;
-  const int b = blockIdx.x;
-  const int Tn = p.T;
-  if (instance_stage<T>(p, sa, b) != ST_LQ) return;
-  const WsLayout L = ws_layout_of(p, sa);
-  T* const w = sa.ws + size_t(b) * sa.ws_stride;
-  SolveState<T>* const st = reinterpret_cast<SolveState<T>*>(w + L.state);
-  const int sacc = __builtin_amdgcn_readfirstlane(st->sacc);
-  PadGame<T> g;
-  g.n = p.n; g.m = p.m; g.N = p.N; g.T_steps = Tn;
-  g.udim = p.udim; g.uoff = p.uoff; g.pt = &p.pairs;
-  g.A = w + L.A; g.Bm = w + L.B; g.Q = w + L.Q; g.l = w + L.l; g.R = w + L.R; g.r = w + L.r;
-  g.x0 = nullptr;
-  g.P = sacc ? sa.P + size_t(b) * Tn * p.m * p.n : w + L.P1;  // strategy buffer 1 - sacc
-  g.alpha = sacc ? sa.alpha + size_t(b) * Tn * p.m : w + L.al1;
-  g.dx = nullptr;
-  g.want_ed = 1;
-  g.adaptive = 1;
-  g.symmetric = 1;  // what the quadraticisation stage writes
-  bool blocks = OL;
-  for (int i = 0; i < p.N; i++) blocks = blocks && p.xoff[i + 1] > p.xoff[i];
-  g.xoff = blocks ? p.xoff : nullptr;
-  padded_sweep_instance<T, NX, NP, MU, OL>(g, pa.ptp, pa.pad + size_t(b) * pa.pad_stride, sm);
-  if (threadIdx.x == 0) {
-    st->expected_decrease = sm[PS::ED_SLOT];
-    st->num_iterations += 1;
-    st->step = sa.forced_steps ? sa.forced_steps[size_t(b) * sa.fixed_iters + (st->num_iterations - 1)]
-                               : T(solver_real_of(p, b, ILQG_SOLVER_INITIAL_ALPHA_SCALING, sa.prm.initial_alpha_scaling));
-    st->bt = 0;
-    st->stage = ST_ROLLOUT;
-  }
-}
-
-// ilqg_lq_feedback_batch / ilqg_lq_openloop_batch for a shape without an instantiation of its own, on the padded sweep.
-template <typename T, int NX, int NP, int MU, bool OL>
-__global__ void __launch_bounds__((PadSweep<T, NX, NP, MU, OL>::NT), (PadSweep<T, NX, NP, MU, OL>::WG_PER_CU))
-padded_lq_batch_kernel(LQBatchArgs<T> a, GenDims d, PairTable pt, PadArgs<T> pa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* sm = reinterpret_cast<T*>(smem_raw);
-  const size_t b = blockIdx.x, Tn = d.T, n = d.n, m = d.m, N = d.N;
-  PadGame<T> g;
-  g.n = d.n; g.m = d.m; g.N = d.N; g.T_steps = d.T;
-  g.udim = d.udim; g.uoff = d.uoff; g.pt = &pt;
-  g.A = a.A + b * Tn * n * n;
-  g.Bm = a.Bm + b * Tn * n * m;
-  g.Q = a.Q + b * Tn * N * n * n;
-  g.l = a.l + b * Tn * N * n;
-  g.R = a.R + b * Tn * pt.Rsz;
-  g.r = a.r + b * Tn * pt.rsz;
-  g.x0 = a.x0 ? a.x0 + b * n : nullptr;
-  g.P = a.P + b * Tn * m * n;
-  g.alpha = a.alpha + b * Tn * m;
-  g.dx = a.dx ? a.dx + b * Tn * n : nullptr;
-  g.want_ed = 0;
-  g.adaptive = OL ? 0 : a.adaptive;
-  g.symmetric = 0;
-  g.xoff = nullptr;
-  padded_sweep_instance<T, NX, NP, MU, OL>(g, pa.ptp, pa.pad + b * pa.pad_stride, sm);
-}
-
-// The sweep of the run-time-dimensioned solve path (lq_part_generic, ilqg_solve.hpp).
-template <typename T>
-__global__ void __launch_bounds__(256) gen_lq_kernel(DevProblem p, SolveArgs<T> sa) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const int b = blockIdx.x;
-  if (instance_stage<T>(p, sa, b) != ST_LQ) return;
-  lq_part_generic<T>(p, sa, b, reinterpret_cast<T*>(smem_raw));
-}
-
-template <typename T>
-__global__ void mfma_selftest_kernel(const T* X, const T* Y, const T* C, T* out) {
-  mfma_selftest<T>(X, Y, C, out);
-}
 
 // The measured-bandwidth denominator of bench.py's roofline ("measure achievable BW on the box with a copy
 // kernel"): every workgroup copies one contiguous 16 KB piece, four 16-byte loads per lane in flight before the first
@@ -793,836 +103,6 @@ __global__ void __launch_bounds__(256) copy_bandwidth_kernel(copy_v4f* __restric
     for (size_t k = i; k < b1; k += 256) dst[k] = src[k];
   }
 }
-
-// ------------------------------------------------------------------------------------
-// Host side
-// ------------------------------------------------------------------------------------
-
-// Large dynamic-LDS launches: ask for the opt-in limit; a refusal is not fatal by itself (the launch
-// reports the real error if the size is unusable), so it must not poison the sticky error state.
-void raise_lds_limit(const void* kern, size_t lds) {
-  if (lds <= 48 * 1024) return;
-  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) (void)hipGetLastError();
-}
-
-// Supported (n, N, m_i) instantiations.  n=14/16/15/24: BASELINE configs 2-5;
-// (4,2,2): config 1 (TwoPlayerUnicycle4D); (2,2,1): test_lq_solver's point mass;
-// (6,3,2): synthetic parity cases.
-#if defined(ILQG_DIMS_HEADER)
-#include ILQG_DIMS_HEADER  // experiment builds: a generated subset of the list below (__graft_entry__.build_hip_library)
-#else
-#define ILQG_FOR_DIMS(X) X(14, 3, 2) X(16, 3, 2) X(15, 3, 2) X(24, 4, 2) X(18, 3, 2) X(12, 2, 2) X(10, 2, 2) X(4, 2, 2) X(6, 2, 1) X(3, 2, 1) X(3, 1, 1) X(2, 2, 1) X(6, 3, 2) X(2, 1, 2) X(8, 2, 2) X(17, 3, 2) X(8, 2, 1)
-#endif
-
-#if !defined(ILQG_PART_NX)
-// The list as a table, one entry per shape with DimsLaunch's members in both precisions (kShapes, below DimsLaunch):
-// the entry of (n, N, m_i), or nullptr where the shape has no instantiation.
-struct ShapeEntry;
-const ShapeEntry* find_shape(int n, int N, int mu);
-#endif
-
-}  // namespace
-
-#include "ilqg_problem.hpp"  // the problem object: its host tables, its device buffers, the handle
-#include "ilqg_instances.hpp"  // per-instance declarations and bindings on it
-#include "ilqg_schedule.hpp"  // how a solve runs: decide_schedule and the per-round choices
-
-// Launchers of the kernels that are instantiated per (n, N, m_i).  Members are defined out of class (not inline),
-// so `extern template struct DimsLaunch<...>` in the main unit of a split build leaves their code — and the
-// kernels behind them — to the unit that instantiates them explicitly.
-template <typename T, int NX, int NP, int MU>
-struct __attribute__((visibility("hidden"))) DimsLaunch {
-  static ilqg_status lq(const ilqg_dims* d, const PairTable& pt, const void* A, const void* Bm, const void* Q,
-                        const void* l, const void* R, const void* r, const void* x0, void* P, void* alpha, void* dx,
-                        hipStream_t stream);
-  static ilqg_status lq_openloop(const ilqg_dims* d, const PairTable& pt, const void* A, const void* Bm,
-                                 const void* Q, const void* l, const void* R, const void* r, const void* x0, void* P,
-                                 void* alpha, void* dx, void* costates, hipStream_t stream);
-  static ilqg_status solve(ilqg_problem* p, int32_t batch, const void* x0, void* xs, void* us, void* P, void* alpha,
-                           void* total_costs, int32_t* iters, int32_t* status, int32_t* converged, void* workspace,
-                           const ilqg_solve_options& opt, hipStream_t stream);
-  // pointers in QuadBatchArgs' order: xs us lambdas mu t_extreme A Bm Q l R r merit_part cost_part active
-  // expr: the problem holds an expression cost (ilqg_problem::has_expression)
-  static ilqg_status rows(const DevProblem& d, int32_t batch, const void* const* ptrs, bool expr, hipStream_t stream);
-  // the sweep of a run-time-dimensioned solve whose game is embedded in this shape (padded_lq_kernel);
-  // pad_elems_out != nullptr: only report the scratch elements one instance needs
-  static ilqg_status lq_padded(const DevProblem& d, const void* solve_args, const PairTable& ptp, void* pad,
-                               size_t* pad_elems_out, bool open_loop, hipStream_t stream);
-  // ilqg_lq_feedback_batch / ilqg_lq_openloop_batch of a game embedded in this shape (padded_lq_batch_kernel): `d`, `pt`
-  // are the game's own dimensions and control blocks, `ptp` its blocks at MU x MU
-  static ilqg_status lq_padded_batch(const ilqg_dims* d, const PairTable& pt, const PairTable& ptp, bool open_loop,
-                                     const void* A, const void* Bm, const void* Q, const void* l, const void* R,
-                                     const void* r, const void* x0, void* P, void* alpha, void* dx, hipStream_t stream);
-};
-
-template <typename T, int NX, int NP, int MU>
-ilqg_status DimsLaunch<T, NX, NP, MU>::rows(const DevProblem& d, int32_t batch, const void* const* q, bool expr,
-                                            hipStream_t stream) {
-  const QuadBatchArgs<T> g{(const T*)q[0], (const T*)q[1], (const T*)q[2], (const T*)q[3], (const int*)q[4], (T*)q[5],
-                           (T*)q[6], (T*)q[7], (T*)q[8], (T*)q[9], (T*)q[10], (T*)q[11], (T*)q[12], (const int*)q[13]};
-  // the widest chunk that leaves a CU three workgroups of this kernel
-  const int cw = rows_chunk_width(d.n, d.m, d.rp_pslots, d.rp_lslots, sizeof(T), size_t(48) * 1024);
-  const size_t lds = rows_maps_bytes(d) + rows_lds_elems(d.n, d.m, d.rp_pslots, d.rp_lslots, cw) * sizeof(T);
-  auto kern = expr ? rows_kernel<T, NX, NP, MU, true> : rows_kernel<T, NX, NP, MU>;
-  // (a problem that holds an expression subsystem: the interpreter that linearises it; such a problem sits in a
-  // plain-RK4 shape or on the run-time-dimensioned path)
-  if constexpr (NX == 0 || dims_use_plain_rk4(NX, NP, MU)) {
-    bool xdyn = false;
-    for (int i = 0; i < d.N; i++) xdyn = xdyn || d.sub_kind[i] == ILQG_DYN_EXPRESSION;
-    if (xdyn) kern = rows_kernel<T, NX, NP, MU, true, true>;
-  }
-  raise_lds_limit((const void*)kern, lds);
-  hipLaunchKernelGGL(kern, dim3((d.T + cw - 1) / cw, batch), dim3(64), lds, stream, d, g, cw);
-  HIP_TRY(hipGetLastError());
-  return ILQG_OK;
-}
-
-template <typename T, int NX, int NP, int MU>
-ilqg_status DimsLaunch<T, NX, NP, MU>::lq(const ilqg_dims* d, const PairTable& pt, const void* A, const void* Bm,
-                                          const void* Q, const void* l, const void* R, const void* r, const void* x0,
-                                          void* P, void* alpha, void* dx, hipStream_t stream) {
-  using C = LQCfg<T, NX, NP, MU>;
-  LQBatchArgs<T> g(d, A, Bm, Q, l, R, r, x0, P, alpha, dx);
-  if (dx) {
-    const size_t need = size_t(d->batch) * d->T * (NP * (NX + 1) + NX) * sizeof(T);
-    ilqg_status s = Scratch().reserve(need);
-    if (s != ILQG_OK) return s;
-    g.scratch = (T*)ilqg_shared::scratch_state().ptr;
-  }
-  // ilqg_dims::sweep_formulation = ILQG_CHOICE_OFF selects the VALU/LDS formulation where the MFMA one is the default
-  const bool valu = C::USE_MFMA && d->sweep_formulation == ILQG_CHOICE_OFF;
-  const bool use_pw = C::USE_MFMA && !valu;
-  const size_t lds = size_t(use_pw ? MfmaSweepLds<T, NX, NP, MU>::ELEMS : C::LDS_ELEMS) * sizeof(T);
-  auto kern = valu ? lq_feedback_kernel<T, NX, NP, MU, true> : lq_feedback_kernel<T, NX, NP, MU, false>;
-  const int nt = valu ? LQFeedbackThreads<T, NX, NP, MU, true>::NT : LQFeedbackThreads<T, NX, NP, MU, false>::NT;
-  raise_lds_limit((const void*)kern, lds);
-  hipLaunchKernelGGL(kern, dim3(d->batch), dim3(nt), lds, stream, g, pt);
-  HIP_TRY(hipGetLastError());
-  return ILQG_OK;
-}
-
-template <typename T, int NX, int NP, int MU>
-ilqg_status DimsLaunch<T, NX, NP, MU>::lq_openloop(const ilqg_dims* d, const PairTable& pt, const void* A,
-                                                   const void* Bm, const void* Q, const void* l, const void* R,
-                                                   const void* r, const void* x0, void* P, void* alpha, void* dx,
-                                                   void* costates, hipStream_t stream) {
-  using O = OLCfg<T, NX, NP, MU>;
-  LQBatchArgs<T> g(d, A, Bm, Q, l, R, r, x0, P, alpha, dx);
-  g.costates = (T*)costates;
-  const size_t need = size_t(d->batch) * d->T * (costates ? O::ROW_FAT : O::ROW) * sizeof(T);
-  ilqg_status s = Scratch().reserve(need);
-  if (s != ILQG_OK) return s;
-  g.scratch = (T*)ilqg_shared::scratch_state().ptr;
-  g.adaptive = 0;
-  const size_t lds = size_t(O::LDS_ELEMS) * sizeof(T);
-  auto kern = lq_openloop_kernel<T, NX, NP, MU>;
-  raise_lds_limit((const void*)kern, lds);
-  hipLaunchKernelGGL(kern, dim3(d->batch), dim3(O::NT), lds, stream, g, pt);
-  HIP_TRY(hipGetLastError());
-  return ILQG_OK;
-}
-
-template <typename T, int NX, int NP, int MU>
-ilqg_status DimsLaunch<T, NX, NP, MU>::lq_padded(const DevProblem& d, const void* solve_args, const PairTable& ptp,
-                                                 void* pad, size_t* pad_elems_out, bool open_loop, hipStream_t stream) {
-  if constexpr (NX == 0) {
-    return fail(ILQG_ERR_UNSUPPORTED, "no shape to embed the game in");
-  } else {
-    auto go = [&](auto ol) -> ilqg_status {
-      constexpr bool OL = decltype(ol)::value;
-      const PadLayout<T, NX, NP, MU, OL> PL(d.T, ptp.Rsz, ptp.rsz);
-      if (pad_elems_out) {
-        *pad_elems_out = PL.total;
-        return ILQG_OK;
-      }
-      const SolveArgs<T>& sa = *static_cast<const SolveArgs<T>*>(solve_args);
-      PadArgs<T> pa{(T*)pad, PL.total, ptp};
-      using PS = PadSweep<T, NX, NP, MU, OL>;
-      auto kern = padded_lq_kernel<T, NX, NP, MU, OL>;
-      const size_t lds = PS::LDS_ELEMS * sizeof(T);
-      raise_lds_limit((const void*)kern, lds);
-      hipLaunchKernelGGL(kern, dim3(sa.batch), dim3(PS::NT), lds, stream, d, sa, pa);
-      HIP_TRY(hipGetLastError());
-      return ILQG_OK;
-    };
-    return open_loop ? go(std::true_type{}) : go(std::false_type{});
-  }
-}
-
-template <typename T, int NX, int NP, int MU>
-ilqg_status DimsLaunch<T, NX, NP, MU>::lq_padded_batch(const ilqg_dims* d, const PairTable& pt, const PairTable& ptp,
-                                                       bool open_loop, const void* A, const void* Bm, const void* Q,
-                                                       const void* l, const void* R, const void* r, const void* x0,
-                                                       void* P, void* alpha, void* dx, hipStream_t stream) {
-  if constexpr (NX == 0) {
-    return fail(ILQG_ERR_UNSUPPORTED, "no shape to embed the game in");
-  } else {
-    auto go = [&](auto ol) -> ilqg_status {
-      constexpr bool OL = decltype(ol)::value;
-      const PadLayout<T, NX, NP, MU, OL> PL(d->T, ptp.Rsz, ptp.rsz);
-      const ilqg_status s = Scratch().reserve(size_t(d->batch) * PL.total * sizeof(T));
-      if (s != ILQG_OK) return s;
-      const GenDims gd = gen_dims_of(d->n, d->num_players, d->udim, d->T);
-      const LQBatchArgs<T> g(d, A, Bm, Q, l, R, r, x0, P, alpha, dx);
-      PadArgs<T> pa{(T*)ilqg_shared::scratch_state().ptr, PL.total, ptp};
-      using PS = PadSweep<T, NX, NP, MU, OL>;
-      auto kern = padded_lq_batch_kernel<T, NX, NP, MU, OL>;
-      const size_t lds = PS::LDS_ELEMS * sizeof(T);
-      raise_lds_limit((const void*)kern, lds);
-      hipLaunchKernelGGL(kern, dim3(d->batch), dim3(PS::NT), lds, stream, g, gd, pt, pa);
-      HIP_TRY(hipGetLastError());
-      return ILQG_OK;
-    };
-    return open_loop ? go(std::true_type{}) : go(std::false_type{});
-  }
-}
-
-namespace {
-
-ilqg_status check_device() {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    return fail(ILQG_ERR_NO_DEVICE, "no HIP device visible: libilqg_hip.so has no CPU fallback");
-  return ILQG_OK;
-}
-
-}  // namespace
-
-// The round counters' way back to the host.  A counted solve reads them once per round (twice with the augmented
-// Lagrangian's restarts), and while it does the device idles: what a read-back costs is the gap between two rounds.
-// A copy command plus a stream synchronisation is ~20 us of that; instead a one-wave kernel behind the round's last
-// launch stores the four counters and then a sequence number into host memory (pinned, coherent, mapped), and the
-// host spins on the sequence number; a device fault shows up in the periodic hipStreamQuery.  Where the pinned mirror
-// has no device address (hipHostGetDevicePointer failed) the counters come back by the copy + synchronise form.
-namespace {
-__global__ void ilq_publish_kernel(int* counts, int* host, int seq) {
-  const int t = threadIdx.x;
-  if (t < 4) {
-    __hip_atomic_store(host + t, counts[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    counts[t] = 0;  // ... and the next round finds them cleared (ilqg_problem::counters_clean): one fill command less
-  }
-  __threadfence_system();
-  if (t == 0) __hip_atomic_store(host + 8, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// How many instances of a masked batch take part (ilqg_solve_options::active): into the fourth round counter.
-__global__ void ilq_count_active_kernel(const int* active, int batch, int* counts) {
-  int mine = 0;
-  for (int b = threadIdx.x; b < batch; b += blockDim.x) mine += active[b] != 0;
-  for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
-  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(counts + 3, mine);
-}
-
-inline ilqg_status read_round_counters(ilqg_problem* p, hipStream_t stream) {
-  p->counters_clean = false;
-  if (!p->h_unfinished_dev) {
-    HIP_TRY(hipMemcpyAsync(p->h_unfinished.get(), p->d_unfinished.get(), 4 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return ILQG_OK;
-  }
-  const int seq = ++p->publish_seq;
-  hipLaunchKernelGGL(ilq_publish_kernel, dim3(1), dim3(64), 0, stream, p->d_unfinished.get(), p->h_unfinished_dev, seq);
-  HIP_TRY(hipGetLastError());
-  p->counters_clean = true;
-  volatile int* const flag = p->h_unfinished.get() + 8;
-  for (long long spins = 0;; spins++) {
-    if (__atomic_load_n(const_cast<int*>(flag), __ATOMIC_ACQUIRE) == seq) return ILQG_OK;
-    __builtin_ia32_pause();
-    if ((spins & 0xffff) == 0xffff) {  // every ~65 k polls: has the stream died, or drained without our store?
-      const hipError_t q = hipStreamQuery(stream);
-      if (q == hipSuccess) {
-        if (__atomic_load_n(const_cast<int*>(flag), __ATOMIC_ACQUIRE) == seq) return ILQG_OK;
-        return fail(ILQG_ERR_HIP, "the round counters never reached the host");
-      }
-      if (q != hipErrorNotReady) return fail(ILQG_ERR_HIP, std::string("hipStreamQuery: ") + hipGetErrorString(q));
-    }
-  }
-}
-}  // namespace
-
-// The outer loop's clock of AugmentedLagrangianSolver::Solve under a max_runtime (src/augmented_lagrangian_solver.cpp:
-// 104-110,193): `elapsed` starts at the first inner solve's ALLOWANCE (max_runtime / max_solver_iters, not the time it
-// took), every outer iteration adds its wall time, and another one starts only while
-// elapsed < max_runtime - timer_.RuntimeUpperBound().  A batch shares the clock.  It runs without a gap from the first
-// exit launch that restarted an instance until the solve returns — whoever is restarted or not at the launches in
-// between (round 5 re-armed it only when a launch restarted somebody: with staggered instances whole inner solves went
-// uncounted).  The LoopTimer's samples are outer-iteration durations: every restart-bearing exit launch opens an
-// interval, and each later exit launch (one exists only when some inner solve has ended) closes the oldest open one —
-// exact for a batch in lockstep, the inner-solve length of the earliest group when instances are staggered; never the
-// gap between two neighbouring rounds.  before_exit() is called in front of every exit launch and says whether instances
-// whose inner solve has ended may still restart.
-struct AlOuterClock {
-  ilqg_problem* p;
-  bool on;
-  double max_runtime, elapsed, last = 0.0;
-  bool running = false;
-  static constexpr int kOpen = 32;
-  double open_since[kOpen];
-  int open_head = 0, open_count = 0;
-  AlOuterClock(ilqg_problem* p_, bool on_, double max_runtime_, double first_allowance)
-      : p(p_), on(on_), max_runtime(max_runtime_), elapsed(first_allowance) {}
-  static double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-  bool before_exit() {  // true: the outer loop is closed
-    if (!on) return false;
-    const double now = wall();
-    if (running) {
-      elapsed += now - last;
-      last = now;
-      if (open_count > 0) {
-        p->al_loop_timer.add(now - open_since[open_head]);
-        open_head = (open_head + 1) % kOpen;
-        open_count--;
-      }
-    }
-    return !(elapsed < max_runtime - p->al_loop_timer.upper_bound());
-  }
-  void after_exit(int restarted) {
-    if (!on || !restarted) return;
-    const double now = wall();
-    if (!running) {
-      running = true;
-      last = now;
-    }
-    if (open_count < kOpen) {
-      open_since[(open_head + open_count) % kOpen] = now;
-      open_count++;
-    }
-  }
-};
-
-// ---------------------------------------------------------------------------------------------------------------
-// The round protocol both solve drivers share (DimsLaunch::solve on the specialised kernels, generic_solve on the
-// run-time-dimensioned ones).  Each driver fills a RoundPlan and run_rounds launches it; what differs between the two
-// is a value of the plan, never a question of who is calling.
-// ---------------------------------------------------------------------------------------------------------------
-namespace {
-
-// The anytime exit of one inner solve (ilqg_solve_options::max_runtime): the loop condition of src/ilq_solver.cpp:
-// 123-124, read where the batch is about to start an iteration, so timed solves do not batch rounds into bursts.  The
-// augmented-Lagrangian solver gives each inner solve of a constrained problem max_runtime / max_solver_iters
-// (src/augmented_lagrangian_solver.cpp:85-88), which is also where its AlOuterClock starts.
-struct InnerClock {
-  ilqg_problem* p;
-  bool on;
-  double budget, elapsed = 0.0, tic = 0.0;
-  bool iteration_open = false;
-  InnerClock(ilqg_problem* p_, bool on_, double max_runtime, bool al_constrained)
-      : p(p_), on(on_),
-        budget(!on_ ? 0.0 : al_constrained ? max_runtime / double(p_->desc.params.max_solver_iters) : max_runtime) {}
-  bool deadline_passed() {  // in front of an iteration: the one in flight ends here; true: the next may not start
-    const double now = AlOuterClock::wall();
-    if (iteration_open) {
-      p->loop_timer.add(now - tic);
-      elapsed += now - tic;
-      iteration_open = false;
-    }
-    return !(elapsed < budget - p->loop_timer.upper_bound());
-  }
-  void open_iteration() {
-    if (!on) return;
-    tic = AlOuterClock::wall();
-    iteration_open = true;
-  }
-  void restart() { elapsed = 0.0; }  // an augmented-Lagrangian restart: the next inner solve's own budget
-};
-
-ilqg_status iteration_bound(long long round, long long cap) {
-  return round > cap ? fail(ILQG_ERR_HIP, "solve did not terminate within its iteration bound") : ILQG_OK;
-}
-
-// What follows the per-instance blocks of a solve's workspace (ws_tail), as pointers.
-template <typename T>
-struct SolveTail {
-  int* pass_ids;    // [2][batch]: this round's back-tracking instances, the next round's
-  T* probe_pool;    // the speculative line search's candidates
-  int pool_entries;
-};
-
-// The SolveArgs fields every solve fills alike; the schedule's own ones (prof, rows_cw, compact, ...) are the driver's.
-template <typename T>
-SolveArgs<T> solve_args_of(const ilqg_problem* p, int32_t batch, const void* x0, void* xs, void* us, void* P,
-                           void* alpha, void* total_costs, int32_t* iters, int32_t* status, int32_t* converged,
-                           void* workspace, const ilqg_solve_options& opt, SolveTail<T>* tail) {
-  const DevProblem& d = p->dev;
-  SolveArgs<T> sa{};
-  sa.ol_row = p->desc.params.open_loop ? ol_row_elems(d.n, d.m, d.N) : 0;
-  sa.al_mode = opt.augmented_lagrangian ? 1 : 0;
-  sa.x0 = (const T*)x0; sa.xs = (T*)xs; sa.us = (T*)us; sa.P = (T*)P; sa.alpha = (T*)alpha;
-  sa.total_costs = (T*)total_costs; sa.iters = iters; sa.status = status; sa.converged = converged;
-  sa.ws = (T*)workspace;
-  sa.ws_stride = ws_layout_of(d, sa.ol_row, sa.al_mode).total;
-  sa.fixed_iters = opt.fixed_iters;
-  sa.batch = batch;
-  sa.prm = p->desc.params;
-  sa.active = opt.active;
-  sa.forced_steps = (const T*)opt.forced_steps;
-  sa.unfinished = p->d_unfinished.get();
-  sa.first = opt.resume ? 2 : 1;
-  const WsTail t = ws_tail(d, batch, sizeof(T), sa.ol_row);
-  tail->pass_ids = reinterpret_cast<int*>(static_cast<char*>(workspace) + t.ids_off);
-  tail->probe_pool = reinterpret_cast<T*>(static_cast<char*>(workspace) + t.pool_off);
-  tail->pool_entries = t.pool_entries;
-  return sa;
-}
-
-// The iterate log (ilqg_solve_options::iterate_log): checked and its counts cleared where the solve begins ...
-template <typename T>
-ilqg_status iterate_log_open(const ilqg_solve_options& opt, int32_t batch, hipStream_t stream, IterLog<T>* lg) {
-  *lg = IterLog<T>{};
-  if (!opt.iterate_log) return ILQG_OK;
-  const ilqg_iterate_log& il = *opt.iterate_log;
-  if (!il.xs || !il.us || !il.costs || !il.count || il.capacity < 1)
-    return fail(ILQG_ERR_INVALID, "iterate log: xs, us, costs, count and a capacity of at least one are required");
-  *lg = IterLog<T>{(T*)il.xs, (T*)il.us, (T*)il.costs, (T*)il.P, (T*)il.alpha, il.count, il.capacity};
-  HIP_TRY(hipMemsetAsync(il.count, 0, sizeof(int) * size_t(batch), stream));
-  return ILQG_OK;
-}
-
-// ... and copied in front of every exit / sweep launch
-template <typename T>
-ilqg_status iterate_log_launch(const ilqg_problem* p, const SolveArgs<T>& sa, const IterLog<T>& lg, hipStream_t stream) {
-  if (!lg.count) return ILQG_OK;
-  hipLaunchKernelGGL(ilq_log_kernel<T>, dim3(sa.batch), dim3(256), 0, stream, p->dev, sa, lg);
-  HIP_TRY(hipGetLastError());
-  return ILQG_OK;
-}
-
-// Split passes: the decision kernel lists the instances that want another pass (the initial quadraticisation,
-// back-tracking), and the next round covers those only — a tail of rounds that lasts until the last of them has made up
-// its mind.  The sweeps and exits the batch asks for wait until then: the sweep is launched once per iteration, which
-// keeps the batch in step (a sweep launch with a handful of instances costs a full sweep's latency).
-template <typename T>
-struct RoundLists {
-  SolveArgs<T>& sa;             // sa.ids: the instances of this round (null: the whole batch)
-  int* const pass_ids;          // the two lists (SolveTail)
-  const long long cap;          // the driver's iteration bound in rounds
-  int round_instances;          // how many instances this round covers
-  int list = 0;                 // which list is free for the round to write
-  int tail_rounds = 0;          // rounds since the whole batch was last in one
-  int tail_first_instances = 0;  // instances in the current tail's first round
-  bool probed_in_tail = false;  // the current tail has launched a probing pass
-  int waiting_lq = 0, waiting_exit = 0;  // instances already through this iteration's line search
-  RoundLists(SolveArgs<T>& sa_, int* pass_ids_, long long cap_)
-      : sa(sa_), pass_ids(pass_ids_), cap(cap_), round_instances(sa_.batch) {}
-  int* free_list() const { return pass_ids + size_t(list) * sa.batch; }
-  // a round over listed instances that probes probe_k step sizes of each (fewer than two: no probing launch)
-  ilqg_status tail_round(bool probe, int probe_k) {
-    tail_rounds++;
-    if (!probe) return ILQG_OK;
-    // an instance every candidate of which was rejected waits in ST_PROBE and is skipped by the regular pass: it is
-    // only picked up again by the next probing launch, so a tail that has probed must keep probing (the list only
-    // shrinks and the ramp only grows, so this cannot trigger; if it ever does, fail instead of dropping instances)
-    if (probed_in_tail && probe_k < 2) return fail(ILQG_ERR_HIP, "a probing line-search tail lost its probe launch");
-    if (probe_k >= 2) probed_in_tail = true;
-    return ILQG_OK;
-  }
-  // The round's counters are back.  *again: the instances it listed go round again, by themselves; otherwise the batch
-  // is whole again and *want_lq / *want_exit are what its iteration asks for.
-  ilqg_status after_round(const int* counters, long long round, bool* again, int* want_lq, int* want_exit) {
-    waiting_lq += counters[0];
-    waiting_exit += counters[1];
-    *again = counters[3] != 0;
-    if (*again) {
-      const ilqg_status s = iteration_bound(round, cap);
-      if (s != ILQG_OK) return s;
-      if (!sa.ids) tail_first_instances = counters[3];
-      sa.ids = sa.ids_next;
-      round_instances = counters[3];
-      list ^= 1;
-      return ILQG_OK;
-    }
-    sa.ids = nullptr;
-    round_instances = sa.batch;
-    tail_rounds = 0;
-    probed_in_tail = false;
-    *want_lq = waiting_lq;
-    *want_exit = waiting_exit;
-    waiting_lq = waiting_exit = 0;
-    return ILQG_OK;
-  }
-};
-
-// One kernel of a round as a driver chose it; the grid is the round's.
-template <typename T>
-struct KernelLaunch {
-  void (*kernel)(DevProblem, SolveArgs<T>) = nullptr;  // null: the solve has no such launch
-  int threads = 64;
-  size_t lds = 0;
-};
-
-// The sweep of a run-time-dimensioned solve on the padded kernels of an instantiated shape (DimsLaunch::lq_padded).
-using PaddedSweep = ilqg_status (*)(const DevProblem&, const void*, const PairTable&, void*, size_t*, bool, hipStream_t);
-
-// What a solve launches and how its rounds go, as its driver chose them: run_rounds reads nothing else about the
-// schedule.  The split-pass launches (roll to prows) exist where `lists` holds.
-template <typename T>
-struct RoundPlan {
-  KernelLaunch<T> trial;                // the fused pass
-  KernelLaunch<T> roll, rows, decide;   // the split pass
-  KernelLaunch<T> proll, proll_fat, proll_single, proll_lanes, prows;  // probing rollouts (null: no such form), their rows
-  KernelLaunch<T> sweep, exit;          // (the sweep: unless `padded` runs it)
-  PaddedSweep padded = nullptr;
-  const PairTable* pad_pairs = nullptr; void* pad = nullptr;  // the padded sweep's control blocks and scratch
-  SolveSchedule s{};                    // the rounds' flags, cap, row_chunks, lane_width, num_cus (ilqg_schedule.hpp)
-  bool exit_fill_first = false;  // clear the round counters in front of the exit launch where they are not clean
-};
-
-// LDS limits of every launch of a plan (raise_lds_limit; the padded sweep raises its own)
-template <typename T>
-void raise_lds_limits(const RoundPlan<T>& pl) {
-  for (const KernelLaunch<T>* k : {&pl.trial, &pl.roll, &pl.rows, &pl.decide, &pl.proll, &pl.proll_fat, &pl.proll_single,
-                                   &pl.proll_lanes, &pl.prows, &pl.sweep, &pl.exit})
-    if (k->kernel) raise_lds_limit((const void*)k->kernel, k->lds);
-}
-
-// The rounds of a solve, on either driver's plan.  One round = a pass (the fused trial kernel, or the split kernels over
-// the whole batch or over the listed back-tracking instances with their probing launches), then, for the instances
-// that asked, the exit kernel and the sweep.  The kernels count what their instances wait for; with fixed_iters = K
-// (no AL) and no counting the sequence is known — trial, K x (sweep, trial), exit — otherwise the host reads the counts
-// back each round, which makes a free-running solve synchronous with respect to `stream`.
-template <typename T>
-ilqg_status run_rounds(ilqg_problem* p, SolveArgs<T>& sa, const SolveTail<T>& tail, const RoundPlan<T>& plan,
-                       const ilqg_solve_options& opt, hipStream_t stream) {
-  const DevProblem& d = p->dev;
-  const int batch = sa.batch;
-  const SolveSchedule& sc = plan.s;
-  raise_lds_limits(plan);
-  IterLog<T> lg;
-  ilqg_status s = iterate_log_open(opt, batch, stream, &lg);
-  if (s != ILQG_OK) return s;
-  const bool al_constrained = sa.al_mode && d.num_constraints > 0;
-  InnerClock clock(p, sc.timed, opt.max_runtime, al_constrained);
-  AlOuterClock outer(p, sc.timed && al_constrained, opt.max_runtime, clock.budget);
-  p->counters_clean = false;  // whatever an earlier solve left in the round counters
-  RoundLists<T> rl(sa, tail.pass_ids, sc.cap);
-  auto launch = [&](const KernelLaunch<T>& k, dim3 grid) -> ilqg_status {
-    hipLaunchKernelGGL(k.kernel, grid, dim3(k.threads), k.lds, stream, d, sa);
-    HIP_TRY(hipGetLastError());
-    return ILQG_OK;
-  };
-  auto sweep = [&]() -> ilqg_status {
-    const ilqg_status s = plan.padded ? plan.padded(d, &sa, *plan.pad_pairs, plan.pad, nullptr, p->desc.params.open_loop != 0, stream)
-                                      : launch(plan.sweep, dim3(batch));
-    if (s == ILQG_OK && sa.clear_counters) p->counters_clean = true;  // (SolveArgs::clear_counters)
-    return s;
-  };
-  bool deep_tails = false;  // a tail of this solve kept half of its list through three rounds (round_probe_candidates)
-  // the listed instances' next step sizes side by side; their states move to the first acceptable one
-  auto probe_round = [&](int instances, int probe_k) -> ilqg_status {
-    sa.probe_pool = tail.probe_pool;
-    sa.probe_k = probe_k;
-    const int C = sc.lane_width, proll_y = probe_pair_rows(sc, probe_k);
-    const ProbeForm form = probe_form(sc, opt, instances, probe_k);
-    const ilqg_status s = form == PROBE_LANES    ? launch(plan.proll_lanes, dim3(instances, (probe_k + C - 1) / C))
-                          : form == PROBE_SINGLE ? launch(plan.proll_single, dim3(instances, probe_k))
-                                                 : launch(form == PROBE_FAT ? plan.proll_fat : plan.proll, dim3(instances, proll_y));
-    if (s != ILQG_OK || launch(plan.prows, dim3(sc.row_chunks, instances * probe_k)) != ILQG_OK) return ILQG_ERR_HIP;
-    return launch(KernelLaunch<T>{ilq_probe_pick_kernel<T>, kProbeCandidates, 0}, dim3(instances));
-  };
-  auto pass = [&]() -> ilqg_status {
-    if (sc.counted && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished.get(), 0, 4 * sizeof(int), stream));
-    p->counters_clean = false;  // (the round's kernels count into them)
-    if (!sc.split && !sa.ids) {
-      sa.ids_next = sc.handoff ? rl.free_list() : nullptr;
-      const ilqg_status s = launch(plan.trial, dim3(batch));
-      sa.first = 0;
-      return s;
-    }
-    sa.ids_next = rl.free_list();
-    const int instances = rl.round_instances;
-    if (sa.ids) {
-      const int probe_k = round_probe_candidates(sc, opt, tail.pool_entries, instances, rl.tail_rounds, rl.tail_first_instances, &deep_tails);
-      ilqg_status s = rl.tail_round(sc.probe, probe_k);
-      if (s == ILQG_OK && sc.probe && probe_k >= 2) s = probe_round(instances, probe_k);
-      if (s != ILQG_OK) return s;
-    }
-    sa.round_count = instances;
-    if (launch(plan.roll, dim3(sc.pairs ? (instances + 1) / 2 : instances)) != ILQG_OK) return ILQG_ERR_HIP;
-    sa.first = 0;
-    if (launch(plan.rows, dim3(sc.row_chunks, instances)) != ILQG_OK) return ILQG_ERR_HIP;
-    return launch(plan.decide, dim3(instances));
-  };
-  // Free-running solves: the kernels select their instances by the stage each one is in, so a round launched for
-  // nobody is harmless — the host therefore enqueues BURSTS of whole rounds (trial, exit, sweep) and reads the
-  // counters back once per burst instead of once per round (a read-back is a stream synchronisation: ~20-30 us against
-  // a ~0.45 ms round of a single instance).  The burst doubles up to eight rounds while no instance is back-tracking
-  // and falls back to one as soon as one is (those go through the probing passes, which need the lists every round).
-  const bool fixed = opt.fixed_iters > 0 && !sa.al_mode;
-  int burst = 1;
-  bool exit_pending = false;  // a burst round went without its exit launch (see the burst loop)
-  for (long long round = 0;; round++) {
-    if (sc.bursts && !sa.ids) {
-      // a fixed-iteration solve knows its last round: no burst runs past it
-      const long long left = fixed ? (long long)opt.fixed_iters - round : (long long)burst;
-      for (int q = 1; q < burst && q <= left; q++) {  // rounds without a read-back
-        s = pass();
-        if (s != ILQG_OK) return s;
-        if (iterate_log_launch(p, sa, lg, stream) != ILQG_OK) return ILQG_ERR_HIP;
-        // The exit path inside a burst only where it starts something (the augmented Lagrangian's next inner solve);
-        // an ILQSolver::Solve that ends here waits for the burst's last round, whose exit launch is then unconditional
-        // (a launch for nobody is ~5 us of every round of a lone instance).
-        if (sa.al_mode) {
-          if (launch(plan.exit, dim3(batch)) != ILQG_OK) return ILQG_ERR_HIP;
-        } else {
-          exit_pending = true;
-        }
-        s = sweep();
-        if (s != ILQG_OK) return s;
-        round++;
-      }
-    }
-    s = pass();
-    if (s != ILQG_OK) return s;
-    int want_lq = 1, want_exit = 0;
-    if (sc.counted) {
-      if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
-      want_lq = p->h_unfinished[0];
-      want_exit = p->h_unfinished[1];
-      if (sc.lists) {
-        bool again = false;
-        s = rl.after_round(p->h_unfinished.get(), round, &again, &want_lq, &want_exit);
-        if (s != ILQG_OK) return s;
-        if (again) {
-          burst = 1;
-          continue;
-        }
-      }
-      if (sc.bursts) burst = p->h_unfinished[3] ? 1 : (burst < 8 ? burst * 2 : 8);
-    } else if (round == opt.fixed_iters) {
-      want_lq = 0;
-      want_exit = 1;
-    }
-    if (exit_pending) {  // instances that ended in a burst round without an exit launch
-      want_exit = 1;
-      exit_pending = false;
-    }
-    // The end of an iteration of the batch: want_lq instances wait for a sweep and want_exit for the exit path.  The
-    // anytime exit's deadline (which turns the sweep into an exit), the iterate log, the exit launch and the restarts it
-    // made, the sweep.
-    if (clock.on && want_lq && clock.deadline_passed()) {
-      hipLaunchKernelGGL(ilq_deadline_kernel<T>, dim3(batch), dim3(64), 0, stream, d, sa);
-      HIP_TRY(hipGetLastError());
-      want_exit = 1;
-      want_lq = 0;
-    }
-    if ((want_exit || want_lq) && iterate_log_launch(p, sa, lg, stream) != ILQG_OK) return ILQG_ERR_HIP;
-    int restarted = 0;
-    if (want_exit) {
-      if (plan.exit_fill_first && !p->counters_clean) HIP_TRY(hipMemsetAsync(p->d_unfinished.get(), 0, 4 * sizeof(int), stream));
-      if (outer.before_exit()) sa.outer_closed = 1;  // out of time: inner solves that end now are the last ones
-      if (launch(plan.exit, dim3(batch)) != ILQG_OK) return ILQG_ERR_HIP;
-      p->counters_clean = false;
-      if (sc.read_restarts) {
-        if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
-        restarted = p->h_unfinished[2];
-        if (restarted) clock.restart();
-        outer.after_exit(restarted);
-      }
-    }
-    if (want_lq) {
-      clock.open_iteration();
-      s = sweep();
-      if (s != ILQG_OK) return s;
-    }
-    if (!want_lq && !restarted) return ILQG_OK;  // the solve has ended
-    if (iteration_bound(round, sc.cap) != ILQG_OK) return ILQG_ERR_HIP;
-  }
-}
-
-}  // namespace
-
-#define DT_DISPATCH(p, CALL) ((p)->desc.dtype == ILQG_F32 ? CALL(float) : CALL(double))
-
-// The compile-time facts of an instantiation the schedule's policy reads (ShapeTraits, ilqg_schedule.hpp)
-template <typename T, int NX, int NP, int MU>
-constexpr ShapeTraits shape_traits() {
-  using C = LQCfg<T, NX, NP, MU>;
-  using O = OLCfg<T, NX, NP, MU>;
-  using W1 = W1Cfg<T, NX, NP, MU>;
-  static_assert(O::ROW == ol_row_elems(NX, NP * MU, NP) && O::ROW_FAT == ol_row_elems(NX, NP * MU, NP, true), "ol_row_elems");
-  ShapeTraits t{};
-  t.nx = NX; t.np = NP; t.mu = MU; t.elem = int(sizeof(T));
-  t.trial_waves = TrialWaves<T>::W;
-  t.use_mfma = C::USE_MFMA;
-  t.one_tile = C::MFMA_ONE_TILE;
-  t.has_1w = W1::SUPPORTED && C::USE_MFMA && C::MFMA_ONE_TILE;
-  t.has_packed = sizeof(T) == 4 && C::USE_MFMA && C::MFMA_ONE_TILE && NP == 3;
-  if constexpr (C::USE_MFMA) {
-    t.has_forms = C::MFMA_ONE_TILE && SolveRows<NP * MU, NX + 1>::FITS;
-    t.has_bconst = t.has_forms && NX < 16 && MU == 2;
-    t.pw_lds_elems = MfmaSweepLds<T, NX, NP, MU>::ELEMS + (C::MFMA_ONE_TILE ? 0 : 4);
-  }
-  if constexpr (W1::SUPPORTED && C::USE_MFMA && C::MFMA_ONE_TILE) t.w1_lds_elems = W1::ELEMS;
-  t.w1_words = W1::kWords;
-  t.ol_threads = O::NT; t.ol_lds_elems = O::LDS_ELEMS;
-  t.valu_threads = C::NT; t.valu_lds_elems = C::LDS_ELEMS;
-  t.fwd_elems = 4 * 2 * ((NX * NX + C::SCR + 3) & ~3) + 2 * NX + 8;
-  t.pairs = rollout_pairs(NX, NP, MU);
-  t.may_xdyn = dims_use_plain_rk4(NX, NP, MU);
-  t.rows_in_regs = rows_state_in_registers(NX, NP * MU);
-  t.partials_room = fused_partials_room(int(sizeof(T)), NX, NP, MU);
-  t.lane_width = rollout_lanes_per_wave(NP > 0 ? NP : 1);
-#define X(ID_, NX_, NP_, MU_)                                                             \
-  if constexpr (NX_ == NX && NP_ == NP && MU_ == MU) {                                   \
-    t.static_ids[t.num_static] = ID_;                                                     \
-    t.static_in_regs[t.num_static++] = static_prog_in_registers<StaticRowProg<ID_>>();    \
-  }
-  ILQG_STATIC_PROGS(X)
-#undef X
-  return t;
-}
-
-inline ProblemFacts problem_facts(const ilqg_problem* p) {
-  return {p->desc.params, p->static_prog, p->b_constant, p->has_expression, p->has_expression_dynamics, p->bindings.any(),
-          p->dev.inst_solver != 0};
-}
-
-// The one place a row program's (kind, bound, static id) picks an instantiation: f(PROGID, BOUND) as integral constants,
-// for the fused trial kernel, the split row kernel and the probing row kernel of a shape (NX = 0: the run-time-dimensioned
-// kernels).  A registered structure goes before the expression kinds (it holds none); a problem with per-instance tables
-// bound runs twins of its own where the kernel has one (ilqg_solve.hpp).
-template <typename R, int NX, int NP, int MU, typename F>
-R for_row_program(int prog_kind, int static_id, bool bound, F f) {
-  using Bound = std::true_type;
-  using Unbound = std::false_type;
-#define X(ID_, NX_, NP_, MU_)                                  \
-  if constexpr (NX_ == NX && NP_ == NP && MU_ == MU)           \
-    if (static_id == ID_)                                      \
-      return bound ? f(std::integral_constant<int, kBoundProg + ID_>{}, Bound{}) : f(std::integral_constant<int, ID_>{}, Unbound{});
-  ILQG_STATIC_PROGS(X)
-#undef X
-  if constexpr (NX == 0 || dims_use_plain_rk4(NX, NP, MU))
-    if (prog_kind == PROG_EXPR_DYN)
-      return bound ? f(std::integral_constant<int, kExprDynProg>{}, Bound{}) : f(std::integral_constant<int, kExprDynProg>{}, Unbound{});
-  if (prog_kind == PROG_EXPR)
-    return bound ? f(std::integral_constant<int, kExprProg>{}, Bound{}) : f(std::integral_constant<int, kExprProg>{}, Unbound{});
-  return bound ? f(std::integral_constant<int, 0>{}, Bound{}) : f(std::integral_constant<int, 0>{}, Unbound{});
-}
-template <typename T>
-using SolveKernel = void (*)(DevProblem, SolveArgs<T>);
-template <typename T, int NX, int NP, int MU>
-SolveKernel<T> rows_kernel_of(int prog_kind, int static_id, bool bound) {
-  return for_row_program<SolveKernel<T>, NX, NP, MU>(prog_kind, static_id, bound, [](auto id, auto) {
-    return SolveKernel<T>(ilq_rows_kernel<T, NX, NP, MU, decltype(id)::value>);
-  });
-}
-template <typename T, int NX, int NP, int MU>
-SolveKernel<T> probe_rows_kernel_of(int prog_kind, int static_id, bool bound) {
-  return for_row_program<SolveKernel<T>, NX, NP, MU>(prog_kind, static_id, bound, [](auto id, auto) {
-    return SolveKernel<T>(ilq_probe_rows_kernel<T, NX, NP, MU, decltype(id)::value>);
-  });
-}
-
-// The sweep instantiation of (sweep_kind, sweep_forms)
-template <typename T, int NX, int NP, int MU>
-SolveKernel<T> sweep_kernel_of(const SolveSchedule& s) {
-  static constexpr ShapeTraits st = shape_traits<T, NX, NP, MU>();
-  if (s.sweep_kind == LQ_OPEN_LOOP_COMPACT) return ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP_COMPACT>;
-  if (s.sweep_kind == LQ_OPEN_LOOP) return ilq_lq_kernel<T, NX, NP, MU, LQ_OPEN_LOOP>;
-  if constexpr (!st.use_mfma) {
-    return ilq_lq_kernel<T, NX, NP, MU, LQ_VALU_FEEDBACK>;
-  } else {
-    auto forms_of = [&](auto kind) -> SolveKernel<T> {
-      constexpr int KIND = decltype(kind)::value;
-      if constexpr (st.has_bconst && KIND != LQ_SINGLE_WAVE)
-        if (s.sweep_forms == 2) return ilq_lq_kernel<T, NX, NP, MU, KIND, 2>;
-      if constexpr (st.has_forms)
-        if (s.sweep_forms == 0) return ilq_lq_kernel<T, NX, NP, MU, KIND, 0>;
-      return ilq_lq_kernel<T, NX, NP, MU, KIND>;
-    };
-    if constexpr (st.has_1w)
-      if (s.sweep_kind == LQ_SINGLE_WAVE) return forms_of(std::integral_constant<int, LQ_SINGLE_WAVE>{});
-    if constexpr (st.has_packed)
-      if (s.sweep_kind == LQ_PLAYER_WAVES_PACKED) return forms_of(std::integral_constant<int, LQ_PLAYER_WAVES_PACKED>{});
-    return forms_of(std::integral_constant<int, LQ_PLAYER_WAVES>{});
-  }
-}
-
-// A schedule's decisions as kernel addresses: nothing is decided here.
-template <typename T, int NX, int NP, int MU>
-RoundPlan<T> bind_plan(const SolveSchedule& s) {
-  constexpr int W = TrialWaves<T>::W;
-  constexpr bool kMayXdyn = dims_use_plain_rk4(NX, NP, MU);
-  RoundPlan<T> plan;
-  plan.s = s;
-  plan.trial = {for_row_program<SolveKernel<T>, NX, NP, MU>(s.prog_kind, s.static_prog, s.bound != 0, [](auto id, auto bound) {
-                  return SolveKernel<T>(ilq_trial_kernel<T, NX, NP, MU, W, decltype(id)::value, decltype(bound)::value>);
-                }), 64 * W, size_t(s.lds_trial)};
-  plan.sweep = {sweep_kernel_of<T, NX, NP, MU>(s), s.sweep_threads, size_t(s.lds_sweep)};
-  plan.exit = {ilq_exit_kernel<T, NX, NP, MU>, s.nt_exit, size_t(s.lds_exit)};
-  if (!s.lists) return plan;
-  plan.roll = {ilq_roll_kernel<T, NX, NP, MU>, 64, size_t(s.lds_roll)};
-  plan.rows = {rows_kernel_of<T, NX, NP, MU>(s.prog_kind, s.static_id, s.bound != 0), 64, size_t(s.lds_rows)};
-  plan.decide = {s.decide_solver ? ilq_decide_kernel<T, NX, NP, MU, true> : ilq_decide_kernel<T, NX, NP, MU, false>, 64, size_t(s.lds_decide)};
-  plan.prows = {probe_rows_kernel_of<T, NX, NP, MU>(s.prog_kind, s.static_id, s.bound != 0), 64, size_t(s.lds_prows)};
-  plan.proll = {ilq_probe_roll_kernel<T, NX, NP, MU>, 64, size_t(s.lds_proll)};
-  plan.proll_fat = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8>, 64, size_t(s.lds_proll)};  // (fp32: the same kernel)
-  if (s.proll_single) plan.proll_single = {ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, true>, 64, size_t(s.lds_proll_single)};
-  if (s.proll_lanes) plan.proll_lanes = {ilq_probe_roll_lanes_kernel<T, NX, NP, MU>, 64, size_t(s.lds_proll_lanes)};
-  if constexpr (kMayXdyn)  // (a plain-RK4 shape: one rollout per wavefront, no paired or lane-per-candidate form)
-    if (s.prog_kind == PROG_EXPR_DYN) {
-      plan.roll.kernel = ilq_roll_kernel<T, NX, NP, MU, true>;
-      plan.proll.kernel = ilq_probe_roll_kernel<T, NX, NP, MU, false, false, true>;
-      plan.proll_fat.kernel = ilq_probe_roll_kernel<T, NX, NP, MU, sizeof(T) == 8, false, true>;
-    }
-  return plan;
-}
-
-// The specialised solve: its arguments, the mask's count where the schedule wants it (the only device interaction before
-// the rounds), the schedule (decide_schedule, ilqg_schedule.hpp), its kernels (bind_plan), the rounds.
-template <typename T, int NX, int NP, int MU>
-ilqg_status DimsLaunch<T, NX, NP, MU>::solve(ilqg_problem* p, int32_t batch, const void* x0, void* xs, void* us,
-                                             void* P, void* alpha, void* total_costs, int32_t* iters, int32_t* status,
-                                             int32_t* converged, void* workspace, const ilqg_solve_options& opt,
-                                             hipStream_t stream) {
-  const DevProblem& d = p->dev;
-  SolveTail<T> tail;
-  SolveArgs<T> sa = solve_args_of<T>(p, batch, x0, xs, us, P, alpha, total_costs, iters, status, converged, workspace, opt, &tail);
-#if ILQG_DIAGNOSTIC_BUILD
-  sa.prof = g_prof;
-#endif
-  // ws_tail places the lists behind the augmented-Lagrangian layout (the larger one): whatever al_mode this solve runs in
-  if (ws_layout_of(d, sa.ol_row, 1).total < ws_layout_of(d, sa.ol_row, sa.al_mode).total)
-    return fail(ILQG_ERR_INVALID, "workspace layout: the tail offset does not cover this solve's per-instance blocks");
-  int sched_batch = batch;
-  if (schedule_counts_mask(opt)) {
-    HIP_TRY(hipMemsetAsync(p->d_unfinished.get(), 0, 4 * sizeof(int), stream));  // (whatever an earlier solve left there)
-    hipLaunchKernelGGL(ilq_count_active_kernel, dim3(1), dim3(256), 0, stream, opt.active, int(batch), p->d_unfinished.get());
-    HIP_TRY(hipGetLastError());
-    if (read_round_counters(p, stream) != ILQG_OK) return ILQG_ERR_HIP;
-    sched_batch = p->h_unfinished[3] > 0 ? p->h_unfinished[3] : 1;
-  }
-  int num_cus = 256, dev = 0;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) num_cus = prop.multiProcessorCount;
-  static constexpr ShapeTraits traits = shape_traits<T, NX, NP, MU>();
-  const SolveSchedule s = decide_schedule(traits, d, problem_facts(p), opt, batch, sched_batch, num_cus, kProfile);
-  sa.rows_cw = s.rows_cw;
-  sa.compact = s.compact;
-  sa.defer_forward = s.defer_forward;
-  sa.prio_div = s.prio_div;
-  sa.lds_part = s.lds_part;
-  sa.clear_counters = 1;
-  p->last_schedule = s.word;
-  return run_rounds(p, sa, tail, bind_plan<T, NX, NP, MU>(s), opt, stream);
-}
-
-#if defined(ILQG_PART_NX)
-// instantiation unit of a split build: this (n, N, m_i) in both precisions, nothing else
-template struct DimsLaunch<float, ILQG_PART_NX, ILQG_PART_NP, ILQG_PART_MU>;
-template struct DimsLaunch<double, ILQG_PART_NX, ILQG_PART_NP, ILQG_PART_MU>;
-#else
-#if defined(ILQG_SPLIT_BUILD)
-// The list's one expansion besides the table: without these declarations the table's addresses would instantiate every
-// shape's launchers, and the kernels behind them, in this unit as well.
-#define X(NX_, NP_, MU_)                                   \
-  extern template struct DimsLaunch<float, NX_, NP_, MU_>; \
-  extern template struct DimsLaunch<double, NX_, NP_, MU_>;
-ILQG_FOR_DIMS(X)
-#undef X
-#endif
-
-namespace {
 
 // Index of a precision in a ShapeEntry's pairs
 inline int dtype_index(int32_t dtype) { return dtype == ILQG_F32 ? 0 : 1; }
@@ -1803,9 +283,7 @@ static ilqg_status launch_lq_generic(const ilqg_dims* d, const PairTable& pt, bo
   }
   auto kern = lq_generic_kernel<T>;
   raise_lds_limit((const void*)kern, lds);
-  hipLaunchKernelGGL(kern, dim3(d->batch), dim3(kGenSweepThreads), lds, stream, g, gd, pt, open_loop ? 1 : 0, row);
-  HIP_TRY(hipGetLastError());
-  return ILQG_OK;
+  return launch(kern, dim3(d->batch), dim3(kGenSweepThreads), lds, stream, g, gd, pt, open_loop ? 1 : 0, row);
 }
 
 // The sweep of ilqg_lq_feedback_batch / ilqg_lq_openloop_batch on the first route that takes the game: its shape's own
@@ -1842,10 +320,8 @@ static ilqg_status launch_feedback_costates(const ilqg_dims* d, const PairTable&
   const size_t lds = costates_lds_elems(cd.n, cd.N) * sizeof(T);
   auto kern = lq_feedback_costates_kernel<T>;
   raise_lds_limit((const void*)kern, lds);
-  hipLaunchKernelGGL(kern, dim3(d->batch), dim3(256), lds, st, cd, pt, (const T*)A, (const T*)Bm, (const T*)Q, (const T*)l,
-                     (const T*)R, (const T*)r, (const T*)P, (const T*)alpha, (const T*)dx, (T*)zs, (T*)costates);
-  HIP_TRY(hipGetLastError());
-  return ILQG_OK;
+  return launch(kern, dim3(d->batch), dim3(256), lds, st, cd, pt, (const T*)A, (const T*)Bm, (const T*)Q, (const T*)l,
+                (const T*)R, (const T*)r, (const T*)P, (const T*)alpha, (const T*)dx, (T*)zs, (T*)costates);
 }
 
 // The argument checks of ilqg_lq_feedback_batch / ilqg_lq_openloop_batch and their control blocks; `uniform`: one m_i
@@ -1911,14 +387,10 @@ void ilqg_debug_set_profile_buffer(void* buf) { g_prof = (long long*)buf; }
 ilqg_status ilqg_selftest_mfma(int32_t dtype, const void* X, const void* Y, const void* C, void* out, void* stream) {
   ilqg_status s = check_device();
   if (s != ILQG_OK) return s;
-  if (dtype == ILQG_F32)
-    hipLaunchKernelGGL(mfma_selftest_kernel<float>, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)X,
-                       (const float*)Y, (const float*)C, (float*)out);
-  else
-    hipLaunchKernelGGL(mfma_selftest_kernel<double>, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)X,
-                       (const double*)Y, (const double*)C, (double*)out);
-  HIP_TRY(hipGetLastError());
-  return ILQG_OK;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch(mfma_selftest_kernel<T>, dim3(1), dim3(64), 0, (hipStream_t)stream, (const T*)X, (const T*)Y, (const T*)C, (T*)out);
+  });
 }
 int32_t ilqg_abi_version(void) { return ILQG_ABI_VERSION; }
 
@@ -1929,10 +401,8 @@ ilqg_status ilqg_copy_bandwidth(void* dst, const void* src, size_t bytes, void* 
     return fail(ILQG_ERR_INVALID, "ilqg_copy_bandwidth: 16-byte aligned buffers and a multiple of 16 bytes");
   const size_t n16 = bytes / 16;
   const size_t blocks = (n16 + 1023) / 1024;  // 16 KB per workgroup
-  hipLaunchKernelGGL(copy_bandwidth_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     reinterpret_cast<copy_v4f*>(dst), reinterpret_cast<const copy_v4f*>(src), n16);
-  HIP_TRY(hipGetLastError());
-  return ILQG_OK;
+  return launch(copy_bandwidth_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                reinterpret_cast<copy_v4f*>(dst), reinterpret_cast<const copy_v4f*>(src), n16);
 }
 
 ilqg_status ilqg_problem_row_program(const ilqg_problem* p, int32_t* words_out, int32_t capacity, int32_t* num_words,
@@ -2261,9 +731,10 @@ ilqg_status ilqg_problem_bind_instance_routes(ilqg_problem* p, int32_t batch, co
   const size_t count = size_t(batch) * size_t(d.total_segs);
   // a new table; one of the same size is rewritten in place, in stream order
   if (!p->bindings.bound[kBindRoutes] || batch != p->bindings.batch) {
-#define CALL(TY_) upload(std::vector<TY_>(), count * kSegStride + 1, "instance route table", &segs_of<TY_>(p->d_route_segs))
-    const ilqg_status s = DT_DISPATCH(p, CALL);
-#undef CALL
+    const ilqg_status s = with_dtype(p->desc.dtype, [&](auto tag) {
+      using T = decltype(tag);
+      return upload(std::vector<T>(), count * kSegStride + 1, "instance route table", &segs_of<T>(p->d_route_segs));
+    });
     if (s != ILQG_OK) {
       (void)ilqg_problem_bind_instance_routes(p, 0, nullptr, stream);
       return s;
@@ -2271,16 +742,12 @@ ilqg_status ilqg_problem_bind_instance_routes(ilqg_problem* p, int32_t batch, co
   }
   if (count > 0) {
     const dim3 grid((unsigned)((count + 255) / 256));
-#define CALL(TY_)                                                                                                           \
-  [&]() -> ilqg_status {                                                                                                    \
-    hipLaunchKernelGGL(route_segments_kernel<TY_>, grid, dim3(256), 0, (hipStream_t)stream, d.poly_off, d.num_polylines,    \
-                       p->d_route_cols.get(), points, p->route_points, segs_of<TY_>(p->d_segs).get(), d.total_segs, batch,  \
-                       segs_of<TY_>(p->d_route_segs).get());                                                                \
-    HIP_TRY(hipGetLastError());                                                                                             \
-    return ILQG_OK;                                                                                                         \
-  }()
-    if (ilqg_status s = DT_DISPATCH(p, CALL)) return s;
-#undef CALL
+    if (ilqg_status s = with_dtype(p->desc.dtype, [&](auto tag) {
+      using T = decltype(tag);
+      return launch(route_segments_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, d.poly_off, d.num_polylines,
+                    p->d_route_cols.get(), points, p->route_points, segs_of<T>(p->d_segs).get(), d.total_segs, batch,
+                    segs_of<T>(p->d_route_segs).get());
+    })) return s;
   }
   if (p->desc.dtype == ILQG_F32) d.segs_f = p->d_route_segs.f.get(); else d.segs_d = p->d_route_segs.d.get();
   d.seg_inst_stride = d.total_segs * kSegStride;
@@ -2332,15 +799,11 @@ ilqg_status ilqg_instance_time_nominals_build(const ilqg_problem* p, int32_t bat
   const size_t count = size_t(batch) * size_t(num_tables) * size_t(d.T);
   const dim3 grid((unsigned)((count + 255) / 256));
   // the BAKED segment table (a ROUTE_PROGRESS term's polyline never varies per instance), in the handle's precision
-#define CALL(TY_)                                                                                                  \
-  [&]() -> ilqg_status {                                                                                           \
-    hipLaunchKernelGGL(time_nominals_kernel<TY_>, grid, dim3(256), 0, (hipStream_t)stream, p->d_tnom_tables.get(), \
-                       num_tables, d.T, d.dt, speed_pos, segs_of<TY_>(p->d_segs).get(), batch, nominals);          \
-    HIP_TRY(hipGetLastError());                                                                                    \
-    return ILQG_OK;                                                                                                \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch(time_nominals_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, p->d_tnom_tables.get(),
+                  num_tables, d.T, d.dt, speed_pos, segs_of<T>(p->d_segs).get(), batch, nominals);
+  });
 }
 
 ilqg_status ilqg_problem_pairs(const ilqg_problem* p, ilqg_pair* pairs_host, int32_t* npairs) {
@@ -2366,18 +829,14 @@ ilqg_status ilqg_rollout_batch(const ilqg_problem* p, int32_t batch, const void*
   if (batch <= 0) return ILQG_OK;
   if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
   const DevProblem& d = p->dev;
-#define CALL(TY_)                                                                                              \
-  [&]() -> ilqg_status {                                                                                     \
-    RolloutBatchArgs<TY_> g{(const TY_*)x0, (const TY_*)xs_ref, (const TY_*)us_ref, (const TY_*)P, (const TY_*)alpha,    \
-                          (const TY_*)alpha_scale, (TY_*)xs, (TY_*)us, active};                                    \
-    auto kern = p->has_expression_dynamics ? rollout_kernel<TY_, true> : rollout_kernel<TY_, false>;             \
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(64), rollout_lds_elems(d.n, d.m) * sizeof(TY_),                  \
-                       (hipStream_t)stream, d, g);                                                           \
-    HIP_TRY(hipGetLastError());                                                                              \
-    return ILQG_OK;                                                                                          \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    RolloutBatchArgs<T> g{(const T*)x0, (const T*)xs_ref, (const T*)us_ref, (const T*)P, (const T*)alpha,
+                          (const T*)alpha_scale, (T*)xs, (T*)us, active};
+    auto kern = p->has_expression_dynamics ? rollout_kernel<T, true> : rollout_kernel<T, false>;
+    return launch(kern, dim3(batch), dim3(64), rollout_lds_elems(d.n, d.m) * sizeof(T),
+                  (hipStream_t)stream, d, g);
+  });
 }
 
 ilqg_status ilqg_linearize_batch(const ilqg_problem* p, int32_t batch, const void* xs, const void* us, void* A,
@@ -2411,15 +870,11 @@ ilqg_status ilqg_total_costs_batch(const ilqg_problem* p, int32_t batch, const v
   s = launch_linquad(p, p->dev, batch, xs, us, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                      nullptr, nullptr, ilqg_shared::scratch_state().ptr, active, stream);
   if (s != ILQG_OK) return s;
-#define CALL(TY_)                                                                                             \
-  [&]() -> ilqg_status {                                                                                    \
-    hipLaunchKernelGGL(costs_reduce_kernel<TY_>, dim3(batch), dim3(64), 0, (hipStream_t)stream, d,            \
-                       (const TY_*)ilqg_shared::scratch_state().ptr, (TY_*)costs, t_extreme, active);                              \
-    HIP_TRY(hipGetLastError());                                                                             \
-    return ILQG_OK;                                                                                         \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch(costs_reduce_kernel<T>, dim3(batch), dim3(64), 0, (hipStream_t)stream, d,
+                  (const T*)ilqg_shared::scratch_state().ptr, (T*)costs, t_extreme, active);
+  });
 }
 
 void ilqg_default_solve_options(ilqg_solve_options* o) {
@@ -2494,16 +949,12 @@ ilqg_status ilqg_solve_state_batch(const ilqg_problem* p, int32_t batch, const v
   const DevProblem& d = p->dev;
   const int ol_row = p->desc.params.open_loop ? ol_row_elems(d.n, d.m, d.N) : 0;
   const WsLayout L = ws_layout_of(d, ol_row, augmented_lagrangian ? 1 : 0);
-#define CALL(TY_)                                                                                                  \
-  [&]() -> ilqg_status {                                                                                         \
-    hipLaunchKernelGGL(solve_state_kernel<TY_>, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream,        \
-                       (const TY_*)workspace, L.total, L.state, batch, (TY_*)last_merit, (TY_*)expected_decrease,   \
-                       (TY_*)step, backtracks);                                                                    \
-    HIP_TRY(hipGetLastError());                                                                                  \
-    return ILQG_OK;                                                                                              \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch(solve_state_kernel<T>, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                  (const T*)workspace, L.total, L.state, batch, (T*)last_merit, (T*)expected_decrease,
+                  (T*)step, backtracks);
+  });
 }
 
 ilqg_status ilqg_receding_horizon_shift_batch(const ilqg_problem* p, int32_t batch, const void* x0, double t0,
@@ -2542,39 +993,31 @@ ilqg_status ilqg_receding_horizon_shift_batch(const ilqg_problem* p, int32_t bat
   if (new_plan_t0_host) *new_plan_t0_host = new_t0;
   if (batch <= 0) return ILQG_OK;
   if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
-#define CALL(TY_)                                                                                                  \
-  [&]() -> ilqg_status {                                                                                         \
-    RecedingArgs<TY_> g{};                                                                                         \
-    g.plan = PlanBuffers<TY_>{(TY_*)xs, (TY_*)us, (TY_*)P, (TY_*)alpha, nullptr, nullptr, plan_t0, d.T};          \
-    g.x = (const TY_*)x0; g.t = t0; g.planner_runtime = planner_runtime;                                           \
-    g.xs = (TY_*)xs; g.us = (TY_*)us; g.P = (TY_*)P; g.alpha = (TY_*)alpha; g.x0_next = (TY_*)x0_next;             \
-    g.first_step = first_step;                                                                                     \
-    auto kern = p->has_expression_dynamics ? receding_sync_kernel<TY_, true> : receding_sync_kernel<TY_, false>;     \
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(TY_),                                 \
-                       (hipStream_t)stream, d, g);                                                                 \
-    HIP_TRY(hipGetLastError());                                                                                  \
-    return ILQG_OK;                                                                                              \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    RecedingArgs<T> g{};
+    g.plan = PlanBuffers<T>{(T*)xs, (T*)us, (T*)P, (T*)alpha, nullptr, nullptr, plan_t0, d.T};
+    g.x = (const T*)x0; g.t = t0; g.planner_runtime = planner_runtime;
+    g.xs = (T*)xs; g.us = (T*)us; g.P = (T*)P; g.alpha = (T*)alpha; g.x0_next = (T*)x0_next;
+    g.first_step = first_step;
+    auto kern = p->has_expression_dynamics ? receding_sync_kernel<T, true> : receding_sync_kernel<T, false>;
+    return launch(kern, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(T),
+                  (hipStream_t)stream, d, g);
+  });
 }
 
 static ilqg_status launch_strategy_costs(const ilqg_problem* p, int32_t batch, const void* x0, const void* xs,
                                          const void* us, const void* P, const void* alpha, double eps, int open_loop,
                                          int euler, int moves, void* costs, void* stream) {
   const DevProblem& d = p->dev;
-#define CALL(TY_)                                                                                                  \
-  [&]() -> ilqg_status {                                                                                         \
-    StrategyCostArgs<TY_> g{(const TY_*)x0, (const TY_*)xs, (const TY_*)us, (const TY_*)P, (const TY_*)alpha,      \
-                            (TY_*)costs, TY_(eps), open_loop, euler, batch};                                       \
-    const size_t lds = quad_tables_bytes(d, sizeof(TY_)) + strategy_cost_lds_elems(d.n, d.m, d.num_terms) * sizeof(TY_); \
-    auto kern = p->has_expression_dynamics ? strategy_costs_kernel<TY_, true> : strategy_costs_kernel<TY_, false>; \
-    hipLaunchKernelGGL(kern, dim3(batch, moves), dim3(64), lds, (hipStream_t)stream, d, g);                       \
-    HIP_TRY(hipGetLastError());                                                                                  \
-    return ILQG_OK;                                                                                              \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    StrategyCostArgs<T> g{(const T*)x0, (const T*)xs, (const T*)us, (const T*)P, (const T*)alpha,
+                            (T*)costs, T(eps), open_loop, euler, batch};
+    const size_t lds = quad_tables_bytes(d, sizeof(T)) + strategy_cost_lds_elems(d.n, d.m, d.num_terms) * sizeof(T);
+    auto kern = p->has_expression_dynamics ? strategy_costs_kernel<T, true> : strategy_costs_kernel<T, false>;
+    return launch(kern, dim3(batch, moves), dim3(64), lds, (hipStream_t)stream, d, g);
+  });
 }
 
 ilqg_status ilqg_strategy_costs_batch(const ilqg_problem* p, int32_t batch, const void* x0, const void* xs,
@@ -2602,15 +1045,11 @@ ilqg_status ilqg_check_local_nash_batch(const ilqg_problem* p, int32_t batch, co
   s = launch_strategy_costs(p, batch, x0, xs, us, P, alpha, max_perturbation, open_loop ? 1 : 0, 1, moves, ilqg_shared::scratch_state().ptr,
                             stream);
   if (s != ILQG_OK) return s;
-#define CALL(TY_)                                                                                                  \
-  [&]() -> ilqg_status {                                                                                         \
-    hipLaunchKernelGGL(nash_verdict_kernel<TY_>, dim3(batch), dim3(64), 0, (hipStream_t)stream, d,                 \
-                       (const TY_*)ilqg_shared::scratch_state().ptr, moves, batch, is_nash, (TY_*)margin);                            \
-    HIP_TRY(hipGetLastError());                                                                                  \
-    return ILQG_OK;                                                                                              \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch(nash_verdict_kernel<T>, dim3(batch), dim3(64), 0, (hipStream_t)stream, d,
+                  (const T*)ilqg_shared::scratch_state().ptr, moves, batch, is_nash, (T*)margin);
+  });
 }
 
 ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batch, const void* xs, const void* us,
@@ -2629,8 +1068,8 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
   if (chunk > batch) chunk = batch;
   ilqg_status s = Scratch().reserve(per_inst * chunk);
   if (s != ILQG_OK) return s;
-  hipLaunchKernelGGL(fill_int_kernel<int>, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, is_psd, 1, batch);
-  HIP_TRY(hipGetLastError());
+  s = launch(fill_int_kernel<int>, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, is_psd, 1, batch);
+  if (s != ILQG_OK) return s;
   for (int b0 = 0; b0 < batch; b0 += chunk) {
     const int nb = (batch - b0 < chunk) ? batch - b0 : chunk;
     char* base = (char*)ilqg_shared::scratch_state().ptr;
@@ -2645,15 +1084,11 @@ ilqg_status ilqg_check_sufficient_nash_batch(const ilqg_problem* p, int32_t batc
     s = launch_linquad(p, full, nb, xs_c, us_c, nullptr, nullptr, nullptr, nullptr, nullptr, Q, l, R, r, nullptr, nullptr,
                        nullptr, stream);
     if (s != ILQG_OK) break;
-#define CALL(TY_)                                                                                                  \
-  [&]() -> ilqg_status {                                                                                         \
-    hipLaunchKernelGGL(psd_check_kernel<TY_>, dim3(d.T, nb), dim3(64), 0, (hipStream_t)stream, full, (TY_*)Q, (TY_*)R, \
-                       is_psd + b0);                                                                               \
-    HIP_TRY(hipGetLastError());                                                                                  \
-    return ILQG_OK;                                                                                              \
-  }()
-    s = DT_DISPATCH(p, CALL);
-#undef CALL
+    s = with_dtype(p->desc.dtype, [&](auto tag) {
+      using T = decltype(tag);
+      return launch(psd_check_kernel<T>, dim3(d.T, nb), dim3(64), 0, (hipStream_t)stream, full, (T*)Q, (T*)R,
+                    is_psd + b0);
+    });
     if (s != ILQG_OK) break;
   }
   return s;
@@ -2677,20 +1112,16 @@ ilqg_status ilqg_plan_integrate_batch(const ilqg_problem* p, int32_t batch, int3
   if (batch <= 0) return ILQG_OK;
   if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
   const DevProblem& d = p->dev;
-#define CALL(TY_)                                                                                                  \
-  [&]() -> ilqg_status {                                                                                         \
-    PlanIntegrateArgs<TY_> g{};                                                                                    \
-    g.plan = PlanBuffers<TY_>{(TY_*)plan_xs, (TY_*)plan_us, (TY_*)plan_P, (TY_*)plan_alpha, (int*)plan_len,       \
-                              (double*)plan_t0, 0.0, plan_rows};                                                   \
-    g.t_from = t_from; g.t_to = t_to; g.must_contain = must_contain; g.x = (TY_*)x; g.active = active;             \
-    auto kern = p->has_expression_dynamics ? plan_integrate_kernel<TY_, true> : plan_integrate_kernel<TY_, false>;   \
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(TY_),                                 \
-                       (hipStream_t)stream, d, g);                                                                 \
-    HIP_TRY(hipGetLastError());                                                                                  \
-    return ILQG_OK;                                                                                              \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    PlanIntegrateArgs<T> g{};
+    g.plan = PlanBuffers<T>{(T*)plan_xs, (T*)plan_us, (T*)plan_P, (T*)plan_alpha, (int*)plan_len,
+                              (double*)plan_t0, 0.0, plan_rows};
+    g.t_from = t_from; g.t_to = t_to; g.must_contain = must_contain; g.x = (T*)x; g.active = active;
+    auto kern = p->has_expression_dynamics ? plan_integrate_kernel<T, true> : plan_integrate_kernel<T, false>;
+    return launch(kern, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(T),
+                  (hipStream_t)stream, d, g);
+  });
 }
 
 ilqg_status ilqg_receding_horizon_sync_batch(const ilqg_problem* p, int32_t batch, int32_t plan_rows,
@@ -2710,22 +1141,18 @@ ilqg_status ilqg_receding_horizon_sync_batch(const ilqg_problem* p, int32_t batc
   if (batch <= 0) return ILQG_OK;
   if (ilqg_status sb = instance_batch_check(p, batch, false)) return sb;
   const DevProblem& d = p->dev;
-#define CALL(TY_)                                                                                                  \
-  [&]() -> ilqg_status {                                                                                         \
-    RecedingArgs<TY_> g{};                                                                                         \
-    g.plan = PlanBuffers<TY_>{(TY_*)plan_xs, (TY_*)plan_us, (TY_*)plan_P, (TY_*)plan_alpha, (int*)plan_len,       \
-                              (double*)plan_t0, 0.0, plan_rows};                                                   \
-    g.x = (const TY_*)x; g.t = t; g.planner_runtime = planner_runtime;                                             \
-    g.xs = (TY_*)xs; g.us = (TY_*)us; g.P = (TY_*)P; g.alpha = (TY_*)alpha; g.x0_next = (TY_*)x0_next;             \
-    g.solve_t0 = solve_t0; g.first_step = first_step; g.active = active;                                           \
-    auto kern = p->has_expression_dynamics ? receding_sync_kernel<TY_, true> : receding_sync_kernel<TY_, false>;     \
-    hipLaunchKernelGGL(kern, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(TY_),                                 \
-                       (hipStream_t)stream, d, g);                                                                 \
-    HIP_TRY(hipGetLastError());                                                                                  \
-    return ILQG_OK;                                                                                              \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    RecedingArgs<T> g{};
+    g.plan = PlanBuffers<T>{(T*)plan_xs, (T*)plan_us, (T*)plan_P, (T*)plan_alpha, (int*)plan_len,
+                              (double*)plan_t0, 0.0, plan_rows};
+    g.x = (const T*)x; g.t = t; g.planner_runtime = planner_runtime;
+    g.xs = (T*)xs; g.us = (T*)us; g.P = (T*)P; g.alpha = (T*)alpha; g.x0_next = (T*)x0_next;
+    g.solve_t0 = solve_t0; g.first_step = first_step; g.active = active;
+    auto kern = p->has_expression_dynamics ? receding_sync_kernel<T, true> : receding_sync_kernel<T, false>;
+    return launch(kern, dim3(batch), dim3(64), (d.n + d.m + 2) * sizeof(T),
+                  (hipStream_t)stream, d, g);
+  });
 }
 
 ilqg_status ilqg_solution_splice_batch(const ilqg_problem* p, int32_t batch, int32_t plan_rows, void* plan_xs,
@@ -2740,20 +1167,15 @@ ilqg_status ilqg_solution_splice_batch(const ilqg_problem* p, int32_t batch, int
     return fail(ILQG_ERR_INVALID, "plan_rows must leave room for five saved rows (T + 5)");
   if (batch <= 0) return ILQG_OK;
   const DevProblem& d = p->dev;
-#define CALL(TY_)                                                                                                  \
-  [&]() -> ilqg_status {                                                                                         \
-    SpliceArgs<TY_> g{};                                                                                           \
-    g.plan = PlanBuffers<TY_>{(TY_*)plan_xs, (TY_*)plan_us, (TY_*)plan_P, (TY_*)plan_alpha, plan_len, plan_t0,    \
-                              0.0, plan_rows};                                                                     \
-    g.xs = (const TY_*)xs; g.us = (const TY_*)us; g.P = (const TY_*)P; g.alpha = (const TY_*)alpha;               \
-    g.solve_t0 = solve_t0; g.converged = converged; g.active = active;                                             \
-    hipLaunchKernelGGL(splice_kernel<TY_>, dim3(batch), dim3(64), 0, (hipStream_t)stream, d, g);                   \
-    HIP_TRY(hipGetLastError());                                                                                  \
-    return ILQG_OK;                                                                                              \
-  }()
-  return DT_DISPATCH(p, CALL);
-#undef CALL
+  return with_dtype(p->desc.dtype, [&](auto tag) {
+    using T = decltype(tag);
+    SpliceArgs<T> g{};
+    g.plan = PlanBuffers<T>{(T*)plan_xs, (T*)plan_us, (T*)plan_P, (T*)plan_alpha, plan_len, plan_t0,
+                              0.0, plan_rows};
+    g.xs = (const T*)xs; g.us = (const T*)us; g.P = (const T*)P; g.alpha = (const T*)alpha;
+    g.solve_t0 = solve_t0; g.converged = converged; g.active = active;
+    return launch(splice_kernel<T>, dim3(batch), dim3(64), 0, (hipStream_t)stream, d, g);
+  });
 }
 
 }  // extern "C"
-#endif  // !ILQG_PART_NX

@@ -1,14 +1,19 @@
 // ilqg_instances.hpp — the host side of what makes the games of one batch differ (ilqg.h: per-instance cost parameters,
 // subsystem parameters, routes, time nominals): the declaration checks, declare_instance_columns, the checks over the
 // binding record (ilqg_problem::bindings: every "bound for a batch of N" refusal, the tables from a chunk's first
-// instance) and the two table-builder kernels.  Part of ilqg_api.hip's main unit, included once behind ilqg_problem.hpp;
+// instance) and the two table-builder kernels.  Included by the main unit alone (ilqg_api.hip);
 // the extern "C" entry points stay there.
 #pragma once
 
-#include "ilqg_problem.hpp"
+#include <string>
+#include <vector>
 
-#if !defined(ILQG_PART_NX)
+#include "ilqg_problem.hpp"
+#include "ilqg_problem_build.hpp"  // upload
+#include "ilqg_shared.hpp"         // fail, HIP_TRY
+
 namespace {
+using namespace ilqg;
 
 // ---- per-instance cost parameters (ilqg.h) ----
 const char* cost_kind_name(int kind) {  // ilqg_cost_kind without its prefix
@@ -327,4 +332,3 @@ __global__ void __launch_bounds__(256) time_nominals_kernel(const int* tables, i
   time_nominal<S>(tab[1] != 0, speed_pos[2 * bq], speed_pos[2 * bq + 1], k, dt, segs + size_t(tab[2]) * kSegStride, tab[3],
                   out + 2 * gid);
 }
-#endif  // !ILQG_PART_NX

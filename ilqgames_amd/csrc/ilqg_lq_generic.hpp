@@ -21,6 +21,7 @@
 #include "ilqg_pairs.hpp"
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define ILQG_HD __host__ __device__ __forceinline__
 #else
 #define ILQG_HD inline

@@ -62,7 +62,7 @@ struct PlanStepper {
         if (t == s) {
           T xj[kSubStatesMax];
           for (int e = 0; e < kSubStatesMax; e++) xj[e] = e < xd ? sx[xo + e] : T(0);
-          // no row of this problem reads the time: the host refuses plan integration of one that does (ilqg_api.hip)
+          // no row of this problem reads the time: the host refuses plan integration of one that does (refuse_time_reading_dynamics, ilqg_api.hip)
           sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], xd, Lp, interval, xj, su[uo], su[uo + 1], 0.0);
           for (int e = 0; e < xd; e++) sx[xo + e] = xj[e];
         }

@@ -30,6 +30,7 @@
 
 #include "ilqg_common.hpp"
 #include "ilqg_models.hpp"
+#include "ilqg_stages.hpp"  // QuadArgs, DevProblem's accessors
 
 #ifndef ILQG_ROWS_XREG
 #define ILQG_ROWS_XREG 1  // the split row kernels keep a row's state in registers (0: the LDS image, for A/B measurements)

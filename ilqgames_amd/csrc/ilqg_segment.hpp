@@ -1,6 +1,6 @@
 // ilqg_segment.hpp — one LineSegment2 (include/ilqgames/geometry/line_segment2.h:55-62) of the segment table
 // (DevProblem::segs_f / segs_d), in the one form the host builder (build_segments, ilqg_problem.hpp) and the device
-// builder of a per-instance route table (route_segments_kernel, ilqg_api.hip) both call.  Plain C++ apart from the two
+// builder of a per-instance route table (route_segments_kernel, ilqg_instances.hpp) both call.  Plain C++ apart from the two
 // function attributes: a host-only program includes it as it is.
 #pragma once
 

@@ -23,6 +23,7 @@
 #include "ilqg_lq_feedback2.hpp"
 #include "ilqg_lq_feedback1w.hpp"
 #include "ilqg_lq_generic.hpp"
+#include "ilqg_rows.hpp"
 #include "ilqg_stages.hpp"
 
 namespace ilqg {
@@ -912,7 +913,7 @@ __device__ __forceinline__ int trial_last_chunk_begin(int Tn, int cw) {
 // unbound fused kernel two registers (and, n = 14 in fp64, a spill), so that one stays the code it was.  The one-wave
 // rollout kernel of the split pass (TRIAL_ROLL) has room for it and looks at run time.
 // SOLVER_COLS: the decision section reads the instance's solver parameters (solver_params_of).  False only in the
-// decision kernel's twin for problems with no solver column bound (ilq_decide_kernel's SOLVER, ilqg_api.hip), which reads
+// decision kernel's twin for problems with no solver column bound (ilq_decide_kernel's SOLVER, ilqg_kernels.hpp), which reads
 // the descriptor alone; independent of BOUND, which is about the rollout's and the rows' tables.
 template <typename T, int NX, int NP, int MU, int W, int PHASE = TRIAL_FUSED, int PROGID = 0, bool BOUND = (PROGID >= kBoundProg),
           bool SOLVER_COLS = true>
@@ -1259,7 +1260,7 @@ __device__ __forceinline__ void deadline_part_instance(const DevProblem& p, cons
 // pay for the others): LQ_VALU_FEEDBACK, LQ_PLAYER_WAVES (PW above) or LQ_OPEN_LOOP.
 enum { LQ_VALU_FEEDBACK = 0, LQ_PLAYER_WAVES = 1, LQ_OPEN_LOOP = 2, LQ_PLAYER_WAVES_PACKED = 3, LQ_OPEN_LOOP_COMPACT = 4,
        LQ_SINGLE_WAVE = 5 };  // _SINGLE_WAVE: the one-tile feedback sweep with one wave per instance (ilqg_lq_feedback1w.hpp)
-// _PACKED: ilqg_api.hip; _COMPACT: the open-loop sweep reading compact rows (its own instantiation: register budget)
+// _PACKED: ilqg_kernels.hpp; _COMPACT: the open-loop sweep reading compact rows (its own instantiation: register budget)
 // FORMS: ilqg_solve_options::sweep_forms — the one-tile feedback sweeps' solve with read-lanes (0) or row broadcasts (1),
 // and the player-parallel sweep with B's constant entries in registers on top of them (2: lq_feedback_instance_mfma_pw's
 // BCONST; the launcher picks it for a problem whose B qualifies, RowProgramHost::b_constant).

@@ -910,5 +910,3 @@ __device__ __forceinline__ void costs_reduce(const DevProblem& p, const T* cost_
 }
 
 }  // namespace ilqg
-
-#include "ilqg_rows.hpp"

@@ -1,6 +1,6 @@
 // ilqg_time_nominal.hpp — one per-step nominal of a time-dependent cost (DevProblem::time_nominal_f / _d), in the one
 // form the host builder (build_time_nominals, ilqg_problem.hpp) and the device builder of a per-instance table
-// (time_nominals_kernel, ilqg_api.hip) both call.  NominalPathLengthCost (src/nominal_path_length_cost.cpp:53): the
+// (time_nominals_kernel, ilqg_instances.hpp) both call.  NominalPathLengthCost (src/nominal_path_length_cost.cpp:53): the
 // double product t_k * speed.  RouteProgressCost (src/route_progress_cost.cpp:57-59): Polyline2::PointAt
 // (src/polyline2.cpp:68-103) at a route position that is a scalar of the geometry made from a double expression.  Plain
 // C++ apart from the two function attributes: a host-only program includes it (and ilqg_segment.hpp) as it is.

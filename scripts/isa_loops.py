@@ -1,6 +1,6 @@
 """Instruction mix of the loops of one kernel in a hipcc -S listing (no GPU needed).
 
-  hipcc --offload-arch=gfx950 -O3 ... --cuda-device-only -S ilqg_api.hip -o d14.s
+  hipcc --offload-arch=gfx950 -O3 ... -DILQG_PART_NX=14 -DILQG_PART_NP=3 -DILQG_PART_MU=2 --cuda-device-only -S ilqg_dims.hip -o d14.s
   python scripts/isa_loops.py d14.s ilq_lq_kernelIdLi14ELi3ELi2ELi1E
 
 Prints, for every backward branch (a loop), the number of instructions between the label and the branch by class

@@ -246,7 +246,7 @@ def test_padded_sweep_is_reported_requested_and_refused(hip, oracle):
     r14 = oracle.OracleProblem(spec14).solve(abi.F64, x14, fixed_iters=3)
     for out in (g, h):
         assert rel_err(_np(out["xs"]), r14["xs"]) < 1e-7 and rel_err(_np(out["P"]), r14["rawP"]) < 1e-6
-    # five players: no instantiated shape has five (ILQG_FOR_DIMS, csrc/ilqg_api.hip)
+    # five players: no instantiated shape has five (ILQG_FOR_DIMS, csrc/ilqg_shapes.hpp)
     s5 = abi.ProblemSpec(T=10)
     for _ in range(5):
         s5.add_player(abi.DYN_UNICYCLE_4D, 0.0)

@@ -54,7 +54,7 @@ def test_lq_feedback_matches_reference_python_golden(hip, name):
 
 
 # `dims` of this test and of test_lq_openloop_matches_oracle_random: every shape the library instantiates (ILQG_FOR_DIMS,
-# csrc/ilqg_api.hip) — tests/test_host_boundary.py::test_every_instantiated_shape_has_its_sweep_tests holds them to it.
+# csrc/ilqg_shapes.hpp) — tests/test_host_boundary.py::test_every_instantiated_shape_has_its_sweep_tests holds them to it.
 # (A new shape goes to the end of each: the ids of the cases are their positions.)
 @pytest.mark.parametrize("dims", [(14, 3, 2), (16, 3, 2), (15, 3, 2), (24, 4, 2), (18, 3, 2), (10, 2, 2), (6, 3, 2),
                                   (4, 2, 2), (6, 2, 1), (3, 2, 1), (3, 1, 1), (2, 2, 1), (17, 3, 2), (8, 2, 1),

@@ -45,11 +45,11 @@ def test_library_has_no_dangling_internal_symbol():
 
 
 def test_every_instantiated_shape_has_its_sweep_tests():
-    """The (n, N, m_i) list of the library — the `#define ILQG_FOR_DIMS(X)` line of csrc/ilqg_api.hip, read the way
+    """The (n, N, m_i) list of the library — the `#define ILQG_FOR_DIMS(X)` line of csrc/ilqg_shapes.hpp, read the way
     __graft_entry__.build_hip_library reads it — is the `dims` parametrisation of the two stand-alone sweep tests of
     tests/test_gpu_parity.py: a shape added to the library cannot go without them."""
     import test_gpu_parity
-    src = os.path.join(ROOT, "ilqgames_amd", "csrc", "ilqg_api.hip")
+    src = os.path.join(ROOT, "ilqgames_amd", "csrc", "ilqg_shapes.hpp")
     line = next(l for l in open(src) if l.startswith("#define ILQG_FOR_DIMS(X)"))
     shapes = [tuple(int(v) for v in m) for m in re.findall(r"X\((\d+), (\d+), (\d+)\)", line)]
     assert shapes and len(set(shapes)) == len(shapes)
@@ -58,6 +58,27 @@ def test_every_instantiated_shape_has_its_sweep_tests():
         tested = [tuple(v) for mark in test.pytestmark if mark.name == "parametrize" and mark.args[0] == "dims"
                   for v in mark.args[1]]
         assert set(tested) == set(shapes) and len(tested) == len(shapes), test.__name__
+
+
+def test_every_library_header_compiles_on_its_own(tmp_path):
+    """Every csrc/*.hpp includes what it uses: a translation unit that holds nothing but `#include "X.hpp"` passes the
+    compiler's syntax pass (host and gfx950), with the library's include paths.  At most eight compilers at a time."""
+    from concurrent.futures import ThreadPoolExecutor
+    csrc = os.path.join(ROOT, "ilqgames_amd", "csrc")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")  # (as __graft_entry__.build_hip_library takes it)
+    headers = sorted(f for f in os.listdir(csrc) if f.endswith(".hpp"))
+    assert len(headers) > 20
+
+    def check(header):
+        unit = tmp_path / (header[:-4] + ".hip")
+        unit.write_text('#include "%s"\n' % header)
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I" + csrc,
+                            "-I" + os.path.join(ROOT, "include"), str(unit)], capture_output=True, text=True, timeout=600)
+        return header, r.returncode, r.stderr
+
+    with ThreadPoolExecutor(max_workers=8) as pool:
+        failed = ["%s:\n%s" % (h, err[-2000:]) for h, rc, err in pool.map(check, headers) if rc != 0]
+    assert not failed, "\n".join(failed)
 
 
 def test_struct_layouts_match_the_c_header():
