@@ -1159,15 +1159,19 @@ __device__ __forceinline__ T term_evaluate_leaf(const QuadTables<T>& tb, int ti,
   return term_evaluate_leaf_of<T, V>(tb, c, v, dim, step);
 }
 
-// ExtremeValueCost::ExtremeCost, src/extreme_value_cost.cpp:66-85: index of the active child.  The children are
-// evaluated at step 0 whatever step the parent is at (an open point for time-dependent children).
+// ExtremeValueCost::ExtremeCost, src/extreme_value_cost.cpp:66-85: index of the active child.  `step`: the step the
+// parent is evaluated at, which the reference hands on to its children — an expression child is evaluated at it (its
+// PUSH_TIME pushes that step's time, as in the row programs); a built-in child at step 0 whatever step the parent is at
+// (an open point for the time-dependent built-in kinds).
 template <typename T, typename V>
-__device__ __forceinline__ int extreme_child(const QuadTables<T>& tb, const DevTerm& c, const V& v, int dim, T* value_out) {
+__device__ __forceinline__ int extreme_child(const QuadTables<T>& tb, const DevTerm& c, const V& v, int dim, int step,
+                                             T* value_out) {
   const bool is_min = c.flags & ILQG_FLAG_IS_MIN;
   T ext = is_min ? dinf<T>() : -dinf<T>();
   int best = c.child_begin;
   for (int q = 0; q < c.child_count; q++) {
-    const T value = term_evaluate_leaf<T, V>(tb, c.child_begin + q, v, dim, 0);
+    const DevTerm ch = tb.terms[c.child_begin + q];
+    const T value = term_evaluate_leaf_of<T, V>(tb, ch, v, dim, term_is_expression(ch.kind) ? step : 0);
     if ((is_min && value < ext) || (!is_min && value > ext)) {
       ext = value;
       best = c.child_begin + q;

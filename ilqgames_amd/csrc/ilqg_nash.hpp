@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(64) strategy_costs_kernel(DevProblem p, Strate
       const int at_step = (a.open_loop && c.role == ILQG_ROLE_STATE_COST) ? kk + 1 : kk;
       if ((c.role == ILQG_ROLE_STATE_COST || c.role == ILQG_ROLE_CONTROL_COST) && at_step >= c.k_start) {
         if (c.kind == ILQG_COST_EXTREME_VALUE)
-          (void)extreme_child<T>(tb, c, at + c.arg_off, c.arg_dim, &value);
+          (void)extreme_child<T>(tb, c, at + c.arg_off, c.arg_dim, at_step, &value);
         else
           value = term_evaluate_leaf<T>(tb, ti, at + c.arg_off, c.arg_dim, at_step);
       }

@@ -272,14 +272,26 @@ ilqg_status check_expression_term(const ilqg_problem_desc& desc, int ti, int arg
   } else {
     if (constraint_role)
       return fail(ILQG_ERR_UNSUPPORTED, where + "an expression is a cost: a constraint role is not supported");
-    bool child = c.role == ILQG_ROLE_CHILD;
+    // A child (ilqg.h): role ILQG_ROLE_CHILD and inside the child range of exactly one ExtremeValueCost — both or neither
+    int parents = 0, parent = -1;
     for (int q = 0; q < desc.num_terms; q++)
       if (desc.terms[q].kind == ILQG_COST_EXTREME_VALUE && ti >= desc.terms[q].child_begin &&
-          ti < desc.terms[q].child_begin + desc.terms[q].child_count)
-        child = true;
-    if (child) return fail(ILQG_ERR_UNSUPPORTED, where + "an expression cannot be an EXTREME_VALUE child");
-    if (c.role != ILQG_ROLE_STATE_COST && c.role != ILQG_ROLE_CONTROL_COST)
-      return fail(ILQG_ERR_INVALID, where + "its role must be a top-level state or control cost");
+          ti < desc.terms[q].child_begin + desc.terms[q].child_count) {
+        parents++;
+        parent = q;
+      }
+    if (c.role == ILQG_ROLE_CHILD && parents == 0)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "a term with ILQG_ROLE_CHILD that no ILQG_COST_EXTREME_VALUE term lists cannot be "
+                                            "an EXTREME_VALUE child: put it inside one parent's [child_begin, child_begin + child_count)");
+    if (c.role != ILQG_ROLE_CHILD && parents > 0)
+      return fail(ILQG_ERR_UNSUPPORTED, where + "a term with a top-level role cannot be an EXTREME_VALUE child (term " +
+                                            std::to_string(parent) + " lists it): give it ILQG_ROLE_CHILD");
+    if (parents > 1)
+      return fail(ILQG_ERR_INVALID, where + std::to_string(parents) + " ILQG_COST_EXTREME_VALUE terms list it (the last: term " +
+                                        std::to_string(parent) + "): a term cannot be an EXTREME_VALUE child of more than one parent");
+    if (c.role != ILQG_ROLE_STATE_COST && c.role != ILQG_ROLE_CONTROL_COST && c.role != ILQG_ROLE_CHILD)
+      return fail(ILQG_ERR_INVALID, where + "its role must be a top-level state or control cost, or ILQG_ROLE_CHILD under an "
+                                        "ExtremeValueCost");
   }
   if (c.idx[0] < 0 || c.idx[0] >= arg_dim)
     return fail(ILQG_ERR_INVALID, where + "idx[0] = " + std::to_string(c.idx[0]) + " is outside its argument vector (dimension " +

@@ -349,16 +349,22 @@ inline bool build_row_program(const DevProblem& d, const std::vector<DevTerm>& d
         if (c.player != i || c.role != role) continue;
         if (c.kind == ILQG_COST_EXTREME_VALUE) {
           if (c.child_count < 1 || c.child_count > 255) { *err = "row program: bad ExtremeValueCost"; return false; }
+          // (an expression child is a leaf like a top-level expression cost: both of its ops carry its pattern — only an
+          // expression's depends on idx[1] / idx[2] — and its program's offset, and its stack is counted into the scratch)
           for (int q = 0; q < c.child_count; q++) {
             const DevTerm& ch = dt[c.child_begin + q];
+            const bool expr = term_is_expression(ch.kind);
+            if (expr) expr_scratch = kExprStackScalars;
             want_closest(ch, c);
-            emit_op(ROP_EXT_EVAL, 0, 0, q, ch, c, 0, term_pattern_of(ch.kind, ch.idx[0]), c.child_begin + q);
+            emit_op(ROP_EXT_EVAL, 0, 0, q, ch, c, expr ? ch.polyline : 0, term_pattern_of(ch.kind, ch.idx[0], ch.idx[1], ch.idx[2]),
+                    c.child_begin + q);
           }
           for (int q = 0; q < c.child_count; q++) {
             const DevTerm& ch = dt[c.child_begin + q];
             want_closest(ch, c);
             const int b0 = leaf_sids(ch, c);
-            emit_op(ROP_EXT_APPLY, b0, int(sids.size()) - b0, q, ch, c, 0, term_pattern_of(ch.kind, ch.idx[0]), c.child_begin + q);
+            emit_op(ROP_EXT_APPLY, b0, int(sids.size()) - b0, q, ch, c, term_is_expression(ch.kind) ? ch.polyline : 0,
+                    term_pattern_of(ch.kind, ch.idx[0], ch.idx[1], ch.idx[2]), c.child_begin + q);
           }
         } else if (c.kind == ILQG_COST_WEIGHTED_CONVEX_PROXIMITY) {
           // four ops (ilqg_models.hpp): the position block carries the value, then the speed block and the two

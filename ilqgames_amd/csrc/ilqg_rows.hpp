@@ -858,6 +858,15 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
         const bool deriv = do_quad && live && (((full >> c.player) & 1u) || c.role == ILQG_ROLE_CONTROL_COST);
         const bool need = deriv || (want_cost && is_cost && live);
         if (!__any(need)) return;
+        if constexpr (PROG::kExpr) {
+          // An expression child of an ExtremeValueCost: its EXT_EVAL op wants the value alone — the jet without second
+          // derivatives computes the same f of every op —, its EXT_APPLY op the jet, and only where some lane of the wave
+          // has this child as its extreme (the EXT_EVAL ops' values decided that: ext_best)
+          if (mode == ROP_EXT_APPLY && term_is_expression(c.kind) && !__any(deriv && ext_best == aux)) {
+            if (aux == 0 && is_cost && live) ctot += ext_value;
+            return;
+          }
+        }
         const T lambda = (c.slot >= 0 && a.lambdas) ? a.lambdas[c.slot * p.T + tidx] : T(0);
 #if ILQG_PROFILE2
         ILQG_QPH(2);
@@ -884,8 +893,8 @@ __device__ __forceinline__ void rows_chunk(const DevProblem& p, const short* map
             if (two) ey = ey - v[c.idx[3]];
           }
           ExprJet<T> j;
-          expr_eval_jet<T>(prog, T(c.weight), T(c.value), ex, ey, quad_out, ExprStack<T>{col + (NPS + li_live) * cws, cws}, &j,
-                           T(tt));  // RelativeTime(row), what PUSH_TIME pushes
+          expr_eval_jet<T>(prog, T(c.weight), T(c.value), ex, ey, quad_out && mode != ROP_EXT_EVAL,
+                           ExprStack<T>{col + (NPS + li_live) * cws, cws}, &j, T(tt));  // RelativeTime(row), what PUSH_TIME pushes
           if (c.kind == ILQG_CONSTRAINT_EXPRESSION) {
             // Constraint::ModifyDerivatives (modify_derivatives, ilqg_models.hpp) with the equality-aware Mu of the affine
             // constraints; a gradient-only evaluation holds zeros in the jet's second derivatives and scatters none

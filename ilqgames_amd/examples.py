@@ -928,13 +928,14 @@ def expression_twin(spec):
     return twin, replaced
 
 
-def expression_game_twin(spec):
+def expression_game_twin(spec, children=False):
     """expression_twin's restatements and, beside them, those of the kinds that couple players or bound them, written over
     relative inputs (X = v[idx0] - v[idx2], Y = v[idx1] - v[idx3]) and as abi.CONSTRAINT_EXPRESSION terms:
     ProximityCost 0.5 w hinge(v - sqrt(X^2 + Y^2))^2, RelativeDistanceCost w sqrt(X^2 + Y^2), QuadraticDifferenceCost
     0.5 w (X^2 + Y^2), a top-level SignedDistanceCost +-(v - sqrt(X^2 + Y^2)), ProximityConstraint
     +-(sqrt(X^2 + Y^2) - v) and SingleDimensionConstraint x - v / v - x on a state or a control — each with the same
-    weight, value, role, player, multiplier slot and gate; every other term as it is.
+    weight, value, role, player, multiplier slot and gate; every other term as it is.  `children`: a SignedDistanceCost
+    that is a child of an ExtremeValueCost is restated too, role abi.ROLE_CHILD kept (reachability_twin).
     -> (the twin, the number of terms replaced)."""
     from . import abi
     from .abi import Expr
@@ -943,7 +944,8 @@ def expression_game_twin(spec):
         x, y, w, v = Expr.x(), Expr.y(), Expr.weight(), Expr.value()
         dist = (x.square() + y.square()).sqrt()
         oriented = bool(t["flags"] & abi.FLAG_ORIENTED)
-        cost = t["role"] in (abi.ROLE_STATE_COST, abi.ROLE_CONTROL_COST)
+        cost = t["role"] in (abi.ROLE_STATE_COST, abi.ROLE_CONTROL_COST) or \
+            (children and t["role"] == abi.ROLE_CHILD and t["kind"] == abi.COST_SIGNED_DISTANCE)
         constraint = t["role"] in (abi.ROLE_STATE_CONSTRAINT, abi.ROLE_CONTROL_CONSTRAINT)
         kind, idx = abi.COST_EXPRESSION, tuple(t["idx"])
         if cost and t["kind"] == abi.COST_PROXIMITY:
@@ -1013,6 +1015,70 @@ def expression_game_scene(T=100, dt=0.1):
     x0 = np.zeros(10)
     x0[[X[0], Y[0], H[0], V[0]]] = [0.0, -12.0, float(f(np.pi / 2)), 5.0]
     x0[[X[1], Y[1], H[1], V[1]]] = [-5.0, 10.0, float(f(-np.pi / 2)), 4.0]
+    s.x0 = x0
+    s.position_dims, s.heading_dims, s.speed_dims = list(zip(X, Y)), H, V
+    return s
+
+
+def reachability_twin(spec):
+    """expression_game_twin(spec) with the SignedDistanceCost children of every ExtremeValueCost restated as well, as
+    abi.COST_EXPRESSION children +-(v - sqrt(X^2 + Y^2)) over relative inputs: the parents, their child ranges and every
+    child's role, value and place in the table stay.  -> (the twin, the number of terms replaced)."""
+    return expression_game_twin(spec, children=True)
+
+
+# shaped_reachability_scene's sets (its C++ twin: tests/host/shaped_reachability_scene.h): the box player 1 reaches as
+# (x_lo, x_hi, y_lo, y_hi); the keep-out ellipse around player 1 (radius along X, Y axis ratio); the disc that moves along
+# y = 0 (centre's x at t = 0, its speed, radius); the keep-out half-plane x < bound
+SHAPED_BOX = (-1.5, 1.5, -1.0, 3.0)
+SHAPED_ELLIPSE = (4.0, 0.5)
+SHAPED_DISC = (-8.0, 3.0, 2.5)
+SHAPED_HALF_PLANE = -8.5
+SHAPED_CHILDREN = ("p1_box_right", "p1_box_left", "p1_box_top", "p1_box_bottom", "p2_ellipse", "p2_moving_disc", "p2_half_plane")
+
+
+def shaped_reachability_scene(T=100, dt=0.1):
+    """A test scene, NOT a reference example: two Car5D (n = 10, the specialised (10, 2, 2) kernels) in a reach-avoid game
+    whose sets no built-in kind expresses — every child of the two ExtremeValueCosts is an abi.COST_EXPRESSION term, a
+    signed distance (positive outside the set to reach, positive inside a set to avoid).  Player 1 (structure MIN over time)
+    reaches a box: the max of x - v, v - x, y - v, v - y with v the four faces.  Player 2 (structure MAX over time) keeps
+    out of the union of an ellipse around player 1, v - sqrt(X^2 + (Y / 0.5)^2) over the relative position (two relative
+    inputs), a disc moving along y = 0, v - sqrt(((x - c) - s t)^2 + y^2) over its own position through Expr.time() (two
+    plain inputs) and the half-plane x < v, v - x (one input): the max of the three.  Both carry control costs and a
+    nominal-speed cost."""
+    from .abi import Expr
+    prm = SolverParams.default()
+    prm.max_backtracking_steps = 100
+    prm.initial_alpha_scaling = 0.1
+    prm.convergence_tolerance = 0.01
+    prm.expected_decrease_fraction = 0.1
+    prm.max_solver_iters = 40
+    s = ProblemSpec(T, dt, prm)
+    s.add_player(DYN_CAR_5D, 4.0, state_reg=1.0, control_reg=1.0, structure=abi.MIN)
+    s.add_player(DYN_CAR_5D, 4.0, state_reg=1.0, control_reg=1.0, structure=abi.MAX)
+    X, Y, H, PHI, V = [0, 5], [1, 6], [2, 7], [3, 8], [4, 9]
+    for i in range(2):
+        s.quadratic(i, 1.0, 0, 0.0, control_of=i)  # omega
+        s.quadratic(i, 0.5, 1, 0.0, control_of=i)  # acceleration
+        s.name_term("p%d_nominal_speed" % (i + 1), s.quadratic(i, 0.1, V[i], 5.0 if i == 0 else 4.0))
+    x, y, v, t = Expr.x(), Expr.y(), Expr.value(), Expr.time()
+    xlo, xhi, ylo, yhi = SHAPED_BOX
+    faces = [(x - v, X[0], xhi), (v - x, X[0], xlo), (x - v, Y[0], yhi), (v - x, Y[0], ylo)]
+    begin = len(s.terms)
+    s.extreme_value(0, [(lambda role, f=f: s.expression(0, f[0], (f[1],), value=f[2], role=role)) for f in faces], is_min=False)
+    radius, ratio = SHAPED_ELLIPSE
+    c, speed, disc_radius = SHAPED_DISC
+    ellipse = v - (x.square() + (y / ratio).square()).sqrt()
+    disc = v - (moving_obstacle_offset(x, c, speed).square() + y.square()).sqrt()
+    s.extreme_value(1, [lambda role: s.expression(1, ellipse, (X[1], Y[1]), value=radius, relative_to=(X[0], Y[0]), role=role),
+                        lambda role: s.expression(1, disc, (X[1], Y[1]), value=disc_radius, role=role),
+                        lambda role: s.expression(1, v - x, (X[1],), value=SHAPED_HALF_PLANE, role=role)], is_min=False)
+    for q, name in enumerate(SHAPED_CHILDREN):
+        s.name_term(name, begin + q + (1 if q >= 4 else 0))  # (player 1's parent sits between the two child ranges)
+    f = np.float32
+    x0 = np.zeros(10)
+    x0[[X[0], Y[0], H[0], V[0]]] = [0.0, -6.0, float(f(np.pi / 2)), 5.0]
+    x0[[X[1], Y[1], H[1], V[1]]] = [-5.0, 5.0, float(f(-np.pi / 2)), 4.0]
     s.x0 = x0
     s.position_dims, s.heading_dims, s.speed_dims = list(zip(X, Y)), H, V
     return s

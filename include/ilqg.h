@@ -230,7 +230,18 @@ typedef enum {
    * its argument vector, evaluated and differentiated to second order on the device (forward mode, ilqg_expr_op below).
    * idx[0] = input x, idx[1] = input y or -1; `polyline` = offset of the program's block in
    * ilqg_problem_desc::dense_params: [L, (opcode_0, imm_0), ..., (opcode_{L-1}, imm_{L-1})] as floats.  The program's
-   * result is the term's value: `weight` and `value` enter only where it pushes them.  Top-level state / control cost.
+   * result is the term's value: `weight` and `value` enter only where it pushes them.  Top-level state / control cost, or
+   * a child of an ExtremeValueCost.
+   *
+   * As a child.  The term is a well-formed child exactly when its role is ILQG_ROLE_CHILD AND it lies inside the
+   * [child_begin, child_begin + child_count) range of exactly one ILQG_COST_EXTREME_VALUE term; either without the other
+   * is refused (ILQG_ERR_UNSUPPORTED: "... cannot be an EXTREME_VALUE child"), two parents are ILQG_ERR_INVALID.  A child
+   * takes everything a top-level expression cost takes — one or two inputs, the relative forms, PUSH_WEIGHT / PUSH_VALUE
+   * (per instance where declared), PUSH_TIME — over the state (arg = -1), as every child; role, player, `first_step` gate
+   * and cost structure are the parent's.  Max / min over such children is the union / intersection of the sets whose
+   * signed distances the programs are.  The parent's value and active child at a step come from the children's values at
+   * that step, first strict improvement in table order (src/extreme_value_cost.cpp:66-85); only the active child's jet
+   * is scattered.  An ILQG_CONSTRAINT_EXPRESSION or dynamics-row term is never a child, nor is an ExtremeValueCost.
    *
    * Relative inputs (both expression kinds).  idx[2] = idx[3] = -1: the inputs are the entries themselves, as above.
    * idx[2] >= 0: the inputs are differences, rounded once in the solve's scalar type as the built-in kinds round theirs,
@@ -282,8 +293,10 @@ typedef enum {
  * PUSH_TIME.  t is the time the reference's ILQSolver hands the object at that step, RelativeTimeTracker::RelativeTime(k):
  * double(k) * dt, rounded once to the solve's scalar type.  It is relative to the start of the window: in a
  * receding-horizon loop a time-reading cost or constraint sees what NominalPathLengthCost sees there.  In the value-only
- * walks of the open-loop form the step is the one the term is evaluated at there (the "next step" index).  A child of an
- * ExtremeValueCost cannot be an expression, so no program is evaluated at a step of a parent's.
+ * walks of the open-loop form the step is the one the term is evaluated at there (the "next step" index).  An expression
+ * child of an ExtremeValueCost reads the time of the step its parent is evaluated at, as the reference's parent hands its
+ * own t to its children — in the row stage and in the value-only walks alike (the built-in time-dependent kinds, as
+ * children, are still evaluated at step 0 there).
  *   In an ILQG_DYN_ROW_EXPRESSION program t is the time of the stage being evaluated: the linearisation is at t_k = k dt,
  *   the Euler form integrates at t_k, and the two RK4 half-steps of h = dt / 2 evaluate their stages at t0, t0 + h/2,
  *   t0 + h/2, t0 + h with t0 = k dt and then k dt + h (MultiPlayerDynamicalSystem::Integrate), each time formed in double
