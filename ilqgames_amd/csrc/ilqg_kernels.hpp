@@ -244,7 +244,8 @@ __global__ void __launch_bounds__(64 * W, (sizeof(T) == 4 && W == 2) ? ILQG_TRIA
   }
   const short* maps = rows_maps_load(p, smem_raw);
   T* sm = reinterpret_cast<T*>(smem_raw + rows_maps_bytes(p));
-  trial_part_instance<T, NX, NP, MU, W, TRIAL_FUSED, PROGID, BOUND>(p, maps, sa, b, sm);
+  // (its own type: the fused form reads the two arguments again from the argument segment, trial_args_again)
+  trial_part_instance<T, NX, NP, MU, W, TRIAL_FUSED, PROGID, BOUND, true, decltype(&ilq_trial_kernel<T, NX, NP, MU, W, PROGID, BOUND>)>(p, maps, sa, b, sm);
 }
 
 // The same pass cut into three launches (ilqg_solve.hpp, TRIAL_ROLL / rows_part_instance / TRIAL_DECIDE), for

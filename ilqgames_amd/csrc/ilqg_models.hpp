@@ -332,9 +332,9 @@ __device__ __forceinline__ float div_by(float x, float c, float rc) {
 template <typename T, bool DIST = false, bool DUB = false, bool CHAINS = true>
 __device__ __forceinline__ void sub_integrate_stages(int kind, T L, double interval, T* x, T u0, T u1, int q, int lane,
                                                      T* gth, bool any_car, T d0, T d1, unsigned long long group,
-                                                     int qsel) {
+                                                     int qsel, const TrigConsts& tk = TrigConsts()) {
   const T h = T(interval / 2.0);
-  const T six = T(6.0), rsix = T(1.0) / T(6.0), rL = T(1.0) / L;
+  const T six = T(6.0), rsix = sizeof(T) == 8 ? T(tk.sixth) : T(1.0) / T(6.0), rL = T(1.0) / L;
   const bool dubins = DUB && kind == ILQG_DYN_DUBINS_CAR;
   const bool car = DIST ? false : (kind == ILQG_DYN_CAR_5D || kind == ILQG_DYN_CAR_6D);
   const bool car6 = car && kind == ILQG_DYN_CAR_6D;
@@ -368,7 +368,7 @@ __device__ __forceinline__ void sub_integrate_stages(int kind, T L, double inter
   // ---- heading at this lane's stage ----
   T th_q = ang_q, th_end = ang_end;
   if (any_car) {  // wave-uniform
-    const T kth = car ? h * (div_by(v_q, L, rL) * fast_tan<CHAINS>(ang_q, group)) : T(0);
+    const T kth = car ? h * (div_by(v_q, L, rL) * fast_tan<CHAINS>(ang_q, group, tk)) : T(0);
     gth[lane] = kth;
     lds_sync(true);
     const T* g = gth + (lane & ~7);
@@ -387,7 +387,7 @@ __device__ __forceinline__ void sub_integrate_stages(int kind, T L, double inter
   }
   // ---- position rates of this lane's stage, then the two RK4 combinations ----
   T sn, cs;
-  fast_sincos<CHAINS>(th_q, &sn, &cs, group);
+  fast_sincos<CHAINS>(th_q, &sn, &cs, group, tk);
   const T kx = DIST ? h * t_fma(v_q, cs, d0) : h * (v_q * cs);
   const T ky = DIST ? h * t_fma(v_q, sn, d1) : h * (v_q * sn);
   T* gxy = gth + 64;

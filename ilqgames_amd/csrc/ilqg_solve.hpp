@@ -18,6 +18,8 @@
 #define ILQG_ROLL_PRIO 1  // the integrating wave of a trial pass issues ahead of the row waves it shares SIMDs with (fp32 headline +1.7 %, fp64 +0.3 %)
 #endif
 
+#include <type_traits>
+
 #include "ilqg_lq.hpp"
 #include "ilqg_lq_openloop.hpp"
 #include "ilqg_lq_feedback2.hpp"
@@ -196,9 +198,13 @@ __device__ __forceinline__ void instance_mark_done(const DevProblem& p, const So
 template <typename T>
 struct InstanceBuffers {
   T *w, *xs0, *us0, *P0, *al0;
-  const WsLayout L;
+  WsLayout L;  // (not const: trial_part_instance derives the members a second time, derive())
   __device__ InstanceBuffers(const DevProblem& p, const SolveArgs<T>& sa, int b)
       : L(ws_layout_of(p, sa)) {
+    derive(p, sa, b);
+  }
+  // the pointer members from the arguments (trial_part_instance derives them a second time)
+  __device__ __forceinline__ void derive(const DevProblem& p, const SolveArgs<T>& sa, int b) {
     w = sa.ws + size_t(b) * sa.ws_stride;
     // two operating-point buffers and two strategy buffers; buffer 0 is the caller's
     xs0 = sa.xs + size_t(b) * p.T * p.n;
@@ -887,6 +893,15 @@ __host__ __device__ constexpr bool fused_rollout_room(int elem_bytes, int nx, in
   return elem_bytes == 4 || (progid > 0 && nx == 14 && np == 3 && mu == 2);
 }
 
+// Which fused kernels read their arguments again behind the rollout and hold the step loop's constants and masks in the
+// scalar registers that frees (trial_args_again below; rollout_instance's HOLD): the kernels of (14, 3, 2) that take the
+// lean loop, fp64 with straight-line rows and every fp32 one.  A stack-budget fact like the one above: the fp32 fused
+// kernels of (15, 3, 2), (16, 3, 2), (24, 4, 2) and (10, 2, 2) came out with a 32-byte stack frame that nothing accesses
+// where they had none (scripts/kernel_regs.sh), so they, and the shapes not looked at, keep the form they had.
+__host__ __device__ constexpr bool fused_reread_room(int elem_bytes, int nx, int np, int mu, int progid) {
+  return nx == 14 && np == 3 && mu == 2 && fused_rollout_room(elem_bytes, nx, np, mu, progid);
+}
+
 // Which of the fused kernels with a register-held static row stage keep running reductions over partials in LDS
 // (trial_part_instance's LDS_RED; the launcher adds the LDS block for exactly these): a register-budget fact like
 // fused_rollout_room above, taken the same way.  fp64 (14, 3, 2): 233 -> 252 registers (bound: 235 -> 255), no scratch;
@@ -907,6 +922,35 @@ __device__ __forceinline__ int trial_last_chunk_begin(int Tn, int cw) {
   return ILQG_SHORT_CHUNK_LAST ? ((Tn + cw - 1) / cw - 1) * cw : Tn - cw;
 }
 
+// The fused kernel's two arguments, read AGAIN from the kernel-argument segment.  Wave 0 needs most of what the kernel
+// derives from them (buffer addresses, the workspace layout, the row stage's tables) only behind its rollout, and scalar
+// values that merely wait there take the registers the rollout's step loop wants for its constants and lane masks: the
+// compiler keeps a value once loaded, it does not load it twice.  Behind the rollout the wave therefore takes both
+// arguments from a pointer to the segment that the optimiser cannot connect to the first one (FRESH: an empty asm with
+// the pointer as an in-out scalar operand, as the step loop's lane roles) — a few scalar loads per pass.  The kernels
+// that call this take exactly (DevProblem p, SolveArgs<T> sa): the segment holds the two as a struct would.
+template <typename T>
+struct TrialKernelArgs {
+  DevProblem p;
+  SolveArgs<T> sa;
+};
+// A kernel that may call it: KERNEL is the type of a pointer to the kernel, handed down by the kernel itself
+template <typename KERNEL>
+struct takes_trial_kernel_args : std::false_type {};
+template <typename T>
+struct takes_trial_kernel_args<void (*)(DevProblem, SolveArgs<T>)> : std::true_type {};
+template <typename T, bool FRESH>
+__device__ __forceinline__ void trial_args_again(const DevProblem*& pp, const SolveArgs<T>*& sap) {
+  static_assert(std::is_standard_layout<DevProblem>::value && std::is_standard_layout<SolveArgs<T>>::value &&
+                    std::is_standard_layout<TrialKernelArgs<T>>::value,
+                "offsetof below, and the segment's layout, are those of standard-layout structs");
+  typedef const __attribute__((address_space(4))) char* karg_ptr;
+  karg_ptr ka = (karg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  if constexpr (FRESH) asm volatile("" : "+s"(ka));
+  pp = (const DevProblem*)(ka + offsetof(TrialKernelArgs<T>, p));
+  sap = (const SolveArgs<T>*)(ka + offsetof(TrialKernelArgs<T>, sa));
+}
+
 // PROGID: 0 = the row stage interprets the problem's row program; k = straight-line code for registered structure k
 // BOUND: the fused kernel of a problem with per-instance parameters bound — its rollout takes the subsystems' parameters
 // from the instance's row of the table.  Kernels of their own, as the bound straight-line row code is: the read costs the
@@ -916,36 +960,48 @@ __device__ __forceinline__ int trial_last_chunk_begin(int Tn, int cw) {
 // decision kernel's twin for problems with no solver column bound (ilq_decide_kernel's SOLVER, ilqg_kernels.hpp), which reads
 // the descriptor alone; independent of BOUND, which is about the rollout's and the rows' tables.
 template <typename T, int NX, int NP, int MU, int W, int PHASE = TRIAL_FUSED, int PROGID = 0, bool BOUND = (PROGID >= kBoundProg),
-          bool SOLVER_COLS = true>
-__device__ __forceinline__ void trial_part_instance(const DevProblem& p, const short* maps,
-                                                    const SolveArgs<T>& sa, int b, T* sm) {
+          bool SOLVER_COLS = true, typename KERNEL = void>
+__device__ __forceinline__ void trial_part_instance(const DevProblem& p_arg, const short* maps,
+                                                    const SolveArgs<T>& sa_arg, int b, T* sm) {
   static_assert(PHASE == TRIAL_FUSED || W == 1, "the split phases run one wave per instance");
   static_assert(NX > 0 || PHASE != TRIAL_FUSED, "the run-time-dimensioned path (NX = 0) runs the split passes");
-  const int n = NX > 0 ? NX : p.n, N = NX > 0 ? NP : p.N, m = NX > 0 ? NP * MU : p.m;
-  const int Tn = p.T;
-  const InstanceBuffers<T> ib(p, sa, b);
+  // REREAD: the fused kernels that fused_reread_room names read the two arguments again behind the rollout
+  // (trial_args_again above).  pp / sap: where the arguments are read from at this point of the function — the
+  // parameters themselves in every other instantiation, which are the code they were.
+  constexpr bool REREAD = PHASE == TRIAL_FUSED && W == 2 && NX > 0 && fused_reread_room(int(sizeof(T)), NX, NP, MU, PROGID);
+  static_assert(!REREAD || takes_trial_kernel_args<KERNEL>::value,
+                "REREAD reads (DevProblem, SolveArgs<T>) from the kernel-argument segment: the calling kernel hands down its "
+                "own type (KERNEL), and it must take exactly these two arguments");
+  const DevProblem* pp = &p_arg;
+  const SolveArgs<T>* sap = &sa_arg;
+  if constexpr (REREAD) trial_args_again<T, false>(pp, sap);
+  const int n = NX > 0 ? NX : pp->n, N = NX > 0 ? NP : pp->N, m = NX > 0 ? NP * MU : pp->m;
+  // (what follows down to part_lds is derived from the two arguments; not const because REREAD derives it twice)
+  int Tn = pp->T;
+  InstanceBuffers<T> ib(*pp, *sap, b);
   const WsLayout& L = ib.L;
-  T* const w = ib.w;
-  int* const t_extreme = ib.t_extreme();
-  T* const lambdas = w + L.lambdas;  // Constraint::lambdas_, zero-initialised (types.h:128)
-  T* const costs = sa.total_costs + size_t(b) * N;
+  T* w = ib.w;
+  int* t_extreme = ib.t_extreme();
+  T* lambdas = w + L.lambdas;  // Constraint::lambdas_, zero-initialised (types.h:128)
+  T* costs = sap->total_costs + size_t(b) * N;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
 
   const size_t re = PHASE == TRIAL_DECIDE ? 0 : (rollout_lds_elems(n, m) + 3) & ~size_t(3);  // (trial_phase_lds_bytes)
-  const size_t qe = trial_phase_quad_elems<T>(p, PHASE, sa.rows_cw, prog_is_static(PROGID) && PHASE == TRIAL_FUSED);
+  size_t qe = trial_phase_quad_elems<T>(*pp, PHASE, sap->rows_cw, prog_is_static(PROGID) && PHASE == TRIAL_FUSED);
   constexpr int RW = W > 1 ? W - 1 : 1;     // row waves: all but the integrating wave 0
   const int rwave = W > 1 ? wave - 1 : 0;   // this wave's row scratch (-1: wave 0 of a multi-wave workgroup has none)
   T* const sm_roll = sm;
-  T* const sm_quad = sm + re + size_t(rwave < 0 ? 0 : rwave) * qe;
+  T* sm_quad = sm + re + size_t(rwave < 0 ? 0 : rwave) * qe;
   T* const sm_quad0 = sm + re;  // the first row wave's scratch doubles as reduction scratch between passes
-  int* const flags = reinterpret_cast<int*>(sm + re + size_t(RW) * qe);  // [0] rows ready, [1] next chunk to claim
-  T* const ed_slot = reinterpret_cast<T*>(flags + 2);  // deferred ExpectedDecrease, from the first row wave to everyone
-  T* const part_lds = reinterpret_cast<T*>(flags + 4);  // SolveArgs::lds_part: the per-row partials and their running values
+  int* flags = reinterpret_cast<int*>(sm + re + size_t(RW) * qe);  // [0] rows ready, [1] next chunk to claim
+  T* ed_slot = reinterpret_cast<T*>(flags + 2);  // deferred ExpectedDecrease, from the first row wave to everyone
+  T* part_lds = reinterpret_cast<T*>(flags + 4);  // SolveArgs::lds_part: the per-row partials and their running values
+  (void)lambdas;
 
-  SolveState<T> s = trial_state_begin<T>(p, sa, ib, b, n, N, m);
-  tl_stamp(sa.prof, b, 0, t == 0);
-  if (kTimeline && PHASE == TRIAL_FUSED && sa.prof && lane == 0 && wave < 2)  // where this wave sits, as the sweep's waves say it (ilqg_lq.hpp): slots 30, 31
-    sa.prof[size_t(b) * 96 + 32 + 30 + wave] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+  SolveState<T> s = trial_state_begin<T>(*pp, *sap, ib, b, n, N, m);
+  tl_stamp(sap->prof, b, 0, t == 0);
+  if (kTimeline && PHASE == TRIAL_FUSED && sap->prof && lane == 0 && wave < 2)  // where this wave sits, as the sweep's waves say it (ilqg_lq.hpp): slots 30, 31
+    sap->prof[size_t(b) * 96 + 32 + 30 + wave] = (long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
                                                ((long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
   const long long pr_start = clock64();
   long long qph[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // linquad phase profile of this wave (diagnostics)
@@ -957,16 +1013,17 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
     const bool roll = PHASE != TRIAL_DECIDE && s.stage == ST_ROLLOUT;  // TRIAL_DECIDE: the pass's rollout is behind it
     RolloutArgs<T> ra;
     if (roll) {
-      trial_rollout_args<T>(sa, ib, b, n, s, ra);
-      if constexpr (BOUND || PHASE == TRIAL_ROLL) ra.iv = instance_values(p, b);
+      trial_rollout_args<T>(*sap, ib, b, n, s, ra);
+      if constexpr (BOUND || PHASE == TRIAL_ROLL) ra.iv = instance_values(*pp, b);
     }
     if (t == 0) {
       flags[0] = roll ? 0 : Tn;
       flags[1] = 0;
     }
     __syncthreads();
-    tl_stamp(sa.prof, b, 1, t == 0);
-    if (roll && wave == 0) {
+    tl_stamp(sap->prof, b, 1, t == 0);
+    // (REREAD: a branch the compiler knows to be uniform, so that what is read again behind it stays in scalar registers)
+    if (REREAD ? uniform(int(roll && wave == 0)) != 0 : (roll && wave == 0)) {
 #if ILQG_ROLL_PRIO
       __builtin_amdgcn_s_setprio(ILQG_ROLL_PRIO);
 #endif
@@ -974,16 +1031,35 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
         rollout_instance<T, NX, NP * MU, (NX == 4 && NP == 2), (MU == 1), (NX == 3 && NP == 2 && MU == 1),
                          (NX == 4 * NP && MU == 2 && NP <= 2), dims_use_plain_rk4(NX, NP, MU),
                          fused_rollout_room(int(sizeof(T)), NX, NP, MU, PROGID),
-                         (PROGID == kExprDynProg) && dims_use_plain_rk4(NX, NP, MU)>(
-                                         p, ra, sm_roll, lane, W > 1 ? &flags[0] : nullptr,
-                                         (kProfile && sa.prof) ? rph : nullptr, kTimeline ? sa.prof : nullptr, b);
+                         (PROGID == kExprDynProg) && dims_use_plain_rk4(NX, NP, MU), REREAD>(
+                                         *pp, ra, sm_roll, lane, W > 1 ? &flags[0] : nullptr,
+                                         (kProfile && sap->prof) ? rph : nullptr, kTimeline ? sap->prof : nullptr, b);
       else
-        rollout_instance_rt<T, (PROGID == kExprDynProg)>(p, ra, sm_roll, lane);
+        rollout_instance_rt<T, (PROGID == kExprDynProg)>(*pp, ra, sm_roll, lane);
 #if ILQG_ROLL_PRIO
       __builtin_amdgcn_s_setprio(0);
 #endif
     }
-    tl_stamp(sa.prof, b, 2, t == 0);
+    // REREAD, behind the rollout: the same values from the arguments read again, so that none of them is live across the
+    // step loop.  Both waves take this path (the row wave pays a few scalar loads per pass for it): re-derived on wave
+    // 0's branch alone, the values meet the row wave's at the join and the compiler moves them all to vector registers.
+    // (Spelled out here: as a lambda over the locals it left a dead 32-byte stack frame in the fp32 kernels.)
+    if constexpr (REREAD) {
+      trial_args_again<T, true>(pp, sap);
+      Tn = pp->T;
+      ib.L = ws_layout_of(*pp, *sap);
+      ib.derive(*pp, *sap, b);
+      w = ib.w;
+      t_extreme = ib.t_extreme();
+      lambdas = w + L.lambdas;
+      costs = sap->total_costs + size_t(b) * N;
+      qe = trial_phase_quad_elems<T>(*pp, PHASE, sap->rows_cw, prog_is_static(PROGID) && PHASE == TRIAL_FUSED);
+      sm_quad = sm + re + size_t(rwave < 0 ? 0 : rwave) * qe;
+      flags = reinterpret_cast<int*>(sm + re + size_t(RW) * qe);
+      ed_slot = reinterpret_cast<T*>(flags + 2);
+      part_lds = reinterpret_cast<T*>(flags + 4);
+    }
+    tl_stamp(sap->prof, b, 2, t == 0);
     if (roll && W == 1) {
       __syncthreads();
       if (t == 0) flags[0] = Tn;
@@ -1000,17 +1076,17 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
     // Q_INIT, Q_LIN: a few per solve) and every other kernel reduce from global memory as before.
     constexpr bool LDS_RED = PHASE == TRIAL_FUSED && prog_is_static(PROGID) && W == 2 && fused_partials_room(int(sizeof(T)), NX, NP, MU) &&
                              ProgInRegisters<typename RowProgSel<PROGID>::type>::value && rows_state_in_registers(NX, NP * MU);
-    const bool lds_red = LDS_RED && sa.lds_part != 0 && qmode == Q_TRIAL;
+    const bool lds_red = LDS_RED && sap->lds_part != 0 && qmode == Q_TRIAL;
     if constexpr (PHASE == TRIAL_FUSED) {
-    QuadArgs<T> qa = trial_quad_args<T, BOUND>(p, ib, s, sa.compact != 0, b);
+    QuadArgs<T> qa = trial_quad_args<T, BOUND>(*pp, ib, s, sap->compact != 0, b);
     if (lds_red) {
       qa.lds_merit = part_lds;
       qa.lds_cost = part_lds + size_t(Tn) * N * 2;
     }
-    qa.phacc = (kProfile && sa.prof) ? qph : nullptr;
-    qa.tl = kTimeline ? sa.prof : nullptr;
+    qa.phacc = (kProfile && sap->prof) ? qph : nullptr;
+    qa.tl = kTimeline ? sap->prof : nullptr;
     qa.tl_b = b;
-    long long tq0 = (kProfile && sa.prof) ? clock64() : 0;
+    long long tq0 = (kProfile && sap->prof) ? clock64() : 0;
     // The sweep's forward pass (delta_xs, src/lq_feedback_solver.cpp:217-241) and ILQSolver::ExpectedDecrease
     // (:364-398), deferred to here: the first row wave runs them from the sweep's scratch rows while wave 0
     // integrates, before its first chunk overwrites the linearisation they read.
@@ -1024,22 +1100,22 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
       fa.dx = nullptr;
       fa.ed_out = ed_slot;
       fa.T_steps = Tn;
-      if (sa.compact) {
+      if (sap->compact) {
         fa.compact = w + L.Q;
-        fa.compact_tab = p.row_prog + p.rp_compact_off;
-        fa.dt = p.dt;
+        fa.compact_tab = pp->row_prog + pp->rp_compact_off;
+        fa.dt = pp->dt;
       }
       constexpr int FWD_LDSE = 4 * 2 * ((NX * NX + LQCfg<T, NX, NP, MU>::SCR + 3) & ~3) + 2 * NX + 8;
       lq_forward_pass_body<T, NX, NP, MU, 64, FWD_LDSE>(fa, sm_quad, lane);
     }
-    tl_stamp(sa.prof, b, 3, rwave == 0 && lane == 0);
+    tl_stamp(sap->prof, b, 3, rwave == 0 && lane == 0);
     // A static row stage that keeps a chunk in registers (no LDS scratch: ilqg_rows.hpp) lets BOTH waves work on the
     // chunk that can only start when the rollout has ended: the integrating wave, idle from then on, takes one half of
     // its passes, the row wave the other — that chunk's time is what the launch ends with.
     typedef typename RowProgSel<PROGID>::type RowProg;
     constexpr bool SHARE_LAST = prog_is_static(PROGID) && W == 2 && ProgInRegisters<RowProg>::value && rows_state_in_registers(NX, NP * MU);
     if constexpr (SHARE_LAST) {
-      const int cw = sa.rows_cw;
+      const int cw = sap->rows_cw;
       const int nchunks = (Tn + cw - 1) / cw;
       const int rem = Tn % cw;
       constexpr unsigned first_half = static_prog_pass_split<typename RowProg::S>();
@@ -1053,16 +1129,16 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
         const int nrows = SHORT_LAST ? (Tn - k0 < cw ? Tn - k0 : cw) : ((rem != 0 && c == 0) ? rem : cw);
         if (wave != 0)
           while (progress_observe(&flags[0]) < k0 + nrows) __builtin_amdgcn_s_sleep(8);
-        tl_stamp(sa.prof, b, 4 + 2 * (c < 3 ? c : 3), wave != 0 && lane == 0);
+        tl_stamp(sap->prof, b, 4 + 2 * (c < 3 ? c : 3), wave != 0 && lane == 0);
         const unsigned mask = c == nchunks - 1 ? (wave == 0 ? first_half : ~first_half) : ~0u;
-        rows_chunk<T, NX, NP * MU, NP, true, false, RowProg, LDS_RED>(p, maps, qa, k0, nrows, cw, sm_quad, lane, mask);
-        tl_stamp(sa.prof, b, 5 + 2 * (c < 3 ? c : 3), wave != 0 && lane == 0);
+        rows_chunk<T, NX, NP * MU, NP, true, false, RowProg, LDS_RED>(*pp, maps, qa, k0, nrows, cw, sm_quad, lane, mask);
+        tl_stamp(sap->prof, b, 5 + 2 * (c < 3 ? c : 3), wave != 0 && lane == 0);
         // (the chunks come in row order and all but the last are this wave's alone: its own LDS stores, in order)
-        if (lds_red && c < nchunks - 1) partials_extend<T>(p, part_lds, t_extreme, k0, k0 + nrows, c == 0, 64, 65);
+        if (lds_red && c < nchunks - 1) partials_extend<T>(*pp, part_lds, t_extreme, k0, k0 + nrows, c == 0, 64, 65);
       }
     } else
     if (rwave >= 0) {
-      const int cw = sa.rows_cw;
+      const int cw = sap->rows_cw;
       const int nchunks = (Tn + cw - 1) / cw;
       auto claim = [&]() {
         int c = 0;
@@ -1077,14 +1153,14 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
         const int k0 = rem == 0 ? c * cw : (c == 0 ? 0 : rem + (c - 1) * cw);
         const int nrows = (rem != 0 && c == 0) ? rem : cw;
         while (progress_observe(&flags[0]) < k0 + nrows) __builtin_amdgcn_s_sleep(8);
-        if (kProfile && sa.prof) { const long long tq1 = clock64(); qph[6] += tq1 - tq0; }
-        tl_stamp(sa.prof, b, 4 + 2 * (c < 3 ? c : 3), lane == 0);
+        if (kProfile && sap->prof) { const long long tq1 = clock64(); qph[6] += tq1 - tq0; }
+        tl_stamp(sap->prof, b, 4 + 2 * (c < 3 ? c : 3), lane == 0);
         // (the register-held rows of the split kernels gain nothing for the interpreter here — measured, B = 1024: 1.45 ->
         // 1.435 M it/s; the static form reads its entries straight out of them)
         rows_chunk<T, NX, NP * MU, NP, (prog_is_static(PROGID) && rows_state_in_registers(NX, NP * MU)), false, typename RowProgSel<PROGID>::type>(
-            p, maps, qa, k0, nrows, cw, sm_quad, lane);
-        tl_stamp(sa.prof, b, 5 + 2 * (c < 3 ? c : 3), lane == 0);
-        if (kProfile && sa.prof) { tq0 = clock64(); qph[7] += 1; }
+            *pp, maps, qa, k0, nrows, cw, sm_quad, lane);
+        tl_stamp(sap->prof, b, 5 + 2 * (c < 3 ? c : 3), lane == 0);
+        if (kProfile && sap->prof) { tq0 = clock64(); qph[7] += 1; }
       }
     }
     }
@@ -1105,15 +1181,15 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
       __syncthreads();
     }
     // ---- reductions and the line-search decision (wave-uniform, identical on every wave) ----
-    tl_stamp(sa.prof, b, 12, t == 0);
+    tl_stamp(sap->prof, b, 12, t == 0);
     // The instance's solver parameters (solver_params_of), read HERE and not at kernel entry: they are uniform per
     // workgroup and scalar, and nothing of them is live across the rollout and the row stage, where the fp64 kernels
     // have no register to spare.
-    ilqg_solver_params prm = sa.prm;
-    if constexpr (SOLVER_COLS) prm = solver_params_of(p, sa.prm, b);
-    const int max_iters = solve_max_iters(sa, prm);
+    ilqg_solver_params prm = sap->prm;
+    if constexpr (SOLVER_COLS) prm = solver_params_of(*pp, sap->prm, b);
+    const int max_iters = solve_max_iters(*sap, prm);
     if (qmode == Q_COSTS) {
-      costs_reduce<T>(p, w + L.cpart, costs, t_extreme, sm_quad0, int(qe));
+      costs_reduce<T>(*pp, w + L.cpart, costs, t_extreme, sm_quad0, int(qe));
       s.qmode = Q_INIT;
       s.stage = ST_QUAD;
     } else if (qmode == Q_INIT) {
@@ -1127,16 +1203,16 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
         if (lds_red) {
           // what is left of both chains: the last chunk's rows (all of them where the horizon is one chunk), the merit
           // on the workgroup's first lane and the costs beside it on the row wave
-          partials_extend<T>(p, part_lds, t_extreme, trial_last_chunk_begin(Tn, sa.rows_cw), Tn, Tn <= sa.rows_cw, 0, 64);
+          partials_extend<T>(*pp, part_lds, t_extreme, trial_last_chunk_begin(Tn, sap->rows_cw), Tn, Tn <= sap->rows_cw, 0, 64);
           lds_sync(false);
           merit_v = T(0.5) * part_lds[size_t(Tn) * N * 3];
           costs_ready = true;
         } else
-        costs_ready = merit_costs_reduce<T>(p, w + L.mpart, w + L.cpart, t_extreme, sm_quad0, int(qe), &merit_v);
-        const T merit = costs_ready ? uniform(merit_v) : uniform(merit_reduce<T>(p, w + L.mpart, sm_quad0, int(qe)));
-        tl_stamp(sa.prof, b, 14, t == 0);
+        costs_ready = merit_costs_reduce<T>(*pp, w + L.mpart, w + L.cpart, t_extreme, sm_quad0, int(qe), &merit_v);
+        const T merit = costs_ready ? uniform(merit_v) : uniform(merit_reduce<T>(*pp, w + L.mpart, sm_quad0, int(qe)));
+        tl_stamp(sap->prof, b, 14, t == 0);
         const T scaled = T(prm.expected_decrease_fraction) * s.step * s.expected_decrease;
-        accepted = (s.last_merit - merit >= scaled) || sa.forced_steps != nullptr;  // CheckArmijoCondition :350-362
+        accepted = (s.last_merit - merit >= scaled) || sap->forced_steps != nullptr;  // CheckArmijoCondition :350-362
         if (accepted) {
           const T diff = s.last_merit - merit;
           s.has_converged =
@@ -1152,12 +1228,12 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
         s.acc_scale = s.step;
         s.accepted_iters++;
         if (lds_red)  // (an accepted trial ends the launch's passes: no barrier behind the stores)
-          costs_commit<T, false>(p, part_lds, costs, t_extreme);
+          costs_commit<T, false>(*pp, part_lds, costs, t_extreme);
         else if (costs_ready)  // TotalCosts of the accepted iterate (:158)
-          costs_commit<T>(p, sm_quad0, costs, t_extreme);
+          costs_commit<T>(*pp, sm_quad0, costs, t_extreme);
         else
-          costs_reduce<T>(p, w + L.cpart, costs, t_extreme, sm_quad0, int(qe));
-        s.stage = (s.num_iterations < max_iters && (sa.fixed_iters > 0 || !s.has_converged)) ? ST_LQ : ST_INNER_DONE;
+          costs_reduce<T>(*pp, w + L.cpart, costs, t_extreme, sm_quad0, int(qe));
+        s.stage = (s.num_iterations < max_iters && (sap->fixed_iters > 0 || !s.has_converged)) ? ST_LQ : ST_INNER_DONE;
       } else {
         s.bt++;
         s.rejected++;
@@ -1170,29 +1246,29 @@ __device__ __forceinline__ void trial_part_instance(const DevProblem& p, const s
         }
       }
     }
-    tl_stamp(sa.prof, b, 15, t == 0);
+    tl_stamp(sap->prof, b, 15, t == 0);
     if (PHASE == TRIAL_DECIDE) break;  // another pass, if the instance needs one, is the host's to launch
     // hand-off (the host gave a list to fill): a rejected step leaves the fused kernel too — the rest of this line
     // search goes through the split passes, where the next step sizes are probed side by side
-    if (PHASE == TRIAL_FUSED && sa.ids_next != nullptr && s.stage == ST_ROLLOUT && s.bt > 0) break;
+    if (PHASE == TRIAL_FUSED && sap->ids_next != nullptr && s.stage == ST_ROLLOUT && s.bt > 0) break;
   }
   state_store<T>(w, L, s);
-  tl_stamp(sa.prof, b, 13, t == 0);
+  tl_stamp(sap->prof, b, 13, t == 0);
   if (PHASE == TRIAL_ROLL) return;
   // wants a sweep / wants the exit path / (split passes only) wants another pass
   if (t == 0) {
     const int slot = s.stage == ST_LQ ? 0 : (s.stage == ST_ROLLOUT || s.stage == ST_QUAD) ? 3 : 1;
-    const int at = atomicAdd(sa.unfinished + slot, 1);
-    if (slot == 3 && sa.ids_next) sa.ids_next[at] = b;
+    const int at = atomicAdd(sap->unfinished + slot, 1);
+    if (slot == 3 && sap->ids_next) sap->ids_next[at] = b;
   }
-  if (kProfile && t == 0 && sa.prof) sa.prof[size_t(b) * 96 + 1] += clock64() - pr_start;
-  if (kProfile && t == 0 && sa.prof) {
+  if (kProfile && t == 0 && sap->prof) sap->prof[size_t(b) * 96 + 1] += clock64() - pr_start;
+  if (kProfile && t == 0 && sap->prof) {
 #pragma unroll
-    for (int i = 0; i < 4; i++) sa.prof[size_t(b) * 96 + 88 + i] += rph[i];
+    for (int i = 0; i < 4; i++) sap->prof[size_t(b) * 96 + 88 + i] += rph[i];
   }
-  if (kProfile && lane == 0 && sa.prof && wave < 2) {
+  if (kProfile && lane == 0 && sap->prof && wave < 2) {
 #pragma unroll
-    for (int i = 0; i < 8; i++) sa.prof[size_t(b) * 96 + 64 + 8 * wave + i] += qph[i];
+    for (int i = 0; i < 8; i++) sap->prof[size_t(b) * 96 + 64 + 8 * wave + i] += qph[i];
   }
 }
 

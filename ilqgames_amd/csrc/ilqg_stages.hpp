@@ -92,13 +92,36 @@ __device__ __forceinline__ void dma_g2l_wave(const void* g_, void* l, int nbytes
 // polynomial steps as the compiler forms them: the two registers the leaner stream costs are a spilled pair there.
 // XDYN (with GEN): the game may hold ILQG_DYN_EXPRESSION subsystems (sub_integrate_expr, ilqg_models.hpp) — instantiations
 // of their own, picked for the problems that hold one, so that every other problem's kernels are the code they were.
+// The step's dt for rollout_instance: the value its HOLD form read in front of the loop, else the field where it is used.
+template <bool HELD>
+__device__ __forceinline__ double step_dt(const DevProblem& p, double held) {
+  if constexpr (HELD) return held;
+  else return p.dt;
+}
+
+// HOLD (with ROOM): the caller has scalar registers to spare across the step loop — the fused trial kernel that reads its
+// arguments again behind the rollout (trial_args_again, ilqg_solve.hpp) — and the loop keeps in them what it otherwise
+// re-makes every step: the double trigonometry's literal constants (TrigConsts, ilqg_trig.hpp), made opaque HERE, in
+// front of the loop, so that they are set up once per rollout and do not live anywhere else in the kernel.
 template <typename T, int CN = 0, int CM = 0, bool DIST = false, bool DUB = false, bool AIR = false, bool PM = false,
-          bool GEN = false, bool ROOM = true, bool XDYN = false>
+          bool GEN = false, bool ROOM = true, bool XDYN = false, bool HOLD = false>
 __device__ __forceinline__ void rollout_instance(const DevProblem& p, const RolloutArgs<T>& a, T* sm, int t,
                                                  int* ready = nullptr, long long* phacc = nullptr,
                                                  long long* tl = nullptr, int tl_b = 0) {
   const int n = CN > 0 ? CN : p.n, m = CM > 0 ? CM : p.m, N = p.N, Tn = p.T;
+  // HOLD: read in front of the step loop (that caller's `p` is not one the compiler reads ahead of a branch); otherwise
+  // where they are used, as the compiler has always placed them
+  const double dt_held = HOLD ? p.dt : 0.0;
+  const bool pm_held = HOLD && PM && p.sub_kind[0] == ILQG_DYN_POINT_MASS_2D;
   constexpr int NT = 64;
+  if constexpr (HOLD && ROOM) {
+    // the LDS base as a value of this rollout's own: the kernel's is live from entry to exit and, spilled, was re-read at
+    // every use in the step loop (16-byte aligned, as every caller's block is: the wide LDS accesses depend on it)
+    auto l = (__attribute__((address_space(3))) T*)sm;
+    asm volatile("" : "+s"(l));
+    __builtin_assume((reinterpret_cast<__UINTPTR_TYPE__>(l) & 15u) == 0);
+    sm = (T*)l;
+  }
   T* sx = sm;       // [n] current state
   T* sdx = sx + n;  // [n]
   T* su = sdx + n;  // [m]
@@ -142,6 +165,10 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
   // in front of the loop they are lane masks in scalar register pairs, and the fused trial kernel has none to spare: it
   // kept them in lanes of a spill register, two read-lanes and a wait state per use.
   int qv = q, tv = t;
+  if constexpr (HOLD && ROOM) asm volatile("" : "+v"(qv), "+v"(tv));  // opaque once: the masks are formed here, not at kernel entry
+  TrigConsts tk;
+  if constexpr (HOLD && ROOM && sizeof(T) == 8)
+    asm volatile("" : "+s"(tk.two_over_pi), "+s"(tk.pio2_1), "+s"(tk.pio2_2), "+s"(tk.pio2_3), "+s"(tk.fast_limit), "+s"(tk.s7), "+s"(tk.c7), "+s"(tk.sixth));
   long long rc0 = (kProfile && phacc) ? clock64() : 0, rc1;
 #define ILQG_RPH(i) do { if (kProfile && phacc) { __builtin_amdgcn_sched_barrier(0); rc1 = clock64(); __builtin_amdgcn_sched_barrier(0); phacc[i] += rc1 - rc0; rc0 = rc1; } } while (0)
 #pragma unroll 1
@@ -149,7 +176,7 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
     // Block k of [P | alpha | u_ref | x_ref] was requested a whole step ago, and the rows of step k - 1 were stored
     // then too: this wait finds nothing in flight, and with it the release below is free.
     dma_wait();
-    if constexpr (ROOM) asm volatile("" : "+v"(qv), "+v"(tv));  // lane_roles_opaque: no instruction, the same values every step
+    if constexpr (ROOM && !HOLD) asm volatile("" : "+v"(qv), "+v"(tv));  // lane_roles_opaque: no instruction, the same values every step
     if (kTimeline && (k & 31) == 0) tl_stamp(tl, tl_b, 20 + (k >> 5), t == 0);
     if (ready) progress_publish(ready, k);
     const T* sP = stg + (k & 1) * WP;  // [m*n] gains of this step
@@ -220,21 +247,21 @@ __device__ __forceinline__ void rollout_instance(const DevProblem& p, const Roll
         for (int s = 0; s < N; s++) {
           if (p.sub_kind[s] != ILQG_DYN_EXPRESSION) continue;
           if (grp == s)
-            sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], p.xoff[s + 1] - p.xoff[s], Lp, p.dt, xj, u0, u1, double(k) * p.dt);
+            sub_integrate_expr<T>(dense_const<T>(p), p.dyn_rows[s], p.xoff[s + 1] - p.xoff[s], Lp, step_dt<HOLD>(p, dt_held), xj, u0, u1, double(k) * step_dt<HOLD>(p, dt_held));
         }
-        if (integ && kind != ILQG_DYN_EXPRESSION) sub_integrate8<T>(kind, Lp, p.dt, xj, u0, u1);
+        if (integ && kind != ILQG_DYN_EXPRESSION) sub_integrate8<T>(kind, Lp, step_dt<HOLD>(p, dt_held), xj, u0, u1);
       } else if constexpr (GEN) {
-        if (integ) sub_integrate8<T>(kind, Lp, p.dt, xj, u0, u1);
+        if (integ) sub_integrate8<T>(kind, Lp, step_dt<HOLD>(p, dt_held), xj, u0, u1);
       } else if constexpr (AIR) {
-        if (grp == 0) sub_integrate<T>(kind, Lp, p.dt, xj, u0, u1, air_vp);  // every lane of the group keeps the state
+        if (grp == 0) sub_integrate<T>(kind, Lp, step_dt<HOLD>(p, dt_held), xj, u0, u1, air_vp);  // every lane of the group keeps the state
       } else if constexpr (DIST) {
         const bool dist = integ && kind == ILQG_DYN_UNICYCLE_4D_DISTURBED;  // the next player's (dx, dy)
         const T d0 = dist ? su[uo + 2] : T(0), d1 = dist ? su[uo + 3] : T(0);
-        sub_integrate_stages<T, true, false, ROOM>(kind, Lp, p.dt, xj, u0, u1, q, t, gth, false, d0, d1, ~0ull, qv);
-      } else if (PM && p.sub_kind[0] == ILQG_DYN_POINT_MASS_2D) {
-        sub_integrate<T>(kind, Lp, p.dt, xj, u0, u1);
+        sub_integrate_stages<T, true, false, ROOM>(kind, Lp, step_dt<HOLD>(p, dt_held), xj, u0, u1, q, t, gth, false, d0, d1, ~0ull, qv, tk);
+      } else if (HOLD ? pm_held : (PM && p.sub_kind[0] == ILQG_DYN_POINT_MASS_2D)) {
+        sub_integrate<T>(kind, Lp, step_dt<HOLD>(p, dt_held), xj, u0, u1);
       } else {
-        sub_integrate_stages<T, false, DUB, ROOM>(kind, Lp, p.dt, xj, u0, u1, q, t, gth, any_car, T(0), T(0), ~0ull, qv);
+        sub_integrate_stages<T, false, DUB, ROOM>(kind, Lp, step_dt<HOLD>(p, dt_held), xj, u0, u1, q, t, gth, any_car, T(0), T(0), ~0ull, qv, tk);
       }
     }
     ILQG_RPH(2);

@@ -35,16 +35,29 @@ namespace ilqg {
 constexpr double kTrigFastLimit = 1.0e9;
 constexpr float kTrigFastLimitF = 2.0e3f;
 
+// The constants of the double fast path that the compiler sets up as literal pairs in scalar registers beside every use:
+// 2/pi, the three pieces of pi/2, the range limit and the two leading polynomial coefficients.  By default they ARE those
+// literals.  A caller with a step loop around the functions and scalar registers to spare may hand in a copy whose members
+// it has made opaque in front of the loop (rollout_instance's HOLD, ilqg_stages.hpp): they then stay in seven register
+// pairs across the loop instead of fourteen moves a sine-and-cosine or a tangent.  The same values, the same operations.
+struct TrigConsts {
+  double two_over_pi = 0x1.45f306dc9c883p-1;
+  double pio2_1 = 0x1.921fb54442d18p+0, pio2_2 = 0x1.1a62633145c07p-54, pio2_3 = -0x1.f1976b7ed8fbcp-110;
+  double fast_limit = kTrigFastLimit;
+  double s7 = 1.58969099521155010221e-10, c7 = -1.13596475577881948265e-11;
+  double sixth = 1.0 / 6.0;  // not trigonometry: the RK4 combinations' factor, which the same step loops use (sub_integrate_stages)
+};
+
 // r = x - n pi/2 with n = rint(x 2/pi); returns n's low bits
-__host__ __device__ __forceinline__ int trig_reduce(double x, double* r) {
-  const double n = __builtin_rint(x * 0x1.45f306dc9c883p-1);
-  double t = __builtin_fma(-n, 0x1.921fb54442d18p+0, x);
-  t = __builtin_fma(-n, 0x1.1a62633145c07p-54, t);
-  t = __builtin_fma(-n, -0x1.f1976b7ed8fbcp-110, t);
+__host__ __device__ __forceinline__ int trig_reduce(double x, double* r, const TrigConsts& k = TrigConsts()) {
+  const double n = __builtin_rint(x * k.two_over_pi);
+  double t = __builtin_fma(-n, k.pio2_1, x);
+  t = __builtin_fma(-n, k.pio2_2, t);
+  t = __builtin_fma(-n, k.pio2_3, t);
   *r = t;
   return int(n);
 }
-__host__ __device__ __forceinline__ int trig_reduce(float x, float* r) {
+__host__ __device__ __forceinline__ int trig_reduce(float x, float* r, const TrigConsts& = TrigConsts()) {
   const float n = __builtin_rintf(x * 0.6366197466850281f);
   float t = __builtin_fmaf(-n, 1.5707963705062866f, x);
   t = __builtin_fmaf(-n, -4.371138828673793e-08f, t);
@@ -62,11 +75,12 @@ __host__ __device__ __forceinline__ int trig_reduce(float x, float* r) {
 // The two leading coefficients are asked for in scalar registers (a literal pair set up beside the call, as the compiler
 // did before), the other ten in vector registers.  The same fused multiply-adds, each rounding once, on the host as on
 // the device.
-__host__ __device__ __forceinline__ void trig_poly_chains(double z, double* ps, double* pc) {
+__host__ __device__ __forceinline__ void trig_poly_chains(double z, double* ps, double* pc, const TrigConsts& k = TrigConsts()) {
   constexpr double S2 = -1.66666666666666324348e-01, S3 = 8.33333333332248946124e-03, S4 = -1.98412698298579493134e-04,
-                   S5 = 2.75573137070700676789e-06, S6 = -2.50507602534068634195e-08, S7 = 1.58969099521155010221e-10;
+                   S5 = 2.75573137070700676789e-06, S6 = -2.50507602534068634195e-08;
   constexpr double C2 = 4.16666666666666019037e-02, C3 = -1.38888888888741095749e-03, C4 = 2.48015872894767294178e-05,
-                   C5 = -2.75573143513906633035e-07, C6 = 2.08757232129817482790e-09, C7 = -1.13596475577881948265e-11;
+                   C5 = -2.75573143513906633035e-07, C6 = 2.08757232129817482790e-09;
+  const double S7 = k.s7, C7 = k.c7;
 #if defined(__HIP_DEVICE_COMPILE__)
   double s, c;
   asm("v_fma_f64 %0, %2, %3, %4\n\t"
@@ -103,11 +117,11 @@ __host__ __device__ __forceinline__ void trig_poly_chains(double z, double* ps, 
 // keep the compiler's own (it may hold coefficients as literals there, and they have no registers for ten pairs at once).
 // The same operations either way.
 template <bool CHAINS = false>
-__host__ __device__ __forceinline__ void trig_kernels(double r, double* s, double* c) {
+__host__ __device__ __forceinline__ void trig_kernels(double r, double* s, double* c, const TrigConsts& k = TrigConsts()) {
   const double z = r * r;
   double ps, pc;
   if constexpr (CHAINS) {
-    trig_poly_chains(z, &ps, &pc);
+    trig_poly_chains(z, &ps, &pc, k);
   } else {
     ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
     pc = __builtin_fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
@@ -126,7 +140,7 @@ __host__ __device__ __forceinline__ void trig_kernels(double r, double* s, doubl
   *c = w + __builtin_fma(z * z, pc, (1.0 - w) - hz);
 }
 template <bool CHAINS = false>
-__host__ __device__ __forceinline__ void trig_kernels(float r, float* s, float* c) {
+__host__ __device__ __forceinline__ void trig_kernels(float r, float* s, float* c, const TrigConsts& = TrigConsts()) {
   const float z = r * r;
   float ps = __builtin_fmaf(z, 2.7183114939898219064e-06f, -1.98393348360966317347e-04f);
   float pc = __builtin_fmaf(z, 2.43904487962774090654e-05f, -1.38867637746099294692e-03f);
@@ -139,10 +153,10 @@ __host__ __device__ __forceinline__ void trig_kernels(float r, float* s, float* 
 }
 
 template <typename T, bool CHAINS = false>
-__host__ __device__ __forceinline__ void fast_sincos_core(T x, T* s, T* c) {
+__host__ __device__ __forceinline__ void fast_sincos_core(T x, T* s, T* c, const TrigConsts& k = TrigConsts()) {
   T r, sr, cr;
-  const int n = trig_reduce(x, &r);
-  trig_kernels<CHAINS>(r, &sr, &cr);
+  const int n = trig_reduce(x, &r, k);
+  trig_kernels<CHAINS>(r, &sr, &cr, k);
   const bool swap = n & 1;
   const T sv = swap ? cr : sr, cv = swap ? sr : cr;
   *s = (n & 2) ? -sv : sv;
@@ -274,8 +288,9 @@ __host__ __device__ inline void large_sincos(double x, double* s, double* c) {
 // (the branch is voted over the group on the device so that the common case is one uniform test; a lane inside the fast
 // range computes the fast form whatever its neighbours hold)
 template <bool CHAINS = false>
-__host__ __device__ __forceinline__ void fast_sincos(double x, double* s, double* c, unsigned long long group = ~0ull) {
-  const bool mine = !(__builtin_fabs(x) <= kTrigFastLimit);
+__host__ __device__ __forceinline__ void fast_sincos(double x, double* s, double* c, unsigned long long group = ~0ull,
+                                                     const TrigConsts& k = TrigConsts()) {
+  const bool mine = !(__builtin_fabs(x) <= k.fast_limit);
 #if defined(__HIP_DEVICE_COMPILE__)
   const bool any = trig_group_any(mine, group);
 #else
@@ -288,10 +303,11 @@ __host__ __device__ __forceinline__ void fast_sincos(double x, double* s, double
       return;
     }
   }
-  fast_sincos_core<double, CHAINS>(x, s, c);
+  fast_sincos_core<double, CHAINS>(x, s, c, k);
 }
 template <bool CHAINS = false>  // (the float kernels take their coefficients as literals: one form)
-__host__ __device__ __forceinline__ void fast_sincos(float x, float* s, float* c, unsigned long long group = ~0ull) {
+__host__ __device__ __forceinline__ void fast_sincos(float x, float* s, float* c, unsigned long long group = ~0ull,
+                                                     const TrigConsts& = TrigConsts()) {
   const bool mine = !(__builtin_fabsf(x) <= kTrigFastLimitF);
 #if defined(__HIP_DEVICE_COMPILE__)
   const bool any = trig_group_any(mine, group);
@@ -335,10 +351,10 @@ __host__ __device__ __forceinline__ float trig_div(float a, float b) {
   return __builtin_fmaf(__builtin_fmaf(-q, b, a), rc, q);
 }
 template <typename T, bool CHAINS = false>
-__host__ __device__ __forceinline__ T fast_tan_core(T x) {
+__host__ __device__ __forceinline__ T fast_tan_core(T x, const TrigConsts& k = TrigConsts()) {
   T r, sr, cr;
-  const int n = trig_reduce(x, &r);
-  trig_kernels<CHAINS>(r, &sr, &cr);
+  const int n = trig_reduce(x, &r, k);
+  trig_kernels<CHAINS>(r, &sr, &cr, k);
   const bool odd = n & 1;
   return trig_div(odd ? -cr : sr, odd ? sr : cr);
 }
@@ -356,8 +372,8 @@ __host__ __device__ inline double large_tan(double x) {
   return s / c;
 }
 template <bool CHAINS = false>
-__host__ __device__ __forceinline__ double fast_tan(double x, unsigned long long group = ~0ull) {
-  const bool mine = !(__builtin_fabs(x) <= kTrigFastLimit);
+__host__ __device__ __forceinline__ double fast_tan(double x, unsigned long long group = ~0ull, const TrigConsts& k = TrigConsts()) {
+  const bool mine = !(__builtin_fabs(x) <= k.fast_limit);
 #if defined(__HIP_DEVICE_COMPILE__)
   const bool any = trig_group_any(mine, group);
 #else
@@ -367,10 +383,10 @@ __host__ __device__ __forceinline__ double fast_tan(double x, unsigned long long
   if (__builtin_expect(any, 0)) {
     if (mine) return large_tan(x);
   }
-  return fast_tan_core<double, CHAINS>(x);
+  return fast_tan_core<double, CHAINS>(x, k);
 }
 template <bool CHAINS = false>
-__host__ __device__ __forceinline__ float fast_tan(float x, unsigned long long group = ~0ull) {
+__host__ __device__ __forceinline__ float fast_tan(float x, unsigned long long group = ~0ull, const TrigConsts& = TrigConsts()) {
   const bool mine = !(__builtin_fabsf(x) <= kTrigFastLimitF);
 #if defined(__HIP_DEVICE_COMPILE__)
   const bool any = trig_group_any(mine, group);
